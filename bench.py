@@ -12,7 +12,9 @@ two-scalar score/done all-reduce.
 Weak scaling: every rank owns `--games` games, a contiguous shard of a generation
 of N x games (seeds and colours follow the global game index, trainer.cpp:243-255).
 The timed region is bracketed by barrier + device synchronisation; the time is the
-max over ranks; rank 0 prints ONE JSON line.
+max over ranks; rank 0 prints ONE JSON line on stdout, and the whole record (with the side
+measurements that line summarises in detail.summary) on stderr.  `--dump-outputs DIR` writes
+what the last timed generation computed, for comparing two builds output for output.
 
 Workload (BASELINE.json configs[1] / SURVEY 8d): 4096 games per GPU, 400
 simulations per move, 16 searches per evaluation, c_puct 1.0, epsilon 0.25,
@@ -126,7 +128,28 @@ def parse():
     ap.add_argument("--engine", default="hip", choices=("hip", "emu"),
                     help="hip = the product (libcorintho_hip.so on an MI355X).  emu = CPU rehearsal of the multi-rank path for "
                          "the tests only: the lane-loop build of the same kernel source (tests/emu) over gloo; never a result")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed generation hands its caller (its samples, score and "
+                         "mate length) as DIR/<name>.npy, to compare two builds output for output (with N > 1: <name>_rank<r>.npy)")
     return ap.parse_args()
+
+
+DUMP_ROWS = 65536  # sample rows kept by --dump-outputs over all ranks: 65536 x (166 + 1) float32 + a float64 index = 44 MB
+
+
+def dump_outputs(trainer, path, suffix="", max_rows=DUMP_ROWS):
+    """What a caller of the timed path receives after a generation: the un-augmented samples of export_samples()
+    (state + search policy, outcome; writeSamples' x8 symmetry expansion is a function of them), score() and
+    avg_mate_length().  Above max_rows sample rows, a fixed seeded sample of them with their row indices."""
+    os.makedirs(path, exist_ok=True)
+    sp, oc = trainer.export_samples()
+    n = sp.shape[0]
+    idx = np.arange(n) if n <= max_rows else np.sort(np.random.default_rng(0).choice(n, max_rows, replace=False))
+    arrays = {"samples_state_policy": sp[idx], "samples_outcome": oc[idx], "samples_row_index": idx.astype(np.float64),
+              "num_samples": np.array([n], np.float64), "score": np.array([trainer.score()], np.float32),
+              "avg_mate_length": np.array([trainer.avg_mate_length()], np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
 
 
 def launch_ranks(args):
@@ -542,6 +565,10 @@ def main():
     else:
         job_searches, job_evals, job_rows = float(totals["searches"]), float(totals["evals"]), float(totals["nn_rows"])
         job_samples = float(totals["samples"])
+    if args.dump_outputs:
+        # the trainer still holds the last timed generation here: the gather check and the variants below reset it
+        # every rank writes its own shard's; DUMP_ROWS is shared among them (64 MB in all)
+        dump_outputs(tr, args.dump_outputs, "_rank%d" % rank if world > 1 else "", DUMP_ROWS // world)
 
     gather_check = None
     if use_dist and args.check_gather:
@@ -742,7 +769,12 @@ def main():
         }
         if world == 1 and args.cpu_games > 0:
             out["cpu_baseline"] = cpu_baseline(args, arch, weights_by_arch, out["detail"]["evals_per_game"])
-        print(json.dumps(out))
+        # The whole record goes to stderr.  The result line on stdout leaves out the side measurements, whose rates
+        # detail.summary carries: with them the line grows past 24 KB, more than a reader of the output's tail can parse.
+        sys.stderr.write(json.dumps(out) + "\n")
+        sys.stderr.flush()
+        side = ("variants", "no_eval_cache", "two_pools", "recycled", "trained_checkpoint", "configs")
+        print(json.dumps(dict(out, detail={k: v for k, v in out["detail"].items() if k not in side})))
     if use_dist:
         dist.destroy_process_group()
 

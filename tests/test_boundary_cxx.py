@@ -5,13 +5,11 @@ coded in C++.  Every request batch, the three sample arrays, score, mate length 
 file must equal the CPU oracle's, bit for bit.  Runs against the emulation build of the engine
 here and against libcorintho_hip.so on the MI355X (-m gpu).
 
-Second test (build container only): the reference's own main.pyx, with nothing but the `extern
-from` path changed, cythonizes and COMPILES against this Trainer and links with the engine library
-(it is not imported: keras is absent)."""
+Second test: the reference's own main.pyx, with nothing but the `extern from` path changed, cythonized by
+build() into oracle/_ref/main.cpp (oracle/ref_main.py), COMPILES against this Trainer and links with the
+engine library (it is not imported: keras is absent)."""
 import os
-import re
 import subprocess
-import sys
 import sysconfig
 
 import numpy as np
@@ -19,7 +17,6 @@ import pytest
 
 from oracle import oracle as O
 from tests import harness as H
-from tests.conftest import REFERENCE
 from tests.engines import ENGINES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -116,29 +113,20 @@ def test_cpp_dockermc_chooses_the_oracles_moves(engine, tmp_path):
 
 def test_reference_main_pyx_compiles_against_this_trainer(tmp_path):
     """main.pyx:17 `cdef extern from "../cpp/src/trainer.cpp"` -> this repository's trainer.cpp; everything
-    else of the reference's Cython module unchanged.  Cythonize + compile + link (python/setup.py:15-38 flags)."""
-    pyx = os.path.join(REFERENCE, "corintho_ai/python/main.pyx")
-    if not os.path.exists(pyx):
-        pytest.skip("reference tree not mounted")
-    try:
-        import Cython  # noqa: F401
-    except ImportError:
-        pytest.skip("cython not installed")
+    else of the reference's Cython module unchanged.  Compile + link the module build() cythonized (python/setup.py:15-38
+    flags)."""
+    cpp = os.path.join(ROOT, "oracle", "_ref", "main.cpp")
+    if not os.path.exists(cpp):
+        pytest.skip("oracle/_ref/main.cpp not built: build() found no reference checkout or no Cython")
     from corintho_ai_amd import build
 
     build.build()
-    text = open(pyx).read()
-    new_path = os.path.join(ROOT, "corintho_ai_amd", "cpp", "trainer.cpp")
-    patched, n = re.subn(r'cdef extern from "\.\./cpp/src/trainer\.cpp"', 'cdef extern from "%s"' % new_path, text)
-    assert n == 1
-    (tmp_path / "main.pyx").write_text(patched)
-    subprocess.check_call([sys.executable, "-m", "cython", "--cplus", "-3", "main.pyx"], cwd=tmp_path)
     inc = sysconfig.get_paths()["include"]
     libdir = os.path.join(ROOT, "corintho_ai_amd")
     so = str(tmp_path / "main_ext.so")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-fopenmp", "-DNDEBUG", "-shared", "-fPIC", "-I" + inc, "-I" + np.get_include(),
-                           "-DNPY_NO_DEPRECATED_API=NPY_1_7_API_VERSION", "main.cpp", "-o", so, "-L" + libdir, "-lcorintho_hip",
-                           "-Wl,-rpath," + libdir], cwd=tmp_path)
+                           "-I" + os.path.join(ROOT, "corintho_ai_amd", "cpp"), "-DNPY_NO_DEPRECATED_API=NPY_1_7_API_VERSION", cpp,
+                           "-o", so, "-L" + libdir, "-lcorintho_hip", "-Wl,-rpath," + libdir], cwd=tmp_path)
     # the extension defines the module init and calls the engine's C ABI through the Trainer members
     syms = subprocess.check_output(["nm", "-D", "--undefined-only", so]).decode()
     for s in ("ca_trainer_create", "ca_trainer_do_iteration", "ca_trainer_write_requests", "ca_trainer_write_samples",

@@ -1,6 +1,6 @@
 """A statistical pin against results the REFERENCE itself holds: its rating tournament
 (corintho_ai/rating/results.txt: `player1 player2 wins draws losses`, first player's view;
-players in rating/tourney/players.txt) contains one pairing that can be re-played exactly at
+players in rating/tourney/players.txt; both committed under tests/golden/reference/) contains one pairing that can be re-played exactly at
 negligible cost -- player 95 = the last checkpoint (model_93) searching with max_searches = 1,
 searches_per_eval = 1, c_puct 3, epsilon 0.25 (`93 1 1 3.0 0.25 0`) against player 96 = the uniformly
 random player (`-1 1600 16 3.0 0.25 1`):
@@ -48,12 +48,10 @@ REF_SECOND = (846, 0, 343)   # the random player moves first: ITS wins, draws, l
 
 
 def test_the_quoted_rows_are_the_reference_rows():
-    path = os.path.join(REFERENCE, "corintho_ai/rating/results.txt")
-    if not os.path.exists(path):
-        pytest.skip("reference tree not mounted")
+    path = os.path.join(REFERENCE, "rating/results.txt")
     rows = {tuple(map(int, l.split()[:2])): tuple(map(int, l.split()[2:])) for l in open(path) if l.strip()}
     assert rows[(95, 96)] == REF_FIRST and rows[(96, 95)] == REF_SECOND
-    players = open(os.path.join(REFERENCE, "corintho_ai/rating/tourney/players.txt")).read().split("\n")
+    players = open(os.path.join(REFERENCE, "rating/tourney/players.txt")).read().split("\n")
     assert players[1 + 95] == "93 1 1 3.0 0.25 0" and players[1 + 96] == "-1 1600 16 3.0 0.25 1"
 
 
@@ -169,13 +167,11 @@ REF_RANDOM_ROWS = {  # against player 96, the random player: the searcher never 
 
 
 def test_the_real_search_rows_are_the_reference_rows():
-    path = os.path.join(REFERENCE, "corintho_ai/rating/results.txt")
-    if not os.path.exists(path):
-        pytest.skip("reference tree not mounted")
+    path = os.path.join(REFERENCE, "rating/results.txt")
     rows = {tuple(map(int, l.split()[:2])): tuple(map(int, l.split()[2:])) for l in open(path) if l.strip()}
     for k, v in {**REF_SEARCH_ROWS, **REF_RANDOM_ROWS}.items():
         assert rows[k] == v, k
-    players = open(os.path.join(REFERENCE, "corintho_ai/rating/tourney/players.txt")).read().split("\n")
+    players = open(os.path.join(REFERENCE, "rating/tourney/players.txt")).read().split("\n")
     for pid, mid in PLAYER_MODEL.items():
         assert players[1 + pid] == "%d 1600 16 3.0 0.25 0" % mid
 
@@ -382,9 +378,7 @@ def _population_rows():
 
 
 def test_the_population_rows_are_the_reference_rows():
-    path = os.path.join(REFERENCE, "corintho_ai/rating/results.txt")
-    if not os.path.exists(path):
-        pytest.skip("reference tree not mounted")
+    path = os.path.join(REFERENCE, "rating/results.txt")
     import json
 
     rows = {tuple(map(int, l.split()[:2])): tuple(map(int, l.split()[2:])) for l in open(path) if l.strip()}
@@ -392,7 +386,7 @@ def test_the_population_rows_are_the_reference_rows():
     assert len(d["rows"]) == 600 and len(d["players"]) == 25
     for a, b, w, dr, l in d["rows"]:
         assert rows[(a, b)] == (w, dr, l)
-    players = open(os.path.join(REFERENCE, "corintho_ai/rating/tourney/players.txt")).read().split("\n")
+    players = open(os.path.join(REFERENCE, "rating/tourney/players.txt")).read().split("\n")
     for p in d["players"]:
         assert players[1 + p] == "%d 1600 16 3.0 0.25 0" % (93 - p)
     assert len(_population_rows()) == 156

@@ -15,10 +15,13 @@ from corintho_ai_amd import savedmodel_import as SI
 from oracle import oracle as O
 from tests import harness as H
 from tests import ref_nets
+from tests.conftest import REFERENCE
 from tests.engines import ENGINES, make_trainer
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "savedmodel.npz")
-REF_MODEL = "/root/reference/corintho_ai/model"
+# the reference model directory's variables/ (the reader needs nothing else): its index and the head of its data shard that
+# holds every layer variable (tools/gen_reference_fixtures.py)
+REF_VARIABLES = os.path.join(REFERENCE, "model", "variables.npz")
 
 
 # ---- a TensorBundle writer for the tests: sorted table with prefix compression, several data blocks, one shard
@@ -147,10 +150,16 @@ def load():
         return {k: z[k] for k in z.files}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODEL), reason="reference tree not mounted")
-def test_the_fixture_is_the_reference_model():
-    """build container only: the committed weights are what the reader finds in the reference's model directory"""
-    assert SI.mlp12x100_from_savedmodel(REF_MODEL).tobytes() == load()["weights"].tobytes()
+def test_the_fixture_is_the_reference_model(tmp_path):
+    """the committed weights are what the reader finds in the reference's model directory: its variables/ rebuilt from
+    the reference's index and data shard, the optimizer's slots at the shard's end (never read as weights) as zeros"""
+    with np.load(REF_VARIABLES) as z:
+        index, head, size = z["index"].tobytes(), z["data_head"].tobytes(), int(z["data_size"])
+    d = tmp_path / "model" / "variables"
+    d.mkdir(parents=True)
+    (d / "variables.index").write_bytes(index)
+    (d / "variables.data-00000-of-00001").write_bytes(head + bytes(size - len(head)))
+    assert SI.mlp12x100_from_savedmodel(str(tmp_path / "model")).tobytes() == load()["weights"].tobytes()
 
 
 def test_fixture_holds_batchnorm_unfolded():

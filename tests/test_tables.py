@@ -1,13 +1,13 @@
-"""The generated constant tables: digests (always) and, in the build container,
-value-for-value equality with the reference header read as text
-(corintho_ai/cpp/include/util.h:85-702)."""
+"""The generated constant tables: digests, and value-for-value equality with the tables of the reference header
+(corintho_ai/cpp/include/util.h:85-702), whose values tests/golden/reference/util_tables.npz holds
+(tools/gen_reference_fixtures.py)."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 
+from tests.conftest import REFERENCE
 from tools import gen_tables as gt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,6 +16,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.fixture(scope="module")
 def tables():
     return gt.build_all()
+
+
+@pytest.fixture(scope="module")
+def reference_tables():
+    with np.load(os.path.join(REFERENCE, "util_tables.npz")) as z:
+        return {k: z[k] for k in z.files}
 
 
 def test_digests_match_golden(tables):
@@ -51,41 +57,26 @@ def test_gamma_table_shape(tables):
     assert abs(float(gm.astype(np.float64).mean()) - 0.3) < 1e-6  # E[Gamma(0.3,1)] = 0.3
 
 
-def _parse_ints(block):
-    return [int(x) for x in re.findall(r"-?\d+", block)]
-
-
-def test_line_breakers_equal_reference(tables, reference_util_h):
-    src = reference_util_h
-    s = src[src.index("line_breakers = {"):src.index("// Number of buckets")]
-    strs = re.findall(r'bitset<kNumMoves>\(\s*((?:"[01]+"\s*)+)\)', s)
-    assert len(strs) == 102
-    for idx, t in enumerate(strs):
-        bits = "".join(re.findall(r'"([01]+)"', t))
-        assert len(bits) == 96
+def test_line_breakers_equal_reference(tables, reference_tables):
+    bits = reference_tables["line_breakers_bits"]
+    assert bits.shape == (102, 96)
+    for idx, row in enumerate(bits):
         m = 0
-        for k, ch in enumerate(bits):  # bitset string: char k is bit 95-k
-            if ch == "1":
-                m |= 1 << (95 - k)
+        for k in range(96):  # column k: bit k of the 96-bit mask
+            if row[k]:
+                m |= 1 << k
         assert m == tables[0][idx], "line %d" % idx
 
 
-def test_gamma_samples_equal_reference(tables, reference_util_h):
-    src = reference_util_h
-    s = src[src.index("gamma_samples[kNumGammaBuckets] = {"):]
-    s = s[s.index("{") + 1:s.index("};")]
-    ref = np.array([float(x) for x in re.findall(r"[-+0-9.e]+", s)]).astype(np.float32)
-    assert ref.shape == (1024,)
+def test_gamma_samples_equal_reference(tables, reference_tables):
+    ref = reference_tables["gamma_samples"]
+    assert ref.dtype == np.float32 and ref.shape == (1024,)
     assert np.array_equal(ref.view(np.uint32), tables[1].view(np.uint32))
 
 
-def test_symmetries_equal_reference(tables, reference_util_h):
-    src = reference_util_h
-    s = src[src.index("space_symmetries[kNumSymmetries][kBoardSize] = {"):]
-    a = s[s.index("{"):s.index("};")]
-    sp = np.array(_parse_ints(a)).reshape(8, 16)
-    s2 = src[src.index("move_symmetries[kNumSymmetries][kNumMoves] = {"):]
-    b = s2[s2.index("{"):s2.index("};")]
-    mv = np.array(_parse_ints(b)).reshape(8, 96)
+def test_symmetries_equal_reference(tables, reference_tables):
+    sp = reference_tables["space_symmetries"]
+    mv = reference_tables["move_symmetries"]
+    assert sp.shape == (8, 16) and mv.shape == (8, 96)
     assert np.array_equal(sp, tables[2])
     assert np.array_equal(mv, tables[3])

@@ -12,8 +12,8 @@ macros to
   corintho_ai_amd/csrc/tables.inc   (product, HIP device constants)
   oracle/tables.inc                 (CPU oracle)
 `tests/test_tables.py` checks the generated values against digests recorded in
-tests/golden/tables.json and, when /root/reference is mounted, against the
-reference header parsed as text.
+tests/golden/tables.json and against the values of the reference header
+(tests/golden/reference/util_tables.npz, tools/gen_reference_fixtures.py).
 
 Derivation rules
 ----------------
