@@ -110,7 +110,9 @@ struct Pool {
   int first_start = 0;       /* iteration at which the stagger releases the pool's first game (trainer.cpp:184-186) */
   int timed[2] = {0, 0};     /* the window's last iteration carries the events */
   unsigned long long *word = nullptr; /* pinned: [parity] counter word copied at the end of window parity 0 / 1, [2 + parity] rows the
-                             * network evaluated in that iteration (evaluation cache) */
+                             * network evaluated in that iteration (evaluation cache), [4 + parity] the pool's steps cut so far
+                             * (work_counter[CO_WC_CUTS]) */
+  unsigned long long cuts_seen = 0; /* that count at the last window collected (at the start of the run: read when it began) */
   /* the pool's view of the evaluation cache (EvalCache).  The table (c_hdr, c_val, c_done) is ONE for the trainer and
    * belongs to pool 0 -- the other pools hold copies of the pointers, not buffers of their own */
   EvalCache cache = {};
@@ -171,7 +173,7 @@ struct ca_trainer {
   double mcts_timed_ms = 0, nn_timed_ms = 0, pack_timed_ms = 0;
   int64_t timed_launches = 0, nn_timed_rows = 0;
   int64_t nn_rows_evaluated = 0; /* rows the network kernels worked on (= nn_rows without the evaluation cache) */
-  int64_t steps_cut = 0, step_budget_last = 0; /* ca_config.step_budget: steps of the last run that stopped at their budget; the last budget */
+  int64_t steps_cut = 0, step_budget_last = 0; /* ca_config.step_budget: steps of the generation that stopped at their budget; the last budget */
   bool cache_clean = false;      /* the pools' tables hold nothing of an earlier generation */
   int64_t cache_clears = 0;
   /* the evaluation cache serves fused training (and fused analysis): one network, rows packed by the search kernel */
@@ -419,6 +421,7 @@ struct ca_trainer {
     mcts_timed_ms = nn_timed_ms = pack_timed_ms = 0;
     timed_launches = nn_timed_rows = 0;
     nn_rows_evaluated = 0;
+    steps_cut = step_budget_last = 0;
     cache_clean = false; /* run_pools empties the tables before the first iteration of the new generation */
     if (logbuf.p) {
       rt_memset(logbuf.p, 0, (size_t)num_logged * CO_LOG_CAP * 4, stream);
@@ -548,7 +551,8 @@ struct ca_trainer {
     P.row_counter = nullptr; /* counted in fused mode only */
     P.fused_pack = 0;
     P.defer_handover = 0;
-    /* ca_config.step_budget: n > 0 that many scans, 0 automatic (CO_STEP_BUDGET_K16 / 16 x the pool's mean), -1 none;
+    /* ca_config.step_budget: n > 0 n microseconds (n scans on the emulation build, which has no clock:
+     * CO_STEP_UNITS_PER_CONFIG_UNIT), 0 automatic (CO_STEP_BUDGET_K16 / 16 x the pool's mean), -1 none;
      * below -1 (diagnostic): automatic with the factor -n / 16 */
     P.step_budget = cfg.step_budget > 0 ? cfg.step_budget : 0;
     P.step_budget_k16 = cfg.step_budget == 0 ? CO_STEP_BUDGET_K16 : cfg.step_budget < -1 ? -cfg.step_budget : 0;
@@ -1017,8 +1021,8 @@ struct ca_trainer {
         for (auto &e : q.ev[w]) rt_event_create(&e);
         rt_event_create(&q.polled[w]);
       }
-      rt_host_alloc((void **)&q.word, 32);
-      memset(q.word, 0, 32);
+      rt_host_alloc((void **)&q.word, 48);
+      memset(q.word, 0, 48);
       memset(&q.cache, 0, sizeof q.cache);
       rt_event_create(&q.quiet);
       if (use_cache()) {
@@ -1086,7 +1090,12 @@ struct ca_trainer {
       }
       cache_clean = true;
     }
+    /* the steps cut so far (a run that resumes a generation: not zero), what the first window of each pool is compared with */
+    std::vector<unsigned long long> wc((size_t)CO_WC_WORDS * CO_MAX_POOLS);
+    rt_d2h(wc.data(), work_counter.p, wc.size() * 8, stream);
+    rt_sync(stream);
     for (auto &q : pools) {
+      q.cuts_seen = wc[CO_WC_WORDS * (&q - &pools[0]) + CO_WC_CUTS];
       q.finished = false;
       q.running = q.n;
       q.idle = 0;
@@ -1109,8 +1118,10 @@ struct ca_trainer {
     rt_event_sync(q.polled[parity]);
     unsigned long long c = q.word[parity];
     const unsigned long long evaluated = q.cache.hdr ? q.word[2 + parity] & 0xFFFFFFFFull : c & 0xFFFFFFFFull;
-    q.running = (int)((c >> 32) & 0xFFFFFFull); /* (bits 56..: games of the iteration that held their leaves back, mcts.h co_step_tail) */
-    const bool holding = (c >> 56) != 0;
+    q.running = (int)(c >> 32); /* (bits 32..63: the pool's running games, the low word its rows) */
+    /* steps cut in the window: games held their leaves back (mcts.h co_step_tail), which submits no rows for them */
+    const bool holding = q.word[4 + parity] != q.cuts_seen;
+    q.cuts_seen = q.word[4 + parity];
     if (q.timed[parity]) {
       /* one iteration per window is timed (three event records per launch pair cost 1-4 % of
        * the wall time); its batch size is the counter word just read */
@@ -1123,12 +1134,13 @@ struct ca_trainer {
       q.timed[parity] = 0;
     }
     q.launched[parity] = 0;
-    q.finished = ((c >> 32) & 0xFFFFFFull) == 0;
+    q.finished = (c >> 32) == 0;
     if (!q.finished && (c & 0xFFFFFFFFull) == 0 && !holding) {
       /* main.pyx:161-163 raises when NO game has a request.  A pool whose first game the
        * staggered start (trainer.cpp:184-186) has not released yet has running games and no
        * rows by construction: that is not the reference's error condition */
-      /* (an iteration whose games all stopped at their step budget has no rows either -- `holding`: that is not it) */
+      /* (an iteration whose games all stopped at their step budget has no rows either -- `holding`, a window in which steps
+       * were cut: that is not it) */
       if (q.word_iter[parity] > q.first_start && ++q.idle > 16) failure = "No requests during training";
     } else {
       q.idle = 0;
@@ -1310,6 +1322,7 @@ struct ca_trainer {
           if (q.finished) continue;
           rt_d2h(&q.word[parity], pack_counter.p + CO_PACK_STRIDE * (&q - &pools[0]) + counter_slot, 8, q.st);
           if (q.cache.hdr) rt_d2h(&q.word[2 + parity], q.c_count + 4 * counter_slot, 4, q.st);
+          rt_d2h(&q.word[4 + parity], work_counter.p + (size_t)CO_WC_WORDS * (&q - &pools[0]) + CO_WC_CUTS, 8, q.st);
           q.word_iter[parity] = trainer_iteration - 1;
           rt_event_record(q.polled[parity], q.st);
         }

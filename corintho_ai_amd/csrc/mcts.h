@@ -2814,8 +2814,10 @@ CO_DEV void co_step_tail(const EngineParams &P, CoWave &w, int g, int done) {
   if (packs && w.gc.held) {
     /* the step stopped at its budget: the game is running and submits nothing; its leaves (request rows, records and keys
      * are in place) wait for the rest of their batch, the generator outputs owed to them are reserved with the others' */
-    /* (bits 56..: games that hold their leaves back -- the host tells an iteration without rows from "no game has a request") */
-    co_atomic_add_u64(P.pack_counter + (P.iteration & 1), (1ull << 32) | (1ull << 56));
+    /* (still running, no rows.  A held game is counted in the pool's CO_WC_CUTS word only, which the host copies with this
+     * one at every poll to tell a window without rows from "no game has a request"; a count of held games in bits 56.. of
+     * this word was 8 bits wide and read 256 of them as none) */
+    co_atomic_add_u64_noret(P.pack_counter + (P.iteration & 1), 1ull << 32);
     if (P.work_counter) co_atomic_add_u64_noret(P.work_counter + CO_WC_CUTS, 1ull); /* (ca_stats.steps_cut) */
     w.gc.noise_held = w.noise_words;
     return;

@@ -86,7 +86,7 @@ typedef struct ca_config {
    * the batch of searches_per_eval is complete (or the move's searches run out), so the game performs exactly the
    * reference's sequence of operations -- only spread over more iterations.  It bounds what a launch waits for: its
    * slowest game (endgame positions under a trained network: simulations ten levels deep, half of them ending in
-   * terminal leaves that queue nothing).  0 = automatic (1.6 x the running mean of the pool's steps), n > 0 = n
+   * terminal leaves that queue nothing).  0 = automatic (1.5 x the running mean of the pool's steps), n > 0 = n
    * microseconds, -1 = no limit (below -1, diagnostic: automatic with the factor -n / 16).  Results are identical either
    * way; the number of iterations of a generation is not. */
   int32_t step_budget;
@@ -228,7 +228,7 @@ typedef struct ca_stats {
   double mcts_timed_ms, nn_timed_ms;
   int64_t resident_slots; /* slots of the pool (= num_games unless it recycles, ca_config.resident) */
   int64_t nn_rows_evaluated; /* rows the network kernels worked on; nn_rows - this = rows served by the evaluation cache */
-  int64_t steps_cut;         /* ca_config.step_budget: game steps of the last ca_trainer_run that stopped at their budget and went on in the next iteration */
+  int64_t steps_cut;         /* ca_config.step_budget: game steps of the generation (since ca_trainer_reset, over every ca_trainer_run) that stopped at their budget and went on in the next iteration */
   int64_t step_budget_last;  /* the budget (microseconds) the first pool's last launch worked under; 0 = none */
 } ca_stats;
 int ca_trainer_stats(ca_trainer *t, ca_stats *out);

@@ -348,3 +348,120 @@ def test_step_budget_changes_nothing_but_the_iterations(engine):
     for g in range(G):
         assert np.array_equal(t.trace(g), o.trace(g)), g
     assert all(x.tobytes() == y.tobytes() for x, y in zip(H.get_samples(t), H.get_samples(o)))
+
+
+# A pool of 256 or more games in which every game stops at its budget in the same iteration: no rows, all games running.
+# The host must not take a run of such iterations for the reference's "No requests during training" (it did: a count of the
+# holding games in 8 bits of the pool's pack word read 256 of them as none, and 17 polls in a row on that phase ended the run).
+# 1600 simulations of 16 per step at a budget of one scan (the emulation build) or one microsecond (the device): a move lasts
+# ~270 iterations, a step ~4, and the polled iteration lands on the all-holding phase window after window.
+_WRAP_CASES = [pytest.param("emu", 256, 1, id="emu-256x1"), pytest.param("emu", 512, 2, id="emu-512x2")] + [
+    pytest.param("hip", G, pools, marks=pytest.mark.gpu, id="hip-%dx%d" % (G, pools))
+    for G, pools in ((256, 1), (512, 2), (1024, 1), (4096, 4))]
+
+
+@pytest.mark.parametrize("engine,G,pools", _WRAP_CASES)
+def test_step_budget_with_every_game_of_a_pool_holding(engine, G, pools):
+    t = make_trainer(engine, G, "", 31, 1600, 16, 1.0, 0.25, 0, 1, False, stagger=False, pools=pools, step_budget=1)
+    t.set_net(1, nets.init_mlp12x100(seed=3, bn_noise=True))
+    assert not t.run(max_iterations=400)
+    st = t.stats()
+    assert st["pools"] == pools
+    assert st["iterations"] == 400
+    assert st["steps_cut"] > 0
+    t.close()
+
+
+# Whole generations at the pool sizes around the fused pack word's field widths, every step after its first group cut:
+# bit for bit the unlimited run's games.
+@pytest.mark.parametrize("G,pools", [(255, 1), (256, 1), (257, 1), (512, 2)])
+def test_step_budget_of_one_scan_at_pool_size_boundaries(G, pools):
+    S_, spe, seed = 64, 16, 31
+    w = nets.init_mlp12x100(seed=3, bn_noise=True)
+    runs = {}
+    for budget in (-1, 1):
+        t = make_trainer("emu", G, "", seed, S_, spe, 1.0, 0.25, 0, 1, False, stagger=False, trace=True, pools=pools,
+                         step_budget=budget)
+        t.set_net(1, w)
+        assert t.run()
+        st = t.stats()
+        assert st["pools"] == pools
+        assert st["nn_rows"] == st["evals"]
+        runs[budget] = (_digest(t, G), [t.trace(g).tobytes() for g in range(G)], st)
+        t.close()
+    assert runs[1][0] == runs[-1][0]
+    assert runs[1][1] == runs[-1][1]
+    assert runs[1][2]["iterations"] > runs[-1][2]["iterations"]
+    assert runs[1][2]["steps_cut"] > 0 and runs[-1][2]["steps_cut"] == 0
+
+
+@pytest.mark.gpu
+def test_512_game_generation_with_every_step_cut_whole_on_the_oracle():
+    """cfg4's setting (1600 sims/move, Dirichlet noise, seed 4321, the bench's network) on two pools of 256 games with a
+    budget of one microsecond: the same games as the unlimited run, and every game on the oracle"""
+    import time
+
+    from corintho_ai_amd import NET_RESCNN4_H3
+    from tests.test_configs_gpu import _replay_whole_generation
+
+    G, S_, spe, seed = 512, 1600, 16, 4321
+    w = nets.init_rescnn4(0)
+    runs = {}
+    for budget in (-1, 1):
+        t0 = time.time()
+        t = make_trainer("hip", G, "", seed, S_, spe, 1.0, 0.25, 0, 1, False, stagger=False, trace=True, pools=2, step_budget=budget)
+        t.set_net(NET_RESCNN4_H3, w)
+        assert t.run()
+        st = t.stats()
+        assert st["pools"] == 2 and st["nn_rows"] == st["evals"] > 0
+        runs[budget] = (_digest(t, G), [t.trace(g).tobytes() for g in range(G)], st, t)
+        print("budget %d: %d iterations, %d steps cut, %.1f s" % (budget, st["iterations"], st["steps_cut"], time.time() - t0))
+    assert runs[1][0] == runs[-1][0]
+    assert runs[1][1] == runs[-1][1]
+    assert runs[-1][2]["steps_cut"] == 0 and runs[1][2]["steps_cut"] > 0
+    assert runs[1][2]["iterations"] >= 2 * runs[-1][2]["iterations"]
+    t0 = time.time()
+    _replay_whole_generation(runs[1][3], G, S_, spe, seed)
+    print("oracle replay: %.1f s" % (time.time() - t0))
+
+
+# ca_stats.steps_cut counts per generation, like `iterations`: over a generation played in capped pieces it is the whole
+# generation's count, and a reset sets it back to 0.
+@pytest.mark.parametrize("engine", ENGINES)
+def test_steps_cut_over_a_generation_played_in_pieces(engine):
+    G, S_, spe, seed = 24, 60, 8, 31
+    budget = 3 if engine == "emu" else 1  # emulation build: scans (deterministic); device: microseconds
+    w = nets.init_mlp12x100(seed=3, bn_noise=True)
+    whole = make_trainer(engine, G, "", seed, S_, spe, 1.0, 0.25, 0, 1, False, stagger=False, trace=True, step_budget=budget)
+    whole.set_net(1, w)
+    assert whole.run()
+    want, want_cut = _digest(whole, G), whole.stats()["steps_cut"]
+    traces = [whole.trace(g).tobytes() for g in range(G)]
+    assert want_cut > 0
+    t = make_trainer(engine, G, "", seed, S_, spe, 1.0, 0.25, 0, 1, False, stagger=False, trace=True, step_budget=budget)
+    t.set_net(1, w)
+    cuts = [t.stats()["steps_cut"]]
+    assert cuts[0] == 0
+    pieces = 0
+    while not t.run(max_iterations=7):
+        cuts.append(t.stats()["steps_cut"])
+        pieces += 1
+        assert pieces < 1000
+    cuts.append(t.stats()["steps_cut"])
+    assert pieces > 2
+    assert all(a <= b for a, b in zip(cuts, cuts[1:])), cuts
+    assert _digest(t, G) == want
+    assert [t.trace(g).tobytes() for g in range(G)] == traces
+    if engine == "emu":
+        assert cuts[-1] == want_cut
+    t.reset(seed)
+    st = t.stats()
+    assert st["steps_cut"] == 0 and st["step_budget_last"] == 0 and st["iterations"] == 0
+    assert t.run()
+    assert _digest(t, G) == want
+    if engine == "emu":
+        assert t.stats()["steps_cut"] == want_cut
+    else:
+        assert t.stats()["steps_cut"] > 0
+    whole.close()
+    t.close()
