@@ -50,33 +50,13 @@ struct EngineError : std::runtime_error {
   EngineError(int c, const std::string &m) : std::runtime_error(m), code(c) {}
 };
 
-extern "C" int ca_device_check(int device) {
-#ifdef CO_EMU
-  (void)device;
-  return CA_OK;
-#else
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= device) {
-    g_last_error = "no HIP device " + std::to_string(device) + " visible";
-    return CA_ERR_DEVICE;
-  }
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
-    g_last_error = "hipGetDeviceProperties failed";
-    return CA_ERR_DEVICE;
-  }
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
-    g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-    return CA_ERR_DEVICE;
-  }
-  return CA_OK;
-#endif
-}
-
 template <typename T>
 struct DevBuf {
   T *p = nullptr;
   size_t n = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept { return std::swap(p, o.p), std::swap(n, o.n), *this; }
   void alloc(size_t count, rt_stream_t s) { /* zeroed, the clear queued on s (rt.h) */
     release();
     n = count;
@@ -90,40 +70,39 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
-#define CO_MAX_POOLS 4
-#ifndef CO_POOL_POLL
-#define CO_POOL_POLL 16 /* fused training: iterations between polls of a pool's counter (round 5, three pools: 4 / 8 / 16 / 32 / 64 = 134.4 / 131.6 / 130.0 / 129.8 / 130.0 ms per mlp12x100 generation, 395.0 / 393.6 / 391.9 / 391.8 / 392.9 with rescnn4) */
-#endif
-
-/* one independent slice of the games in fused training (run_pools) */
-struct Pool {
-  /* (every handle starts null: a pool whose set-up failed half way is torn down like any other) */
-  rt_stream_t st = {};
-  int lo = 0, n = 0, row_base = 0;
-  bool finished = false;
-  int idle = 0;
-  int running = 0; /* games of the pool still running at its last poll */
-  rt_event_t ev[2][4] = {}; /* per window parity: start / after search / after cache probe / after network of the TIMED iteration */
-  rt_event_t polled[2] = {};
-  int launched[2] = {0, 0};  /* iterations queued in the window of that parity */
-  int word_iter[2] = {0, 0}; /* Trainer::searches_done_ of the iteration whose counter word was copied */
-  int first_start = 0;       /* iteration at which the stagger releases the pool's first game (trainer.cpp:184-186) */
-  int timed[2] = {0, 0};     /* the window's last iteration carries the events */
-  unsigned long long *word = nullptr; /* pinned: [parity] counter word copied at the end of window parity 0 / 1, [2 + parity] rows the
-                             * network evaluated in that iteration (evaluation cache), [4 + parity] the pool's steps cut so far
-                             * (work_counter[CO_WC_CUTS]) */
-  unsigned long long cuts_seen = 0; /* that count at the last window collected (at the start of the run: read when it began) */
-  /* the pool's view of the evaluation cache (EvalCache).  The table (c_hdr, c_val, c_done) is ONE for the trainer and
-   * belongs to pool 0 -- the other pools hold copies of the pointers, not buffers of their own */
-  EvalCache cache = {};
-  uint32_t *c_hdr = nullptr, *c_count = nullptr, *c_done = nullptr;
-  float *c_val = nullptr;
-  int32_t *c_in_idx = nullptr, *c_out_idx = nullptr;
-  unsigned long long *c_totals = nullptr;
-  size_t c_entries = 0;
-  double c_inserted_est = 0; /* entries taken since the table was last emptied (estimate: timed iteration x window) */
-  rt_event_t quiet = {};     /* emptying the shared table: the pool's stream has reached the iteration boundary */
+template <typename H, void (*Destroy)(H)>
+struct RtHandle {
+  H h = {};
+  RtHandle() = default;
+  RtHandle(RtHandle &&o) noexcept : h(o.h) { o.h = H{}; }
+  RtHandle &operator=(RtHandle &&o) noexcept { return std::swap(h, o.h), *this; }
+  ~RtHandle() { Destroy(h); }
+  operator H() const { return h; }
 };
+struct Stream : RtHandle<rt_stream_t, rt_stream_destroy> {
+  void create() { rt_stream_create(&h); }
+#ifdef CO_EXP_CU_MASK
+  void create_masked(int p, int n, int mode) { rt_stream_create_masked(&h, p, n, mode); }
+#endif
+};
+struct Event : RtHandle<rt_event_t, rt_event_destroy> {
+  void create() { rt_event_create(&h); }
+};
+template <typename T>
+struct Pinned : RtHandle<void *, rt_host_free> { /* page-locked host memory */
+  void alloc(size_t count) {
+    rt_host_alloc(&h, count * sizeof(T));
+    memset(h, 0, count * sizeof(T));
+  }
+  T &operator[](size_t i) const { return ((T *)h)[i]; }
+};
+
+/* the search kernel (K3) over slots [pool_lo, pool_lo + n) of e */
+static void launch_mcts_step(const EngineParams &e, int n, rt_stream_t s) {
+  RT_LAUNCH(co_k_mcts_step, (n + CO_K3_WAVES - 1) / CO_K3_WAVES, CO_WAVE * CO_K3_WAVES, s, e);
+}
+
+#include "pools.h"
 
 struct ca_trainer {
   ca_config cfg;
@@ -131,8 +110,8 @@ struct ca_trainer {
   int R = 0;          /* slots of the pool = games resident at a time; R < G: slots are recycled (EngineParams::results) */
   bool recycle = false;
   uint32_t cap_units = 0;
-  rt_stream_t stream = {};
-  EngineParams P;
+  Stream stream;
+  EngineParams P; /* what stays fixed between runs; a launch takes its own copy (params) */
   DevBuf<GameCtl> games;
   DevBuf<TreeCtl> trees;
   DevBuf<uint4> arena, pend_key;
@@ -151,7 +130,7 @@ struct ca_trainer {
   DevBuf<GameCtl> results;   /* [G] finished games by index (recycling pools) */
   DevBuf<uint32_t> seeds_dev; /* [G] per-game generator seeds (recycling pools) */
   DevBuf<int32_t> ctl;
-  int32_t *h_ctl = nullptr; /* pinned: {batch rows, all done, any error, games not done} of the last scan */
+  Pinned<int32_t> h_ctl; /* {batch rows, all done, any error, games not done} of the last scan */
   /* buffers of the host-facing calls, kept (and grown on demand) instead of allocated per call */
   DevBuf<int32_t> ws_off, fw_rows;
   DevBuf<float> ws_gs, ws_ev, ws_pr, fw_in70, fw_in, fw_ev, fw_pr;
@@ -187,7 +166,7 @@ struct ca_trainer {
   }
 
   /* tournament mode (ca_tourney): per-match players, per-match seeds, the reference's read offsets */
-  bool tourney = false;
+  bool tourney = false, exact_offsets = false;
   std::vector<PlayerCfg> host_pcfg; /* [2G] */
   std::vector<uint32_t> match_seeds; /* [G] */
   DevBuf<PlayerCfg> pcfg;
@@ -200,28 +179,10 @@ struct ca_trainer {
   std::vector<uint32_t> an_seed;  /* [G] */
   std::vector<int32_t> an_pre;    /* [G] Node result of a position that is terminal as given, else 0 */
 
+  CacheTable table; /* fused training with the evaluation cache (entries 0: none) */
   std::vector<Pool> pools;
-  void free_pools() {
-    for (auto &q : pools) {
-      for (int w = 0; w < 2; ++w) {
-        for (auto &e : q.ev[w]) rt_event_destroy(e);
-        rt_event_destroy(q.polled[w]);
-      }
-      rt_host_free(q.word);
-      rt_event_destroy(q.quiet);
-      const bool owner = &q == &pools[0]; /* the shared table is pool 0's */
-      for (void *b : {owner ? (void *)q.c_hdr : nullptr, (void *)q.c_count, owner ? (void *)q.c_val : nullptr, (void *)q.c_in_idx,
-                      (void *)q.c_out_idx, (void *)q.c_totals, owner ? (void *)q.c_done : nullptr})
-        rt_free(b);
-      rt_stream_destroy(q.st);
-    }
-    pools.clear();
-  }
   ~ca_trainer() {
-    free_pools();
     for (auto &r : host_regs) rt_host_unregister(r.first);
-    rt_host_free(h_ctl);
-    rt_stream_destroy(stream);
   }
 
   template <typename T>
@@ -255,8 +216,20 @@ struct ca_trainer {
       }
   }
 
-  void init(const ca_config &c) {
+  /* a tournament's trainer (ca_tourney): one match per game */
+  struct TourneySetup {
+    std::vector<PlayerCfg> players; /* [2G] both sides of every match */
+    std::vector<uint32_t> seeds;    /* [G] */
+    bool exact_offsets;             /* ca_tourney_set_exact_offsets */
+  };
+  void init(const ca_config &c, const TourneySetup *tour = nullptr) {
     cfg = c;
+    if (tour) {
+      tourney = true;
+      host_pcfg = tour->players;
+      match_seeds = tour->seeds;
+      exact_offsets = tour->exact_offsets;
+    }
     if (cfg.analyse) {
       cfg.testing = 1;    /* trainmc.cpp:43 */
       cfg.no_stagger = 1;
@@ -268,7 +241,7 @@ struct ca_trainer {
     G = cfg.num_games;
     spe = cfg.searches_per_eval;
     rt_set_device(cfg.device);
-    rt_stream_create(&stream);
+    stream.create();
     uint32_t cap = cfg.arena_units;
     if (cap == 0) {
       /* a tree gains at most one node per simulation on its own turns; a node is
@@ -319,7 +292,7 @@ struct ca_trainer {
     row_idx.alloc((size_t)R * spe, stream);
     nn_in70.alloc((size_t)R * spe * CO_GAME_STATE_SIZE, stream);
     ctl.alloc(4, stream);
-    rt_host_alloc((void **)&h_ctl, 16);
+    h_ctl.alloc(4);
     nn_eval.alloc((size_t)R * spe, stream);
     nn_probs.alloc((size_t)R * spe * CO_NUM_MOVES, stream);
     if (!cfg.testing) samples.alloc((size_t)G * CO_MAX_PLIES * CO_SAMPLE_FLOATS, stream); /* by game */
@@ -520,7 +493,7 @@ struct ca_trainer {
     P.trace_on = cfg.trace;
     P.analyse = cfg.analyse;
     P.pcfg = tourney ? pcfg.p : nullptr;
-    P.read_offset = tourney ? read_offset.p : nullptr;
+    P.read_offset = tourney && !exact_offsets ? read_offset.p : nullptr; /* exact: co_step_row reads the writeRequests rows */
     P.arena_state = nullptr;
     P.scan_phase = 0;
     P.games = games.p;
@@ -569,13 +542,22 @@ struct ca_trainer {
 #endif
   }
 
+  /* the engine parameters of one launch for model `to_play` (-1: every game) at the current iteration; the launch site
+   * sets whatever else is its own (fused pools, the arena's device state, force_choose) on its copy */
+  EngineParams params(int to_play) const {
+    EngineParams e = P;
+    e.to_play = to_play;
+    e.iteration = trainer_iteration;
+    return e;
+  }
+
   /* offsets + compact batch for model `to_play` (K4); ONE host synchronisation, on 16 bytes */
   bool any_error = false;
   void pack(int to_play) {
     if (scan_valid && scan_valid_for == to_play) return;
-    P.to_play = to_play;
-    RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, P);
-    RT_LAUNCH(co_k_compact, R, CO_WAVE, stream, P);
+    const EngineParams e = params(to_play);
+    RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, e);
+    RT_LAUNCH(co_k_compact, R, CO_WAVE, stream, e);
     rt_d2h(h_ctl, ctl.p, 16, stream);
     rt_sync(stream);
     last_total = h_ctl[0];
@@ -647,9 +629,7 @@ struct ca_trainer {
     } else {
       rt_memset(req_offset.p, 0, ((size_t)R + 1) * 4, stream);
     }
-    P.to_play = to_play;
-    P.iteration = trainer_iteration;
-    RT_LAUNCH(co_k_mcts_step, ((R) + CO_K3_WAVES - 1) / CO_K3_WAVES, CO_WAVE * CO_K3_WAVES, stream, P);
+    launch_mcts_step(params(to_play), R, stream);
     if (to_play == -1) ++trainer_iteration;
     ++iterations;
     ++mcts_launches;
@@ -691,14 +671,13 @@ struct ca_trainer {
   void tourney_do_iteration(const float *evals, const float *probs, int32_t rows, int id) {
     size_t cap = (size_t)R * spe;
     if (rows < 0 || (size_t)rows > cap) rows = (int32_t)cap;
-    P.to_play = id;
-    RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, P); /* offsets at entry */
+    const EngineParams e = params(id);
+    RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, e); /* offsets at entry */
     if (rows > 0 && evals && probs) {
       rt_h2d(nn_eval.p, evals, (size_t)rows * 4, stream);
       rt_h2d(nn_probs.p, probs, (size_t)rows * CO_NUM_MOVES * 4, stream);
     }
-    P.iteration = trainer_iteration;
-    RT_LAUNCH(co_k_mcts_step, ((R) + CO_K3_WAVES - 1) / CO_K3_WAVES, CO_WAVE * CO_K3_WAVES, stream, P);
+    launch_mcts_step(e, R, stream);
     ++iterations;
     ++mcts_launches;
     scan_valid = false;
@@ -711,6 +690,28 @@ struct ca_trainer {
     for (int g = 0; g < G; ++g)
       if (!host_games[g].done) return false;
     return true;
+  }
+  /* one round of ca_tourney::run for model `id`: its requests packed (Tourney::writeRequests), evaluated by `net`, its
+   * matches iterated (Tourney::doIteration); a random player's dummy id (< 0) has nothing to evaluate */
+  void tourney_round(int id, CoNet *net) {
+    const EngineParams e = params(id);
+    RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, e); /* offsets + batch of model `id` */
+    if (id >= 0) {
+      RT_LAUNCH(co_k_compact, G, CO_WAVE, stream, e);
+      net->forward(nn_in.p, G * spe, req_offset.p + G, nn_eval.p, nn_probs.p, stream);
+      ++nn_launches;
+    }
+    launch_mcts_step(e, G, stream);
+    ++mcts_launches;
+    ++iterations;
+  }
+  /* the all-done flag, refreshed by a scan for model `id` */
+  bool tourney_poll_done(int id) {
+    RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, params(id));
+    int32_t d = 0;
+    rt_d2h(&d, all_done.p, 4, stream);
+    rt_sync(stream);
+    return d != 0;
   }
 
   int32_t num_samples() {
@@ -915,11 +916,9 @@ struct ca_trainer {
   void finish_analysis() {
     if (!cfg.analyse) throw EngineError(CA_ERR_STATE, "ca_trainer_finish: not an analysis trainer");
     if (iterations == 0) do_iteration(nullptr, nullptr, -1);
-    P.to_play = -1;
-    P.iteration = trainer_iteration;
-    P.force_choose = 1;
-    RT_LAUNCH(co_k_mcts_step, ((R) + CO_K3_WAVES - 1) / CO_K3_WAVES, CO_WAVE * CO_K3_WAVES, stream, P);
-    P.force_choose = 0;
+    EngineParams e = params(-1);
+    e.force_choose = 1;
+    launch_mcts_step(e, R, stream);
     ++mcts_launches;
     scan_valid = false;
     host_games_valid = false;
@@ -942,14 +941,17 @@ struct ca_trainer {
        * pools, and in the middle of a generation the pending leaves point into them (pend_src): refuse that. */
       std::unique_ptr<CoNet> old = std::move(nets[0]);
       nets[0] = std::move(fresh);
-      const bool toggles = (pools[0].cache.hdr != nullptr) != use_cache();
+      const bool toggles = (table.entries != 0) != use_cache();
       if (toggles && iterations > 0 && !finished) {
         nets[0] = std::move(old);
         throw EngineError(CA_ERR_STATE, "ca_trainer_set_net: this network turns the evaluation cache " +
-                                            std::string(pools[0].cache.hdr ? "off" : "on") +
+                                            std::string(table.entries ? "off" : "on") +
                                             " in the middle of a generation; finish or reset the generation first");
       }
-      if (toggles) free_pools(); /* rebuilt with / without tables */
+      if (toggles) { /* rebuilt with / without the table */
+        pools.clear();
+        table.release();
+      }
     } else {
       nets[slot] = std::move(fresh);
     }
@@ -1002,109 +1004,60 @@ struct ca_trainer {
     nets[slot]->forward(d_in, rows_cap, d_rows, d_eval, d_probs, stream);
   }
 
-  /* the pools of a fused run: streams, events, the host words the counters are copied to, and -- with the evaluation
-   * cache -- ONE table for all of them plus every pool's index and counter arrays */
+  /* the pools of a fused run (pools.h) and, with the evaluation cache, ONE table for all of them */
   void pools_create(int npools) {
-    free_pools();
+    pools.clear();
+    table.release(); /* (before the new table is sized by the free device memory) */
     pools.resize(npools);
     for (int p = 0; p < npools; ++p) {
       Pool &q = pools[p];
-#ifdef CO_EXP_CU_MASK /* diagnostic build (profiles/r06_coresident.md): every pool's stream on its own share of the compute units */
-      rt_stream_create_masked(&q.st, p, npools, CO_EXP_CU_MASK);
-#else
-      rt_stream_create(&q.st);
-#endif
-      q.lo = (int)((int64_t)R * p / npools);
-      q.n = (int)((int64_t)R * (p + 1) / npools) - q.lo;
-      q.row_base = q.lo * spe;
-      for (int w = 0; w < 2; ++w) {
-        for (auto &e : q.ev[w]) rt_event_create(&e);
-        rt_event_create(&q.polled[w]);
-      }
-      rt_host_alloc((void **)&q.word, 48);
-      memset(q.word, 0, 48);
-      memset(&q.cache, 0, sizeof q.cache);
-      rt_event_create(&q.quiet);
+      q.create(p, npools, R, spe);
       if (use_cache()) {
-        if (p == 0) {
-          /* ONE table for all pools: a power of two of at least 8192 entries per slot (a 4096-game generation at 400
-           * simulations asks for ~4100 distinct positions per game), within 1/6 of the free device memory */
-          size_t want = (size_t)R * 8192, n = 1;
-          while (n < want) n <<= 1;
-          const size_t per = 16 + CO_CACHE_VAL_FLOATS * 4;
-          while (n > 1024 && n * per > rt_mem_free() / 6) n >>= 1;
-          if (cfg.eval_cache > 0) { /* given */
-            n = (size_t)1 << (cfg.eval_cache < 6 ? 6 : cfg.eval_cache > 30 ? 30 : cfg.eval_cache);
-            if (n * per > rt_mem_free() / 2)
-              throw EngineError(CA_ERR_ARG, "ca_config.eval_cache: a table of 2^" + std::to_string(cfg.eval_cache) +
-                                                " entries does not fit in the free device memory");
-          }
-          q.c_entries = n;
-          rt_malloc((void **)&q.c_hdr, n * 16, q.st);
-          /* table values + one scratch element per request row of every pool */
-          rt_malloc((void **)&q.c_val, (n + (size_t)R * spe) * CO_CACHE_VAL_FLOATS * 4, q.st);
-          rt_malloc((void **)&q.c_done, 4 * CO_MAX_POOLS, q.st);
-        } else {
-          q.c_entries = pools[0].c_entries;
-          q.c_hdr = pools[0].c_hdr;
-          q.c_val = pools[0].c_val;
-          q.c_done = pools[0].c_done;
-        }
-        const size_t rows = (size_t)q.n * spe;
-        rt_malloc((void **)&q.c_in_idx, rows * 4, q.st);
-        rt_malloc((void **)&q.c_out_idx, rows * 4, q.st);
-        rt_malloc((void **)&q.c_count, 32, q.st);
-        rt_malloc((void **)&q.c_totals, 16, q.st);
-        q.cache.hdr = q.c_hdr;
-        q.cache.val = q.c_val;
-        q.cache.mask = (uint32_t)(q.c_entries - 1);
-        q.cache.scratch_base = (uint32_t)q.row_base;
-        q.cache.pool_bits = (uint32_t)p << CO_CACHE_POOL_SHIFT;
-        q.cache.done = q.c_done;
-        q.cache.in_idx = q.c_in_idx;
-        q.cache.out_idx = q.c_out_idx;
-        q.cache.count = q.c_count;
-        q.cache.totals = q.c_totals;
-        rt_sync(q.st);
+        if (p == 0) table.create(cfg.eval_cache, R, spe, q.st);
+        q.attach(table, p, spe);
       }
     }
     cache_clean = true; /* freshly zeroed */
+  }
+
+  /* the pools' work-counter words (EngineParams::work_counter) as the device holds them now */
+  std::vector<unsigned long long> read_work_counters() {
+    std::vector<unsigned long long> wc((size_t)CO_WC_WORDS * CO_MAX_POOLS);
+    rt_d2h(wc.data(), work_counter.p, wc.size() * 8, stream);
+    rt_sync(stream);
+    return wc;
+  }
+
+  /* device time by kernel family, estimated from the timed launches; with_pack: the fused pools' cache probe too (the
+   * arena books its compaction directly) */
+  void estimate_device_times(bool with_pack) {
+    if (timed_launches == 0) return;
+    mcts_ms = mcts_timed_ms * (double)mcts_launches / (double)timed_launches;
+    nn_ms = nn_timed_ms * (double)nn_launches / (double)timed_launches;
+    if (with_pack) pack_ms = pack_timed_ms * (double)nn_launches / (double)timed_launches;
   }
 
   /* a run starts: an emptied table when the generation does (or a new network came), the pools' host-side state.
    * Returns whether the table was emptied here. */
   bool pools_begin_run() {
     const bool cache_clean_now = use_cache() && !cache_clean;
-    if (use_cache() && !cache_clean) {
+    if (cache_clean_now) {
       /* a generation starts with an empty table: nothing evaluated in an earlier generation is carried over */
+      table.empty(pools[0].st, true);
       for (auto &q : pools) {
-        if (&q == &pools[0]) {
-          rt_memset(q.c_hdr, 0, q.c_entries * 16, q.st);
-          rt_memset(q.c_done, 0, 4 * CO_MAX_POOLS, q.st); /* (the iteration count starts again with the generation) */
-        }
         if (iterations == 0) { /* (in mid-generation -- a new network, set_net -- the rows evaluated so far stay counted: ADVICE round 4) */
-          rt_memset(q.c_count, 0, 32, q.st);
-          rt_memset(q.c_totals, 0, 16, q.st);
+          rt_memset(q.count.p, 0, 32, q.st);
+          rt_memset(q.totals.p, 0, 16, q.st);
         }
         rt_sync(q.st);
+        q.c_inserted_est = 0;
       }
       cache_clean = true;
     }
     /* the steps cut so far (a run that resumes a generation: not zero), what the first window of each pool is compared with */
-    std::vector<unsigned long long> wc((size_t)CO_WC_WORDS * CO_MAX_POOLS);
-    rt_d2h(wc.data(), work_counter.p, wc.size() * 8, stream);
-    rt_sync(stream);
-    for (auto &q : pools) {
-      q.cuts_seen = wc[CO_WC_WORDS * (&q - &pools[0]) + CO_WC_CUTS];
-      q.finished = false;
-      q.running = q.n;
-      q.idle = 0;
-      q.launched[0] = q.launched[1] = 0;
-      q.timed[0] = q.timed[1] = 0;
-      q.word_iter[0] = q.word_iter[1] = 0;
-      q.first_start = P.stagger_div > 0 ? (P.game_base + q.lo) / P.stagger_div : 0;
-      if (cache_clean_now) q.c_inserted_est = 0;
-    }
+    const std::vector<unsigned long long> wc = read_work_counters();
+    for (auto &q : pools)
+      q.begin_run(wc[CO_WC_WORDS * (&q - &pools[0]) + CO_WC_CUTS], P.stagger_div > 0 ? (P.game_base + q.lo) / P.stagger_div : 0);
     return cache_clean_now;
   }
 
@@ -1150,11 +1103,7 @@ struct ca_trainer {
   /* a run is over (its streams are drained): device times from the timed launches, errors, the rows evaluated, the step
    * budget's statistics */
   void pools_finish_run(const std::string &failure) {
-    if (timed_launches > 0) {
-      /* device time by kernel family, estimated from the timed launches */
-      mcts_ms = mcts_timed_ms * (double)mcts_launches / (double)timed_launches;
-      nn_ms = nn_timed_ms * (double)nn_launches / (double)timed_launches;
-    }
+    estimate_device_times(true);
     if (!failure.empty()) throw EngineError(CA_ERR_ENGINE, failure);
     pack(-1); /* refresh the done flag and the batch description */
     check_errors();
@@ -1168,30 +1117,25 @@ struct ca_trainer {
         /* booked by the probe kernels, plus the two iterations whose counters nobody has booked yet (at most one is non-zero) */
         unsigned long long tot[2] = {0, 0};
         uint32_t cnt[8] = {0};
-        rt_d2h(tot, q.c_totals, 16, q.st);
-        rt_d2h(cnt, q.c_count, 32, q.st);
+        rt_d2h(tot, q.totals.p, 16, q.st);
+        rt_d2h(cnt, q.count.p, 32, q.st);
         rt_sync(q.st);
         nn_rows_evaluated += (int64_t)tot[0] + cnt[0] + cnt[4];
       }
     }
-    {
-      /* step budget: a pool's word CO_WC_CUTS counts the steps that were cut, CO_WC_BUDGET + {0, 1} hold the last two budgets */
-      std::vector<unsigned long long> wc((size_t)CO_WC_WORDS * CO_MAX_POOLS);
-      rt_d2h(wc.data(), work_counter.p, wc.size() * 8, stream);
-      rt_sync(stream);
-      steps_cut = 0;
-      for (size_t p = 0; p < pools.size(); ++p) steps_cut += (int64_t)wc[CO_WC_WORDS * p + CO_WC_CUTS];
-      step_budget_last = P.step_budget > 0 ? P.step_budget : (int64_t)std::max(wc[CO_WC_BUDGET], wc[CO_WC_BUDGET + 1]) / CO_STEP_UNITS_PER_CONFIG_UNIT;
-    }
-    if (timed_launches > 0) pack_ms = pack_timed_ms * (double)nn_launches / (double)timed_launches;
+    /* step budget: a pool's word CO_WC_CUTS counts the steps that were cut, CO_WC_BUDGET + {0, 1} hold the last two budgets */
+    const std::vector<unsigned long long> wc = read_work_counters();
+    steps_cut = 0;
+    for (size_t p = 0; p < pools.size(); ++p) steps_cut += (int64_t)wc[CO_WC_WORDS * p + CO_WC_CUTS];
+    step_budget_last = P.step_budget > 0 ? P.step_budget : (int64_t)std::max(wc[CO_WC_BUDGET], wc[CO_WC_BUDGET + 1]) / CO_STEP_UNITS_PER_CONFIG_UNIT;
   }
 
   /* The table is half full: start over (returns true).  Between two iterations of EVERY pool, when no entry is pending. */
   bool cache_empty_when_half_full(int npools) {
-    if (!pools[0].cache.hdr) return false;
+    if (!table.entries) return false;
     double taken = 0;
     for (auto &q : pools) taken += q.c_inserted_est;
-    if (taken > 0.5 * (double)pools[0].c_entries) {
+    if (taken > 0.5 * (double)table.entries) {
       /* the table is half full: start over (a long generation asks for far more positions than any table holds;
        * what is asked for again is mostly recent -- the trees of the games in play).  Between two iterations of
        * EVERY pool, when no entry is pending: each stream has the same iterations queued at this point; pool 0's
@@ -1200,7 +1144,7 @@ struct ca_trainer {
         rt_event_record(pools[p].quiet, pools[p].st);
         rt_stream_wait(pools[0].st, pools[p].quiet);
       }
-      rt_memset(pools[0].c_hdr, 0, pools[0].c_entries * 16, pools[0].st);
+      table.empty(pools[0].st, false);
       rt_event_record(pools[0].quiet, pools[0].st);
       for (int p = 1; p < npools; ++p) rt_stream_wait(pools[p].st, pools[0].quiet);
       for (auto &q : pools) q.c_inserted_est = 0;
@@ -1212,11 +1156,11 @@ struct ca_trainer {
 
   /* one iteration of pool p on its stream: the search launch (with the step's share of the engine parameters: the pool's
    * slice, its counters, the evaluation cache's claim rules) and the network launch behind it; `timed`: with HIP events */
-  void pool_queue_iteration(int p, int npools, bool emptied, long long &guard_from, int poll, int parity, int in_window, bool timed) {
+  void pool_queue_iteration(const EngineParams &run_params, int p, int npools, bool emptied, long long &guard_from, int poll,
+                            int parity, int in_window, bool timed) {
     Pool &q = pools[p];
     if (q.finished) return;
-    EngineParams pp = P;
-    pp.iteration = trainer_iteration;
+    EngineParams pp = run_params;
     /* Deferring the new mover's first searches to the next step (mcts.h co_game_step) balances
      * the waves of a full launch but costs the game one more iteration per ply; once the pool
      * has thinned out, an iteration is as long as its slowest wave anyway and the number of
@@ -1250,9 +1194,9 @@ struct ca_trainer {
      * then not launched at all and the small-batch kernel's grid shrinks -- a launch whose workgroups all leave at
      * once still costs their dispatch (for the pixel-major kernel: one 160 KB LDS allocation per 32 rows of capacity). */
     const int cap_rows = (q.running < q.n ? (q.running > 0 ? q.running : 1) : q.n) * spe;
-    rt_event_t *e = q.ev[parity];
+    Event *e = q.ev[parity];
     if (timed) rt_event_record(e[0], q.st);
-    RT_LAUNCH(co_k_mcts_step, ((q.n) + CO_K3_WAVES - 1) / CO_K3_WAVES, CO_WAVE * CO_K3_WAVES, q.st, pp);
+    launch_mcts_step(pp, q.n, q.st);
     if (timed) rt_event_record(e[1], q.st);
     if (q.cache.hdr) {
       /* the search kernel has resolved every request row to an element of the cache's value array; the network
@@ -1260,13 +1204,14 @@ struct ca_trainer {
        * out_idx */
       if (timed) rt_event_record(e[2], q.st);
       CoNetIO io;
-      io.in_idx = q.c_in_idx;
-      io.out_idx = q.c_out_idx;
+      io.in_idx = q.cache.in_idx;
+      io.out_idx = q.cache.out_idx;
       io.eval_stride = CO_CACHE_VAL_FLOATS;
       io.probs_stride = CO_CACHE_VAL_FLOATS;
       io.alone = npools == 1;
       net_used = true;
-      nets[0]->forward(req.p, cap_rows, (const int32_t *)(q.c_count + 4 * (trainer_iteration & 1)), q.c_val, q.c_val + 4, q.st, io);
+      nets[0]->forward(req.p, cap_rows, (const int32_t *)(q.cache.count + 4 * (trainer_iteration & 1)), q.cache.val, q.cache.val + 4,
+                       q.st, io);
       if (timed) rt_event_record(e[3], q.st);
     } else {
       if (timed) rt_event_record(e[2], q.st);
@@ -1293,10 +1238,8 @@ struct ca_trainer {
     if ((int)pools.size() != npools) pools_create(npools);
     const bool cache_clean_now = pools_begin_run();
     rt_sync(stream);
-    P.to_play = -1;
-    P.row_counter = nullptr;
-    P.fused_pack = 1;
-    P.defer_handover = 1;
+    EngineParams run_params = params(-1); /* (the iteration: set per launch) */
+    run_params.fused_pack = 1;
     int64_t it = 0;
     int in_window = 0, window = 0;
     bool all_finished = false;
@@ -1309,8 +1252,9 @@ struct ca_trainer {
       bool emptied = emptied_before_resuming; /* (EvalCache::no_claim) */
       emptied_before_resuming = false;
       if (cache_empty_when_half_full(npools)) emptied = true;
+      run_params.iteration = trainer_iteration;
       for (int p = 0; p < npools; ++p)
-        pool_queue_iteration(p, npools, emptied, guard_from, poll, parity, in_window,
+        pool_queue_iteration(run_params, p, npools, emptied, guard_from, poll, parity, in_window,
                              in_window == poll - 1 || (max_iterations > 0 && it + 1 == max_iterations));
       const int counter_slot = trainer_iteration & 1;
       ++trainer_iteration;
@@ -1321,7 +1265,7 @@ struct ca_trainer {
         for (auto &q : pools) {
           if (q.finished) continue;
           rt_d2h(&q.word[parity], pack_counter.p + CO_PACK_STRIDE * (&q - &pools[0]) + counter_slot, 8, q.st);
-          if (q.cache.hdr) rt_d2h(&q.word[2 + parity], q.c_count + 4 * counter_slot, 4, q.st);
+          if (q.cache.hdr) rt_d2h(&q.word[2 + parity], q.cache.count + 4 * counter_slot, 4, q.st);
           rt_d2h(&q.word[4 + parity], work_counter.p + (size_t)CO_WC_WORDS * (&q - &pools[0]) + CO_WC_CUTS, 8, q.st);
           q.word_iter[parity] = trainer_iteration - 1;
           rt_event_record(q.polled[parity], q.st);
@@ -1344,12 +1288,6 @@ struct ca_trainer {
       rt_sync(q.st);
       for (int w = 0; w < 2; ++w) pool_collect(q, (window + w) & 1, poll, failure);
     }
-    P.fused_pack = 0;
-    P.defer_handover = 0;
-    P.pool_lo = 0;
-    P.pool_n = R;
-    P.pool_row_base = 0;
-    P.pack_counter = pack_counter.p;
     host_games_valid = false;
     scan_valid = false;
     pools_finish_run(failure);
@@ -1375,27 +1313,25 @@ struct ca_trainer {
      * one finds a row count of zero, so the host only looks every eighth iteration.  Requests
      * are packed by K4 in game order (the reference's request order). */
     const int poll = 8;
-    std::vector<rt_event_t> ev(4);
-    for (auto &e : ev) rt_event_create(&e);
-    P.arena_state = arena_state.p;
-    P.row_counter = row_counter.p;
-    P.fused_pack = 0;
-    P.defer_handover = 0;
-    P.to_play = 0;
+    Event ev[4];
+    for (auto &e : ev) e.create();
+    EngineParams e = params(0);
+    e.arena_state = arena_state.p;
+    e.row_counter = row_counter.p;
     int64_t it = 0;
     int32_t st[5] = {0, 0, 0, 0, 0};
     std::string failure;
     while (!finished && (max_iterations <= 0 || it < max_iterations)) {
       const bool timed = (it % poll) == poll - 1 || (max_iterations > 0 && it + 1 == max_iterations);
-      P.iteration = trainer_iteration;
-      P.scan_phase = 0;
-      RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, P); /* offsets at entry (trainer.cpp:208-215) */
+      e.iteration = trainer_iteration;
+      e.scan_phase = 0;
+      RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, e); /* offsets at entry (trainer.cpp:208-215) */
       if (timed) rt_event_record(ev[0], stream);
-      RT_LAUNCH(co_k_mcts_step, ((R) + CO_K3_WAVES - 1) / CO_K3_WAVES, CO_WAVE * CO_K3_WAVES, stream, P);
+      launch_mcts_step(e, R, stream);
       if (timed) rt_event_record(ev[1], stream);
-      P.scan_phase = 1;
-      RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, P);
-      RT_LAUNCH(co_k_compact, R, CO_WAVE, stream, P);
+      e.scan_phase = 1;
+      RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, e);
+      RT_LAUNCH(co_k_compact, R, CO_WAVE, stream, e);
       if (timed) rt_event_record(ev[2], stream);
       net_used = true;
       for (int slot = 0; slot < 2; ++slot) /* get_predictions, main.pyx:74-81 */
@@ -1423,18 +1359,11 @@ struct ca_trainer {
       }
     }
     rt_sync(stream);
-    for (auto &e : ev) rt_event_destroy(e);
     rt_d2h(st, arena_state.p, sizeof st, stream);
     rt_sync(stream);
-    P.arena_state = nullptr;
-    P.scan_phase = 0;
-    P.row_counter = nullptr;
     host_games_valid = false;
     scan_valid = false;
-    if (timed_launches > 0) {
-      mcts_ms = mcts_timed_ms * (double)mcts_launches / (double)timed_launches;
-      nn_ms = nn_timed_ms * (double)nn_launches / (double)timed_launches;
-    }
+    estimate_device_times(false);
     if (!failure.empty()) throw EngineError(CA_ERR_ENGINE, failure);
     pack(st[0]); /* refresh the done flag and the batch description */
     check_errors();
@@ -1447,7 +1376,146 @@ struct ca_trainer {
   }
 };
 
+/* ---- Tourney (tourney.cpp): its matches are the games of one trainer */
+struct ca_tourney {
+  int device = 0;
+  uint32_t arena_units = 0;
+  int trace = 0;
+  std::map<int, PlayerCfg> players;            /* Tourney::players_ (tourney.h:42) */
+  std::vector<std::pair<int, int>> matches;    /* addMatch order */
+  std::vector<char> match_logging;             /* addMatch's `logging` */
+  std::string log_folder;                      /* Tourney::log_folder_ (tourney.h:46) */
+  bool seen_done = false;
+  std::mt19937 generator;                      /* default constructed: seed 5489 (tourney.h:43) */
+  std::vector<uint32_t> seeds;
+  std::unique_ptr<ca_trainer> pool;            /* built at the first query after the last addMatch */
+  struct PendingNet {
+    int kind;
+    std::vector<float> w;
+  };
+  std::map<int, PendingNet> net_specs;         /* fused mode: model id -> network (ca_tourney_set_net) */
+  std::map<int, std::unique_ptr<CoNet>> nets;
+  bool exact_offsets = false;                  /* ca_tourney_set_exact_offsets */
+
+  /* The loop of rating/tourney.pyx:122-160 with the networks on the GPU: for every model id in
+   * ascending order, pack that model's requests (Tourney::writeRequests), evaluate them, iterate
+   * its matches (Tourney::doIteration, which reads the evaluations through the reference's offset
+   * table).  The evaluation arrays persist between rounds like the driver's, so the result is the
+   * one the compat protocol gives with the same networks. */
+  bool run(int64_t max_rounds) {
+    ca_trainer &p = built();
+    std::vector<int> ids;
+    for (auto &m : matches)
+      for (int pid : {m.first, m.second}) {
+        int id = players.at(pid).model_id;
+        if (std::find(ids.begin(), ids.end(), id) == ids.end()) ids.push_back(id);
+      }
+    std::sort(ids.begin(), ids.end());
+    for (int id : ids) {
+      if (id < 0) continue;
+      if (!nets.count(id)) {
+        auto it = net_specs.find(id);
+        if (it == net_specs.end()) throw EngineError(CA_ERR_STATE, "ca_tourney_run: no network for model id " + std::to_string(id));
+        std::unique_ptr<CoNet> n(co_net_create(it->second.kind, it->second.w.data(), it->second.w.size(),
+                                               (size_t)p.G * p.spe, p.stream));
+        if (!n) throw EngineError(CA_ERR_ARG, "unknown net kind or bad weight count");
+        nets[id] = std::move(n);
+      }
+    }
+    int64_t rounds = 0;
+    bool done = p.tourney_all_done();
+    while (!done && (max_rounds <= 0 || rounds < max_rounds)) {
+      for (int id : ids) p.tourney_round(id, id >= 0 ? nets[id].get() : nullptr);
+      ++rounds;
+      /* the host looks at the all-done flag every eighth round only (a round that finds every match
+       * finished launches kernels that return at once), so the queue never runs dry in between */
+      if ((rounds & 7) == 0 || (max_rounds > 0 && rounds >= max_rounds)) done = p.tourney_poll_done(ids.front());
+    }
+    p.scan_valid = false;
+    p.host_games_valid = false;
+    p.check_errors();
+    if (done) all_done(); /* (writes the match logs) */
+    return done;
+  }
+
+  /* Tourney::all_done (tourney.cpp:14-21); the log files of the matches are written the first time it is true */
+  bool all_done() {
+    ca_trainer &p = built();
+    const bool done = p.tourney_all_done();
+    if (done && !seen_done) {
+      seen_done = true;
+      p.maybe_write_logs();
+    }
+    return done;
+  }
+
+  ca_trainer &built() {
+    if (pool) return *pool;
+    if (matches.empty()) throw EngineError(CA_ERR_STATE, "tourney without matches");
+    ca_trainer::TourneySetup setup{{}, seeds, exact_offsets};
+    ca_config c;
+    memset(&c, 0, sizeof c);
+    c.num_games = (int32_t)matches.size();
+    c.device = device;
+    c.testing = 1;
+    c.no_stagger = 1;
+    c.trace = trace;
+    c.arena_units = arena_units;
+    c.c_puct = 1.0f;
+    c.max_searches = 1;
+    c.searches_per_eval = 1;
+    for (auto &m : matches) {
+      for (int side = 0; side < 2; ++side) {
+        const PlayerCfg &p = players.at(side == 0 ? m.first : m.second);
+        setup.players.push_back(p);
+        if (!p.random) {
+          c.max_searches = std::max(c.max_searches, p.max_searches);
+          c.searches_per_eval = std::max(c.searches_per_eval, p.searches_per_eval);
+        }
+      }
+    }
+    auto t = std::make_unique<ca_trainer>();
+    t->init(c, &setup);
+    /* tourney.cpp:83-96: a match added with logging = true writes <log_folder>/match_<p1>_<p2>_<index>.txt */
+    std::vector<int> logged;
+    std::vector<std::string> paths;
+    for (size_t i = 0; i < matches.size(); ++i)
+      if (match_logging[i]) {
+        logged.push_back((int)i);
+        paths.push_back(log_folder + "/match_" + std::to_string(matches[i].first) + "_" + std::to_string(matches[i].second) + "_" +
+                        std::to_string(i) + ".txt");
+      }
+    if (!logged.empty()) t->set_log_records(logged, paths, true);
+    pool = std::move(t);
+    return *pool;
+  }
+};
+
 /* ------------------------------------------------------------------- C ABI */
+extern "C" int ca_device_check(int device) {
+#ifdef CO_EMU
+  (void)device;
+  return CA_OK;
+#else
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= device) {
+    g_last_error = "no HIP device " + std::to_string(device) + " visible";
+    return CA_ERR_DEVICE;
+  }
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
+    g_last_error = "hipGetDeviceProperties failed";
+    return CA_ERR_DEVICE;
+  }
+  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
+    g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
+    return CA_ERR_DEVICE;
+  }
+  return CA_OK;
+#endif
+}
+
+/* Owners of runtime resources: move-only, null until allocated or created, released once by their destructor */
 #define CA_GUARD(...)                     \
   try {                                   \
     __VA_ARGS__;                          \
@@ -1527,142 +1595,135 @@ extern "C" int ca_trainer_set_logging(ca_trainer *t, const char *log_folder, int
   CA_TGUARD(t->set_logging(log_folder, num_logged))
 }
 extern "C" int ca_trainer_reset(ca_trainer *t, int32_t seed) { CA_TGUARD(t->reset_games(seed)) }
-/* ------------------------------------------------------------------ Tourney C ABI */
-struct ca_tourney {
-  int device = 0;
-  uint32_t arena_units = 0;
-  int trace = 0;
-  std::map<int, PlayerCfg> players;            /* Tourney::players_ (tourney.h:42) */
-  std::vector<std::pair<int, int>> matches;    /* addMatch order */
-  std::vector<char> match_logging;             /* addMatch's `logging` */
-  std::string log_folder;                      /* Tourney::log_folder_ (tourney.h:46) */
-  bool seen_done = false;
-  std::mt19937 generator;                      /* default constructed: seed 5489 (tourney.h:43) */
-  std::vector<uint32_t> seeds;
-  std::unique_ptr<ca_trainer> pool;            /* built at the first query after the last addMatch */
-  struct PendingNet {
-    int kind;
-    std::vector<float> w;
-  };
-  std::map<int, PendingNet> net_specs;         /* fused mode: model id -> network (ca_tourney_set_net) */
-  std::map<int, std::unique_ptr<CoNet>> nets;
-  bool exact_offsets = false;                  /* ca_tourney_set_exact_offsets */
+/* diagnostic builds (-DCO_PROF): summed in-kernel cycle stamps, see mcts.h; not in the public header */
+extern "C" int ca_trainer_prof(ca_trainer *t, unsigned long long out[2 * CO_NPROF + 24]) {
+  CA_TGUARD({
+    /* nothing is written to `out` unless this is a stamped build: a caller of the shipped library with a buffer sized for
+     * an earlier round's layout gets the error, not an overflow (ADVICE round 5) */
+    if (!t->prof.p) throw EngineError(CA_ERR_STATE, "not a -DCO_PROF build");
+    for (int i = 0; i < 2 * CO_NPROF + 24; ++i) out[i] = 0;
+    std::vector<unsigned long long> h((size_t)t->R * CO_NPROF);
+    rt_d2h(h.data(), t->prof.p, h.size() * 8, t->stream);
+    rt_sync(t->stream);
+    for (int g = 0; g < t->R; ++g)
+      for (int i = 0; i < CO_NPROF; ++i) out[i] += h[(size_t)g * CO_NPROF + i];
+    /* [CO_NPROF ..): clocks, the histogram of wave-step times, then the phase sums of the slow wave-steps alone */
+    rt_d2h(out + CO_NPROF, t->prof.p + (size_t)t->R * CO_NPROF, (size_t)(24 + CO_NPROF) * 8, t->stream);
+    rt_sync(t->stream);
+  })
+}
 
-  /* The loop of rating/tourney.pyx:122-160 with the networks on the GPU: for every model id in
-   * ascending order, pack that model's requests (Tourney::writeRequests), evaluate them, iterate
-   * its matches (Tourney::doIteration, which reads the evaluations through the reference's offset
-   * table).  The evaluation arrays persist between rounds like the driver's, so the result is the
-   * one the compat protocol gives with the same networks. */
-  bool run(int64_t max_rounds) {
-    ca_trainer &p = built();
-    std::vector<int> ids;
-    for (auto &m : matches)
-      for (int pid : {m.first, m.second}) {
-        int id = players.at(pid).model_id;
-        if (std::find(ids.begin(), ids.end(), id) == ids.end()) ids.push_back(id);
-      }
-    std::sort(ids.begin(), ids.end());
-    for (int id : ids) {
-      if (id < 0) continue;
-      if (!nets.count(id)) {
-        auto it = net_specs.find(id);
-        if (it == net_specs.end()) throw EngineError(CA_ERR_STATE, "ca_tourney_run: no network for model id " + std::to_string(id));
-        std::unique_ptr<CoNet> n(co_net_create(it->second.kind, it->second.w.data(), it->second.w.size(),
-                                               (size_t)p.G * p.spe, p.stream));
-        if (!n) throw EngineError(CA_ERR_ARG, "unknown net kind or bad weight count");
-        nets[id] = std::move(n);
-      }
+extern "C" int ca_trainer_net_forward(ca_trainer *t, int slot, const float *states, int32_t n, float *evals, float *probs) {
+  CA_TGUARD(t->net_forward_host(slot, states, n, evals, probs))
+}
+
+/* kernel-only timing of a network on `rows` resident rows (HIP events on the engine's stream);
+ * diagnostics and the per-kernel roofline of bench.py */
+extern "C" int ca_trainer_net_bench(ca_trainer *t, int slot, const float *states, int32_t rows, int32_t reps, float *ms_per_call) {
+  CA_TGUARD({
+    if (slot < 0 || slot > 1 || !t->nets[slot]) throw EngineError(CA_ERR_STATE, "net slot not set");
+    if ((size_t)rows > t->nets[slot]->max_rows()) throw EngineError(CA_ERR_ARG, "net_bench: too many rows");
+    std::vector<float> pad((size_t)rows * CO_STATE_STRIDE, 0.0f);
+    for (int r = 0; r < rows; ++r)
+      memcpy(&pad[(size_t)r * CO_STATE_STRIDE], states + (size_t)r * CO_GAME_STATE_SIZE, CO_GAME_STATE_SIZE * 4);
+    DevBuf<int32_t> d_n;
+    d_n.alloc(1, t->stream);
+    rt_h2d(t->nn_in.p, pad.data(), pad.size() * 4, t->stream);
+    rt_h2d(d_n.p, &rows, 4, t->stream);
+    t->net_used = true;
+    t->nets[slot]->forward(t->nn_in.p, rows, d_n.p, t->nn_eval.p, t->nn_probs.p, t->stream); /* warm */
+    Event e0, e1;
+    e0.create();
+    e1.create();
+    rt_event_record(e0, t->stream);
+    for (int i = 0; i < reps; ++i) t->nets[slot]->forward(t->nn_in.p, rows, d_n.p, t->nn_eval.p, t->nn_probs.p, t->stream);
+    rt_event_record(e1, t->stream);
+    rt_sync(t->stream);
+    *ms_per_call = rt_event_elapsed_ms(e0, e1) / (float)reps;
+  })
+}
+
+extern "C" int ca_expand_samples(int device, const float *state_policy, const float *outcome, int32_t n, float *gs, float *ev,
+                                 float *pr) {
+  /* host-side K7 for gathered shards: same gathers as co_k_write_samples */
+  (void)device;
+  static const int32_t SS[8][16] = CO_SPACE_SYM_INIT;
+  static const int32_t MS[8][96] = CO_MOVE_SYM_INIT;
+  for (int32_t i = 0; i < n; ++i) {
+    const float *st = state_policy + (size_t)i * CO_SAMPLE_FLOATS;
+    const float *pol = st + CO_GAME_STATE_SIZE;
+    for (int k = 0; k < 8; ++k) {
+      float *g = gs + ((size_t)i * 8 + k) * CO_GAME_STATE_SIZE;
+      float *p = pr + ((size_t)i * 8 + k) * CO_NUM_MOVES;
+      for (int j = 0; j < 64; ++j) g[j] = st[SS[k][j / 4] * 4 + j % 4];
+      for (int j = 64; j < CO_GAME_STATE_SIZE; ++j) g[j] = st[j];
+      for (int j = 0; j < CO_NUM_MOVES; ++j) p[j] = pol[MS[k][j]];
+      ev[(size_t)i * 8 + k] = outcome[i];
     }
-    int64_t rounds = 0;
-    bool done = p.tourney_all_done();
-    while (!done && (max_rounds <= 0 || rounds < max_rounds)) {
-      for (int id : ids) {
-        p.P.to_play = id;
-        p.P.iteration = p.trainer_iteration;
-        RT_LAUNCH(co_k_scan, 1, CO_WAVE, p.stream, p.P); /* offsets + batch of model `id` */
-        if (id >= 0) {
-          RT_LAUNCH(co_k_compact, p.G, CO_WAVE, p.stream, p.P);
-          nets[id]->forward(p.nn_in.p, p.G * p.spe, p.req_offset.p + p.G, p.nn_eval.p, p.nn_probs.p, p.stream);
-          ++p.nn_launches;
-        }
-        RT_LAUNCH(co_k_mcts_step, ((p.G) + CO_K3_WAVES - 1) / CO_K3_WAVES, CO_WAVE * CO_K3_WAVES, p.stream, p.P);
-        ++p.mcts_launches;
-        ++p.iterations;
-      }
-      ++rounds;
-      /* the host looks at the all-done flag every eighth round only (a round that finds every match
-       * finished launches kernels that return at once), so the queue never runs dry in between */
-      if ((rounds & 7) == 0 || (max_rounds > 0 && rounds >= max_rounds)) {
-        p.P.to_play = ids.front();
-        RT_LAUNCH(co_k_scan, 1, CO_WAVE, p.stream, p.P); /* refresh the all-done flag */
-        int32_t d = 0;
-        rt_d2h(&d, p.all_done.p, 4, p.stream);
-        rt_sync(p.stream);
-        done = d != 0;
-      }
-    }
-    p.scan_valid = false;
-    p.host_games_valid = false;
-    p.check_errors();
-    if (done) all_done(); /* (writes the match logs) */
-    return done;
   }
+  return CA_OK;
+}
 
-  /* Tourney::all_done (tourney.cpp:14-21); the log files of the matches are written the first time it is true */
-  bool all_done() {
-    ca_trainer &p = built();
-    const bool done = p.tourney_all_done();
-    if (done && !seen_done) {
-      seen_done = true;
-      p.maybe_write_logs();
+extern "C" int ca_trainer_stats(ca_trainer *t, ca_stats *out) {
+  CA_TGUARD({
+    t->fetch_games();
+    memset(out, 0, sizeof *out);
+    for (int g = 0; g < t->G; ++g) {
+      out->searches += t->host_games[g].searches;
+      out->evals += t->host_games[g].evals;
+      out->nodes += t->host_games[g].nodes;
+      out->plies += t->host_games[g].plies;
     }
-    return done;
-  }
+    std::vector<TreeCtl> ht((size_t)2 * t->R);
+    rt_d2h(ht.data(), t->trees.p, ht.size() * sizeof(TreeCtl), t->stream);
+    rt_sync(t->stream);
+    for (auto &x : ht) out->peak_arena_units = std::max<int64_t>(out->peak_arena_units, x.peak_units);
+    out->iterations = t->iterations;
+    out->mcts_ms = t->mcts_ms;
+    out->nn_ms = t->nn_ms;
+    out->pack_ms = t->pack_ms;
+    out->mcts_launches = t->mcts_launches;
+    out->nn_launches = t->nn_launches;
+    out->nn_rows = t->nn_rows;
+    out->pools = t->pools.empty() ? 1 : (int64_t)t->pools.size();
+    out->resident_slots = t->R;
+    out->nn_rows_evaluated = t->nn_rows_evaluated;
+    out->steps_cut = t->steps_cut;
+    out->step_budget_last = t->step_budget_last;
+    out->timed_launches = t->timed_launches;
+    out->nn_timed_rows = t->nn_timed_rows;
+    out->mcts_timed_ms = t->mcts_timed_ms;
+    out->nn_timed_ms = t->nn_timed_ms;
+  })
+}
 
-  ca_trainer &built() {
-    if (pool) return *pool;
-    if (matches.empty()) throw EngineError(CA_ERR_STATE, "tourney without matches");
-    auto t = std::make_unique<ca_trainer>();
-    t->tourney = true;
-    ca_config c;
-    memset(&c, 0, sizeof c);
-    c.num_games = (int32_t)matches.size();
-    c.device = device;
-    c.testing = 1;
-    c.no_stagger = 1;
-    c.trace = trace;
-    c.arena_units = arena_units;
-    c.c_puct = 1.0f;
-    c.max_searches = 1;
-    c.searches_per_eval = 1;
-    for (auto &m : matches) {
-      for (int side = 0; side < 2; ++side) {
-        const PlayerCfg &p = players.at(side == 0 ? m.first : m.second);
-        t->host_pcfg.push_back(p);
-        if (!p.random) {
-          c.max_searches = std::max(c.max_searches, p.max_searches);
-          c.searches_per_eval = std::max(c.searches_per_eval, p.searches_per_eval);
-        }
-      }
+extern "C" int ca_trainer_game_info(ca_trainer *t, int game, int32_t out[8]) {
+  CA_TGUARD({
+    if (game < 0 || game >= t->G) throw EngineError(CA_ERR_ARG, "game index out of range");
+    t->fetch_games();
+    const GameCtl &gc = t->host_games[game];
+    out[0] = gc.to_play; out[1] = gc.done; out[2] = gc.result; out[3] = gc.n_samples;
+    out[4] = gc.done ? 0 : gc.n_pending; out[5] = gc.error; out[6] = gc.mate_turn; out[7] = gc.plies;
+  })
+}
+
+extern "C" int ca_trainer_trace(ca_trainer *t, int game, int32_t *out, int32_t cap, int32_t *n) {
+  CA_TGUARD({
+    if (!t->cfg.trace) throw EngineError(CA_ERR_STATE, "trace not enabled");
+    if (game < 0 || game >= t->G) throw EngineError(CA_ERR_ARG, "game index out of range");
+    t->fetch_games();
+    int32_t len = t->host_games[game].trace_len;
+    if (len > CO_TRACE_CAP) throw EngineError(CA_ERR_ENGINE, "trace buffer overflow");
+    *n = len;
+    int32_t c = std::min(len, cap);
+    if (out && c > 0) {
+      rt_d2h(out, t->trace.p + (size_t)game * CO_TRACE_CAP, (size_t)c * 4, t->stream);
+      rt_sync(t->stream);
     }
-    t->match_seeds = seeds;
-    t->init(c);
-    /* tourney.cpp:83-96: a match added with logging = true writes <log_folder>/match_<p1>_<p2>_<index>.txt */
-    std::vector<int> logged;
-    std::vector<std::string> paths;
-    for (size_t i = 0; i < matches.size(); ++i)
-      if (match_logging[i]) {
-        logged.push_back((int)i);
-        paths.push_back(log_folder + "/match_" + std::to_string(matches[i].first) + "_" + std::to_string(matches[i].second) + "_" +
-                        std::to_string(i) + ".txt");
-      }
-    if (!logged.empty()) t->set_log_records(logged, paths, true);
-    if (exact_offsets) t->P.read_offset = nullptr; /* co_step_row falls back to the writeRequests rows */
-    pool = std::move(t);
-    return *pool;
-  }
-};
+  })
+}
 
+/* ---- Tourney C ABI */
 extern "C" int ca_tourney_create(int device, uint32_t arena_units, int trace, ca_tourney **out) {
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
@@ -1783,8 +1844,6 @@ extern "C" int ca_tourney_write_scores(ca_tourney *t, const char *filename) {
         f << t->matches[g].first << ' ' << t->matches[g].second << ' ' << ca_trainer::game_score(p.host_games[g]) << '\n';
   })
 }
-extern "C" int ca_trainer_trace(ca_trainer *t, int game, int32_t *out, int32_t cap, int32_t *n);
-extern "C" int ca_trainer_stats(ca_trainer *t, ca_stats *out);
 extern "C" int ca_tourney_trace(ca_tourney *t, int32_t match, int32_t *out, int32_t cap, int32_t *n_out) {
   ca_trainer *p = nullptr;
   try {
@@ -1806,162 +1865,30 @@ extern "C" int ca_tourney_stats(ca_tourney *t, ca_stats *out) {
   return ca_trainer_stats(p, out);
 }
 
-/* diagnostic builds (-DCO_PROF): summed in-kernel cycle stamps, see mcts.h; not in the public header */
-extern "C" int ca_trainer_prof(ca_trainer *t, unsigned long long out[2 * CO_NPROF + 24]) {
-  CA_TGUARD({
-    /* nothing is written to `out` unless this is a stamped build: a caller of the shipped library with a buffer sized for
-     * an earlier round's layout gets the error, not an overflow (ADVICE round 5) */
-    if (!t->prof.p) throw EngineError(CA_ERR_STATE, "not a -DCO_PROF build");
-    for (int i = 0; i < 2 * CO_NPROF + 24; ++i) out[i] = 0;
-    std::vector<unsigned long long> h((size_t)t->R * CO_NPROF);
-    rt_d2h(h.data(), t->prof.p, h.size() * 8, t->stream);
-    rt_sync(t->stream);
-    for (int g = 0; g < t->R; ++g)
-      for (int i = 0; i < CO_NPROF; ++i) out[i] += h[(size_t)g * CO_NPROF + i];
-    /* [CO_NPROF ..): clocks, the histogram of wave-step times, then the phase sums of the slow wave-steps alone */
-    rt_d2h(out + CO_NPROF, t->prof.p + (size_t)t->R * CO_NPROF, (size_t)(24 + CO_NPROF) * 8, t->stream);
-    rt_sync(t->stream);
-  })
+/* ---- stand-alone test entry points, each on a stream of its own */
+static Stream device_stream(int device) {
+  rt_set_device(device);
+  Stream s;
+  s.create();
+  return s;
 }
-
-extern "C" int ca_trainer_net_forward(ca_trainer *t, int slot, const float *states, int32_t n, float *evals, float *probs) {
-  CA_TGUARD(t->net_forward_host(slot, states, n, evals, probs))
-}
-
-/* kernel-only timing of a network on `rows` resident rows (HIP events on the engine's stream);
- * diagnostics and the per-kernel roofline of bench.py */
-extern "C" int ca_trainer_net_bench(ca_trainer *t, int slot, const float *states, int32_t rows, int32_t reps, float *ms_per_call) {
-  CA_TGUARD({
-    if (slot < 0 || slot > 1 || !t->nets[slot]) throw EngineError(CA_ERR_STATE, "net slot not set");
-    if ((size_t)rows > t->nets[slot]->max_rows()) throw EngineError(CA_ERR_ARG, "net_bench: too many rows");
-    std::vector<float> pad((size_t)rows * CO_STATE_STRIDE, 0.0f);
-    for (int r = 0; r < rows; ++r)
-      memcpy(&pad[(size_t)r * CO_STATE_STRIDE], states + (size_t)r * CO_GAME_STATE_SIZE, CO_GAME_STATE_SIZE * 4);
-    DevBuf<int32_t> d_n;
-    d_n.alloc(1, t->stream);
-    rt_h2d(t->nn_in.p, pad.data(), pad.size() * 4, t->stream);
-    rt_h2d(d_n.p, &rows, 4, t->stream);
-    t->net_used = true;
-    t->nets[slot]->forward(t->nn_in.p, rows, d_n.p, t->nn_eval.p, t->nn_probs.p, t->stream); /* warm */
-    rt_event_t e0, e1;
-    rt_event_create(&e0);
-    rt_event_create(&e1);
-    rt_event_record(e0, t->stream);
-    for (int i = 0; i < reps; ++i) t->nets[slot]->forward(t->nn_in.p, rows, d_n.p, t->nn_eval.p, t->nn_probs.p, t->stream);
-    rt_event_record(e1, t->stream);
-    rt_sync(t->stream);
-    *ms_per_call = rt_event_elapsed_ms(e0, e1) / (float)reps;
-    rt_event_destroy(e0);
-    rt_event_destroy(e1);
-  })
-}
-
-extern "C" int ca_expand_samples(int device, const float *state_policy, const float *outcome, int32_t n, float *gs, float *ev,
-                                 float *pr) {
-  /* host-side K7 for gathered shards: same gathers as co_k_write_samples */
-  (void)device;
-  static const int32_t SS[8][16] = CO_SPACE_SYM_INIT;
-  static const int32_t MS[8][96] = CO_MOVE_SYM_INIT;
-  for (int32_t i = 0; i < n; ++i) {
-    const float *st = state_policy + (size_t)i * CO_SAMPLE_FLOATS;
-    const float *pol = st + CO_GAME_STATE_SIZE;
-    for (int k = 0; k < 8; ++k) {
-      float *g = gs + ((size_t)i * 8 + k) * CO_GAME_STATE_SIZE;
-      float *p = pr + ((size_t)i * 8 + k) * CO_NUM_MOVES;
-      for (int j = 0; j < 64; ++j) g[j] = st[SS[k][j / 4] * 4 + j % 4];
-      for (int j = 64; j < CO_GAME_STATE_SIZE; ++j) g[j] = st[j];
-      for (int j = 0; j < CO_NUM_MOVES; ++j) p[j] = pol[MS[k][j]];
-      ev[(size_t)i * 8 + k] = outcome[i];
-    }
-  }
-  return CA_OK;
-}
-
-extern "C" int ca_trainer_stats(ca_trainer *t, ca_stats *out) {
-  CA_TGUARD({
-    t->fetch_games();
-    memset(out, 0, sizeof *out);
-    for (int g = 0; g < t->G; ++g) {
-      out->searches += t->host_games[g].searches;
-      out->evals += t->host_games[g].evals;
-      out->nodes += t->host_games[g].nodes;
-      out->plies += t->host_games[g].plies;
-    }
-    std::vector<TreeCtl> ht((size_t)2 * t->R);
-    rt_d2h(ht.data(), t->trees.p, ht.size() * sizeof(TreeCtl), t->stream);
-    rt_sync(t->stream);
-    for (auto &x : ht) out->peak_arena_units = std::max<int64_t>(out->peak_arena_units, x.peak_units);
-    out->iterations = t->iterations;
-    out->mcts_ms = t->mcts_ms;
-    out->nn_ms = t->nn_ms;
-    out->pack_ms = t->pack_ms;
-    out->mcts_launches = t->mcts_launches;
-    out->nn_launches = t->nn_launches;
-    out->nn_rows = t->nn_rows;
-    out->pools = t->pools.empty() ? 1 : (int64_t)t->pools.size();
-    out->resident_slots = t->R;
-    out->nn_rows_evaluated = t->nn_rows_evaluated;
-    out->steps_cut = t->steps_cut;
-    out->step_budget_last = t->step_budget_last;
-    out->timed_launches = t->timed_launches;
-    out->nn_timed_rows = t->nn_timed_rows;
-    out->mcts_timed_ms = t->mcts_timed_ms;
-    out->nn_timed_ms = t->nn_timed_ms;
-  })
-}
-
-extern "C" int ca_trainer_game_info(ca_trainer *t, int game, int32_t out[8]) {
-  CA_TGUARD({
-    if (game < 0 || game >= t->G) throw EngineError(CA_ERR_ARG, "game index out of range");
-    t->fetch_games();
-    const GameCtl &gc = t->host_games[game];
-    out[0] = gc.to_play; out[1] = gc.done; out[2] = gc.result; out[3] = gc.n_samples;
-    out[4] = gc.done ? 0 : gc.n_pending; out[5] = gc.error; out[6] = gc.mate_turn; out[7] = gc.plies;
-  })
-}
-
-extern "C" int ca_trainer_trace(ca_trainer *t, int game, int32_t *out, int32_t cap, int32_t *n) {
-  CA_TGUARD({
-    if (!t->cfg.trace) throw EngineError(CA_ERR_STATE, "trace not enabled");
-    if (game < 0 || game >= t->G) throw EngineError(CA_ERR_ARG, "game index out of range");
-    t->fetch_games();
-    int32_t len = t->host_games[game].trace_len;
-    if (len > CO_TRACE_CAP) throw EngineError(CA_ERR_ENGINE, "trace buffer overflow");
-    *n = len;
-    int32_t c = std::min(len, cap);
-    if (out && c > 0) {
-      rt_d2h(out, t->trace.p + (size_t)game * CO_TRACE_CAP, (size_t)c * 4, t->stream);
-      rt_sync(t->stream);
-    }
-  })
-}
-
-/* ---- stand-alone test entry points */
-struct TmpStream {
-  rt_stream_t s;
-  explicit TmpStream(int device) {
-    rt_set_device(device);
-    rt_stream_create(&s);
-  }
-  ~TmpStream() { rt_stream_destroy(s); }
-};
 
 extern "C" int ca_rules_legal_moves(int device, const uint64_t *boards, const uint32_t *metas, int32_t n, uint32_t *masks,
                                     int32_t *is_lines) {
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
   CA_GUARD({
-    TmpStream ts(device);
+    const Stream ts = device_stream(device);
     DevBuf<uint64_t> b;
     DevBuf<uint32_t> m, mk;
     DevBuf<int32_t> ln;
-    b.alloc(n, ts.s); m.alloc(n, ts.s); mk.alloc((size_t)n * 3, ts.s); ln.alloc(n, ts.s);
-    rt_h2d(b.p, boards, (size_t)n * 8, ts.s);
-    rt_h2d(m.p, metas, (size_t)n * 4, ts.s);
-    RT_LAUNCH(co_k_rules_batch, n, CO_WAVE, ts.s, (const uint64_t *)b.p, (const uint32_t *)m.p, n, mk.p, ln.p);
-    rt_d2h(masks, mk.p, (size_t)n * 12, ts.s);
-    rt_d2h(is_lines, ln.p, (size_t)n * 4, ts.s);
-    rt_sync(ts.s);
+    b.alloc(n, ts); m.alloc(n, ts); mk.alloc((size_t)n * 3, ts); ln.alloc(n, ts);
+    rt_h2d(b.p, boards, (size_t)n * 8, ts);
+    rt_h2d(m.p, metas, (size_t)n * 4, ts);
+    RT_LAUNCH(co_k_rules_batch, n, CO_WAVE, ts, (const uint64_t *)b.p, (const uint32_t *)m.p, n, mk.p, ln.p);
+    rt_d2h(masks, mk.p, (size_t)n * 12, ts);
+    rt_d2h(is_lines, ln.p, (size_t)n * 4, ts);
+    rt_sync(ts);
   })
 }
 
@@ -1969,21 +1896,21 @@ extern "C" int ca_rules_do_move(int device, uint64_t *boards, uint32_t *metas, c
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
   CA_GUARD({
-    TmpStream ts(device);
+    const Stream ts = device_stream(device);
     DevBuf<uint64_t> b;
     DevBuf<uint32_t> m;
     DevBuf<int32_t> mv;
     DevBuf<float> st;
-    b.alloc(n, ts.s); m.alloc(n, ts.s); mv.alloc(n, ts.s); st.alloc((size_t)n * CO_STATE_STRIDE, ts.s);
-    rt_h2d(b.p, boards, (size_t)n * 8, ts.s);
-    rt_h2d(m.p, metas, (size_t)n * 4, ts.s);
-    rt_h2d(mv.p, moves, (size_t)n * 4, ts.s);
-    RT_LAUNCH(co_k_domove_batch, n, CO_WAVE, ts.s, b.p, m.p, (const int32_t *)mv.p, n, st.p);
+    b.alloc(n, ts); m.alloc(n, ts); mv.alloc(n, ts); st.alloc((size_t)n * CO_STATE_STRIDE, ts);
+    rt_h2d(b.p, boards, (size_t)n * 8, ts);
+    rt_h2d(m.p, metas, (size_t)n * 4, ts);
+    rt_h2d(mv.p, moves, (size_t)n * 4, ts);
+    RT_LAUNCH(co_k_domove_batch, n, CO_WAVE, ts, b.p, m.p, (const int32_t *)mv.p, n, st.p);
     std::vector<float> tmp((size_t)n * CO_STATE_STRIDE);
-    rt_d2h(boards, b.p, (size_t)n * 8, ts.s);
-    rt_d2h(metas, m.p, (size_t)n * 4, ts.s);
-    rt_d2h(tmp.data(), st.p, tmp.size() * 4, ts.s);
-    rt_sync(ts.s);
+    rt_d2h(boards, b.p, (size_t)n * 8, ts);
+    rt_d2h(metas, m.p, (size_t)n * 4, ts);
+    rt_d2h(tmp.data(), st.p, tmp.size() * 4, ts);
+    rt_sync(ts);
     for (int i = 0; i < n; ++i)
       memcpy(states + (size_t)i * CO_GAME_STATE_SIZE, &tmp[(size_t)i * CO_STATE_STRIDE], CO_GAME_STATE_SIZE * 4);
   })
@@ -1993,19 +1920,19 @@ extern "C" int ca_rules_rows(int device, uint64_t *boards, uint32_t *metas, cons
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
   CA_GUARD({
-    TmpStream ts(device);
+    const Stream ts = device_stream(device);
     DevBuf<uint64_t> b;
     DevBuf<uint32_t> m, mk;
     DevBuf<int32_t> mv;
-    b.alloc(n, ts.s); m.alloc(n, ts.s); mk.alloc((size_t)n * 3, ts.s); mv.alloc(n, ts.s);
-    rt_h2d(b.p, boards, (size_t)n * 8, ts.s);
-    rt_h2d(m.p, metas, (size_t)n * 4, ts.s);
-    rt_h2d(mv.p, moves, (size_t)n * 4, ts.s);
-    RT_LAUNCH(co_k_rules_rows, (n + 3) / 4, CO_WAVE, ts.s, b.p, m.p, (const int32_t *)mv.p, n, mk.p);
-    rt_d2h(boards, b.p, (size_t)n * 8, ts.s);
-    rt_d2h(metas, m.p, (size_t)n * 4, ts.s);
-    rt_d2h(masks, mk.p, (size_t)n * 12, ts.s);
-    rt_sync(ts.s);
+    b.alloc(n, ts); m.alloc(n, ts); mk.alloc((size_t)n * 3, ts); mv.alloc(n, ts);
+    rt_h2d(b.p, boards, (size_t)n * 8, ts);
+    rt_h2d(m.p, metas, (size_t)n * 4, ts);
+    rt_h2d(mv.p, moves, (size_t)n * 4, ts);
+    RT_LAUNCH(co_k_rules_rows, (n + 3) / 4, CO_WAVE, ts, b.p, m.p, (const int32_t *)mv.p, n, mk.p);
+    rt_d2h(boards, b.p, (size_t)n * 8, ts);
+    rt_d2h(metas, m.p, (size_t)n * 4, ts);
+    rt_d2h(masks, mk.p, (size_t)n * 12, ts);
+    rt_sync(ts);
   })
 }
 
@@ -2014,19 +1941,19 @@ extern "C" int ca_rng_draw(int device, uint32_t seed, int32_t n, int32_t chunk, 
   if (rc != CA_OK) return rc;
   CA_GUARD({
     if (chunk < 1 || chunk > CO_WAVE) throw EngineError(CA_ERR_ARG, "chunk must be 1..64");
-    TmpStream ts(device);
+    const Stream ts = device_stream(device);
     std::vector<uint32_t> x(CO_MT_N);
     x[0] = seed;
     for (int i = 1; i < CO_MT_N; ++i) x[i] = 1812433253u * (x[i - 1] ^ (x[i - 1] >> 30)) + (uint32_t)i;
     DevBuf<uint32_t> mt, o;
     DevBuf<int32_t> idx;
-    mt.alloc(CO_MT_N, ts.s); o.alloc(n, ts.s); idx.alloc(1, ts.s);
+    mt.alloc(CO_MT_N, ts); o.alloc(n, ts); idx.alloc(1, ts);
     int32_t i0 = CO_MT_N;
-    rt_h2d(mt.p, x.data(), CO_MT_N * 4, ts.s);
-    rt_h2d(idx.p, &i0, 4, ts.s);
-    RT_LAUNCH(co_k_rng_draw, 1, CO_WAVE, ts.s, mt.p, idx.p, n, chunk, o.p);
-    rt_d2h(out, o.p, (size_t)n * 4, ts.s);
-    rt_sync(ts.s);
+    rt_h2d(mt.p, x.data(), CO_MT_N * 4, ts);
+    rt_h2d(idx.p, &i0, 4, ts);
+    RT_LAUNCH(co_k_rng_draw, 1, CO_WAVE, ts, mt.p, idx.p, n, chunk, o.p);
+    rt_d2h(out, o.p, (size_t)n * 4, ts);
+    rt_sync(ts);
   })
 }
 
@@ -2034,12 +1961,12 @@ extern "C" int ca_fp_probe(int device, const float *in, int32_t n, float *out) {
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
   CA_GUARD({
-    TmpStream ts(device);
+    const Stream ts = device_stream(device);
     DevBuf<float> di, dout;
-    di.alloc((size_t)n * 8, ts.s); dout.alloc((size_t)n * 8, ts.s);
-    rt_h2d(di.p, in, (size_t)n * 32, ts.s);
-    RT_LAUNCH(co_k_fp_probe, (n + CO_WAVE - 1) / CO_WAVE, CO_WAVE, ts.s, (const float *)di.p, n, dout.p);
-    rt_d2h(out, dout.p, (size_t)n * 32, ts.s);
-    rt_sync(ts.s);
+    di.alloc((size_t)n * 8, ts); dout.alloc((size_t)n * 8, ts);
+    rt_h2d(di.p, in, (size_t)n * 32, ts);
+    RT_LAUNCH(co_k_fp_probe, (n + CO_WAVE - 1) / CO_WAVE, CO_WAVE, ts, (const float *)di.p, n, dout.p);
+    rt_d2h(out, dout.p, (size_t)n * 32, ts);
+    rt_sync(ts);
   })
 }

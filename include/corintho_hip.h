@@ -220,7 +220,8 @@ typedef struct ca_stats {
   int64_t mcts_launches, nn_launches;
   int64_t nn_rows;       /* rows evaluated by the network kernels */
   int64_t pools;         /* pools the last ca_trainer_run used (1 in arena mode) */
-  /* fused training times one iteration per pool and window of 8 with HIP events (mcts_ms / nn_ms
+  /* fused training times one iteration per pool and polling window of 16 (CO_POOL_POLL), the arena one
+   * iteration in 8, with HIP events (mcts_ms / nn_ms
    * above are then estimates: timed sums scaled by launches / timed launches); exact figures of
    * the timed launches: */
   int64_t timed_launches; /* search + network launch pairs that carried events */
