@@ -2,8 +2,13 @@
 """Self-play throughput of the MI355X engine (BASELINE.json metric:
 "self-play games/sec at 400 sims/move").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W untimed and K timed steps, writes `--dump-outputs` and prints its line: nothing
+else.  `--full` adds the side measurements behind the timed region on one GPU (other network kinds under
+detail.variants, no_eval_cache, two_pools, recycled, trained_checkpoint, configs, roofline.unshared, detail.summary
+and cpu_baseline); the --no-* / --cpu-games / --recycle-games options below trim those.
 
 One STEP = one whole self-play generation of `--games` games per GPU in fused mode
 (search + network on the device), from the first iteration to the last game
@@ -31,8 +36,8 @@ pipe (csrc/nn_rescnn.hip, nn_mlp_split.hip):
   * `rescnn4x6`: both operands as THREE bf16 terms whose sum IS the float32 value, six products
     (float32-equivalent; the default of round 2), at twice the matrix work;
   * `rescnn4`: fp32 MFMA;  `*x3`: two bf16 terms, 16 bits -- narrower than float32, variants only.
-tests/test_net_precision.py and tests/test_trained_golden.py assert these bounds on the GPU; every
-kind is reported under `detail.variants` with its own roofline object.
+tests/test_net_precision.py and tests/test_trained_golden.py assert these bounds on the GPU; with `--full`
+every kind is reported under `detail.variants` with its own roofline object.
 """
 import argparse
 import json
@@ -97,30 +102,37 @@ def parse():
                     help="rescnn4h3 (default) = the 4-block residual CNN BASELINE.json configs[1] names at float32-class two-term "
                          "fp16 split precision; rescnn4x6 = three-term bf16 split (float32-equivalent); rescnn4 = the same network "
                          "on fp32 MFMA; mlp12x100* = the reference's own net; *x3 = two-term bf16 split, narrower than float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the side measurements (one GPU): the other network kinds, the "
+                         "workload without the evaluation cache, at two pools, recycled, with the trained checkpoint, the other "
+                         "BASELINE configurations, the single-pool roofline and the CPU baseline")
     ap.add_argument("--no-mlp-extra", "--no-variants", dest="no_variants", action="store_true",
-                    help="skip the other networks reported under detail.variants")
+                    help="with --full: skip the other networks reported under detail.variants (and detail.no_eval_cache, "
+                         "detail.two_pools)")
     ap.add_argument("--variant-steps", type=int, default=20, help="timed generations per variant (capped by --steps)")
     ap.add_argument("--stagger", action="store_true", help="keep the reference's staggered start")
     ap.add_argument("--tflite", default="", help="with --net mlp12x100*: weights imported from a reference TFLite checkpoint")
     ap.add_argument("--arena-units", type=int, default=0)
-    ap.add_argument("--no-unshared", action="store_true", help="skip the extra single-pool generation behind roofline.unshared (profiling runs)")
+    ap.add_argument("--no-unshared", action="store_true",
+                    help="with --full: skip the extra single-pool generation behind roofline.unshared (profiling runs)")
     ap.add_argument("--pools", type=int, default=0, help="independent game pools on separate streams per GPU (0 = engine default)")
     ap.add_argument("--cpu-games", type=int, default=64,
-                    help="games of the CPU-baseline generation that carries cpu_baseline.value, played to the end (0 = skip)")
+                    help="with --full: games of the CPU-baseline generation that carries cpu_baseline.value, played to the end "
+                         "(0 = skip)")
     ap.add_argument("--cpu-seconds", type=float, default=60.0, help="safety cap of each CPU-baseline leg (a leg that hits it is reported as extrapolated)")
     ap.add_argument("--recycle-games", type=int, default=16384,
-                    help="games of the `recycled` variant: one generation of this many games on --games resident slots "
-                         "(a slot whose game ends takes the next game); 0 = skip")
+                    help="with --full: games of the `recycled` variant: one generation of this many games on --games resident "
+                         "slots (a slot whose game ends takes the next game); 0 = skip")
     ap.add_argument("--no-eval-cache", action="store_true",
-                    help="evaluate every request row (the engine's evaluation cache off); the default run reports this as the "
+                    help="evaluate every request row (the engine's evaluation cache off); --full reports this as the "
                          "`no_eval_cache` variant")
     ap.add_argument("--trained", action="store_true",
                     help="the mlp12x100 kinds search with the reference's last checkpoint (tests/golden/trained_last.npz) instead of "
                          "random-init weights: the narrow, deep trees of every generation after the first (profiling runs)")
     ap.add_argument("--no-trained", action="store_true",
-                    help="skip detail.trained_checkpoint (the reference's last checkpoint through the same workload)")
+                    help="with --full: skip detail.trained_checkpoint (the reference's last checkpoint through the same workload)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip detail.configs (one generation of each other BASELINE configuration: cfg1, cfg4, cfg5, tournament, compat)")
+                    help="with --full: skip detail.configs (one generation of each other BASELINE configuration: cfg1, cfg4, cfg5, tournament, compat)")
     ap.add_argument("--check-gather", action="store_true",
                     help="with a process group (N > 1, or CORINTHO_FORCE_DIST=1 at N = 1): behind the timed region every rank compares "
                          "its block of one more gathered generation with its own export_samples() byte for byte "
@@ -566,7 +578,7 @@ def main():
         job_searches, job_evals, job_rows = float(totals["searches"]), float(totals["evals"]), float(totals["nn_rows"])
         job_samples = float(totals["samples"])
     if args.dump_outputs:
-        # the trainer still holds the last timed generation here: the gather check and the variants below reset it
+        # the trainer still holds the last timed generation here: the gather check and --full's variants below reset it
         # every rank writes its own shard's; DUMP_ROWS is shared among them (64 MB in all)
         dump_outputs(tr, args.dump_outputs, "_rank%d" % rank if world > 1 else "", DUMP_ROWS // world)
 
@@ -593,6 +605,7 @@ def main():
                         "payload_bytes": gatherer.bytes_moved}
 
     if rank == 0:
+        full = args.full and world == 1  # the side measurements below: --full, one GPU
         _, arch, dtype, peak, issued, kname = NETS[args.net]
         flop_per_row = flop_by_arch[arch]
         games_total = world * G * args.steps
@@ -601,7 +614,7 @@ def main():
         mcts_s = totals["mcts_ms"] * 1e-3
         npools = int(totals.get("pools", 1))
         roofline, both = rooflines_of(args.net, totals, npools, wall_s=dt)
-        if npools > 1 and not args.no_unshared and world == 1:
+        if npools > 1 and not args.no_unshared and full:
             # The timed region runs the games as `npools` pools on separate streams, so the durations
             # above are those of kernels SHARING the GPU with the other pool's kernels (their sum
             # exceeds the wall time).  One more generation with a single pool gives the same kernel's
@@ -679,7 +692,7 @@ def main():
                 "samples_gathered": totals["gathered_samples"], "samples_of_all_shards": job_samples}
             if gather_check is not None:
                 out["detail"]["collectives_per_step"]["gather_check"] = gather_check
-        if world == 1 and not args.no_variants:
+        if full and not args.no_variants:
             # the other network kinds on the same pool: the same timed loop, each with its own roofline object
             vsteps = max(1, min(args.variant_steps, args.steps))
             variants = {}
@@ -704,7 +717,7 @@ def main():
                                                   "roofline": roofline_of(args.net, t3, int(t3.get("pools", 1)), wall_s=d3),
                                                   "nn_rows_evaluated_over_requested": t3["nn_rows_evaluated"] / max(t3["nn_rows"], 1)}
                 del tr3
-        if world == 1 and not args.no_variants and npools != 2:
+        if full and not args.no_variants and npools != 2:
             # rounds 1-4 ran two pools per GPU; the same workload that way, for continuity of the per-launch figures
             trp = make_trainer(2)
             n2 = min(5, args.steps)
@@ -712,7 +725,7 @@ def main():
             out["detail"]["two_pools"] = {"games_per_s": G * n2 / dp, "ms_per_step": dp * 1e3 / n2, "steps": n2, "warmup": 1,
                                           "roofline": roofline_of(args.net, tp, int(tp.get("pools", 1)), wall_s=dp)}
             del trp
-        if world == 1 and args.recycle_games > G:
+        if full and args.recycle_games > G:
             # one generation of `recycle_games` games on G resident slots: a slot whose game ends takes the next game
             # (ca_config.resident), so the launches stay full until the games run out instead of thinning with the
             # generation's longest games
@@ -727,7 +740,7 @@ def main():
                 "note": "same workload per game; %d games per generation on %d slots" % (args.recycle_games, G)}
             del tr2
         trained_path = os.path.join(ROOT, "tests", "golden", "trained_last.npz")
-        if world == 1 and not args.no_trained and not emu and os.path.exists(trained_path):
+        if full and not args.no_trained and not emu and os.path.exists(trained_path):
             # The regime every generation after the first lives in (main.pyx:285-322): the search guided by a TRAINED
             # network -- narrow, deep trees, in late plies every second simulation terminal.  The reference's own
             # architecture with the reference's last checkpoint (rating/tflite_models, imported once by
@@ -746,7 +759,7 @@ def main():
                 "steps_cut_per_step": ttc["steps_cut"] / nt, "last_budget_us": ttc.get("step_budget_last", 0),
                 "device_ms_per_step": {"mcts": ttc["mcts_ms"] / nt, "network": ttc["nn_ms"] / nt},
                 "roofline": rt_dom, "roofline_search": rt_both["search"], "roofline_network": rt_both["network"]}
-        if world == 1 and not args.no_configs and not emu and (G, args.sims, args.spe) == (4096, 400, 16):
+        if full and not args.no_configs and not emu and (G, args.sims, args.spe) == (4096, 400, 16):
             # BASELINE.json's other configurations, one generation each on the final tree (tools/run_configs.py), each with
             # its roofline objects: cfg1 (64 x 50), cfg4 (4096 x 1600 + Dirichlet noise: toml/train.toml:2-18), cfg5 (arena,
             # main.pyx:329-349), a tournament, and the host-driven reference protocol (PCIe-inclusive, never `value`)
@@ -754,20 +767,21 @@ def main():
             from tools import run_configs as RC
 
             out["detail"]["configs"] = RC.measure_all(device=local_rank)
-        # the numbers a reader compares `value` with, in one place (each is measured above, same workload)
-        d = out["detail"]
-        out["detail"]["summary"] = {
-            "games_per_s": value,
-            "no_eval_cache_games_per_s": d.get("no_eval_cache", {}).get("games_per_s"),
-            "float32_equivalent_bf16x6_games_per_s": d.get("variants", {}).get("rescnn4x6", {}).get("games_per_s"),
-            "fp32_mfma_games_per_s": d.get("variants", {}).get("rescnn4", {}).get("games_per_s"),
-            "reference_network_mlp12x100h3_games_per_s": d.get("variants", {}).get("mlp12x100h3", {}).get("games_per_s"),
-            "recycled_games_per_s": d.get("recycled", {}).get("games_per_s"),
-            "two_pools_games_per_s": d.get("two_pools", {}).get("games_per_s"),
-            "trained_checkpoint_mlp12x100h3_games_per_s": d.get("trained_checkpoint", {}).get("games_per_s"),
-            "configs_games_per_s": {k: v.get("games_per_s", v.get("matches_per_s")) for k, v in d.get("configs", {}).items()},
-        }
-        if world == 1 and args.cpu_games > 0:
+        if full:
+            # the numbers a reader compares `value` with, in one place (each is measured above, same workload)
+            d = out["detail"]
+            out["detail"]["summary"] = {
+                "games_per_s": value,
+                "no_eval_cache_games_per_s": d.get("no_eval_cache", {}).get("games_per_s"),
+                "float32_equivalent_bf16x6_games_per_s": d.get("variants", {}).get("rescnn4x6", {}).get("games_per_s"),
+                "fp32_mfma_games_per_s": d.get("variants", {}).get("rescnn4", {}).get("games_per_s"),
+                "reference_network_mlp12x100h3_games_per_s": d.get("variants", {}).get("mlp12x100h3", {}).get("games_per_s"),
+                "recycled_games_per_s": d.get("recycled", {}).get("games_per_s"),
+                "two_pools_games_per_s": d.get("two_pools", {}).get("games_per_s"),
+                "trained_checkpoint_mlp12x100h3_games_per_s": d.get("trained_checkpoint", {}).get("games_per_s"),
+                "configs_games_per_s": {k: v.get("games_per_s", v.get("matches_per_s")) for k, v in d.get("configs", {}).items()},
+            }
+        if full and args.cpu_games > 0:
             out["cpu_baseline"] = cpu_baseline(args, arch, weights_by_arch, out["detail"]["evals_per_game"])
         # The whole record goes to stderr.  The result line on stdout leaves out the side measurements, whose rates
         # detail.summary carries: with them the line grows past 24 KB, more than a reader of the output's tail can parse.

@@ -118,6 +118,29 @@ def test_bench_gpus_2_launches_two_ranks_itself():
     assert o1["n_gpus"] == 1 and o1["detail"]["ranks_seen"] == 1 and "collectives_per_step" not in o1["detail"]
 
 
+def test_bench_side_measurements_only_with_full():
+    """a plain run is its timed steps and its line: the side measurements (here the CPU baseline and the recycled
+    generation, left at their defaults) run only with --full, and there they fill their records and detail.summary"""
+    import json
+
+    plain = TINY[:TINY.index("--cpu-games")]
+    side = ("variants", "no_eval_cache", "two_pools", "recycled", "trained_checkpoint", "configs", "summary")
+    r = _bench(["--gpus", "1"] + plain)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 1 and out["warmup"] == 0 and out["value"] > 0
+    assert "cpu_baseline" not in out and "unshared" not in out["roofline"]
+    assert not [k for k in side if k in out["detail"]], sorted(out["detail"])
+    r = _bench(["--gpus", "1", "--full", "--no-variants", "--cpu-games", "2", "--recycle-games", "8"] + plain)
+    assert r.returncode == 0, r.stderr[-2000:]
+    full = json.loads(r.stdout.strip().splitlines()[-1])
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["legs"]["all_cores"]["finished"]
+    s = full["detail"]["summary"]
+    assert s["games_per_s"] == full["value"] and s["recycled_games_per_s"] > 0
+    record = json.loads(r.stderr.strip().splitlines()[-1])  # the whole record on stderr
+    assert record["detail"]["recycled"]["games"] == 8
+
+
 def test_bench_gpus_8_rehearsal():
     """the eight ranks of BASELINE configs[2], tiny, on the emulation build over gloo: every rank seen, the gathered
     samples = the sum of the eight shards, value = all games over the slowest rank's time"""
