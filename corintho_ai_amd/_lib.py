@@ -79,6 +79,8 @@ EXPORTS = [
     "ca_tourney_create", "ca_tourney_destroy", "ca_tourney_set_log_folder", "ca_tourney_add_player", "ca_tourney_add_match", "ca_tourney_all_done",
     "ca_tourney_num_requests", "ca_tourney_write_requests", "ca_tourney_do_iteration", "ca_tourney_write_scores",
     "ca_tourney_set_net", "ca_tourney_run", "ca_tourney_set_exact_offsets", "ca_tourney_num_matches", "ca_tourney_match_info", "ca_tourney_match_score", "ca_tourney_trace", "ca_tourney_stats",
+    "ca_fitter_create", "ca_fitter_destroy", "ca_fitter_set_weights", "ca_fitter_get_weights", "ca_fitter_set_optimizer",
+    "ca_fitter_get_optimizer", "ca_fitter_set_data", "ca_fitter_train", "ca_fitter_evaluate", "ca_fitter_gradients",
 ]
 
 
@@ -139,11 +141,31 @@ def declare(L):
     L.ca_tourney_match_score.argtypes = [vp, C.c_int32, f32p]
     L.ca_tourney_trace.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p]
     L.ca_tourney_stats.argtypes = [vp, C.POINTER(CaStats)]
+    f64p = C.POINTER(C.c_double)
+    fitter = hasattr(L, "ca_fitter_create")  # the emulation build of the engine (tests/emu) has no training kernels
+    if fitter:
+        _declare_fitter(L, vp, f64p)
     for name in EXPORTS:
+        if name.startswith("ca_fitter_") and not fitter:
+            continue
         fn = getattr(L, name)
-        if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy"):
+        if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy"):
             fn.restype = C.c_int
     return L
+
+
+def _declare_fitter(L, vp, f64p):
+    L.ca_fitter_create.argtypes = [C.c_int, C.c_int32, C.POINTER(vp)]
+    L.ca_fitter_destroy.argtypes = [vp]
+    L.ca_fitter_destroy.restype = None
+    L.ca_fitter_set_weights.argtypes = [vp, f32p, C.c_size_t]
+    L.ca_fitter_get_weights.argtypes = [vp, f32p, C.c_size_t]
+    L.ca_fitter_set_optimizer.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_int64]
+    L.ca_fitter_get_optimizer.argtypes = [vp, f32p, f32p, C.c_size_t, C.POINTER(C.c_int64)]
+    L.ca_fitter_set_data.argtypes = [vp, f32p, f32p, f32p, C.c_int32]
+    L.ca_fitter_train.argtypes = [vp, i32p, C.c_int32, C.c_int32, C.c_float, f64p, f32p]
+    L.ca_fitter_evaluate.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, f64p]
+    L.ca_fitter_gradients.argtypes = [vp, i32p, C.c_int32, f32p, f64p]
 
 
 _lib = None

@@ -36,6 +36,8 @@ extern "C" unsigned long long *co_emu_sb_ply(void) { return &co_sb_ply[0][0]; }
 
 static thread_local std::string g_last_error;
 extern "C" const char *ca_last_error(void) { return g_last_error.c_str(); }
+/* for the entry points of the other sources (nn_train.hip) */
+void co_set_last_error(const std::string &m) { g_last_error = m; }
 
 #define CA_TRY try {
 #define CA_CATCH                          \

@@ -1,0 +1,217 @@
+"""Network training on the device: the reference's Keras `model.fit` step (corintho_ai/python/main.pyx:221-272,
+model and compile of wrapper.py:256-282) for mlp12x100, with the HIP kernels of csrc/nn_train.hip.
+
+    res = fit(weights, game_states, eval_labels, prob_labels, epochs=10)
+    trainer.set_net(NET_MLP12X100, res.best_weights)
+
+The arrays are what samples_io.samples_for_training returns.  What Keras does and what is reproduced here:
+  * the last `validation_split` of the rows validate, split before any shuffling (floor(n * (1 - split)) train);
+  * every epoch the training rows go in a fresh permutation, in batches of `batch_size` (the last one partial).
+    Keras's shuffle generator cannot be matched: the permutation is numpy's, seeded by `seed`;
+  * Adam (TF ResourceApplyAdam, epsilon 1e-7) on MSE(value) + 0.25 x categorical cross-entropy(policy), BatchNorm
+    in training mode with moving statistics at momentum 0.99 (the device kernels, DESIGN.md "Network training");
+  * ModelCheckpoint(monitor="val_loss", save_best_only=True): the weights and optimizer state at the end of the first
+    epoch whose val_loss is strictly below every earlier one;
+  * ReduceLROnPlateau(factor=anneal_factor, patience=patience), min_delta 1e-4, no cooldown, no min_lr.
+"""
+import ctypes as C
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _lib
+from .nets import GAME_STATE_SIZE, MLP_NUM_WEIGHTS, NUM_MOVES
+
+MIN_DELTA = 1e-4  # keras.callbacks.ReduceLROnPlateau default
+
+
+def _f32(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if shape is not None and a.shape != shape:
+        a = a.reshape(shape)
+    return a
+
+
+def _ptr(a, t=C.c_float):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+class Fitter:
+    """One device's mlp12x100 fitter (include/corintho_hip.h, "network training").  Losses come back as
+    (value + 0.25 policy, value, policy)."""
+
+    def __init__(self, max_batch=2048, device=0):
+        self._L = _lib.load()
+        self._h = C.c_void_p()
+        self.max_batch = int(max_batch)
+        _lib.check(self._L, self._L.ca_fitter_create(int(device), self.max_batch, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            self._L.ca_fitter_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _check(self, rc):
+        _lib.check(self._L, rc)
+
+    def set_weights(self, weights):
+        w = _f32(weights).ravel()
+        self._check(self._L.ca_fitter_set_weights(self._h, _ptr(w), w.size))
+
+    def get_weights(self):
+        w = np.zeros(MLP_NUM_WEIGHTS, np.float32)
+        self._check(self._L.ca_fitter_get_weights(self._h, _ptr(w), w.size))
+        return w
+
+    def set_optimizer(self, m, v, iterations):
+        m, v = _f32(m).ravel(), _f32(v).ravel()
+        if m.size != v.size:
+            raise ValueError("m and v differ in size")
+        self._check(self._L.ca_fitter_set_optimizer(self._h, _ptr(m), _ptr(v), m.size, int(iterations)))
+
+    def get_optimizer(self):
+        """(m, v, iterations)"""
+        m = np.zeros(MLP_NUM_WEIGHTS, np.float32)
+        v = np.zeros(MLP_NUM_WEIGHTS, np.float32)
+        it = C.c_int64()
+        self._check(self._L.ca_fitter_get_optimizer(self._h, _ptr(m), _ptr(v), m.size, C.byref(it)))
+        return m, v, int(it.value)
+
+    def set_data(self, game_states, eval_labels, prob_labels):
+        s = _f32(game_states)
+        n = s.shape[0] if s.ndim else 0
+        s = _f32(s, (n, GAME_STATE_SIZE))
+        e = _f32(eval_labels, (n,))
+        p = _f32(prob_labels, (n, NUM_MOVES))
+        self._data = (s, e, p)  # the device copy is taken at once; kept only for the caller's inspection
+        self._check(self._L.ca_fitter_set_data(self._h, _ptr(s), _ptr(e), _ptr(p), n))
+
+    def train(self, rows, batch_size, learning_rate, batch_losses=False):
+        """one epoch over `rows` in that order; returns the three mean losses (and the [batches, 3] per-batch ones)"""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        out = np.zeros(3, np.float64)
+        nb = -(-r.size // int(batch_size)) if batch_size > 0 else 0
+        per = np.zeros((max(nb, 1), 3), np.float32) if batch_losses else None
+        self._check(self._L.ca_fitter_train(self._h, _ptr(r, C.c_int32), r.size, int(batch_size),
+                                            float(np.float32(learning_rate)), _ptr(out, C.c_double),
+                                            _ptr(per) if per is not None else None))
+        return (tuple(out), per) if batch_losses else tuple(out)
+
+    def evaluate(self, row0, n_rows, batch_size):
+        out = np.zeros(3, np.float64)
+        self._check(self._L.ca_fitter_evaluate(self._h, int(row0), int(n_rows), int(batch_size), _ptr(out, C.c_double)))
+        return tuple(out)
+
+    def gradients(self, rows):
+        """(gradient of the batch loss in the weight layout, the three losses); no update"""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        g = np.zeros(MLP_NUM_WEIGHTS, np.float32)
+        out = np.zeros(3, np.float64)
+        self._check(self._L.ca_fitter_gradients(self._h, _ptr(r, C.c_int32), r.size, _ptr(g), _ptr(out, C.c_double)))
+        return g, tuple(out)
+
+
+@dataclass
+class FitResult:
+    best_weights: np.ndarray      # ModelCheckpoint(save_best_only): the weights of the best epoch
+    best_optimizer: tuple         # (m, v, iterations) of that epoch
+    best_epoch: int
+    weights: np.ndarray           # after the last epoch
+    optimizer: tuple
+    learning_rate: float          # after the last epoch's ReduceLROnPlateau
+    history: dict = field(default_factory=dict)  # one entry per epoch in each list
+
+
+HISTORY_KEYS = ("loss", "value_loss", "policy_loss", "val_loss", "val_value_loss", "val_policy_loss", "lr")
+
+
+def split_index(n, validation_split):
+    """keras.engine.data_adapter.train_validation_split: rows [0, split_at) train"""
+    return int(np.floor(n * (1.0 - validation_split)))
+
+
+def epoch_order(rng, n_train, shuffle):
+    return rng.permutation(n_train).astype(np.int32) if shuffle else np.arange(n_train, dtype=np.int32)
+
+
+def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, batch_size=2048, epochs=1,
+        validation_split=0.3, shuffle=True, anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, device=0,
+        _backend=None):
+    """main.pyx:249-260 `model.fit(...)` with its callbacks; see the module docstring.  Returns a FitResult.
+    optimizer_state: (m, v, iterations) to resume from; None starts Adam from zeros, as a freshly compiled model."""
+    w = _f32(weights).ravel()
+    if w.size != MLP_NUM_WEIGHTS:
+        raise ValueError("fit: mlp12x100 weights have %d floats, got %d" % (MLP_NUM_WEIGHTS, w.size))
+    states = _f32(game_states)
+    n = states.shape[0] if states.ndim == 2 else -1
+    if states.ndim != 2 or states.shape[1] != GAME_STATE_SIZE:
+        raise ValueError("fit: game_states must be [n, %d]" % GAME_STATE_SIZE)
+    evals = _f32(eval_labels).ravel()
+    probs = _f32(prob_labels)
+    if evals.size != n or probs.shape != (n, NUM_MOVES):
+        raise ValueError("fit: eval_labels must be [n] and prob_labels [n, %d] for n = %d" % (NUM_MOVES, n))
+    if int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError("fit: batch_size must be a positive integer")
+    if int(epochs) != epochs or epochs < 1:
+        raise ValueError("fit: epochs must be a positive integer")
+    if not 0.0 < validation_split < 1.0:
+        raise ValueError("fit: validation_split must lie in (0, 1)")
+    if not learning_rate > 0.0 or not 0.0 < anneal_factor < 1.0 or int(patience) != patience or patience < 0:
+        raise ValueError("fit: learning_rate > 0, anneal_factor in (0, 1) and patience >= 0 are required")
+    split_at = split_index(n, validation_split)
+    if split_at < 1 or split_at >= n:
+        raise ValueError("fit: %d rows leave no training or no validation rows at validation_split=%g"
+                         % (n, validation_split))
+    batch_size, epochs = int(batch_size), int(epochs)
+
+    own = _backend is None
+    be = Fitter(max_batch=batch_size, device=device) if own else _backend
+    try:
+        be.set_weights(w)
+        if optimizer_state is None:
+            be.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
+        else:
+            m, v, it = optimizer_state
+            be.set_optimizer(m, v, it)
+        be.set_data(states, evals, probs)
+        rng = np.random.default_rng(seed)
+        lr = np.float32(learning_rate)
+        history = {k: [] for k in HISTORY_KEYS}
+        ckpt_best, plateau_best, wait = np.inf, np.inf, 0
+        best = None
+        for epoch in range(epochs):
+            order = epoch_order(rng, split_at, shuffle)
+            loss = be.train(order, batch_size, lr)
+            val = be.evaluate(split_at, n - split_at, batch_size)
+            for k, x in zip(HISTORY_KEYS, tuple(loss) + tuple(val) + (lr,)):
+                history[k].append(float(x))
+            val_loss = val[0]
+            if val_loss < ckpt_best:  # ModelCheckpoint(save_best_only=True): np.less
+                ckpt_best = val_loss
+                best = (be.get_weights(), be.get_optimizer(), epoch)
+            if val_loss < plateau_best - MIN_DELTA:  # ReduceLROnPlateau, mode "min"
+                plateau_best, wait = val_loss, 0
+            else:
+                wait += 1
+                if wait >= patience:
+                    lr = np.float32(lr * np.float32(anneal_factor))
+                    wait = 0
+        if best is None:  # every val_loss NaN: Keras saves nothing either; report the starting point
+            raise FloatingPointError("fit: no epoch produced a finite val_loss")
+        return FitResult(best_weights=best[0], best_optimizer=best[1], best_epoch=best[2], weights=be.get_weights(),
+                         optimizer=be.get_optimizer(), learning_rate=float(lr), history=history)
+    finally:
+        if own:
+            be.close()

@@ -306,6 +306,35 @@ int ca_rng_draw(int device, uint32_t seed, int32_t n, int32_t chunk, uint32_t *o
 /* floating-point contract probe, see kernels.h co_k_fp_probe: in [n][8] -> out [n][8] */
 int ca_fp_probe(int device, const float *in, int32_t n, float *out);
 
+
+/* ---- network training (not in the reference, whose generation step calls Keras model.fit, main.pyx:221-272) ----
+ * A ca_fitter fits mlp12x100 (CO_NET_MLP12X100's weights) on the device the way the reference's compiled Keras model
+ * does: Adam, MSE on the value head plus 0.25 x categorical cross-entropy on the policy head, BatchNormalization in
+ * training mode (batch mean and biased variance; moving statistics with momentum 0.99).  Weights, and Adam's m and v,
+ * are in the flat Keras get_weights() layout of ca_trainer_set_net (m and v are 0 at the moving statistics).  Losses:
+ * out_losses[3] = {value + 0.25 policy, value (MSE), policy (cross-entropy)}, means over the rows. */
+typedef struct ca_fitter ca_fitter;
+/* max_batch: the largest batch of ca_fitter_train / _evaluate / _gradients */
+int ca_fitter_create(int device, int32_t max_batch, ca_fitter **out);
+void ca_fitter_destroy(ca_fitter *f);
+int ca_fitter_set_weights(ca_fitter *f, const float *weights, size_t n_floats);
+int ca_fitter_get_weights(ca_fitter *f, float *weights, size_t n_floats);
+/* Adam's slots and step count (Keras optimizer.iterations); a new fitter starts from zeros */
+int ca_fitter_set_optimizer(ca_fitter *f, const float *m, const float *v, size_t n_floats, int64_t iterations);
+int ca_fitter_get_optimizer(ca_fitter *f, float *m, float *v, size_t n_floats, int64_t *iterations);
+/* the sample set, as samples_io.samples_for_training returns it; copied to the device */
+int ca_fitter_set_data(ca_fitter *f, const float *states /* [n][70] */, const float *evals /* [n] */,
+                       const float *probs /* [n][96] */, int32_t n);
+/* one epoch: batches of `batch` rows taken in the order of rows[] (the last one partial), one Adam step each at
+ * learning rate `learning_rate`.  out_losses: means of the batch losses (each before its step) weighted by batch size;
+ * batch_losses (may be null): [ceil(n_rows / batch)][3] */
+int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows, int32_t batch, float learning_rate,
+                    double *out_losses, float *batch_losses);
+/* inference mode (moving statistics) on rows [row0, row0 + n_rows), in batches of `batch` */
+int ca_fitter_evaluate(ca_fitter *f, int32_t row0, int32_t n_rows, int32_t batch, double *out_losses);
+/* the gradient of one batch's loss with respect to every weight (0 at the moving statistics); nothing is updated */
+int ca_fitter_gradients(ca_fitter *f, const int32_t *rows, int32_t n_rows, float *grads, double *out_losses);
+
 #ifdef __cplusplus
 }
 #endif

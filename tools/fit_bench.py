@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""Times the mlp12x100 training step (csrc/nn_train.hip) on one GPU: ms per step at `--batch` rows on a sample set of
+`--rows` rows, rows/s and achieved FLOP/s against the fp32 matrix peak.  A step is 3 x 253.4 KFLOP per row by the
+algorithm (forward, and the two products of the backward pass).  Timing: a synchronised host clock around one
+ca_fitter_train call of `--steps` steps (the call ends by reading its losses back).
+
+--torch also times the same step written in torch-ROCm on the same GPU, in the same process, alternating with the HIP
+path: autograd through the Keras BatchNorm (batch mean, biased variance), Adam as TF's ResourceApplyAdam (epsilon
+outside the root) with torch._foreach ops, moving statistics at momentum 0.99.  It is the yardstick the HIP step has to
+beat; torch is not part of the product path.
+
+    python tools/fit_bench.py --torch [--rows 1000000 --batch 2048 --steps 200 --reps 3] [--out file.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from corintho_ai_amd import nets  # noqa: E402
+from corintho_ai_amd.fit import Fitter  # noqa: E402
+
+FLOP_PER_ROW_STEP = 3 * 2.0 * (70 * 100 + 11 * 100 * 100 + 100 * 97)
+PEAK_FP32_MATRIX = 157.3e12
+PRODUCTION_STEPS = 12_000  # ~2.5 M training rows x 10 epochs at batch 2048
+
+
+def samples(n, seed=0):
+    rng = np.random.default_rng(seed)
+    s = np.zeros((n, 70), np.float32)
+    s[:, :64] = rng.integers(0, 2, (n, 64))
+    s[:, 64:] = rng.integers(0, 5, (n, 6)) * 0.25
+    p = rng.random((n, 96), dtype=np.float32)
+    p /= p.sum(1, keepdims=True)
+    z = rng.choice(np.array([-1.0, 0.0, 1.0], np.float32), n)
+    return s, z, p
+
+
+class TorchStep:
+    """the Keras step in torch-ROCm (autograd)"""
+
+    def __init__(self, w, data, device):
+        import torch
+
+        self.torch = torch
+        self.dev = device
+        lay, p, fi = [], 0, 70
+        for _ in range(12):
+            lay.append((p, fi))
+            p += fi * 100 + 500
+            fi = 100
+        self.lay, self.head = lay, p
+        W = torch.tensor(w, device=device)
+        self.params, self.stats = [], []
+        for k, fi in lay:
+            b = k + fi * 100
+            self.params += [W[k:b].view(fi, 100).clone(), W[b:b + 100].clone(), W[b + 100:b + 200].clone(),
+                            W[b + 200:b + 300].clone()]
+            self.stats += [W[b + 300:b + 400].clone(), W[b + 400:b + 500].clone()]
+        h = self.head
+        self.params += [W[h:h + 100].view(100, 1).clone(), W[h + 100:h + 101].clone(),
+                        W[h + 101:h + 9701].view(100, 96).clone(), W[h + 9701:h + 9797].clone()]
+        for q in self.params:
+            q.requires_grad_(True)
+        self.m = [torch.zeros_like(q) for q in self.params]
+        self.v = [torch.zeros_like(q) for q in self.params]
+        self.it = 0
+        self.s, self.z, self.p = (torch.tensor(a, device=device) for a in data)
+
+    def step(self, rows, lr=1e-3):
+        torch = self.torch
+        x = self.s[rows]
+        P = self.params
+        batch_stats = []
+        for i in range(12):
+            k, b, g, be = P[4 * i:4 * i + 4]
+            a = torch.relu(x @ k + b)
+            mu = a.mean(0)
+            var = ((a - mu) ** 2).mean(0)
+            batch_stats += [mu.detach(), var.detach()]
+            x = g * ((a - mu) * torch.rsqrt(var + 1e-3)) + be
+        kv, bv, kp, bp = P[48:]
+        v = (x @ kv).view(-1) + bv
+        logits = x @ kp + bp
+        loss = ((torch.tanh(v) - self.z[rows]) ** 2).mean() + 0.25 * (
+            -(self.p[rows] * torch.log_softmax(logits, 1)).sum(1)).mean()
+        grads = torch.autograd.grad(loss, P)
+        with torch.no_grad():
+            self.it += 1
+            t = np.float32(self.it)
+            lr_t = float(np.float32(lr) * np.sqrt(np.float32(1) - np.float32(0.999) ** t) / (np.float32(1) - np.float32(0.9) ** t))
+            torch._foreach_lerp_(self.m, grads, 1 - 0.9)
+            torch._foreach_lerp_(self.v, torch._foreach_mul(grads, grads), 1 - 0.999)
+            den = torch._foreach_sqrt(self.v)
+            torch._foreach_add_(den, 1e-7)
+            torch._foreach_addcdiv_(P, self.m, den, value=-lr_t)
+            torch._foreach_lerp_(self.stats, batch_stats, 0.01)
+        return loss
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--batch", type=int, default=2048)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--torch", action="store_true")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    data = samples(a.rows)
+    w = nets.init_mlp12x100(0, bn_noise=True)
+    rng = np.random.default_rng(1)
+    need = (a.steps + a.warmup) * a.batch
+    if max(a.steps, a.warmup) * a.batch > a.rows:
+        raise SystemExit("fit_bench: one call trains at most --rows rows (an epoch): raise --rows or lower --steps")
+    order = np.concatenate([rng.permutation(a.rows) for _ in range(-(-need // a.rows))])[:need].astype(np.int32)
+    ts = None
+    if a.torch:  # torch's runtime comes up first, before the engine library opens the device
+        import torch
+
+        ts = TorchStep(w, data, "cuda:%d" % a.device)
+        torder = torch.tensor(order.astype(np.int64), device=ts.dev)
+    f = Fitter(max_batch=a.batch, device=a.device)
+    f.set_data(*data)
+    f.set_weights(w)
+    f.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
+    f.train(order[:a.warmup * a.batch], a.batch, 1e-3)
+    if ts:
+        for i in range(a.warmup):
+            ts.step(torder[i * a.batch:(i + 1) * a.batch])
+        torch.cuda.synchronize(ts.dev)
+    hip, tor = [], []
+    timed = order[a.warmup * a.batch:]
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        f.train(timed, a.batch, 1e-3)
+        hip.append((time.perf_counter() - t0) * 1e3 / a.steps)
+        if ts:
+            torch.cuda.synchronize(ts.dev)
+            t0 = time.perf_counter()
+            for i in range(a.steps):
+                ts.step(torder[(a.warmup + i) * a.batch:(a.warmup + i + 1) * a.batch])
+            torch.cuda.synchronize(ts.dev)
+            tor.append((time.perf_counter() - t0) * 1e3 / a.steps)
+    f.close()
+
+    def rec(ms):
+        best = min(ms)
+        flops = FLOP_PER_ROW_STEP * a.batch / (best * 1e-3)
+        return {"ms_per_step": best, "ms_per_step_all": ms, "rows_per_s": a.batch / (best * 1e-3), "flop_per_s": flops,
+                "share_of_fp32_matrix_peak": flops / PEAK_FP32_MATRIX,
+                "production_fit_s": best * 1e-3 * PRODUCTION_STEPS}
+
+    out = {"batch": a.batch, "rows": a.rows, "steps": a.steps, "flop_per_row_step": FLOP_PER_ROW_STEP, "hip": rec(hip)}
+    if tor:
+        out["torch"] = rec(tor)
+        out["hip_speedup_over_torch"] = min(tor) / min(hip)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
