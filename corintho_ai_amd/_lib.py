@@ -79,7 +79,7 @@ EXPORTS = [
     "ca_tourney_create", "ca_tourney_destroy", "ca_tourney_set_log_folder", "ca_tourney_add_player", "ca_tourney_add_match", "ca_tourney_all_done",
     "ca_tourney_num_requests", "ca_tourney_write_requests", "ca_tourney_do_iteration", "ca_tourney_write_scores",
     "ca_tourney_set_net", "ca_tourney_run", "ca_tourney_set_exact_offsets", "ca_tourney_num_matches", "ca_tourney_match_info", "ca_tourney_match_score", "ca_tourney_trace", "ca_tourney_stats",
-    "ca_fitter_create", "ca_fitter_destroy", "ca_fitter_set_weights", "ca_fitter_get_weights", "ca_fitter_set_optimizer",
+    "ca_fitter_create", "ca_fitter_create_net", "ca_fitter_destroy", "ca_fitter_set_weights", "ca_fitter_get_weights", "ca_fitter_set_optimizer",
     "ca_fitter_get_optimizer", "ca_fitter_set_data", "ca_fitter_train", "ca_fitter_evaluate", "ca_fitter_gradients",
 ]
 
@@ -156,6 +156,7 @@ def declare(L):
 
 def _declare_fitter(L, vp, f64p):
     L.ca_fitter_create.argtypes = [C.c_int, C.c_int32, C.POINTER(vp)]
+    L.ca_fitter_create_net.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.ca_fitter_destroy.argtypes = [vp]
     L.ca_fitter_destroy.restype = None
     L.ca_fitter_set_weights.argtypes = [vp, f32p, C.c_size_t]

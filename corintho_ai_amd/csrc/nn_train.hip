@@ -16,6 +16,10 @@
 // Every cross-workgroup sum is written as partials and combined in a fixed order by a later launch: no float atomics,
 // no grid-wide barriers, so a step is bitwise reproducible.  The weights live in the Keras get_weights() layout
 // (nn.h) and the kernels read them there with bounds checks, so there is no padded copy to keep in step.
+//
+// rescnn4 (ca_fitter_create_net with CA_NET_RESCNN4) is trained by the same recipe on the network of nets.py: the
+// convolutions and the BatchNorm over channels are the kernels of nn_train_conv.hip, the 1x1 convolutions and dense
+// layers of the heads go through ft_k_gemm, and the data, loss, Adam and guard code below is shared by both networks.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -24,6 +28,7 @@
 
 #include "../../include/corintho_hip.h"
 #include "nn.h"
+#include "nn_train_conv.h"
 
 #define FT_PADW 112    /* activation row stride: 100 features padded to 7 tiles of 16 */
 #define FT_IN_LD 80    /* gathered input row stride: 70 padded to 5 tiles */
@@ -234,10 +239,10 @@ __global__ __launch_bounds__(256) void ft_k_loss(const float *__restrict__ H, co
   d[98] = ce;
 }
 
-/* Column sums of Hd over the B rows (fixed order): the head biases' gradients (when g is given) and the batch's
- * value and policy loss sums (loss[0], loss[1]). */
+/* Column sums of Hd over the B rows (fixed order): the head biases' gradients (when g is given; the policy bias at
+ * off_bp, the value bias at off_bv) and the batch's value and policy loss sums (loss[0], loss[1]). */
 __global__ __launch_bounds__(1024) void ft_k_head_reduce(const float *__restrict__ Hd, int B, float *__restrict__ g,
-                                                        float *__restrict__ loss) {
+                                                        int off_bp, int off_bv, float *__restrict__ loss) {
   __shared__ float red[(FT_BN_RG + 1) * 16];
   const int f = blockIdx.x * 16 + (threadIdx.x & 15), rg = threadIdx.x >> 4;
   float s = 0.0f;
@@ -246,28 +251,51 @@ __global__ __launch_bounds__(1024) void ft_k_head_reduce(const float *__restrict
   s = ft_colsum(red, s);
   if (rg != 0 || f >= 99) return;
   if (f < 96) {
-    if (g) g[FT_BP + f] = s;
+    if (g) g[off_bp + f] = s;
   } else if (f == 96) {
-    if (g) g[FT_BV] = s;
+    if (g) g[off_bv] = s;
   } else {
     loss[f - 97] = s;
   }
 }
 
-/* The end of a step, one thread per weight: its gradient is the sum of the `nsplit` partials in order.  sidx[i] < 0:
- * a trainable weight, Adam (TF ResourceApplyAdam, epsilon outside the root); sidx[i] >= 0: a moving statistic, moved
- * toward the batch statistic stat[sidx[i]] with momentum 0.99.  apply = 0: write the summed gradient to gout only. */
+/* ReLU backward of a dense layer's output A[B][ld] in place on dA, and the column sums of the result (the layer's bias
+ * gradient) to gbias[0..ncol), in the fixed order of ft_colsum */
+__global__ __launch_bounds__(1024) void ft_k_relu_bwd(float *__restrict__ dA, const float *__restrict__ A, int B, int ld,
+                                                     int ncol, float *__restrict__ gbias) {
+  __shared__ float red[(FT_BN_RG + 1) * 16];
+  const int f = blockIdx.x * 16 + (threadIdx.x & 15), rg = threadIdx.x >> 4;
+  float s = 0.0f;
+  if (f < ncol)
+    for (int r = rg; r < B; r += FT_BN_RG) {
+      const long e = (long)r * ld + f;
+      const float d = A[e] > 0.0f ? dA[e] : 0.0f;
+      dA[e] = d;
+      s += d;
+    }
+  s = ft_colsum(red, s);
+  if (rg == 0 && f < ncol) gbias[f] = s;
+}
+
+/* The end of a step, one thread per weight of the nw: its gradient is the sum of its partials in order.  sidx[i] < 0:
+ * a trainable weight with ns0 (FT_SPLIT0), ns1 (FT_SPLIT1) or one (FT_WHOLE) partial, Adam (TF ResourceApplyAdam,
+ * epsilon outside the root); sidx[i] >= 0: a moving statistic, moved toward the batch statistic stat[sidx[i]] with
+ * momentum 0.99.  apply = 0: write the summed gradient to gout only. */
+#define FT_SPLIT0 -1
+#define FT_SPLIT1 -2
+#define FT_WHOLE -3
 __global__ __launch_bounds__(256) void ft_k_update(float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
-                                                  const float *__restrict__ g, int nsplit, const int32_t *__restrict__ sidx,
-                                                  const float *__restrict__ stat, float lr_t, int apply,
-                                                  float *__restrict__ gout) {
+                                                  const float *__restrict__ g, int nw, int ns0, int ns1,
+                                                  const int32_t *__restrict__ sidx, const float *__restrict__ stat,
+                                                  float lr_t, int apply, float *__restrict__ gout) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= FT_NW) return;
+  if (i >= nw) return;
   const int si = sidx[i];
+  const int nsplit = si == FT_SPLIT0 ? ns0 : si == FT_SPLIT1 ? ns1 : 1;
   if (!apply) {
     float s = 0.0f;
     if (si < 0)
-      for (int k = 0; k < nsplit; ++k) s += g[(long)k * FT_NW + i];
+      for (int k = 0; k < nsplit; ++k) s += g[(long)k * nw + i];
     gout[i] = s;
     return;
   }
@@ -277,7 +305,7 @@ __global__ __launch_bounds__(256) void ft_k_update(float *__restrict__ w, float 
     return;
   }
   float s = 0.0f;
-  for (int k = 0; k < nsplit; ++k) s += g[(long)k * FT_NW + i];
+  for (int k = 0; k < nsplit; ++k) s += g[(long)k * nw + i];
   const float mt = m[i] + (s - m[i]) * (1.0f - 0.9f);
   const float vt = v[i] + (s * s - v[i]) * (1.0f - 0.999f);
   m[i] = mt;
@@ -309,8 +337,32 @@ struct FtError : std::runtime_error {
 
 }  // namespace
 
+/* rescnn4's flat layout (nets._rescnn4_shapes): convolution l = 0 (stem) .. 8 has its kernel at conv_k[l] and bias,
+ * gamma, beta, moving mean, moving variance (64 each) from conv_b[l]; the heads' 1x1 convolutions likewise with 4 and 2
+ * channels from p_b and v_b */
+struct FcLayout {
+  int conv_k[9], conv_b[9];
+  int p_k, p_b, p_dk, p_db, v_k, v_b, v_d1k, v_d1b, v_d2k, v_d2b, nw;
+  FcLayout() {
+    int p = 0;
+    for (int l = 0; l < 9; ++l) {
+      conv_k[l] = p;
+      p += 9 * (l == 0 ? 10 : FC_C) * FC_C;
+      conv_b[l] = p;
+      p += 5 * FC_C;
+    }
+    p_k = p, p_b = p_k + FC_C * 4, p_dk = p_b + 5 * 4, p_db = p_dk + 64 * CA_NUM_MOVES;
+    v_k = p_db + CA_NUM_MOVES, v_b = v_k + FC_C * 2, v_d1k = v_b + 5 * 2, v_d1b = v_d1k + 32 * 64;
+    v_d2k = v_d1b + 64, v_d2b = v_d2k + 64, nw = v_d2b + 1;
+  }
+};
+#define FC_NBN 11 /* BatchNorms of rescnn4: nine convolutions, the policy and the value head's 1x1 */
+
 struct ca_fitter {
   int device = 0;
+  int net = CA_NET_MLP12X100;
+  int nw = FT_NW; /* floats of the weight vector */
+  FcLayout L;
   int max_batch = 0;
   int64_t iterations = 0;
   int32_t n = 0, idx_cap = 0;
@@ -318,39 +370,90 @@ struct ca_fitter {
   FtBuf<float> w, m, v, g, gsum, stat, x0, act, y, h, hd, dy, dz, loss;
   FtBuf<float> states, evals, probs;
   FtBuf<int32_t> sidx, idx;
+  /* rescnn4: the trunk's activations (nine Z, five X, four T), its three gradient buffers (G, GB, DZ), the heads' small
+   * buffers, the mirrored transposed kernels and the partials of the two-stage reductions */
+  FtBuf<float> cact, cgrad, chead, wt, wpart, bnpart;
   std::vector<float> hloss;
 
-  void init(int dev, int mb) {
+  void init(int dev, int kind, int mb) {
     device = dev;
+    net = kind;
     max_batch = mb;
+    nw = kind == CA_NET_RESCNN4 ? L.nw : FT_NW;
     rt_set_device(dev);
     rt_stream_create(&s);
     const size_t rows = (size_t)((mb + 15) / 16 * 16);
-    w.alloc(FT_NW, s);
-    m.alloc(FT_NW, s);
-    v.alloc(FT_NW, s);
-    g.alloc((size_t)FT_NSPLIT * FT_NW, s);
-    gsum.alloc(FT_NW, s);
-    stat.alloc((size_t)2 * CO_MLP_LAYERS * FT_PADW, s);
-    x0.alloc(rows * FT_IN_LD, s);
-    act.alloc((size_t)CO_MLP_LAYERS * rows * FT_PADW, s);
-    y.alloc((size_t)CO_MLP_LAYERS * rows * FT_PADW, s);
+    w.alloc(nw, s);
+    m.alloc(nw, s);
+    v.alloc(nw, s);
+    g.alloc((size_t)FT_NSPLIT * nw, s);
+    gsum.alloc(nw, s);
     h.alloc(rows * FT_PADW, s);
     hd.alloc(rows * FT_PADW, s);
-    dy.alloc(rows * FT_PADW, s);
-    dz.alloc(rows * FT_PADW, s);
-    /* stat index of every weight: -1 trainable, else the batch statistic its moving average follows */
-    std::vector<int32_t> si(FT_NW, -1);
-    for (int l = 0; l < CO_MLP_LAYERS; ++l)
-      for (int f = 0; f < CO_MLP_WIDTH; ++f) {
-        si[ft_off(l, 3) + f] = 2 * l * FT_PADW + f;
-        si[ft_off(l, 4) + f] = (2 * l + 1) * FT_PADW + f;
+    /* stat index of every weight: < 0 trainable (the number of its gradient partials, ft_k_update), else the batch
+     * statistic its moving average follows */
+    std::vector<int32_t> si(nw, FT_SPLIT0);
+    if (kind == CA_NET_RESCNN4) {
+      stat.alloc((size_t)FC_NBN * 128, s);
+      x0.alloc(rows * 16 * FC_IN_LD, s);
+      cact.alloc((size_t)18 * rows * 16 * FC_C, s);
+      cgrad.alloc((size_t)3 * rows * 16 * FC_C, s);
+      chead.alloc(rows * (size_t)(2 * 64 + 4 * 64 + 4 * 32), s);
+      wt.alloc((size_t)8 * FC_WG_FLOATS, s);
+      wpart.alloc((size_t)FC_WG_CHUNKS * FC_WG_FLOATS, s);
+      bnpart.alloc((size_t)FC_BN_SCRATCH, s);
+      si.assign(nw, FT_WHOLE);
+      for (int e = 0; e < 64 * CA_NUM_MOVES; ++e) si[L.p_dk + e] = FT_SPLIT0; /* products over the B rows */
+      for (int e = 0; e < 32 * 64; ++e) si[L.v_d1k + e] = FT_SPLIT0;
+      for (int e = 0; e < 64; ++e) si[L.v_d2k + e] = FT_SPLIT0;
+      for (int e = 0; e < FC_C * 4; ++e) si[L.p_k + e] = FT_SPLIT1; /* products over the B * 16 (position, pixel) rows */
+      for (int e = 0; e < FC_C * 2; ++e) si[L.v_k + e] = FT_SPLIT1;
+      for (int j = 0; j < FC_NBN; ++j) {
+        const int C = bn_c(j), mean = bn_w(j) + 2 * C;
+        for (int c = 0; c < C; ++c) {
+          si[mean + c] = j * 128 + c;
+          si[mean + C + c] = j * 128 + 64 + c;
+        }
       }
-    sidx.alloc(FT_NW, s);
-    rt_h2d(sidx.p, si.data(), FT_NW * sizeof(int32_t), s);
+    } else {
+      stat.alloc((size_t)2 * CO_MLP_LAYERS * FT_PADW, s);
+      x0.alloc(rows * FT_IN_LD, s);
+      act.alloc((size_t)CO_MLP_LAYERS * rows * FT_PADW, s);
+      y.alloc((size_t)CO_MLP_LAYERS * rows * FT_PADW, s);
+      dy.alloc(rows * FT_PADW, s);
+      dz.alloc(rows * FT_PADW, s);
+      for (int l = 0; l < CO_MLP_LAYERS; ++l)
+        for (int f = 0; f < CO_MLP_WIDTH; ++f) {
+          si[ft_off(l, 3) + f] = 2 * l * FT_PADW + f;
+          si[ft_off(l, 4) + f] = (2 * l + 1) * FT_PADW + f;
+        }
+    }
+    sidx.alloc(nw, s);
+    rt_h2d(sidx.p, si.data(), nw * sizeof(int32_t), s);
     rt_sync(s);
   }
   ~ca_fitter() { rt_stream_destroy(s); }
+
+  /* rescnn4's BatchNorm j: channels, and the offset of its gamma (beta, moving mean, moving variance follow) */
+  int bn_c(int j) const { return j < 9 ? FC_C : j == 9 ? 4 : 2; }
+  int bn_w(int j) const { return (j < 9 ? L.conv_b[j] : j == 9 ? L.p_b : L.v_b) + bn_c(j); }
+  size_t crows() const { return (size_t)((max_batch + 15) / 16 * 16) * 16; }
+  float *cZ(int l) { return cact.p + (size_t)l * crows() * FC_C; }        /* convolution l's output, before its BatchNorm */
+  float *cX(int b) { return cact.p + (size_t)(9 + b) * crows() * FC_C; }  /* the stem's (0) and block b - 1's output */
+  float *cT(int b) { return cact.p + (size_t)(14 + b) * crows() * FC_C; } /* block b's first activation */
+  float *cG(int k) { return cgrad.p + (size_t)k * crows() * FC_C; }
+  /* the heads: [B * 16][4] and [B * 16][2] are [B][64] and [B][32] once flattened (pixel * C + channel) */
+  float *hb(int k) { return chead.p + (size_t)k * crows() * 2; }
+  float *h_zp() { return hb(0); }
+  float *h_pa() { return hb(2); }
+  float *h_dpa() { return hb(4); }
+  float *h_dzp() { return hb(6); }
+  float *h_zv() { return hb(8); }
+  float *h_va() { return hb(9); }
+  float *h_dva() { return hb(10); }
+  float *h_dzv() { return hb(11); }
+  float *h_d1() { return hb(12); }
+  float *h_dd1() { return hb(14); }
 
   size_t rows_ld() const { return (size_t)((max_batch + 15) / 16 * 16) * FT_PADW; }
   float *A(int l) { return act.p + l * rows_ld(); }
@@ -373,6 +476,115 @@ struct ca_fitter {
 
   /* forward of rows idx[0..B) (a device pointer); train = batch statistics.  Leaves H = heads' outputs. */
   void forward(const int32_t *rows, int B, bool train) {
+    if (net == CA_NET_RESCNN4)
+      cnn_forward(rows, B, train);
+    else
+      mlp_forward(rows, B, train);
+  }
+  /* the weight gradient of one batch as partials in g; leaves their counts in ns0, ns1 (ft_k_update) */
+  void backward(int B) {
+    if (net == CA_NET_RESCNN4)
+      cnn_backward(B);
+    else
+      ns0 = ns1 = mlp_backward(B);
+  }
+  int ns0 = 1, ns1 = 1;
+  static int split_chunk(int K) { /* rows of one of at most FT_NSPLIT chunks of K, a multiple of 16 */
+    const int kch = (K + FT_NSPLIT - 1) / FT_NSPLIT;
+    return (kch + 15) / 16 * 16;
+  }
+
+  void bn_fwd(int j, const float *Z, const float *res, float *out, int R, bool train) {
+    fc_bn_fwd(s, Z, res, out, R, bn_c(j), w.p + bn_w(j), train ? 1 : 0, bnpart.p, stat.p + j * 128);
+  }
+  void bn_bwd(int j, float *dOut, const float *out, const float *Z, float *dZ, int R, bool keep) {
+    fc_bn_bwd(s, dOut, out, Z, dZ, R, bn_c(j), w.p + bn_w(j), stat.p + j * 128, keep ? 1 : 0, bnpart.p,
+              g.p + bn_w(j) - bn_c(j));
+  }
+
+  void cnn_forward(const int32_t *rows, int B, bool train) {
+    const int R = B * 16;
+    fc_planes(s, states.p, rows, B, x0.p);
+    fc_conv3(s, x0.p, 10, w.p + L.conv_k[0], w.p + L.conv_b[0], cZ(0), B, 0);
+    bn_fwd(0, cZ(0), nullptr, cX(0), R, train);
+    for (int b = 0; b < 4; ++b) {
+      const int l1 = 1 + 2 * b, l2 = 2 + 2 * b;
+      fc_conv3(s, cX(b), FC_C, w.p + L.conv_k[l1], w.p + L.conv_b[l1], cZ(l1), B, 0);
+      bn_fwd(l1, cZ(l1), nullptr, cT(b), R, train);
+      fc_conv3(s, cT(b), FC_C, w.p + L.conv_k[l2], w.p + L.conv_b[l2], cZ(l2), B, 0);
+      bn_fwd(l2, cZ(l2), cX(b), cX(b + 1), R, train);
+    }
+    /* policy: 1x1 convolution to 4 channels, BatchNorm, ReLU, flatten, dense to the 96 logits */
+    FtGemm a = mk(cX(4), FC_C, 1, w.p + L.p_k, 4, 1, h_zp(), 4, 1, R, 4, FC_C);
+    a.bias = w.p + L.p_b;
+    gemm(a);
+    bn_fwd(9, h_zp(), nullptr, h_pa(), R, train);
+    a = mk(h_pa(), 64, 1, w.p + L.p_dk, CA_NUM_MOVES, 1, h.p, FT_PADW, 1, B, CA_NUM_MOVES, 64);
+    a.bias = w.p + L.p_db;
+    gemm(a);
+    /* value: 1x1 convolution to 2 channels, BatchNorm, ReLU, flatten, dense 32 -> 64, ReLU, dense 64 -> 1 */
+    a = mk(cX(4), FC_C, 1, w.p + L.v_k, 2, 1, h_zv(), 2, 1, R, 2, FC_C);
+    a.bias = w.p + L.v_b;
+    gemm(a);
+    bn_fwd(10, h_zv(), nullptr, h_va(), R, train);
+    a = mk(h_va(), 32, 1, w.p + L.v_d1k, 64, 1, h_d1(), 64, 1, B, 64, 32);
+    a.bias = w.p + L.v_d1b, a.relu = 1;
+    gemm(a);
+    a = mk(h_d1(), 64, 1, w.p + L.v_d2k, 1, 1, h.p + 96, FT_PADW, 1, B, 1, 64);
+    a.bias = w.p + L.v_d2b;
+    gemm(a);
+  }
+
+  void cnn_backward(int B) {
+    const int R = B * 16, kb = split_chunk(B), kr = split_chunk(R);
+    ns0 = (B + kb - 1) / kb, ns1 = (R + kr - 1) / kr;
+    float *G = cG(0), *GB = cG(1), *DZ = cG(2);
+    /* policy head: dense kernel, its input's gradient, BatchNorm and ReLU, the 1x1 kernel, G = the trunk output's share */
+    FtGemm a = mk(h_pa(), 1, 64, hd.p, FT_PADW, 1, g.p + L.p_dk, CA_NUM_MOVES, 1, 64, CA_NUM_MOVES, B);
+    a.kchunk = kb, a.c_split = nw;
+    gemm(a);
+    gemm(mk(hd.p, FT_PADW, 1, w.p + L.p_dk, 1, CA_NUM_MOVES, h_dpa(), 64, 1, B, 64, CA_NUM_MOVES));
+    bn_bwd(9, h_dpa(), h_pa(), h_zp(), h_dzp(), R, false);
+    a = mk(cX(4), 1, FC_C, h_dzp(), 4, 1, g.p + L.p_k, 4, 1, FC_C, 4, R);
+    a.kchunk = kr, a.c_split = nw;
+    gemm(a);
+    gemm(mk(h_dzp(), 4, 1, w.p + L.p_k, 1, 4, G, FC_C, 1, R, FC_C, 4));
+    /* value head, added to G */
+    a = mk(h_d1(), 1, 64, hd.p + 96, FT_PADW, 1, g.p + L.v_d2k, 1, 1, 64, 1, B);
+    a.kchunk = kb, a.c_split = nw;
+    gemm(a);
+    gemm(mk(hd.p + 96, FT_PADW, 1, w.p + L.v_d2k, 1, 1, h_dd1(), 64, 1, B, 64, 1));
+    hipLaunchKernelGGL(ft_k_relu_bwd, dim3(4), dim3(1024), 0, s, h_dd1(), (const float *)h_d1(), B, 64, 64, g.p + L.v_d1b);
+    RT_CHECK(hipGetLastError());
+    a = mk(h_va(), 1, 32, h_dd1(), 64, 1, g.p + L.v_d1k, 64, 1, 32, 64, B);
+    a.kchunk = kb, a.c_split = nw;
+    gemm(a);
+    gemm(mk(h_dd1(), 64, 1, w.p + L.v_d1k, 1, 64, h_dva(), 32, 1, B, 32, 64));
+    bn_bwd(10, h_dva(), h_va(), h_zv(), h_dzv(), R, false);
+    a = mk(cX(4), 1, FC_C, h_dzv(), 2, 1, g.p + L.v_k, 2, 1, FC_C, 2, R);
+    a.kchunk = kr, a.c_split = nw;
+    gemm(a);
+    a = mk(h_dzv(), 2, 1, w.p + L.v_k, 1, 2, G, FC_C, 1, R, FC_C, 2);
+    a.accumulate = 1;
+    gemm(a);
+    /* trunk: G is the gradient at block b's output.  Its ReLU-masked copy (kept in G) is both the second BatchNorm's
+     * input gradient and the residual branch's share of the block input's gradient, to which backward-data of the
+     * first convolution is added */
+    fc_wtrans(s, w.p, L.conv_k[1], L.conv_k[2] - L.conv_k[1], 8, wt.p);
+    for (int b = 3; b >= 0; --b) {
+      const int l1 = 1 + 2 * b, l2 = 2 + 2 * b;
+      bn_bwd(l2, G, cX(b + 1), cZ(l2), DZ, R, true);
+      fc_conv3_wgrad(s, cT(b), FC_C, DZ, B, wpart.p, g.p + L.conv_k[l2]);
+      fc_conv3(s, DZ, FC_C, wt.p + (size_t)(l2 - 1) * FC_WG_FLOATS, nullptr, GB, B, 0);
+      bn_bwd(l1, GB, cT(b), cZ(l1), DZ, R, false);
+      fc_conv3_wgrad(s, cX(b), FC_C, DZ, B, wpart.p, g.p + L.conv_k[l1]);
+      fc_conv3(s, DZ, FC_C, wt.p + (size_t)(l1 - 1) * FC_WG_FLOATS, nullptr, G, B, 1);
+    }
+    bn_bwd(0, G, cX(0), cZ(0), DZ, R, false);
+    fc_conv3_wgrad(s, x0.p, 10, DZ, B, wpart.p, g.p + L.conv_k[0]);
+  }
+
+  void mlp_forward(const int32_t *rows, int B, bool train) {
     hipLaunchKernelGGL(ft_k_gather, dim3((B * CA_GAME_STATE_SIZE + 255) / 256), dim3(256), 0, s, (const float *)states.p,
                        rows, B, x0.p);
     RT_CHECK(hipGetLastError());
@@ -400,15 +612,15 @@ struct ca_fitter {
     hipLaunchKernelGGL(ft_k_loss, dim3((B + 255) / 256), dim3(256), 0, s, (const float *)h.p, rows, B,
                        (const float *)evals.p, (const float *)probs.p, hd.p);
     RT_CHECK(hipGetLastError());
+    const bool cnn = net == CA_NET_RESCNN4;
     hipLaunchKernelGGL(ft_k_head_reduce, dim3(FT_PADW / 16), dim3(1024), 0, s, (const float *)hd.p, B,
-                       grads ? g.p : (float *)nullptr, loss.p + 2 * slot);
+                       grads ? g.p : (float *)nullptr, cnn ? L.p_db : FT_BP, cnn ? L.v_d2b : FT_BV, loss.p + 2 * slot);
     RT_CHECK(hipGetLastError());
   }
 
   /* the weight gradient of one batch as FT_NSPLIT-bounded partials in g; returns the number of partials */
-  int backward(int B) {
-    int kch = (B + FT_NSPLIT - 1) / FT_NSPLIT;
-    kch = (kch + 15) / 16 * 16;
+  int mlp_backward(int B) {
+    const int kch = split_chunk(B);
     const int nsplit = (B + kch - 1) / kch;
     /* heads: dKp = Y11^T Hd[:, :96], dKv = Y11^T Hd[:, 96] (row-split partials) */
     FtGemm a = mk(Y(11), 1, FT_PADW, hd.p, FT_PADW, 1, g.p + FT_KP, CA_NUM_MOVES, 1, CO_MLP_WIDTH, CA_NUM_MOVES, B);
@@ -436,8 +648,8 @@ struct ca_fitter {
     return nsplit;
   }
 
-  void update(int nsplit, float lr_t, bool apply) {
-    hipLaunchKernelGGL(ft_k_update, dim3((FT_NW + 255) / 256), dim3(256), 0, s, w.p, m.p, v.p, (const float *)g.p, nsplit,
+  void update(float lr_t, bool apply) {
+    hipLaunchKernelGGL(ft_k_update, dim3((nw + 255) / 256), dim3(256), 0, s, w.p, m.p, v.p, (const float *)g.p, nw, ns0, ns1,
                        (const int32_t *)sidx.p, (const float *)stat.p, lr_t, apply ? 1 : 0, gsum.p);
     RT_CHECK(hipGetLastError());
   }
@@ -498,8 +710,16 @@ struct ca_fitter {
   }
 
 extern "C" int ca_fitter_create(int device, int32_t max_batch, ca_fitter **out) {
+  return ca_fitter_create_net(device, CA_NET_MLP12X100, max_batch, out);
+}
+
+extern "C" int ca_fitter_create_net(int device, int32_t net, int32_t max_batch, ca_fitter **out) {
   if (!out || max_batch < 1 || max_batch > (1 << 20)) {
     co_set_last_error("ca_fitter_create: null argument or max_batch outside [1, 2^20]");
+    return CA_ERR_ARG;
+  }
+  if (net != CA_NET_MLP12X100 && net != CA_NET_RESCNN4) {
+    co_set_last_error("ca_fitter_create_net: net must be CA_NET_MLP12X100 or CA_NET_RESCNN4");
     return CA_ERR_ARG;
   }
   *out = nullptr;
@@ -508,7 +728,7 @@ extern "C" int ca_fitter_create(int device, int32_t max_batch, ca_fitter **out) 
   ca_fitter *f = nullptr;
   try {
     f = new ca_fitter();
-    f->init(device, max_batch);
+    f->init(device, net, max_batch);
   } catch (const std::exception &e) {
     co_set_last_error(e.what());
     delete f;
@@ -528,29 +748,31 @@ extern "C" void ca_fitter_destroy(ca_fitter *f) {
   delete f;
 }
 
-static void ft_check_n(size_t n_floats) {
-  if (n_floats != (size_t)FT_NW) throw FtError(CA_ERR_ARG, "ca_fitter: mlp12x100 has " + std::to_string(FT_NW) + " floats");
+static void ft_check_n(const ca_fitter *f, size_t n_floats) {
+  if (n_floats != (size_t)f->nw)
+    throw FtError(CA_ERR_ARG, std::string("ca_fitter: ") + (f->net == CA_NET_RESCNN4 ? "rescnn4" : "mlp12x100") + " has " +
+                                  std::to_string(f->nw) + " floats");
 }
 
 extern "C" int ca_fitter_set_weights(ca_fitter *f, const float *weights, size_t n_floats) {
-  FT_GUARD(ft_check_n(n_floats); if (!weights) throw FtError(CA_ERR_ARG, "null weights");
-           rt_h2d(f->w.p, weights, FT_NW * sizeof(float), f->s); rt_sync(f->s))
+  FT_GUARD(ft_check_n(f, n_floats); if (!weights) throw FtError(CA_ERR_ARG, "null weights");
+           rt_h2d(f->w.p, weights, f->nw * sizeof(float), f->s); rt_sync(f->s))
 }
 
 extern "C" int ca_fitter_get_weights(ca_fitter *f, float *weights, size_t n_floats) {
-  FT_GUARD(ft_check_n(n_floats); if (!weights) throw FtError(CA_ERR_ARG, "null weights");
-           rt_d2h(weights, f->w.p, FT_NW * sizeof(float), f->s); rt_sync(f->s))
+  FT_GUARD(ft_check_n(f, n_floats); if (!weights) throw FtError(CA_ERR_ARG, "null weights");
+           rt_d2h(weights, f->w.p, f->nw * sizeof(float), f->s); rt_sync(f->s))
 }
 
 extern "C" int ca_fitter_set_optimizer(ca_fitter *f, const float *m, const float *v, size_t n_floats, int64_t iterations) {
-  FT_GUARD(ft_check_n(n_floats); if (!m || !v || iterations < 0) throw FtError(CA_ERR_ARG, "null slots or negative iterations");
-           rt_h2d(f->m.p, m, FT_NW * sizeof(float), f->s); rt_h2d(f->v.p, v, FT_NW * sizeof(float), f->s); rt_sync(f->s);
+  FT_GUARD(ft_check_n(f, n_floats); if (!m || !v || iterations < 0) throw FtError(CA_ERR_ARG, "null slots or negative iterations");
+           rt_h2d(f->m.p, m, f->nw * sizeof(float), f->s); rt_h2d(f->v.p, v, f->nw * sizeof(float), f->s); rt_sync(f->s);
            f->iterations = iterations)
 }
 
 extern "C" int ca_fitter_get_optimizer(ca_fitter *f, float *m, float *v, size_t n_floats, int64_t *iterations) {
-  FT_GUARD(ft_check_n(n_floats); if (!m || !v || !iterations) throw FtError(CA_ERR_ARG, "null output");
-           rt_d2h(m, f->m.p, FT_NW * sizeof(float), f->s); rt_d2h(v, f->v.p, FT_NW * sizeof(float), f->s); rt_sync(f->s);
+  FT_GUARD(ft_check_n(f, n_floats); if (!m || !v || !iterations) throw FtError(CA_ERR_ARG, "null output");
+           rt_d2h(m, f->m.p, f->nw * sizeof(float), f->s); rt_d2h(v, f->v.p, f->nw * sizeof(float), f->s); rt_sync(f->s);
            *iterations = f->iterations)
 }
 
@@ -574,11 +796,11 @@ extern "C" int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows
         const int32_t *r = f->idx.p + (size_t)b * batch;
         f->forward(r, B, true);
         f->loss_terms(r, B, true, b);
-        const int nsplit = f->backward(B);
+        f->backward(B);
         /* Keras Adam: local_step = iterations + 1, lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), in float32 */
         const float t = (float)(f->iterations + 1);
         const float lr_t = learning_rate * (sqrtf(1.0f - powf(0.999f, t)) / (1.0f - powf(0.9f, t)));
-        f->update(nsplit, lr_t, true);
+        f->update(lr_t, true);
         f->iterations += 1;
       } f->losses(nb, n_rows, batch, out_losses, batch_losses))
 }
@@ -601,6 +823,6 @@ extern "C" int ca_fitter_gradients(ca_fitter *f, const int32_t *rows, int32_t n_
   FT_GUARD(f->need_data(); f->check_batch(n_rows); if (!rows || !grads) throw FtError(CA_ERR_ARG, "null argument");
            f->check_rows(rows, n_rows); f->ensure_loss(1);
            rt_h2d(f->idx.p, rows, (size_t)n_rows * sizeof(int32_t), f->s); f->forward(f->idx.p, n_rows, true);
-           f->loss_terms(f->idx.p, n_rows, true, 0); const int nsplit = f->backward(n_rows); f->update(nsplit, 0.0f, false);
-           rt_d2h(grads, f->gsum.p, FT_NW * sizeof(float), f->s); f->losses(1, n_rows, n_rows, out_losses, nullptr))
+           f->loss_terms(f->idx.p, n_rows, true, 0); f->backward(n_rows); f->update(0.0f, false);
+           rt_d2h(grads, f->gsum.p, f->nw * sizeof(float), f->s); f->losses(1, n_rows, n_rows, out_losses, nullptr))
 }

@@ -1,0 +1,376 @@
+// nn_train_conv.hip -- the convolutional kernels of rescnn4's training step ("Network training", rescnn4),
+// float32 on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32).
+//
+// Activations are NHWC [B * 16][C], row = position * 16 + pixel, so a 16-row MFMA tile is one 4x4 board and a 3x3 tap
+// is a permutation of the tile's rows with the off-board rows zero: no im2col buffer exists.
+//   fc_k_conv3       implicit GEMM, forward and (on the mirrored, transposed kernels of fc_k_wtrans) backward-data
+//   fc_k_wgrad       dW = X_shifted^T dZ per row chunk; fc_k_wgrad_sum adds the chunks in order
+//   fc_k_bn_part / _final / _apply      BatchNorm forward with batch statistics, residual add, ReLU
+//   fc_k_bnb_part / _final / _apply     its backward: ReLU mask, residual pass-through, dgamma, dbeta, dZ
+// Every cross-workgroup sum is per-chunk partials combined in chunk order by a later launch: no float atomics, no
+// grid-wide barrier, so a step is bitwise reproducible.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "../../include/corintho_hip.h"
+#include "nn.h"
+#include "nn_train_conv.h"
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+#define FC_POS 4   /* positions of a convolution workgroup, one per wave */
+#define FC_XLD 66  /* LDS row stride of a board tile: lanes (row i, k q) of a 32-lane half on 32 banks (2 i + q) */
+#define FC_WLD 80  /* LDS row stride of [k][n] operands: lanes (k q, n i) of a half on banks 16 q + i */
+
+__global__ __launch_bounds__(256) void fc_k_planes(const float *__restrict__ states, const int32_t *__restrict__ rows, int B,
+                                                   float *__restrict__ x0) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)B * 16 * FC_IN_LD) return;
+  const int c = (int)(e % FC_IN_LD), p = (int)(e / FC_IN_LD % 16);
+  const long r = e / (16 * FC_IN_LD);
+  const float *s = states + (long)rows[r] * CA_GAME_STATE_SIZE;
+  x0[e] = c < 4 ? s[p * 4 + c] : c < 10 ? s[64 + c - 4] : 0.0f;
+}
+
+__global__ __launch_bounds__(256) void fc_k_wtrans(const float *__restrict__ w, int first, int stride, int n,
+                                                   float *__restrict__ wt) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n * FC_WG_FLOATS) return;
+  const int l = e / FC_WG_FLOATS, t = e / (FC_C * FC_C) % 9, co = e / FC_C % FC_C, ci = e % FC_C;
+  wt[e] = w[(long)first + (long)l * stride + ((8 - t) * FC_C + ci) * FC_C + co];
+}
+
+/* One workgroup = FC_POS positions x 64 output channels, a wave per position with four 16x16 accumulators.  The
+ * boards' input rows are staged once, each tap's [CIN][64] weights in turn.  CIN = 16: the stem (weights of ci >= cin
+ * read as zero). */
+template <int CIN>
+__global__ __launch_bounds__(256) void fc_k_conv3(const float *__restrict__ X, const float *__restrict__ W, int cin,
+                                                  const float *__restrict__ bias, float *__restrict__ out, int B,
+                                                  int accumulate) {
+  __shared__ float xs[FC_POS * 16 * FC_XLD];
+  __shared__ float ws[CIN * FC_WLD];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, q = lane >> 4;
+  const long row0 = (long)blockIdx.x * FC_POS * 16, nrow = (long)B * 16;
+  for (int e = threadIdx.x; e < FC_POS * 16 * CIN; e += 256) {
+    const int r = e / CIN, c = e % CIN;
+    xs[r * FC_XLD + c] = row0 + r < nrow ? X[(row0 + r) * CIN + c] : 0.0f;
+  }
+  f32x4 acc[4];
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const int py = i >> 2, px = i & 3;
+  for (int tap = 0; tap < 9; ++tap) {
+    __syncthreads(); /* the previous tap's reads are done */
+    const float *Wt = W + (long)tap * cin * FC_C;
+    for (int e = threadIdx.x; e < CIN * FC_C; e += 256) {
+      const int k = e >> 6, n = e & 63;
+      ws[k * FC_WLD + n] = k < cin ? Wt[e] : 0.0f;
+    }
+    __syncthreads();
+    const int sy = py + tap / 3 - 1, sx = px + tap % 3 - 1;
+    const bool on = sy >= 0 && sy < 4 && sx >= 0 && sx < 4;
+    const float *xr = xs + (wave * 16 + (on ? sy * 4 + sx : 0)) * FC_XLD + q;
+    const float *wr = ws + q * FC_WLD + i;
+#pragma unroll 4
+    for (int k = 0; k < CIN / 4; ++k) {
+      const float a = on ? xr[4 * k] : 0.0f;
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wr[4 * k * FC_WLD + nt * 16], acc[nt], 0, 0, 0);
+    }
+  }
+  /* acc[nt][r] = out[row 4q + r of the wave's board][channel 16 nt + i] */
+  const long pos = (long)blockIdx.x * FC_POS + wave;
+  if (pos >= B) return;
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+    const int co = nt * 16 + i;
+    const float bv = bias ? bias[co] : 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float *o = out + (pos * 16 + 4 * q + r) * FC_C + co;
+      float v = acc[nt][r] + bv;
+      if (accumulate) v = *o + v;
+      *o = v;
+    }
+  }
+}
+
+/* One workgroup = one row chunk (ppc positions) x one kernel row (three taps); a wave per (tap, 16 input channels) with
+ * four accumulators, 3 * CIN / 16 waves.  Four boards of X and dZ are staged at a time; a k step is one board row (four
+ * pixels), skipped where the tap's shift takes the whole row off the board.  part[chunk][tap][ci][co]. */
+template <int CIN>
+__global__ __launch_bounds__(3 * CIN * 4) void fc_k_wgrad(const float *__restrict__ X, const float *__restrict__ dZ, int B,
+                                                          int ppc, int cin, float *__restrict__ part) {
+  __shared__ float xs[64 * FC_WLD];
+  __shared__ float gs[64 * FC_WLD];
+  constexpr int MT = CIN / 16, NT = 3 * MT * 64;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, i = lane & 15, q = lane >> 4;
+  const int dy = (int)blockIdx.y - 1, dx = wave / MT - 1, mt = wave % MT;
+  const int p0 = blockIdx.x * ppc, p1 = min(B, p0 + ppc);
+  f32x4 acc[4];
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const int sx = q + dx;
+  const bool onx = sx >= 0 && sx < 4;
+  for (int pb = p0; pb < p1; pb += 4) {
+    __syncthreads();
+    const long r0 = (long)pb * 16, rend = (long)p1 * 16;
+    for (int e = threadIdx.x; e < 64 * CIN; e += NT) {
+      const int r = e / CIN, c = e % CIN;
+      xs[r * FC_WLD + c] = r0 + r < rend ? X[(r0 + r) * CIN + c] : 0.0f;
+    }
+    for (int e = threadIdx.x; e < 64 * FC_C; e += NT) {
+      const int r = e >> 6, c = e & 63;
+      gs[r * FC_WLD + c] = r0 + r < rend ? dZ[(r0 + r) * FC_C + c] : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int y = 0; y < 4; ++y) {
+        const int sy = y + dy;
+        if (sy < 0 || sy >= 4) continue; /* wave-uniform */
+        const float a = onx ? xs[(j * 16 + sy * 4 + sx) * FC_WLD + mt * 16 + i] : 0.0f;
+        const float *gr = gs + (j * 16 + y * 4 + q) * FC_WLD + i;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, gr[nt * 16], acc[nt], 0, 0, 0);
+      }
+  }
+  /* acc[nt][r] = dW[tap][ci = 16 mt + 4q + r][co = 16 nt + i] of this chunk */
+  const int tap = (dy + 1) * 3 + dx + 1;
+  float *o = part + ((long)blockIdx.x * 9 + tap) * cin * FC_C;
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int ci = mt * 16 + 4 * q + r;
+      if (ci < cin) o[ci * FC_C + nt * 16 + i] = acc[nt][r];
+    }
+}
+
+__global__ __launch_bounds__(256) void fc_k_wgrad_sum(const float *__restrict__ part, int nchunk, int n, float *__restrict__ dW) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  float s = 0.0f;
+  for (int j = 0; j < nchunk; ++j) s += part[(long)j * n + e];
+  dW[e] = s;
+}
+
+/* ---------------------------------------------------------------- BatchNorm over channels
+ * 256 threads = (256 / C) row groups x C channels, so thread t always meets channel t % C and rows are read whole. */
+
+/* sum over the block's row groups in a fixed order, returned to every thread of the channel; red holds 256 + 64 floats */
+__device__ __forceinline__ float fc_groupsum(float *red, float v, int C) {
+  const int c = threadIdx.x % C;
+  __syncthreads();
+  red[threadIdx.x] = v;
+  __syncthreads();
+  if ((int)threadIdx.x < C) {
+    float s = 0.0f;
+    for (int j = 0; j < 256; j += C) s += red[j + c];
+    red[256 + c] = s;
+  }
+  __syncthreads();
+  return red[256 + c];
+}
+
+/* chunk j = rows [j rpc, min(R, (j + 1) rpc)): part[j][0][c] = its mean, part[j][1][c] = sum (z - that mean)^2 */
+__global__ __launch_bounds__(256) void fc_k_bn_part(const float *__restrict__ Z, int R, int C, int rpc, float *__restrict__ part) {
+  __shared__ float red[256 + 64];
+  const int c = threadIdx.x % C, rg = threadIdx.x / C, nrg = 256 / C;
+  const int r0 = blockIdx.x * rpc, r1 = min(R, r0 + rpc);
+  float s = 0.0f;
+  for (int r = r0 + rg; r < r1; r += nrg) s += Z[(long)r * C + c];
+  const float mean = fc_groupsum(red, s, C) / (float)(r1 - r0);
+  float s2 = 0.0f;
+  for (int r = r0 + rg; r < r1; r += nrg) {
+    const float d = Z[(long)r * C + c] - mean;
+    s2 += d * d;
+  }
+  s2 = fc_groupsum(red, s2, C);
+  if (rg == 0) {
+    part[(blockIdx.x * 2) * 64 + c] = mean;
+    part[(blockIdx.x * 2 + 1) * 64 + c] = s2;
+  }
+}
+
+/* the chunks combined in order: mean = sum n_j mean_j / R, variance = sum (M2_j + n_j (mean_j - mean)^2) / R (biased) */
+__global__ __launch_bounds__(64) void fc_k_bn_final(const float *__restrict__ part, int nch, int R, int rpc, int C,
+                                                    float *__restrict__ stat) {
+  const int c = threadIdx.x;
+  if (c >= C) return;
+  float sm = 0.0f;
+  for (int j = 0; j < nch; ++j) sm += part[(j * 2) * 64 + c] * (float)(min(R, (j + 1) * rpc) - j * rpc);
+  const float mu = sm / (float)R;
+  float m2 = 0.0f;
+  for (int j = 0; j < nch; ++j) {
+    const float d = part[(j * 2) * 64 + c] - mu;
+    m2 += part[(j * 2 + 1) * 64 + c] + (float)(min(R, (j + 1) * rpc) - j * rpc) * (d * d);
+  }
+  stat[c] = mu;
+  stat[64 + c] = m2 / (float)R;
+}
+
+/* out = relu(gamma (z - mu) rsqrt(var + eps) + beta (+ res)); 4096 elements per block */
+__global__ __launch_bounds__(256) void fc_k_bn_apply(const float *__restrict__ Z, const float *__restrict__ res,
+                                                     float *__restrict__ out, long n, int C, const float *__restrict__ bn,
+                                                     const float *__restrict__ mean, const float *__restrict__ var) {
+  const int c = threadIdx.x % C;
+  const float mu = mean[c], rstd = 1.0f / sqrtf(var[c] + (float)CO_BN_EPS), ga = bn[c], be = bn[C + c];
+  const long e0 = (long)blockIdx.x * 4096 + threadIdx.x;
+#pragma unroll 4
+  for (int k = 0; k < 16; ++k) {
+    const long e = e0 + k * 256;
+    if (e >= n) return;
+    float y = ga * ((Z[e] - mu) * rstd) + be;
+    if (res) y = y + res[e];
+    out[e] = y > 0.0f ? y : 0.0f;
+  }
+}
+
+/* The backward reductions and the per-channel constants made from them are float64.  In exact arithmetic dZ sums to 0
+ * over the rows of a channel; a constant rounded to float32 and subtracted from every one of B * 16 rows leaves a sum
+ * of that many half ulps instead, which the next layer's weight gradient multiplies by the mean of its input and every
+ * beta along the residual path inherits.  With float64 sums of the float32 terms (sum xhat among them: it is 0 only as
+ * far as the float32 mean is exact) and one rounding of each dZ, what is left is the rounding of dZ itself. */
+__device__ __forceinline__ double fc_groupsum_d(double *red, double v, int C) {
+  const int c = threadIdx.x % C;
+  __syncthreads();
+  red[threadIdx.x] = v;
+  __syncthreads();
+  if ((int)threadIdx.x < C) {
+    double s = 0.0;
+    for (int j = 0; j < 256; j += C) s += red[j + c];
+    red[256 + c] = s;
+  }
+  __syncthreads();
+  return red[256 + c];
+}
+
+/* chunk partials of sum dY, sum dY xhat and sum xhat, dY = dOut where out > 0 (written back when keep) */
+__global__ __launch_bounds__(256) void fc_k_bnb_part(float *__restrict__ dOut, const float *__restrict__ out,
+                                                     const float *__restrict__ Z, int R, int C, int rpc,
+                                                     const float *__restrict__ stat, int keep, double *__restrict__ part) {
+  __shared__ double red[256 + 64];
+  const int c = threadIdx.x % C, rg = threadIdx.x / C, nrg = 256 / C;
+  const int r0 = blockIdx.x * rpc, r1 = min(R, r0 + rpc);
+  const float mu = stat[c], rstd = 1.0f / sqrtf(stat[64 + c] + (float)CO_BN_EPS);
+  double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  for (int r = r0 + rg; r < r1; r += nrg) {
+    const long e = (long)r * C + c;
+    const float dy = out[e] > 0.0f ? dOut[e] : 0.0f, xh = (Z[e] - mu) * rstd;
+    if (keep) dOut[e] = dy;
+    s1 += (double)dy;
+    s2 += (double)dy * (double)xh;
+    s3 += (double)xh;
+  }
+  s1 = fc_groupsum_d(red, s1, C);
+  s2 = fc_groupsum_d(red, s2, C);
+  s3 = fc_groupsum_d(red, s3, C);
+  if (rg == 0) {
+    part[(blockIdx.x * 3) * 64 + c] = s1;
+    part[(blockIdx.x * 3 + 1) * 64 + c] = s2;
+    part[(blockIdx.x * 3 + 2) * 64 + c] = s3;
+  }
+}
+
+/* g[0..C) = dbias, g[C..2C) = dgamma, g[2C..3C) = dbeta.  The bias feeds a BatchNorm with batch statistics, which
+ * removes any constant per channel: its gradient is identically zero and is written as such.  dgamma = sum dY (xhat -
+ * mean xhat); fin[c] = dgamma / R, fin[64 + c] = mean dY - mean xhat dgamma / R: the two constants of fc_k_bnb_apply. */
+__global__ __launch_bounds__(64) void fc_k_bnb_final(const double *__restrict__ part, int nch, int C, int R,
+                                                     float *__restrict__ g, double *__restrict__ fin) {
+  const int c = threadIdx.x;
+  if (c >= C) return;
+  double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  for (int j = 0; j < nch; ++j) {
+    s1 += part[(j * 3) * 64 + c];
+    s2 += part[(j * 3 + 1) * 64 + c];
+    s3 += part[(j * 3 + 2) * 64 + c];
+  }
+  /* xhat is centred on the float32 mean; what its own mean s3 / R still holds is taken out of dgamma too */
+  const double dg = s2 - (s3 / R) * s1;
+  g[c] = 0.0f;
+  g[C + c] = (float)dg;
+  g[2 * C + c] = (float)s1;
+  fin[c] = dg / R;
+  fin[64 + c] = s1 / R - (s3 / R) * (dg / R);
+}
+
+/* dZ = gamma rstd (dY - xhat mean(dY xhat) - (mean dY - mean xhat mean(dY xhat))), rounded once */
+__global__ __launch_bounds__(256) void fc_k_bnb_apply(const float *__restrict__ dOut, const float *__restrict__ out,
+                                                      const float *__restrict__ Z, float *__restrict__ dZ, long n, int C,
+                                                      const float *__restrict__ bn, const float *__restrict__ stat,
+                                                      const double *__restrict__ fin) {
+  const int c = threadIdx.x % C;
+  const float mu = stat[c], rstd = 1.0f / sqrtf(stat[64 + c] + (float)CO_BN_EPS);
+  const double scale = (double)bn[c] * (double)rstd, mdyx = fin[c], mdy = fin[64 + c];
+  const long e0 = (long)blockIdx.x * 4096 + threadIdx.x;
+#pragma unroll 4
+  for (int k = 0; k < 16; ++k) {
+    const long e = e0 + k * 256;
+    if (e >= n) return;
+    const float dy = out[e] > 0.0f ? dOut[e] : 0.0f, xh = (Z[e] - mu) * rstd;
+    dZ[e] = (float)(scale * ((double)dy - (double)xh * mdyx - mdy));
+  }
+}
+
+/* ------------------------------------------------------------------ launchers */
+#define FC_LAUNCH(k, grid, block, s, ...)                         \
+  do {                                                            \
+    hipLaunchKernelGGL(k, dim3 grid, dim3(block), 0, s, __VA_ARGS__); \
+    RT_CHECK(hipGetLastError());                                  \
+  } while (0)
+
+static inline int fc_bn_rpc(int R) { return 128 * ((R + 128 * FC_BN_CHUNKS - 1) / (128 * FC_BN_CHUNKS)); }
+
+void fc_planes(rt_stream_t s, const float *states, const int32_t *rows, int B, float *x0) {
+  FC_LAUNCH(fc_k_planes, ((unsigned)(((long)B * 16 * FC_IN_LD + 255) / 256)), 256, s, states, rows, B, x0);
+}
+
+void fc_wtrans(rt_stream_t s, const float *w, int first, int stride, int n, float *wt) {
+  FC_LAUNCH(fc_k_wtrans, ((n * FC_WG_FLOATS + 255) / 256), 256, s, w, first, stride, n, wt);
+}
+
+void fc_conv3(rt_stream_t s, const float *X, int cin, const float *W, const float *bias, float *out, int B, int accumulate) {
+  const int grid = (B + FC_POS - 1) / FC_POS;
+  if (cin == FC_C)
+    FC_LAUNCH(fc_k_conv3<FC_C>, (grid), 256, s, X, W, cin, bias, out, B, accumulate);
+  else
+    FC_LAUNCH(fc_k_conv3<FC_IN_LD>, (grid), 256, s, X, W, cin, bias, out, B, accumulate);
+}
+
+void fc_conv3_wgrad(rt_stream_t s, const float *X, int cin, const float *dZ, int B, float *part, float *dW) {
+  int ppc = (B + FC_WG_CHUNKS - 1) / FC_WG_CHUNKS;
+  ppc = ppc < 16 ? 16 : (ppc + 3) / 4 * 4;
+  const int nchunk = (B + ppc - 1) / ppc, n = 9 * cin * FC_C;
+  if (cin == FC_C)
+    FC_LAUNCH(fc_k_wgrad<FC_C>, (nchunk, 3), 3 * FC_C * 4, s, X, dZ, B, ppc, cin, part);
+  else
+    FC_LAUNCH(fc_k_wgrad<FC_IN_LD>, (nchunk, 3), 3 * FC_IN_LD * 4, s, X, dZ, B, ppc, cin, part);
+  FC_LAUNCH(fc_k_wgrad_sum, ((n + 255) / 256), 256, s, (const float *)part, nchunk, n, dW);
+}
+
+void fc_bn_fwd(rt_stream_t s, const float *Z, const float *res, float *out, int R, int C, const float *bn, int train,
+               float *part, float *stat) {
+  const long n = (long)R * C;
+  const float *mean = bn + 2 * C, *var = bn + 3 * C;
+  if (train) {
+    const int rpc = fc_bn_rpc(R), nch = (R + rpc - 1) / rpc;
+    FC_LAUNCH(fc_k_bn_part, (nch), 256, s, Z, R, C, rpc, part);
+    FC_LAUNCH(fc_k_bn_final, (1), 64, s, (const float *)part, nch, R, rpc, C, stat);
+    mean = stat, var = stat + 64;
+  }
+  FC_LAUNCH(fc_k_bn_apply, ((unsigned)((n + 4095) / 4096)), 256, s, Z, res, out, n, C, bn, mean, var);
+}
+
+void fc_bn_bwd(rt_stream_t s, float *dOut, const float *out, const float *Z, float *dZ, int R, int C, const float *bn,
+               const float *stat, int keep, float *part, float *g) {
+  const long n = (long)R * C;
+  const int rpc = fc_bn_rpc(R), nch = (R + rpc - 1) / rpc;
+  FC_LAUNCH(fc_k_bnb_part, (nch), 256, s, dOut, out, Z, R, C, rpc, stat, keep, (double *)part);
+  double *dpart = (double *)part, *fin = dpart + FC_BN_PART; /* the backward partials are float64 */
+  FC_LAUNCH(fc_k_bnb_final, (1), 64, s, (const double *)dpart, nch, C, R, g, fin);
+  FC_LAUNCH(fc_k_bnb_apply, ((unsigned)((n + 4095) / 4096)), 256, s, (const float *)dOut, out, Z, dZ, n, C, bn, stat,
+            (const double *)fin);
+}

@@ -1,5 +1,7 @@
 """Network training on the device: the reference's Keras `model.fit` step (corintho_ai/python/main.pyx:221-272,
-model and compile of wrapper.py:256-282) for mlp12x100, with the HIP kernels of csrc/nn_train.hip.
+model and compile of wrapper.py:256-282) for mlp12x100, with the HIP kernels of csrc/nn_train.hip; and the same recipe
+for rescnn4 (`net=NET_RESCNN4`, csrc/nn_train_conv.hip), whose BatchNorms take batch statistics per channel over all
+(row, pixel) pairs.
 
     res = fit(weights, game_states, eval_labels, prob_labels, epochs=10)
     trainer.set_net(NET_MLP12X100, res.best_weights)
@@ -20,9 +22,18 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .nets import GAME_STATE_SIZE, MLP_NUM_WEIGHTS, NUM_MOVES
+from .nets import GAME_STATE_SIZE, MLP_NUM_WEIGHTS, NUM_MOVES, RESCNN4_NUM_WEIGHTS
+from .trainer import NET_MLP12X100, NET_RESCNN4
 
 MIN_DELTA = 1e-4  # keras.callbacks.ReduceLROnPlateau default
+NETS = {NET_MLP12X100: ("mlp12x100", MLP_NUM_WEIGHTS), NET_RESCNN4: ("rescnn4", RESCNN4_NUM_WEIGHTS)}
+
+
+def net_info(net):
+    """(name, number of weights) of a trainable network kind"""
+    if net not in NETS:
+        raise ValueError("fit: net must be NET_MLP12X100 or NET_RESCNN4, got %r" % (net,))
+    return NETS[net]
 
 
 def _f32(a, shape=None):
@@ -37,14 +48,16 @@ def _ptr(a, t=C.c_float):
 
 
 class Fitter:
-    """One device's mlp12x100 fitter (include/corintho_hip.h, "network training").  Losses come back as
+    """One device's fitter of mlp12x100 or rescnn4 (include/corintho_hip.h, "network training").  Losses come back as
     (value + 0.25 policy, value, policy)."""
 
-    def __init__(self, max_batch=2048, device=0):
+    def __init__(self, max_batch=2048, device=0, net=NET_MLP12X100):
+        self.net = net
+        self.num_weights = net_info(net)[1]
         self._L = _lib.load()
         self._h = C.c_void_p()
         self.max_batch = int(max_batch)
-        _lib.check(self._L, self._L.ca_fitter_create(int(device), self.max_batch, C.byref(self._h)))
+        _lib.check(self._L, self._L.ca_fitter_create_net(int(device), int(net), self.max_batch, C.byref(self._h)))
 
     def close(self):
         if self._h:
@@ -71,7 +84,7 @@ class Fitter:
         self._check(self._L.ca_fitter_set_weights(self._h, _ptr(w), w.size))
 
     def get_weights(self):
-        w = np.zeros(MLP_NUM_WEIGHTS, np.float32)
+        w = np.zeros(self.num_weights, np.float32)
         self._check(self._L.ca_fitter_get_weights(self._h, _ptr(w), w.size))
         return w
 
@@ -83,8 +96,8 @@ class Fitter:
 
     def get_optimizer(self):
         """(m, v, iterations)"""
-        m = np.zeros(MLP_NUM_WEIGHTS, np.float32)
-        v = np.zeros(MLP_NUM_WEIGHTS, np.float32)
+        m = np.zeros(self.num_weights, np.float32)
+        v = np.zeros(self.num_weights, np.float32)
         it = C.c_int64()
         self._check(self._L.ca_fitter_get_optimizer(self._h, _ptr(m), _ptr(v), m.size, C.byref(it)))
         return m, v, int(it.value)
@@ -117,7 +130,7 @@ class Fitter:
     def gradients(self, rows):
         """(gradient of the batch loss in the weight layout, the three losses); no update"""
         r = np.ascontiguousarray(rows, dtype=np.int32)
-        g = np.zeros(MLP_NUM_WEIGHTS, np.float32)
+        g = np.zeros(self.num_weights, np.float32)
         out = np.zeros(3, np.float64)
         self._check(self._L.ca_fitter_gradients(self._h, _ptr(r, C.c_int32), r.size, _ptr(g), _ptr(out, C.c_double)))
         return g, tuple(out)
@@ -148,12 +161,14 @@ def epoch_order(rng, n_train, shuffle):
 
 def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, batch_size=2048, epochs=1,
         validation_split=0.3, shuffle=True, anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, device=0,
-        _backend=None):
+        net=NET_MLP12X100, _backend=None):
     """main.pyx:249-260 `model.fit(...)` with its callbacks; see the module docstring.  Returns a FitResult.
-    optimizer_state: (m, v, iterations) to resume from; None starts Adam from zeros, as a freshly compiled model."""
+    optimizer_state: (m, v, iterations) to resume from; None starts Adam from zeros, as a freshly compiled model.
+    net: NET_MLP12X100 or NET_RESCNN4, the network `weights` belong to."""
+    name, num_weights = net_info(net)
     w = _f32(weights).ravel()
-    if w.size != MLP_NUM_WEIGHTS:
-        raise ValueError("fit: mlp12x100 weights have %d floats, got %d" % (MLP_NUM_WEIGHTS, w.size))
+    if w.size != num_weights:
+        raise ValueError("fit: %s weights have %d floats, got %d" % (name, num_weights, w.size))
     states = _f32(game_states)
     n = states.shape[0] if states.ndim == 2 else -1
     if states.ndim != 2 or states.shape[1] != GAME_STATE_SIZE:
@@ -177,7 +192,7 @@ def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, 
     batch_size, epochs = int(batch_size), int(epochs)
 
     own = _backend is None
-    be = Fitter(max_batch=batch_size, device=device) if own else _backend
+    be = Fitter(max_batch=batch_size, device=device, net=net) if own else _backend
     try:
         be.set_weights(w)
         if optimizer_state is None:

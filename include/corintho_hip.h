@@ -316,6 +316,11 @@ int ca_fp_probe(int device, const float *in, int32_t n, float *out);
 typedef struct ca_fitter ca_fitter;
 /* max_batch: the largest batch of ca_fitter_train / _evaluate / _gradients */
 int ca_fitter_create(int device, int32_t max_batch, ca_fitter **out);
+/* the same for `net` = CA_NET_MLP12X100 (what ca_fitter_create makes) or CA_NET_RESCNN4: the residual CNN in the flat
+ * layout of ca_trainer_set_net, by the same recipe -- every convolution's and both head convolutions' BatchNorm takes
+ * its statistics per channel over the batch's B x 16 (row, pixel) pairs.  Any other net: CA_ERR_ARG.  Every entry
+ * point below serves both; n_floats is checked against the fitter's own weight count. */
+int ca_fitter_create_net(int device, int32_t net, int32_t max_batch, ca_fitter **out);
 void ca_fitter_destroy(ca_fitter *f);
 int ca_fitter_set_weights(ca_fitter *f, const float *weights, size_t n_floats);
 int ca_fitter_get_weights(ca_fitter *f, float *weights, size_t n_floats);

@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
-"""Times the mlp12x100 training step (csrc/nn_train.hip) on one GPU: ms per step at `--batch` rows on a sample set of
-`--rows` rows, rows/s and achieved FLOP/s against the fp32 matrix peak.  A step is 3 x 253.4 KFLOP per row by the
+"""Times the training step of mlp12x100 (csrc/nn_train.hip) or, with --net rescnn4, of the residual CNN
+(csrc/nn_train_conv.hip) on one GPU: ms per step at `--batch` rows on a sample set of `--rows` rows, rows/s and achieved
+FLOP/s against the fp32 matrix peak.  A step is 3 x 253.4 KFLOP per row (3 x 9.65 MFLOP for rescnn4) by the
 algorithm (forward, and the two products of the backward pass).  Timing: a synchronised host clock around one
 ca_fitter_train call of `--steps` steps (the call ends by reading its losses back).
 
 --torch also times the same step written in torch-ROCm on the same GPU, in the same process, alternating with the HIP
 path: autograd through the Keras BatchNorm (batch mean, biased variance), Adam as TF's ResourceApplyAdam (epsilon
-outside the root) with torch._foreach ops, moving statistics at momentum 0.99.  It is the yardstick the HIP step has to
-beat; torch is not part of the product path.
+outside the root) with torch._foreach ops, moving statistics at momentum 0.99.  For rescnn4 it is the same network
+with torch's convolutions and the BatchNorm of the fit (batch mean and biased variance per channel over all rows and
+pixels).  It is the yardstick the HIP step has to beat; torch is not part of the product path.
 
-    python tools/fit_bench.py --torch [--rows 1000000 --batch 2048 --steps 200 --reps 3] [--out file.json]
+    python tools/fit_bench.py --torch [--net rescnn4] [--rows 1000000 --batch 2048 --steps 200 --reps 3] [--out file.json]
 """
 import argparse
 import json
@@ -23,9 +25,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from corintho_ai_amd import nets  # noqa: E402
+from corintho_ai_amd import NET_MLP12X100, NET_RESCNN4  # noqa: E402
 from corintho_ai_amd.fit import Fitter  # noqa: E402
 
-FLOP_PER_ROW_STEP = 3 * 2.0 * (70 * 100 + 11 * 100 * 100 + 100 * 97)
+FLOP_PER_ROW_STEP = {"mlp12x100": 3 * 2.0 * (70 * 100 + 11 * 100 * 100 + 100 * 97),
+                     "rescnn4": 3 * nets.rescnn4_flop_per_row()}
 PEAK_FP32_MATRIX = 157.3e12
 PRODUCTION_STEPS = 12_000  # ~2.5 M training rows x 10 epochs at batch 2048
 
@@ -90,21 +94,88 @@ class TorchStep:
         loss = ((torch.tanh(v) - self.z[rows]) ** 2).mean() + 0.25 * (
             -(self.p[rows] * torch.log_softmax(logits, 1)).sum(1)).mean()
         grads = torch.autograd.grad(loss, P)
-        with torch.no_grad():
-            self.it += 1
-            t = np.float32(self.it)
-            lr_t = float(np.float32(lr) * np.sqrt(np.float32(1) - np.float32(0.999) ** t) / (np.float32(1) - np.float32(0.9) ** t))
-            torch._foreach_lerp_(self.m, grads, 1 - 0.9)
-            torch._foreach_lerp_(self.v, torch._foreach_mul(grads, grads), 1 - 0.999)
-            den = torch._foreach_sqrt(self.v)
-            torch._foreach_add_(den, 1e-7)
-            torch._foreach_addcdiv_(P, self.m, den, value=-lr_t)
-            torch._foreach_lerp_(self.stats, batch_stats, 0.01)
+        self.batch_stats = batch_stats
+        _adam(self, grads, lr)
+        return loss
+
+
+def _adam(ts, grads, lr):
+    """TF ResourceApplyAdam on ts.params and the moving statistics toward ts.batch_stats, with torch._foreach ops"""
+    torch = ts.torch
+    with torch.no_grad():
+        ts.it += 1
+        t = np.float32(ts.it)
+        lr_t = float(np.float32(lr) * np.sqrt(np.float32(1) - np.float32(0.999) ** t) / (np.float32(1) - np.float32(0.9) ** t))
+        torch._foreach_lerp_(ts.m, grads, 1 - 0.9)
+        torch._foreach_lerp_(ts.v, torch._foreach_mul(grads, grads), 1 - 0.999)
+        den = torch._foreach_sqrt(ts.v)
+        torch._foreach_add_(den, 1e-7)
+        torch._foreach_addcdiv_(ts.params, ts.m, den, value=-lr_t)
+        torch._foreach_lerp_(ts.stats, ts.batch_stats, 0.01)
+
+
+class TorchStepCnn:
+    """rescnn4's step in torch-ROCm (autograd): NCHW convolutions with OIHW kernels, the fit's BatchNorm"""
+
+    def __init__(self, w, data, device):
+        import torch
+
+        self.torch = torch
+        self.dev = device
+        W = nets.rescnn4_unpack(w)
+        self.P, self.S = {}, {}
+        for name, a in W.items():
+            t = torch.tensor(a, device=device)
+            if a.ndim == 4:
+                t = t.permute(3, 2, 0, 1).contiguous()  # HWIO -> OIHW
+            elif name in ("p_k", "v_k"):
+                t = t.t().contiguous().view(a.shape[1], a.shape[0], 1, 1)
+            if name.endswith("_bn2") or name.endswith("_bn3"):
+                self.S[name] = t
+            else:
+                self.P[name] = t.requires_grad_(True)
+        self.params, self.stats = list(self.P.values()), list(self.S.values())
+        self.m = [torch.zeros_like(q) for q in self.params]
+        self.v = [torch.zeros_like(q) for q in self.params]
+        self.it = 0
+        self.s, self.z, self.p = (torch.tensor(a, device=device) for a in data)
+
+    def step(self, rows, lr=1e-3):
+        torch = self.torch
+        F = torch.nn.functional
+        P = self.P
+        st = {}
+
+        def cbr(x, pre, pad, res=None):
+            z = F.conv2d(x, P[pre + "_k"], P[pre + "_b"], padding=pad)
+            mu = z.mean((0, 2, 3))
+            var = ((z - mu.view(1, -1, 1, 1)) ** 2).mean((0, 2, 3))
+            st[pre + "_bn2"], st[pre + "_bn3"] = mu.detach(), var.detach()
+            y = P[pre + "_bn0"].view(1, -1, 1, 1) * ((z - mu.view(1, -1, 1, 1)) * torch.rsqrt(var.view(1, -1, 1, 1) + 1e-3)) \
+                + P[pre + "_bn1"].view(1, -1, 1, 1)
+            return torch.relu(y if res is None else y + res)
+
+        s = self.s[rows]
+        n = s.shape[0]
+        x = torch.cat([s[:, :64].view(n, 16, 4), s[:, None, 64:70].expand(n, 16, 6)], 2).view(n, 4, 4, 10).permute(0, 3, 1, 2)
+        h = cbr(x, "stem", 1)
+        for b in range(4):
+            h = cbr(cbr(h, "b%d_c1" % b, 1), "b%d_c2" % b, 1, res=h)
+        pa = cbr(h, "p", 0).permute(0, 2, 3, 1).reshape(n, 64)
+        logits = pa @ P["p_dk"] + P["p_db"]
+        va = cbr(h, "v", 0).permute(0, 2, 3, 1).reshape(n, 32)
+        v = (torch.relu(va @ P["v_d1k"] + P["v_d1b"]) @ P["v_d2k"]).view(-1) + P["v_d2b"]
+        loss = ((torch.tanh(v) - self.z[rows]) ** 2).mean() + 0.25 * (
+            -(self.p[rows] * torch.log_softmax(logits, 1)).sum(1)).mean()
+        grads = torch.autograd.grad(loss, self.params)
+        self.batch_stats = [st[k] for k in self.S]
+        _adam(self, grads, lr)
         return loss
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--net", choices=("mlp12x100", "rescnn4"), default="mlp12x100")
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--batch", type=int, default=2048)
     ap.add_argument("--steps", type=int, default=200)
@@ -115,7 +186,9 @@ def main():
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     data = samples(a.rows)
-    w = nets.init_mlp12x100(0, bn_noise=True)
+    cnn = a.net == "rescnn4"
+    w = nets.init_rescnn4(0, bn_noise=True) if cnn else nets.init_mlp12x100(0, bn_noise=True)
+    flop_per_row_step = FLOP_PER_ROW_STEP[a.net]
     rng = np.random.default_rng(1)
     need = (a.steps + a.warmup) * a.batch
     if max(a.steps, a.warmup) * a.batch > a.rows:
@@ -125,9 +198,9 @@ def main():
     if a.torch:  # torch's runtime comes up first, before the engine library opens the device
         import torch
 
-        ts = TorchStep(w, data, "cuda:%d" % a.device)
+        ts = (TorchStepCnn if cnn else TorchStep)(w, data, "cuda:%d" % a.device)
         torder = torch.tensor(order.astype(np.int64), device=ts.dev)
-    f = Fitter(max_batch=a.batch, device=a.device)
+    f = Fitter(max_batch=a.batch, device=a.device, net=NET_RESCNN4 if cnn else NET_MLP12X100)
     f.set_data(*data)
     f.set_weights(w)
     f.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
@@ -153,12 +226,13 @@ def main():
 
     def rec(ms):
         best = min(ms)
-        flops = FLOP_PER_ROW_STEP * a.batch / (best * 1e-3)
+        flops = flop_per_row_step * a.batch / (best * 1e-3)
         return {"ms_per_step": best, "ms_per_step_all": ms, "rows_per_s": a.batch / (best * 1e-3), "flop_per_s": flops,
                 "share_of_fp32_matrix_peak": flops / PEAK_FP32_MATRIX,
                 "production_fit_s": best * 1e-3 * PRODUCTION_STEPS}
 
-    out = {"batch": a.batch, "rows": a.rows, "steps": a.steps, "flop_per_row_step": FLOP_PER_ROW_STEP, "hip": rec(hip)}
+    out = {"net": a.net, "batch": a.batch, "rows": a.rows, "steps": a.steps, "flop_per_row_step": flop_per_row_step,
+           "hip": rec(hip)}
     if tor:
         out["torch"] = rec(tor)
         out["hip_speedup_over_torch"] = min(tor) / min(hip)
