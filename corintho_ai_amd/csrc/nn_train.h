@@ -1,0 +1,132 @@
+// nn_train.h -- what the training sources share ("Network training"): the fitter's step driver
+// (nn_train.hip) sees a network as an FtNet, one class per network next to its kernels (FtMlp in nn_train_mlp.hip,
+// FtResCnn in nn_train_conv.hip), and both networks are built from the strided GEMM and the column kernels declared
+// here.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/corintho_hip.h"
+#include "nn.h"
+
+#define FT_PADW 112  /* row stride of the heads' outputs H and their gradients Hd (and of the MLP's activations): 7 tiles of 16 */
+#define FT_NSPLIT 16 /* at most this many row chunks per weight gradient (partials of ft_k_gemm) */
+#define FT_BN_RG 64  /* row groups of the column kernels: 16 features x 64 = 1024 threads */
+/* ft_k_update's code of a trainable weight: how many gradient partials it has (FtSplits::rows, ::pixels, or one).  A code
+ * >= 0 is a moving statistic and indexes the batch statistic it follows. */
+#define FT_SPLIT0 -1
+#define FT_SPLIT1 -2
+#define FT_WHOLE -3
+
+#define FT_LAUNCH(kernel, grid, block, stream, ...)                             \
+  do {                                                                          \
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__); \
+    RT_CHECK(hipGetLastError());                                                \
+  } while (0)
+
+template <typename T>
+struct FtBuf {
+  T *p = nullptr;
+  FtBuf() = default;
+  FtBuf(const FtBuf &) = delete;
+  FtBuf &operator=(const FtBuf &) = delete;
+  ~FtBuf() { rt_free(p); }
+  void alloc(size_t n, rt_stream_t s) {
+    rt_free(p);
+    p = nullptr;
+    rt_malloc((void **)&p, n * sizeof(T), s);
+  }
+};
+
+struct FtError : std::runtime_error {
+  int code;
+  FtError(int c, const std::string &m) : std::runtime_error(m), code(c) {}
+};
+
+/* C[m][n] (+)= sum_k A[m][k] B[k][n] over one chunk of k, every operand addressed through strides (so a transpose is
+ * free).  One wave per 16x16 output tile and chunk; chunk s writes C + s * c_split.  Loads outside [0,M) x [k0,k1) and
+ * [k0,k1) x [0,N) are zero and only the M x N block is written. */
+struct FtGemm {
+  const float *A;
+  long sam, sak;
+  const float *B;
+  long sbk, sbn;
+  float *C;
+  long scm, scn, c_split;
+  int M, N, K, kchunk;
+  const float *bias; /* per column n, or null */
+  int relu, accumulate;
+};
+void ft_gemm(rt_stream_t s, const FtGemm &a);
+/* the whole of k in one chunk, no bias, no ReLU, C overwritten */
+inline FtGemm mk(const float *A, long sam, long sak, const float *B, long sbk, long sbn, float *C, long scm, long scn, int M,
+                 int N, int K) {
+  FtGemm a;
+  a.A = A, a.sam = sam, a.sak = sak, a.B = B, a.sbk = sbk, a.sbn = sbn, a.C = C, a.scm = scm, a.scn = scn;
+  a.c_split = 0, a.M = M, a.N = N, a.K = K, a.kchunk = K > 0 ? K : 1, a.bias = nullptr, a.relu = 0, a.accumulate = 0;
+  return a;
+}
+/* rows of one of at most FT_NSPLIT chunks of K, a multiple of 16 */
+inline int ft_split_chunk(int K) { return ((K + FT_NSPLIT - 1) / FT_NSPLIT + 15) / 16 * 16; }
+
+/* ReLU backward of a dense layer's output A[B][ld] in place on dA, and the column sums of the result (the layer's bias
+ * gradient) to gbias[0..ncol): ft_k_relu_bwd */
+void ft_relu_bwd(rt_stream_t s, float *dA, const float *A, int B, int ld, int ncol, float *gbias);
+
+/* Fixed-order sum of the 64 row-group partials of each of the block's 16 features: red[rg][f] -> returned to every
+ * thread of feature f.  Leaves red free for the next use. */
+__device__ __forceinline__ float ft_colsum(float *red, float v) {
+  const int f = threadIdx.x & 15, rg = threadIdx.x >> 4;
+  __syncthreads();
+  red[rg * 16 + f] = v;
+  __syncthreads();
+  if (rg == 0) {
+    float s = 0.0f;
+    for (int j = 0; j < FT_BN_RG; ++j) s += red[j * 16 + f];
+    red[FT_BN_RG * 16 + f] = s;
+  }
+  __syncthreads();
+  return red[FT_BN_RG * 16 + f];
+}
+
+/* what a network's step reads and writes but does not own */
+struct FtShared {
+  rt_stream_t s;
+  float *w;     /* the weights, in the network's flat layout */
+  float *g;     /* gradient partials [FT_NSPLIT][num_weights] */
+  float *stat;  /* batch statistics [stat_floats], where update_table's codes point */
+  float *h;     /* the heads' outputs [B][FT_PADW]: 96 logits, the value at 96 */
+  float *hd;    /* their gradients, from ft_k_loss */
+  const float *states; /* the data set's game states [n][70] */
+};
+
+/* how many partials in g backward left for a weight whose gradient is a sum over the B rows (FT_SPLIT0) and over the
+ * B * 16 (row, pixel) pairs (FT_SPLIT1) */
+struct FtSplits {
+  int rows, pixels;
+};
+
+struct FtNet {
+  virtual ~FtNet() {}
+  virtual const char *name() const = 0;
+  virtual int num_weights() const = 0;
+  virtual size_t stat_floats() const = 0;
+  /* where ft_k_head_reduce writes the gradients of the heads' last biases */
+  virtual int policy_bias() const = 0;
+  virtual int value_bias() const = 0;
+  /* ft_k_update's code of every weight: sidx has num_weights entries */
+  virtual void update_table(std::vector<int32_t> &sidx) const = 0;
+  /* forward of rows[0..B) (a device pointer) of the data set; train = batch statistics (left in stat), else the moving
+   * ones.  Leaves h. */
+  virtual void forward(const FtShared &sh, const int32_t *rows, int B, bool train) = 0;
+  /* from hd and what forward kept: the weight gradient of the batch as partials in g (the heads' last biases excepted) */
+  virtual FtSplits backward(const FtShared &sh, int B) = 0;
+};
+/* kind: CA_NET_MLP12X100 or CA_NET_RESCNN4; the network's own buffers are sized for max_batch rows and cleared on s */
+FtNet *ft_net_create(int kind, int max_batch, rt_stream_t s);
+FtNet *ft_mlp_create(int max_batch, rt_stream_t s);
+FtNet *ft_rescnn_create(int max_batch, rt_stream_t s);

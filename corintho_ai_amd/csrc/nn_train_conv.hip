@@ -1,5 +1,7 @@
-// nn_train_conv.hip -- the convolutional kernels of rescnn4's training step ("Network training", rescnn4),
-// float32 on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32).
+// nn_train_conv.hip -- rescnn4's training step ("Network training", rescnn4): its convolutional kernels,
+// float32 on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32), and below them the network as the fitter sees it
+// (FtResCnn, an FtNet of nn_train.h): layout, buffers, forward and backward.  The heads' 1x1 convolutions and dense
+// layers go through ft_k_gemm (nn_train.hip).
 //
 // Activations are NHWC [B * 16][C], row = position * 16 + pixel, so a 16-row MFMA tile is one 4x4 board and a 3x3 tap
 // is a permutation of the tile's rows with the off-board rows zero: no im2col buffer exists.
@@ -9,15 +11,19 @@
 //   fc_k_bnb_part / _final / _apply     its backward: ReLU mask, residual pass-through, dgamma, dbeta, dZ
 // Every cross-workgroup sum is per-chunk partials combined in chunk order by a later launch: no float atomics, no
 // grid-wide barrier, so a step is bitwise reproducible.
-#include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "../../include/corintho_hip.h"
-#include "nn.h"
-#include "nn_train_conv.h"
+#include "nn_train.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+#define FC_C 64           /* trunk channels */
+#define FC_IN_LD 16       /* input planes: 10 channels padded with zeros to one k tile row of 16 */
+#define FC_BN_CHUNKS 256  /* at most this many row chunks in a BatchNorm reduction */
+#define FC_WG_CHUNKS 128  /* at most this many row chunks in a 3x3 weight gradient */
+#define FC_WG_FLOATS (9 * FC_C * FC_C)
+#define FC_BN_PART (FC_BN_CHUNKS * 3 * 64)         /* BatchNorm chunk partials: float32 forward, float64 backward */
+#define FC_BN_SCRATCH (2 * (FC_BN_PART + 2 * 64)) /* floats of those and of the two per-channel constants behind them */
 #define FC_POS 4   /* positions of a convolution workgroup, one per wave */
 #define FC_XLD 66  /* LDS row stride of a board tile: lanes (row i, k q) of a 32-lane half on 32 banks (2 i + q) */
 #define FC_WLD 80  /* LDS row stride of [k][n] operands: lanes (k q, n i) of a half on banks 16 q + i */
@@ -160,14 +166,16 @@ __global__ __launch_bounds__(256) void fc_k_wgrad_sum(const float *__restrict__ 
 /* ---------------------------------------------------------------- BatchNorm over channels
  * 256 threads = (256 / C) row groups x C channels, so thread t always meets channel t % C and rows are read whole. */
 
-/* sum over the block's row groups in a fixed order, returned to every thread of the channel; red holds 256 + 64 floats */
-__device__ __forceinline__ float fc_groupsum(float *red, float v, int C) {
+/* sum over the block's row groups in a fixed order, returned to every thread of the channel; red holds 256 + 64 of T
+ * (float forward, double backward) */
+template <typename T>
+__device__ __forceinline__ T fc_groupsum(T *red, T v, int C) {
   const int c = threadIdx.x % C;
   __syncthreads();
   red[threadIdx.x] = v;
   __syncthreads();
   if ((int)threadIdx.x < C) {
-    float s = 0.0f;
+    T s = 0;
     for (int j = 0; j < 256; j += C) s += red[j + c];
     red[256 + c] = s;
   }
@@ -234,19 +242,6 @@ __global__ __launch_bounds__(256) void fc_k_bn_apply(const float *__restrict__ Z
  * of that many half ulps instead, which the next layer's weight gradient multiplies by the mean of its input and every
  * beta along the residual path inherits.  With float64 sums of the float32 terms (sum xhat among them: it is 0 only as
  * far as the float32 mean is exact) and one rounding of each dZ, what is left is the rounding of dZ itself. */
-__device__ __forceinline__ double fc_groupsum_d(double *red, double v, int C) {
-  const int c = threadIdx.x % C;
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  if ((int)threadIdx.x < C) {
-    double s = 0.0;
-    for (int j = 0; j < 256; j += C) s += red[j + c];
-    red[256 + c] = s;
-  }
-  __syncthreads();
-  return red[256 + c];
-}
 
 /* chunk partials of sum dY, sum dY xhat and sum xhat, dY = dOut where out > 0 (written back when keep) */
 __global__ __launch_bounds__(256) void fc_k_bnb_part(float *__restrict__ dOut, const float *__restrict__ out,
@@ -265,9 +260,9 @@ __global__ __launch_bounds__(256) void fc_k_bnb_part(float *__restrict__ dOut, c
     s2 += (double)dy * (double)xh;
     s3 += (double)xh;
   }
-  s1 = fc_groupsum_d(red, s1, C);
-  s2 = fc_groupsum_d(red, s2, C);
-  s3 = fc_groupsum_d(red, s3, C);
+  s1 = fc_groupsum(red, s1, C);
+  s2 = fc_groupsum(red, s2, C);
+  s3 = fc_groupsum(red, s3, C);
   if (rg == 0) {
     part[(blockIdx.x * 3) * 64 + c] = s1;
     part[(blockIdx.x * 3 + 1) * 64 + c] = s2;
@@ -316,61 +311,257 @@ __global__ __launch_bounds__(256) void fc_k_bnb_apply(const float *__restrict__ 
 }
 
 /* ------------------------------------------------------------------ launchers */
-#define FC_LAUNCH(k, grid, block, s, ...)                         \
-  do {                                                            \
-    hipLaunchKernelGGL(k, dim3 grid, dim3(block), 0, s, __VA_ARGS__); \
-    RT_CHECK(hipGetLastError());                                  \
-  } while (0)
-
 static inline int fc_bn_rpc(int R) { return 128 * ((R + 128 * FC_BN_CHUNKS - 1) / (128 * FC_BN_CHUNKS)); }
 
-void fc_planes(rt_stream_t s, const float *states, const int32_t *rows, int B, float *x0) {
-  FC_LAUNCH(fc_k_planes, ((unsigned)(((long)B * 16 * FC_IN_LD + 255) / 256)), 256, s, states, rows, B, x0);
+/* x0[B * 16][16] = rescnn4's input planes of states[rows[r]] (nets.rescnn4_input_planes), channels 10..15 zero */
+static void fc_planes(rt_stream_t s, const float *states, const int32_t *rows, int B, float *x0) {
+  FT_LAUNCH(fc_k_planes, (unsigned)(((long)B * 16 * FC_IN_LD + 255) / 256), 256, s, states, rows, B, x0);
 }
 
-void fc_wtrans(rt_stream_t s, const float *w, int first, int stride, int n, float *wt) {
-  FC_LAUNCH(fc_k_wtrans, ((n * FC_WG_FLOATS + 255) / 256), 256, s, w, first, stride, n, wt);
+/* wt[l][tap][co][ci] = w[first + l * stride][8 - tap][ci][co] for the n 64 -> 64 kernels: the operand of backward-data */
+static void fc_wtrans(rt_stream_t s, const float *w, int first, int stride, int n, float *wt) {
+  FT_LAUNCH(fc_k_wtrans, (n * FC_WG_FLOATS + 255) / 256, 256, s, w, first, stride, n, wt);
 }
 
-void fc_conv3(rt_stream_t s, const float *X, int cin, const float *W, const float *bias, float *out, int B, int accumulate) {
+/* out[row][co] (+)= bias[co] + sum over taps and ci of X[row shifted by the tap][ci] W[tap][ci][co]; cin = 10 reads X
+ * with row stride FC_IN_LD, cin = 64 with FC_C.  bias may be null. */
+static void fc_conv3(rt_stream_t s, const float *X, int cin, const float *W, const float *bias, float *out, int B,
+                     int accumulate) {
   const int grid = (B + FC_POS - 1) / FC_POS;
   if (cin == FC_C)
-    FC_LAUNCH(fc_k_conv3<FC_C>, (grid), 256, s, X, W, cin, bias, out, B, accumulate);
+    FT_LAUNCH(fc_k_conv3<FC_C>, grid, 256, s, X, W, cin, bias, out, B, accumulate);
   else
-    FC_LAUNCH(fc_k_conv3<FC_IN_LD>, (grid), 256, s, X, W, cin, bias, out, B, accumulate);
+    FT_LAUNCH(fc_k_conv3<FC_IN_LD>, grid, 256, s, X, W, cin, bias, out, B, accumulate);
 }
 
-void fc_conv3_wgrad(rt_stream_t s, const float *X, int cin, const float *dZ, int B, float *part, float *dW) {
+/* dW[tap][ci][co] = sum over rows of X[row shifted by the tap][ci] dZ[row][co]: per-chunk partials into part
+ * ([FC_WG_CHUNKS][9 * cin * 64]), then their sum in chunk order into dW */
+static void fc_conv3_wgrad(rt_stream_t s, const float *X, int cin, const float *dZ, int B, float *part, float *dW) {
   int ppc = (B + FC_WG_CHUNKS - 1) / FC_WG_CHUNKS;
   ppc = ppc < 16 ? 16 : (ppc + 3) / 4 * 4;
   const int nchunk = (B + ppc - 1) / ppc, n = 9 * cin * FC_C;
   if (cin == FC_C)
-    FC_LAUNCH(fc_k_wgrad<FC_C>, (nchunk, 3), 3 * FC_C * 4, s, X, dZ, B, ppc, cin, part);
+    FT_LAUNCH(fc_k_wgrad<FC_C>, dim3(nchunk, 3), 3 * FC_C * 4, s, X, dZ, B, ppc, cin, part);
   else
-    FC_LAUNCH(fc_k_wgrad<FC_IN_LD>, (nchunk, 3), 3 * FC_IN_LD * 4, s, X, dZ, B, ppc, cin, part);
-  FC_LAUNCH(fc_k_wgrad_sum, ((n + 255) / 256), 256, s, (const float *)part, nchunk, n, dW);
+    FT_LAUNCH(fc_k_wgrad<FC_IN_LD>, dim3(nchunk, 3), 3 * FC_IN_LD * 4, s, X, dZ, B, ppc, cin, part);
+  FT_LAUNCH(fc_k_wgrad_sum, (n + 255) / 256, 256, s, (const float *)part, nchunk, n, dW);
 }
 
-void fc_bn_fwd(rt_stream_t s, const float *Z, const float *res, float *out, int R, int C, const float *bn, int train,
-               float *part, float *stat) {
+/* BatchNorm over the R rows of Z[R][C] (C in {64, 4, 2}), then + res (or null), then ReLU -> out.  bn = gamma, beta,
+ * moving mean, moving variance, C floats each.  train: batch statistics, two stage (per-chunk mean and centred sum of
+ * squares in part (FC_BN_SCRATCH floats), combined in chunk order), left in stat[0..C) and stat[64..64 + C); else the
+ * moving ones. */
+static void fc_bn_fwd(rt_stream_t s, const float *Z, const float *res, float *out, int R, int C, const float *bn, int train,
+                      float *part, float *stat) {
   const long n = (long)R * C;
   const float *mean = bn + 2 * C, *var = bn + 3 * C;
   if (train) {
     const int rpc = fc_bn_rpc(R), nch = (R + rpc - 1) / rpc;
-    FC_LAUNCH(fc_k_bn_part, (nch), 256, s, Z, R, C, rpc, part);
-    FC_LAUNCH(fc_k_bn_final, (1), 64, s, (const float *)part, nch, R, rpc, C, stat);
+    FT_LAUNCH(fc_k_bn_part, nch, 256, s, Z, R, C, rpc, part);
+    FT_LAUNCH(fc_k_bn_final, 1, 64, s, (const float *)part, nch, R, rpc, C, stat);
     mean = stat, var = stat + 64;
   }
-  FC_LAUNCH(fc_k_bn_apply, ((unsigned)((n + 4095) / 4096)), 256, s, Z, res, out, n, C, bn, mean, var);
+  FT_LAUNCH(fc_k_bn_apply, (unsigned)((n + 4095) / 4096), 256, s, Z, res, out, n, C, bn, mean, var);
 }
 
-void fc_bn_bwd(rt_stream_t s, float *dOut, const float *out, const float *Z, float *dZ, int R, int C, const float *bn,
-               const float *stat, int keep, float *part, float *g) {
+/* backward of the same: dOut is the gradient at `out`; dY = dOut where out > 0 (written back to dOut when keep: the
+ * residual branch's share); dZ, and dbias (identically 0), dgamma, dbeta to g[0..3C) */
+static void fc_bn_bwd(rt_stream_t s, float *dOut, const float *out, const float *Z, float *dZ, int R, int C, const float *bn,
+                      const float *stat, int keep, float *part, float *g) {
   const long n = (long)R * C;
   const int rpc = fc_bn_rpc(R), nch = (R + rpc - 1) / rpc;
-  FC_LAUNCH(fc_k_bnb_part, (nch), 256, s, dOut, out, Z, R, C, rpc, stat, keep, (double *)part);
+  FT_LAUNCH(fc_k_bnb_part, nch, 256, s, dOut, out, Z, R, C, rpc, stat, keep, (double *)part);
   double *dpart = (double *)part, *fin = dpart + FC_BN_PART; /* the backward partials are float64 */
-  FC_LAUNCH(fc_k_bnb_final, (1), 64, s, (const double *)dpart, nch, C, R, g, fin);
-  FC_LAUNCH(fc_k_bnb_apply, ((unsigned)((n + 4095) / 4096)), 256, s, (const float *)dOut, out, Z, dZ, n, C, bn, stat,
+  FT_LAUNCH(fc_k_bnb_final, 1, 64, s, (const double *)dpart, nch, C, R, g, fin);
+  FT_LAUNCH(fc_k_bnb_apply, (unsigned)((n + 4095) / 4096), 256, s, (const float *)dOut, out, Z, dZ, n, C, bn, stat,
             (const double *)fin);
 }
+
+/* ------------------------------------------------------------------ the network */
+#define FC_NBN 11       /* BatchNorms of rescnn4: nine convolutions, the policy and the value head's 1x1 */
+#define FC_STAT_LD 128  /* a BatchNorm's slot in stat: the batch mean at 0, the batch variance at 64 (fc_k_bn_final) */
+
+/* rescnn4's flat layout (nets._rescnn4_shapes): convolution l = 0 (stem) .. 8 has its kernel at conv_k[l], the heads'
+ * 1x1 convolutions at p_k and v_k; each is followed by its BatchNorm's (j = l, 9 policy, 10 value) bias, gamma, beta,
+ * moving mean and moving variance, channels(j) floats each.  Then the heads' dense kernels and biases. */
+struct FcLayout {
+  int conv_k[9], bn_b[FC_NBN];
+  int p_k, p_dk, p_db, v_k, v_d1k, v_d1b, v_d2k, v_d2b, nw;
+  FcLayout() {
+    int p = 0;
+    for (int l = 0; l < 9; ++l) {
+      conv_k[l] = p;
+      p += 9 * (l == 0 ? 10 : FC_C) * FC_C;
+      bn_b[l] = p;
+      p += 5 * FC_C;
+    }
+    p_k = p, bn_b[9] = p_k + FC_C * 4, p_dk = bn_b[9] + 5 * 4, p_db = p_dk + 64 * CA_NUM_MOVES;
+    v_k = p_db + CA_NUM_MOVES, bn_b[10] = v_k + FC_C * 2, v_d1k = bn_b[10] + 5 * 2, v_d1b = v_d1k + 32 * 64;
+    v_d2k = v_d1b + 64, v_d2b = v_d2k + 64, nw = v_d2b + 1;
+  }
+  static int channels(int j) { return j < 9 ? FC_C : j == 9 ? 4 : 2; }
+  int bias(int j) const { return bn_b[j]; }
+  int gamma(int j) const { return bn_b[j] + channels(j); }
+  int mean(int j) const { return bn_b[j] + 3 * channels(j); }
+  int var(int j) const { return bn_b[j] + 4 * channels(j); }
+};
+
+/* hands out consecutive pieces of one allocation; with base null it only adds up their sizes */
+struct FcCarver {
+  float *base;
+  size_t used = 0;
+  float *take(size_t n) {
+    float *p = base ? base + used : nullptr;
+    used += n;
+    return p;
+  }
+};
+
+struct FtResCnn : FtNet {
+  const FcLayout L;
+  const size_t rows; /* max_batch rounded up to whole 16-row tiles */
+  FtBuf<float> x0, act, wt, wpart, bnpart;
+  /* pieces of act: activations are [rows * 16][C]; the heads' [rows * 16][4] and [rows * 16][2] are [rows][64] and
+   * [rows][32] once flattened (pixel * C + channel) */
+  float *Z[9], *X[5], *T[4];  /* convolution l's output before its BatchNorm; the stem's (0) and block b - 1's output;
+                                 block b's first activation */
+  float *G, *GB, *DZ;         /* the trunk's three gradient buffers */
+  float *zp, *pa, *dpa, *dzp; /* policy head: the 1x1 convolution's output, its activation, and their gradients */
+  float *zv, *va, *dva, *dzv; /* value head: the same */
+  float *d1, *dd1;            /* the value head's dense layer of 64 and its gradient */
+
+  void carve(FcCarver &c) {
+    const size_t plane = rows * 16 * FC_C;
+    for (float *&p : Z) p = c.take(plane);
+    for (float *&p : X) p = c.take(plane);
+    for (float *&p : T) p = c.take(plane);
+    G = c.take(plane), GB = c.take(plane), DZ = c.take(plane);
+    zp = c.take(rows * 16 * 4), pa = c.take(rows * 64), dpa = c.take(rows * 64), dzp = c.take(rows * 16 * 4);
+    zv = c.take(rows * 16 * 2), va = c.take(rows * 32), dva = c.take(rows * 32), dzv = c.take(rows * 16 * 2);
+    d1 = c.take(rows * 64), dd1 = c.take(rows * 64);
+  }
+
+  FtResCnn(int max_batch, rt_stream_t s) : rows((size_t)((max_batch + 15) / 16 * 16)) {
+    FcCarver count{nullptr}, c{nullptr};
+    carve(count);
+    act.alloc(count.used, s);
+    c.base = act.p;
+    carve(c);
+    x0.alloc(rows * 16 * FC_IN_LD, s);
+    wt.alloc((size_t)8 * FC_WG_FLOATS, s);
+    wpart.alloc((size_t)FC_WG_CHUNKS * FC_WG_FLOATS, s);
+    bnpart.alloc((size_t)FC_BN_SCRATCH, s);
+  }
+  const char *name() const override { return "rescnn4"; }
+  int num_weights() const override { return L.nw; }
+  size_t stat_floats() const override { return (size_t)FC_NBN * FC_STAT_LD; }
+  int policy_bias() const override { return L.p_db; }
+  int value_bias() const override { return L.v_d2b; }
+  void update_table(std::vector<int32_t> &sidx) const override {
+    sidx.assign(L.nw, FT_WHOLE);
+    for (int e = 0; e < 64 * CA_NUM_MOVES; ++e) sidx[L.p_dk + e] = FT_SPLIT0; /* products over the B rows */
+    for (int e = 0; e < 32 * 64; ++e) sidx[L.v_d1k + e] = FT_SPLIT0;
+    for (int e = 0; e < 64; ++e) sidx[L.v_d2k + e] = FT_SPLIT0;
+    for (int e = 0; e < FC_C * 4; ++e) sidx[L.p_k + e] = FT_SPLIT1; /* products over the B * 16 (position, pixel) rows */
+    for (int e = 0; e < FC_C * 2; ++e) sidx[L.v_k + e] = FT_SPLIT1;
+    for (int j = 0; j < FC_NBN; ++j)
+      for (int c = 0; c < L.channels(j); ++c) {
+        sidx[L.mean(j) + c] = j * FC_STAT_LD + c;
+        sidx[L.var(j) + c] = j * FC_STAT_LD + 64 + c;
+      }
+  }
+
+  void bn_fwd(const FtShared &sh, int j, const float *Zj, const float *res, float *out, int R, bool train) {
+    fc_bn_fwd(sh.s, Zj, res, out, R, L.channels(j), sh.w + L.gamma(j), train ? 1 : 0, bnpart.p, sh.stat + j * FC_STAT_LD);
+  }
+  void bn_bwd(const FtShared &sh, int j, float *dOut, const float *out, const float *Zj, float *dZ, int R, bool keep) {
+    fc_bn_bwd(sh.s, dOut, out, Zj, dZ, R, L.channels(j), sh.w + L.gamma(j), sh.stat + j * FC_STAT_LD, keep ? 1 : 0,
+              bnpart.p, sh.g + L.bias(j));
+  }
+
+  void forward(const FtShared &sh, const int32_t *rws, int B, bool train) override {
+    const int R = B * 16;
+    rt_stream_t s = sh.s;
+    float *w = sh.w;
+    fc_planes(s, sh.states, rws, B, x0.p);
+    fc_conv3(s, x0.p, 10, w + L.conv_k[0], w + L.bias(0), Z[0], B, 0);
+    bn_fwd(sh, 0, Z[0], nullptr, X[0], R, train);
+    for (int b = 0; b < 4; ++b) {
+      const int l1 = 1 + 2 * b, l2 = 2 + 2 * b;
+      fc_conv3(s, X[b], FC_C, w + L.conv_k[l1], w + L.bias(l1), Z[l1], B, 0);
+      bn_fwd(sh, l1, Z[l1], nullptr, T[b], R, train);
+      fc_conv3(s, T[b], FC_C, w + L.conv_k[l2], w + L.bias(l2), Z[l2], B, 0);
+      bn_fwd(sh, l2, Z[l2], X[b], X[b + 1], R, train);
+    }
+    /* policy: 1x1 convolution to 4 channels, BatchNorm, ReLU, flatten, dense to the 96 logits */
+    FtGemm a = mk(X[4], FC_C, 1, w + L.p_k, 4, 1, zp, 4, 1, R, 4, FC_C);
+    a.bias = w + L.bias(9);
+    ft_gemm(s, a);
+    bn_fwd(sh, 9, zp, nullptr, pa, R, train);
+    a = mk(pa, 64, 1, w + L.p_dk, CA_NUM_MOVES, 1, sh.h, FT_PADW, 1, B, CA_NUM_MOVES, 64);
+    a.bias = w + L.p_db;
+    ft_gemm(s, a);
+    /* value: 1x1 convolution to 2 channels, BatchNorm, ReLU, flatten, dense 32 -> 64, ReLU, dense 64 -> 1 */
+    a = mk(X[4], FC_C, 1, w + L.v_k, 2, 1, zv, 2, 1, R, 2, FC_C);
+    a.bias = w + L.bias(10);
+    ft_gemm(s, a);
+    bn_fwd(sh, 10, zv, nullptr, va, R, train);
+    a = mk(va, 32, 1, w + L.v_d1k, 64, 1, d1, 64, 1, B, 64, 32);
+    a.bias = w + L.v_d1b, a.relu = 1;
+    ft_gemm(s, a);
+    a = mk(d1, 64, 1, w + L.v_d2k, 1, 1, sh.h + 96, FT_PADW, 1, B, 1, 64);
+    a.bias = w + L.v_d2b;
+    ft_gemm(s, a);
+  }
+
+  FtSplits backward(const FtShared &sh, int B) override {
+    const int R = B * 16, kb = ft_split_chunk(B), kr = ft_split_chunk(R), nw = L.nw;
+    rt_stream_t s = sh.s;
+    float *w = sh.w, *g = sh.g, *hd = sh.hd;
+    /* policy head: dense kernel, its input's gradient, BatchNorm and ReLU, the 1x1 kernel, G = the trunk output's share */
+    FtGemm a = mk(pa, 1, 64, hd, FT_PADW, 1, g + L.p_dk, CA_NUM_MOVES, 1, 64, CA_NUM_MOVES, B);
+    a.kchunk = kb, a.c_split = nw;
+    ft_gemm(s, a);
+    ft_gemm(s, mk(hd, FT_PADW, 1, w + L.p_dk, 1, CA_NUM_MOVES, dpa, 64, 1, B, 64, CA_NUM_MOVES));
+    bn_bwd(sh, 9, dpa, pa, zp, dzp, R, false);
+    a = mk(X[4], 1, FC_C, dzp, 4, 1, g + L.p_k, 4, 1, FC_C, 4, R);
+    a.kchunk = kr, a.c_split = nw;
+    ft_gemm(s, a);
+    ft_gemm(s, mk(dzp, 4, 1, w + L.p_k, 1, 4, G, FC_C, 1, R, FC_C, 4));
+    /* value head, added to G */
+    a = mk(d1, 1, 64, hd + 96, FT_PADW, 1, g + L.v_d2k, 1, 1, 64, 1, B);
+    a.kchunk = kb, a.c_split = nw;
+    ft_gemm(s, a);
+    ft_gemm(s, mk(hd + 96, FT_PADW, 1, w + L.v_d2k, 1, 1, dd1, 64, 1, B, 64, 1));
+    ft_relu_bwd(s, dd1, d1, B, 64, 64, g + L.v_d1b);
+    a = mk(va, 1, 32, dd1, 64, 1, g + L.v_d1k, 64, 1, 32, 64, B);
+    a.kchunk = kb, a.c_split = nw;
+    ft_gemm(s, a);
+    ft_gemm(s, mk(dd1, 64, 1, w + L.v_d1k, 1, 64, dva, 32, 1, B, 32, 64));
+    bn_bwd(sh, 10, dva, va, zv, dzv, R, false);
+    a = mk(X[4], 1, FC_C, dzv, 2, 1, g + L.v_k, 2, 1, FC_C, 2, R);
+    a.kchunk = kr, a.c_split = nw;
+    ft_gemm(s, a);
+    a = mk(dzv, 2, 1, w + L.v_k, 1, 2, G, FC_C, 1, R, FC_C, 2);
+    a.accumulate = 1;
+    ft_gemm(s, a);
+    /* trunk: G is the gradient at block b's output.  Its ReLU-masked copy (kept in G) is both the second BatchNorm's
+     * input gradient and the residual branch's share of the block input's gradient, to which backward-data of the
+     * first convolution is added */
+    fc_wtrans(s, w, L.conv_k[1], L.conv_k[2] - L.conv_k[1], 8, wt.p);
+    for (int b = 3; b >= 0; --b) {
+      const int l1 = 1 + 2 * b, l2 = 2 + 2 * b;
+      bn_bwd(sh, l2, G, X[b + 1], Z[l2], DZ, R, true);
+      fc_conv3_wgrad(s, T[b], FC_C, DZ, B, wpart.p, g + L.conv_k[l2]);
+      fc_conv3(s, DZ, FC_C, wt.p + (size_t)(l2 - 1) * FC_WG_FLOATS, nullptr, GB, B, 0);
+      bn_bwd(sh, l1, GB, T[b], Z[l1], DZ, R, false);
+      fc_conv3_wgrad(s, X[b], FC_C, DZ, B, wpart.p, g + L.conv_k[l1]);
+      fc_conv3(s, DZ, FC_C, wt.p + (size_t)(l1 - 1) * FC_WG_FLOATS, nullptr, G, B, 1);
+    }
+    bn_bwd(sh, 0, G, X[0], Z[0], DZ, R, false);
+    fc_conv3_wgrad(s, x0.p, 10, DZ, B, wpart.p, g + L.conv_k[0]);
+    return {(B + kb - 1) / kb, (R + kr - 1) / kr};
+  }
+};
+
+FtNet *ft_rescnn_create(int max_batch, rt_stream_t s) { return new FtResCnn(max_batch, s); }

@@ -1,7 +1,7 @@
 """Network training on the device: the reference's Keras `model.fit` step (corintho_ai/python/main.pyx:221-272,
-model and compile of wrapper.py:256-282) for mlp12x100, with the HIP kernels of csrc/nn_train.hip; and the same recipe
-for rescnn4 (`net=NET_RESCNN4`, csrc/nn_train_conv.hip), whose BatchNorms take batch statistics per channel over all
-(row, pixel) pairs.
+model and compile of wrapper.py:256-282) for mlp12x100, with the HIP kernels of csrc/nn_train_mlp.hip; and the same
+recipe for rescnn4 (`net=NET_RESCNN4`, csrc/nn_train_conv.hip), whose BatchNorms take batch statistics per channel over
+all (row, pixel) pairs.  The step driver, the loss and Adam are shared by both networks (csrc/nn_train.hip).
 
     res = fit(weights, game_states, eval_labels, prob_labels, epochs=10)
     trainer.set_net(NET_MLP12X100, res.best_weights)

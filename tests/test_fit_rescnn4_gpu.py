@@ -1,6 +1,7 @@
 """rescnn4 training on the MI355X (csrc/nn_train_conv.hip and nn_train.hip through corintho_ai_amd.fit) against the
 float64 restatement of the step (tests/fit_ref_rescnn4.py).  The rule of tests/test_fit_gpu.py: the device's error
-against float64 is at most 4 x the float32 restatement's own error against float64, plus a small floor."""
+against float64 is at most 4 x the float32 restatement's own error against float64, plus a small floor.  The Adam
+steps, the bitwise repeat and the set/get round trip of this network are tests/test_fit_gpu.py's, parametrised."""
 import ctypes as C
 
 import numpy as np
@@ -11,18 +12,13 @@ from corintho_ai_amd.fit import Fitter, fit, split_index
 from tests import fit_ref
 from tests import fit_ref_rescnn4 as R
 from tests import ref_nets
+from tests.test_fit_gpu import _within
 
 pytestmark = pytest.mark.gpu
 
 WEIGHTS = [("init", lambda: nets.init_rescnn4(0)), ("bn-noise", lambda: nets.init_rescnn4(7, bn_noise=True)),
            ("trained-like", lambda: nets.trained_like_rescnn4(1))]
 KINK = 2e-7
-
-
-def _within(dev, f32, f64, floor):
-    e_dev = float(np.max(np.abs(np.asarray(dev, np.float64) - f64)))
-    e_32 = float(np.max(np.abs(np.asarray(f32, np.float64) - f64)))
-    return e_dev <= 4.0 * e_32 + floor, e_dev, e_32
 
 
 def _check_gradient(f, w, data, rows, tag, kink, bad):
@@ -91,76 +87,6 @@ def test_gradients_at_scale_without_a_kink():
                 assert margin >= KINK, (seed, B, margin)
                 _check_gradient(f, w, data, rows, "seed %d B=%d" % (seed, B), False, bad)
     assert not bad, "device error above 4 x float32's: %s" % bad[:12]
-
-
-def test_twenty_adam_steps():
-    """batch losses, moving statistics and held-out inference outputs after 20 steps of 256 rows (raw weights are not
-    compared: Adam's first steps are close to lr * sign(g) and amplify the smallest gradient differences)"""
-    s, z, p = R.synthetic_samples(5120 + 512, 12)
-    w = nets.init_rescnn4(5, bn_noise=True)
-    rows = np.random.default_rng(4).permutation(5120).astype(np.int32)
-    zeros = np.zeros_like(w)
-    with Fitter(max_batch=256, net=NET_RESCNN4) as f:
-        f.set_data(s, z, p)
-        f.set_weights(w)
-        f.set_optimizer(zeros, zeros, 0)
-        _, per = f.train(rows, 256, 1e-3, batch_losses=True)
-        wd = f.get_weights()
-        _, _, it = f.get_optimizer()
-    assert it == 20
-    refs = {}
-    for dt in (R.torch.float64, R.torch.float32):
-        be = R.RefBackend(dt)
-        be.set_weights(w)
-        be.set_optimizer(zeros, zeros, 0)
-        be.set_data(s, z, p)
-        _, pr = be.train(rows, 256, 1e-3, batch_losses=True)
-        refs[dt] = (pr, be.w.astype(np.float64))
-    (p64, w64), (p32, w32) = refs[R.torch.float64], refs[R.torch.float32]
-    ok, ed, e3 = _within(per, p32, p64, 1e-6)
-    print("batch losses dev %.3e f32 %.3e" % (ed, e3))
-    assert ok, ("batch losses", ed, e3)
-    mask = R.stat_mask()
-    ok, ed, e3 = _within(wd[mask], w32[mask], w64[mask], 1e-6)
-    print("moving statistics dev %.3e f32 %.3e" % (ed, e3))
-    assert ok, ("moving statistics", ed, e3)
-    held = slice(5120, 5632)
-    out64 = R.evaluate(w64, s[held], z[held], p[held])[1]
-    out32 = R.evaluate(w32, s[held], z[held], p[held])[1]
-    outd = R.evaluate(wd.astype(np.float64), s[held], z[held], p[held])[1]
-    for k, name in enumerate(("value", "policy")):
-        ok, ed, e3 = _within(outd[k], out32[k], out64[k], 1e-6)
-        print("%s dev %.3e f32 %.3e" % (name, ed, e3))
-        assert ok, (name, ed, e3)
-
-
-def test_two_fits_are_bitwise_identical_and_round_trip():
-    s, z, p = R.synthetic_samples(3000, 13)
-    w = nets.init_rescnn4(6, bn_noise=True)
-    a = fit(w, s, z, p, batch_size=512, epochs=2, seed=3, net=NET_RESCNN4)
-    b = fit(w, s, z, p, batch_size=512, epochs=2, seed=3, net=NET_RESCNN4)
-    assert a.weights.tobytes() == b.weights.tobytes() and a.best_weights.tobytes() == b.best_weights.tobytes()
-    for x, y in zip(a.optimizer[:2], b.optimizer[:2]):
-        assert x.tobytes() == y.tobytes()
-    for x, y in zip(a.best_optimizer[:2], b.best_optimizer[:2]):
-        assert x.tobytes() == y.tobytes()
-    assert a.optimizer[2] == b.optimizer[2] == 2 * -(-split_index(3000, 0.3) // 512)
-    assert a.history == b.history
-    assert a.weights.tobytes() != w.tobytes()
-    mask = R.stat_mask()
-    assert not a.optimizer[0][mask].any() and not a.optimizer[1][mask].any()
-    rng = np.random.default_rng(1)
-    w2 = nets.trained_like_rescnn4(2)
-    m = rng.normal(0, 1e-3, w2.size).astype(np.float32)
-    v = rng.uniform(0, 1e-6, w2.size).astype(np.float32)
-    with Fitter(max_batch=16, net=NET_RESCNN4) as f:
-        f.set_weights(w2)
-        f.set_optimizer(m, v, 1234)
-        assert f.get_weights().tobytes() == w2.tobytes()
-        m2, v2, it = f.get_optimizer()
-        assert m2.tobytes() == m.tobytes() and v2.tobytes() == v.tobytes() and it == 1234
-        with pytest.raises(Exception):
-            f.set_weights(nets.init_mlp12x100(0))
 
 
 def test_whole_loop_small(tmp_path):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Times the training step of mlp12x100 (csrc/nn_train.hip) or, with --net rescnn4, of the residual CNN
-(csrc/nn_train_conv.hip) on one GPU: ms per step at `--batch` rows on a sample set of `--rows` rows, rows/s and achieved
-FLOP/s against the fp32 matrix peak.  A step is 3 x 253.4 KFLOP per row (3 x 9.65 MFLOP for rescnn4) by the
+"""Times the training step of mlp12x100 (csrc/nn_train_mlp.hip) or, with --net rescnn4, of the residual CNN
+(csrc/nn_train_conv.hip), both driven by csrc/nn_train.hip, on one GPU: ms per step at `--batch` rows on a sample set
+of `--rows` rows, rows/s and achieved FLOP/s against the fp32 matrix peak.  A step is 3 x 253.4 KFLOP per row (3 x 9.65 MFLOP for rescnn4) by the
 algorithm (forward, and the two products of the backward pass).  Timing: a synchronised host clock around one
 ca_fitter_train call of `--steps` steps (the call ends by reading its losses back).
 
