@@ -81,6 +81,8 @@ EXPORTS = [
     "ca_tourney_set_net", "ca_tourney_run", "ca_tourney_set_exact_offsets", "ca_tourney_num_matches", "ca_tourney_match_info", "ca_tourney_match_score", "ca_tourney_trace", "ca_tourney_stats",
     "ca_fitter_create", "ca_fitter_create_net", "ca_fitter_destroy", "ca_fitter_set_weights", "ca_fitter_get_weights", "ca_fitter_set_optimizer",
     "ca_fitter_get_optimizer", "ca_fitter_set_data", "ca_fitter_train", "ca_fitter_evaluate", "ca_fitter_gradients",
+    "ca_trainer_device", "ca_fitter_clear_data", "ca_fitter_add_samples", "ca_fitter_add_device_samples",
+    "ca_fitter_add_trainer_samples", "ca_fitter_drop_samples", "ca_fitter_data_info", "ca_fitter_fetch_rows",
 ]
 
 
@@ -112,6 +114,7 @@ def declare(L):
     L.ca_trainer_finish.argtypes = [vp]
     L.ca_trainer_set_logging.argtypes = [vp, C.c_char_p, C.c_int32]
     L.ca_trainer_reset.argtypes = [vp, C.c_int32]
+    L.ca_trainer_device.argtypes = [vp, i32p]
     L.ca_expand_samples.argtypes = [C.c_int, f32p, f32p, C.c_int32, f32p, f32p, f32p]
     L.ca_trainer_stats.argtypes = [vp, C.POINTER(CaStats)]
     L.ca_trainer_game_info.argtypes = [vp, C.c_int, i32p]
@@ -167,6 +170,13 @@ def _declare_fitter(L, vp, f64p):
     L.ca_fitter_train.argtypes = [vp, i32p, C.c_int32, C.c_int32, C.c_float, f64p, f32p]
     L.ca_fitter_evaluate.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, f64p]
     L.ca_fitter_gradients.argtypes = [vp, i32p, C.c_int32, f32p, f64p]
+    L.ca_fitter_clear_data.argtypes = [vp]
+    L.ca_fitter_add_samples.argtypes = [vp, f32p, f32p, C.c_int32]
+    L.ca_fitter_add_device_samples.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_int32]
+    L.ca_fitter_add_trainer_samples.argtypes = [vp, vp, i32p]
+    L.ca_fitter_drop_samples.argtypes = [vp, C.c_int32]
+    L.ca_fitter_data_info.argtypes = [vp, i32p, i32p]
+    L.ca_fitter_fetch_rows.argtypes = [vp, i32p, C.c_int32, f32p, f32p, f32p]
 
 
 _lib = None

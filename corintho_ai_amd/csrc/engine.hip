@@ -1597,6 +1597,12 @@ extern "C" int ca_trainer_set_logging(ca_trainer *t, const char *log_folder, int
   CA_TGUARD(t->set_logging(log_folder, num_logged))
 }
 extern "C" int ca_trainer_reset(ca_trainer *t, int32_t seed) { CA_TGUARD(t->reset_games(seed)) }
+extern "C" int ca_trainer_device(ca_trainer *t, int32_t *device) {
+  CA_GUARD({
+    if (!t || !device) throw EngineError(CA_ERR_ARG, "ca_trainer_device: null argument");
+    *device = t->cfg.device;
+  })
+}
 /* diagnostic builds (-DCO_PROF): summed in-kernel cycle stamps, see mcts.h; not in the public header */
 extern "C" int ca_trainer_prof(ca_trainer *t, unsigned long long out[2 * CO_NPROF + 24]) {
   CA_TGUARD({

@@ -40,6 +40,15 @@ struct FtBuf {
     p = nullptr;
     rt_malloc((void **)&p, n * sizeof(T), s);
   }
+  void release() {
+    rt_free(p);
+    p = nullptr;
+  }
+  void swap(FtBuf &o) {
+    T *t = p;
+    p = o.p;
+    o.p = t;
+  }
 };
 
 struct FtError : std::runtime_error {
@@ -101,7 +110,8 @@ struct FtShared {
   float *stat;  /* batch statistics [stat_floats], where update_table's codes point */
   float *h;     /* the heads' outputs [B][FT_PADW]: 96 logits, the value at 96 */
   float *hd;    /* their gradients, from ft_k_loss */
-  const float *states; /* the data set's game states [n][70] */
+  const float *states; /* the game states [n][70] that forward's rows index: the expanded data set's, or the batch that
+                          ft_k_assemble wrote from a packed one (nn_train.hip) */
 };
 
 /* how many partials in g backward left for a weight whose gradient is a sum over the B rows (FT_SPLIT0) and over the

@@ -13,11 +13,20 @@
 //               gamma and beta, moving statistics from the batch statistics (ft_k_update)      1 launch
 // Every cross-workgroup sum is written as partials and combined in a fixed order by a later launch: no float atomics,
 // no grid-wide barriers, so a step is bitwise reproducible.
+//
+// The data set has two forms.  Expanded: the three arrays of Trainer::writeSamples, 8 symmetry copies of every sample,
+// which the networks' input kernels and ft_k_loss read through the batch's row indices.  Packed: the un-augmented rows of
+// co_k_pack_samples, whose 8n virtual rows (row v = sample v / 8 under symmetry v % 8) exist only batch by batch: one
+// launch (ft_k_assemble) writes the batch's rows as the expanded arrays would hold them and the same kernels, launched
+// the same way, read that batch through an identity index -- so a step is the same to the bit in either form.
 #include <math.h>
 
 #include <memory>
 
 #include "nn_train.h"
+#include "tables.inc"
+
+#define FT_SAMPLE_FLOATS (CA_GAME_STATE_SIZE + CA_NUM_MOVES) /* a packed row: state[70], policy[96] */
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -95,6 +104,49 @@ __global__ __launch_bounds__(256) void ft_k_loss(const float *__restrict__ H, co
   d[96] = 2.0f * err * (1.0f - tv * tv) * inv_b;
   d[97] = err * err;
   d[98] = ce;
+}
+
+/* the engine's symmetry tables (kernels.h CO_SPACE_SYM, CO_MOVE_SYM), from the same initialisers of tables.inc */
+__constant__ int32_t FT_SPACE_SYM[CA_NUM_SYMMETRIES][16] = CO_SPACE_SYM_INIT;
+__constant__ int32_t FT_MOVE_SYM[CA_NUM_SYMMETRIES][CA_NUM_MOVES] = CO_MOVE_SYM_INIT;
+
+/* where a batch's rows are fetched from: a packed set (sp != null) or an expanded one */
+struct FtSource {
+  const float *sp, *oc;               /* state_policy[n][166], outcome[n] */
+  const float *states, *evals, *probs; /* [n][70], [n], [n][96] */
+};
+
+/* The batch of rows[0..B) written compactly: bs[r] = the state, be[r] = the value label and bp[r] = the policy of row
+ * rows[r].  Of a packed set that is virtual row v = rows[r]: sample v / 8 under symmetry k = v % 8, the gathers of
+ * co_k_write_samples (state cell j < 64 from SS[k][j / 4] * 4 + j % 4, cells 64..69 as they are, policy entry m from
+ * MS[k][m]).  One thread per float of the batch's 166-float rows, so a wave writes consecutive floats and reads within
+ * one or two 664-byte samples. */
+__global__ __launch_bounds__(256) void ft_k_assemble(FtSource d, const int32_t *__restrict__ rows, int B,
+                                                    float *__restrict__ bs, float *__restrict__ be,
+                                                    float *__restrict__ bp) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * FT_SAMPLE_FLOATS) return;
+  const int r = e / FT_SAMPLE_FLOATS, c = e % FT_SAMPLE_FLOATS;
+  const int v = rows[r];
+  if (d.sp) {
+    const int i = v >> 3, k = v & 7;
+    const float *src = d.sp + (long)i * FT_SAMPLE_FLOATS;
+    if (c < CA_GAME_STATE_SIZE) {
+      bs[(long)r * CA_GAME_STATE_SIZE + c] = src[c < 64 ? FT_SPACE_SYM[k][c >> 2] * 4 + (c & 3) : c];
+    } else {
+      const int m = c - CA_GAME_STATE_SIZE;
+      bp[(long)r * CA_NUM_MOVES + m] = src[CA_GAME_STATE_SIZE + FT_MOVE_SYM[k][m]];
+    }
+    if (c == 0) be[r] = d.oc[i];
+  } else {
+    if (c < CA_GAME_STATE_SIZE) {
+      bs[(long)r * CA_GAME_STATE_SIZE + c] = d.states[(long)v * CA_GAME_STATE_SIZE + c];
+    } else {
+      const int m = c - CA_GAME_STATE_SIZE;
+      bp[(long)r * CA_NUM_MOVES + m] = d.probs[(long)v * CA_NUM_MOVES + m];
+    }
+    if (c == 0) be[r] = d.evals[v];
+  }
 }
 
 /* Column sums of Hd over the B rows (fixed order): the head biases' gradients (when g is given; the policy bias at
@@ -188,12 +240,16 @@ struct ca_fitter {
   int nw = 0; /* floats of the weight vector */
   int max_batch = 0;
   int64_t iterations = 0;
-  int32_t n = 0, idx_cap = 0;
+  int32_t n = 0, idx_cap = 0; /* addressable rows (8 * ns of a packed set); rows idx holds */
+  bool expanded = false;      /* the form: set by ca_fitter_set_data, until ca_fitter_clear_data */
+  int32_t ns = 0, cap = 0;    /* packed samples, and how many sp and oc have room for */
   rt_stream_t s = nullptr;
   std::unique_ptr<FtNet> net;
   FtBuf<float> w, m, v, g, gsum, stat, h, hd, loss;
-  FtBuf<float> states, evals, probs;
-  FtBuf<int32_t> sidx, idx;
+  FtBuf<float> states, evals, probs; /* the expanded set */
+  FtBuf<float> sp, oc;               /* the packed set: state_policy[cap][166], outcome[cap] */
+  FtBuf<float> bstates, bevals, bprobs; /* one batch of a packed set as ft_k_assemble wrote it: max_batch rows */
+  FtBuf<int32_t> sidx, idx, ident, bidx; /* ident[r] = r, the rows of an assembled batch; bidx: ca_fitter_fetch_rows */
   std::vector<float> hloss;
 
   void init(int dev, int kind, int mb) {
@@ -220,21 +276,36 @@ struct ca_fitter {
   }
   ~ca_fitter() { rt_stream_destroy(s); }
 
-  FtShared shared() const { return FtShared{s, w.p, g.p, stat.p, h.p, hd.p, states.p}; }
+  /* what the kernels of a step read a batch through: row indices into three arrays */
+  struct Batch {
+    const int32_t *rows;
+    const float *states, *evals, *probs;
+  };
+  FtSource source() const { return FtSource{expanded ? nullptr : sp.p, oc.p, states.p, evals.p, probs.p}; }
+  void assemble(const int32_t *rows, int B) {
+    FT_LAUNCH(ft_k_assemble, (B * FT_SAMPLE_FLOATS + 255) / 256, 256, s, source(), rows, B, bstates.p, bevals.p, bprobs.p);
+  }
+  /* the batch of rows[0..B) (a device pointer): the expanded set itself, or a packed set's rows assembled */
+  Batch batch(const int32_t *rows, int B) {
+    if (expanded) return Batch{rows, states.p, evals.p, probs.p};
+    assemble(rows, B);
+    return Batch{ident.p, bstates.p, bevals.p, bprobs.p};
+  }
+  FtShared shared(const Batch &b) const { return FtShared{s, w.p, g.p, stat.p, h.p, hd.p, b.states}; }
 
   /* loss terms of the batch (and the logit / value gradients in Hd); loss sums to loss.p[2 * slot] */
-  void loss_terms(const int32_t *rows, int B, bool grads, int slot) {
-    FT_LAUNCH(ft_k_loss, (B + 255) / 256, 256, s, (const float *)h.p, rows, B, (const float *)evals.p,
-              (const float *)probs.p, hd.p);
+  void loss_terms(const Batch &b, int B, bool grads, int slot) {
+    FT_LAUNCH(ft_k_loss, (B + 255) / 256, 256, s, (const float *)h.p, b.rows, B, b.evals, b.probs, hd.p);
     FT_LAUNCH(ft_k_head_reduce, FT_PADW / 16, 1024, s, (const float *)hd.p, B, grads ? g.p : (float *)nullptr,
               net->policy_bias(), net->value_bias(), loss.p + 2 * slot);
   }
 
   /* forward, loss (sums to slot) and backward of one batch: leaves the gradient partials and returns their counts */
   FtSplits gradient(const int32_t *rows, int B, int slot) {
-    const FtShared sh = shared();
-    net->forward(sh, rows, B, true);
-    loss_terms(rows, B, true, slot);
+    const Batch b = batch(rows, B);
+    const FtShared sh = shared(b);
+    net->forward(sh, b.rows, B, true);
+    loss_terms(b, B, true, slot);
     return net->backward(sh, B);
   }
 
@@ -246,14 +317,85 @@ struct ca_fitter {
   }
 
   void need_data() {
-    if (n <= 0) throw FtError(CA_ERR_STATE, "ca_fitter: no data (ca_fitter_set_data)");
+    if (n <= 0) throw FtError(CA_ERR_STATE, "ca_fitter: no data (ca_fitter_set_data, ca_fitter_add_samples)");
+  }
+  /* room in idx for the nr rows of a call: an expanded set has it from ca_fitter_set_data, a packed one takes what its
+   * largest call asked for, not a share of its capacity */
+  void need_idx(int32_t nr) {
+    if (idx_cap >= nr) return;
+    idx.alloc((size_t)nr, s);
+    idx_cap = nr;
+  }
+  /* the buffers of an assembled batch */
+  void need_stage() {
+    if (bidx.p) return;
+    std::vector<int32_t> id((size_t)max_batch);
+    for (int32_t i = 0; i < max_batch; ++i) id[i] = i;
+    bstates.alloc((size_t)max_batch * CA_GAME_STATE_SIZE, s);
+    bevals.alloc((size_t)max_batch, s);
+    bprobs.alloc((size_t)max_batch * CA_NUM_MOVES, s);
+    ident.alloc((size_t)max_batch, s);
+    rt_h2d(ident.p, id.data(), id.size() * sizeof(int32_t), s);
+    rt_sync(s); /* id is a local */
+    bidx.alloc((size_t)max_batch, s);
+  }
+  void clear_data() {
+    n = 0, ns = 0, cap = 0, idx_cap = 0, expanded = false;
+    states.release(), evals.release(), probs.release(), sp.release(), oc.release(), idx.release();
+  }
+  /* the packed rows [first, first + count) to the front of the buffers they are in (a slide of the window), device to
+   * device without a second buffer: in pieces of `first` rows from the front, each of which ends before its source
+   * begins, queued in order on one stream.  Only a drop of less than 1/64 of what stays goes through new buffers. */
+  void slide_samples(int32_t first, int32_t count) {
+    if ((int64_t)first * 64 < count) {
+      move_samples(first, count, cap);
+      return;
+    }
+    for (int32_t d = 0; d < count; d += first) {
+      const size_t k = (size_t)(count - d < first ? count - d : first);
+      rt_d2d(sp.p + (size_t)d * FT_SAMPLE_FLOATS, sp.p + ((size_t)d + first) * FT_SAMPLE_FLOATS,
+             k * FT_SAMPLE_FLOATS * sizeof(float), s);
+      rt_d2d(oc.p + d, oc.p + d + first, k * sizeof(float), s);
+    }
+    rt_sync(s);
+  }
+  /* the packed rows [first, first + count) to the front of new buffers with room for new_cap samples, device to device */
+  void move_samples(int32_t first, int32_t count, int32_t new_cap) {
+    FtBuf<float> nsp, noc;
+    nsp.alloc((size_t)new_cap * FT_SAMPLE_FLOATS, s);
+    noc.alloc((size_t)new_cap, s);
+    rt_d2d(nsp.p, sp.p + (size_t)first * FT_SAMPLE_FLOATS, (size_t)count * FT_SAMPLE_FLOATS * sizeof(float), s);
+    rt_d2d(noc.p, oc.p + first, (size_t)count * sizeof(float), s);
+    rt_sync(s); /* before the old buffers are freed */
+    sp.swap(nsp);
+    oc.swap(noc);
+    cap = new_cap;
+  }
+  /* room for `add` more packed samples behind the ns there are; capacity grows geometrically */
+  void reserve(int32_t add) {
+    if (expanded) throw FtError(CA_ERR_STATE, "ca_fitter: the data set is expanded (ca_fitter_clear_data first)");
+    if (add < 0) throw FtError(CA_ERR_ARG, "ca_fitter: negative sample count");
+    const int64_t need = (int64_t)ns + add, most = INT32_MAX / CA_NUM_SYMMETRIES;
+    if (need > most) throw FtError(CA_ERR_ARG, "ca_fitter: more than INT32_MAX virtual rows");
+    need_stage();
+    if (need <= cap) return;
+    int64_t nc = 2 * (int64_t)cap > need ? 2 * (int64_t)cap : need;
+    nc = nc < 1024 ? 1024 : nc > most ? most : nc;
+    move_samples(0, ns, (int32_t)nc);
+  }
+  void added(int32_t add) {
+    ns += add;
+    n = ns * CA_NUM_SYMMETRIES;
   }
   void check_n(size_t n_floats) {
     if (n_floats != (size_t)nw)
       throw FtError(CA_ERR_ARG, std::string("ca_fitter: ") + net->name() + " has " + std::to_string(nw) + " floats");
   }
   void check_rows(const int32_t *rows, int32_t nr) {
-    if (nr < 0 || nr > idx_cap) throw FtError(CA_ERR_ARG, "ca_fitter: more rows than the data set holds");
+    if (nr < 0 || nr > n) throw FtError(CA_ERR_ARG, "ca_fitter: more rows than the data set holds");
+    check_range(rows, nr);
+  }
+  void check_range(const int32_t *rows, int32_t nr) {
     for (int32_t i = 0; i < nr; ++i)
       if (rows[i] < 0 || rows[i] >= n) throw FtError(CA_ERR_ARG, "ca_fitter: row index out of range");
   }
@@ -389,7 +531,8 @@ extern "C" int ca_fitter_get_optimizer(ca_fitter *f, float *m, float *v, size_t 
 extern "C" int ca_fitter_set_data(ca_fitter *f, const float *states, const float *evals, const float *probs, int32_t n) {
   return ft_guard(f, [&] {
     if (n < 1 || !states || !evals || !probs) throw FtError(CA_ERR_ARG, "ca_fitter_set_data: empty or null");
-    f->n = 0; /* no data while the buffers are being replaced: a failure below leaves the fitter without, not with half */
+    f->clear_data(); /* no data while the buffers are being replaced: a failure below leaves the fitter without, not with half */
+    f->expanded = true;
     f->states.alloc((size_t)n * CA_GAME_STATE_SIZE, f->s);
     f->evals.alloc((size_t)n, f->s);
     f->probs.alloc((size_t)n * CA_NUM_MOVES, f->s);
@@ -410,6 +553,7 @@ extern "C" int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows
     f->check_batch(batch);
     if (!rows || n_rows < 1) throw FtError(CA_ERR_ARG, "ca_fitter_train: no rows");
     f->check_rows(rows, n_rows);
+    f->need_idx(n_rows);
     const int nb = (n_rows + batch - 1) / batch;
     f->ensure_loss(nb);
     rt_h2d(f->idx.p, rows, (size_t)n_rows * sizeof(int32_t), f->s);
@@ -432,6 +576,7 @@ extern "C" int ca_fitter_evaluate(ca_fitter *f, int32_t row0, int32_t n_rows, in
     f->check_batch(batch);
     if (n_rows < 1 || row0 < 0 || (int64_t)row0 + n_rows > f->n)
       throw FtError(CA_ERR_ARG, "ca_fitter_evaluate: rows out of range");
+    f->need_idx(n_rows);
     std::vector<int32_t> rows(n_rows);
     for (int32_t i = 0; i < n_rows; ++i) rows[i] = row0 + i;
     const int nb = (n_rows + batch - 1) / batch;
@@ -439,9 +584,9 @@ extern "C" int ca_fitter_evaluate(ca_fitter *f, int32_t row0, int32_t n_rows, in
     rt_h2d(f->idx.p, rows.data(), (size_t)n_rows * sizeof(int32_t), f->s);
     for (int b = 0; b < nb; ++b) {
       const int B = b * batch + batch <= n_rows ? batch : n_rows - b * batch;
-      const int32_t *r = f->idx.p + (size_t)b * batch;
-      f->net->forward(f->shared(), r, B, false);
-      f->loss_terms(r, B, false, b);
+      const ca_fitter::Batch bt = f->batch(f->idx.p + (size_t)b * batch, B);
+      f->net->forward(f->shared(bt), bt.rows, B, false);
+      f->loss_terms(bt, B, false, b);
     }
     f->losses(nb, n_rows, batch, out_losses, nullptr);
   });
@@ -453,10 +598,111 @@ extern "C" int ca_fitter_gradients(ca_fitter *f, const int32_t *rows, int32_t n_
     f->check_batch(n_rows);
     if (!rows || !grads) throw FtError(CA_ERR_ARG, "null argument");
     f->check_rows(rows, n_rows);
+    f->need_idx(n_rows);
     f->ensure_loss(1);
     rt_h2d(f->idx.p, rows, (size_t)n_rows * sizeof(int32_t), f->s);
     f->update(f->gradient(f->idx.p, n_rows, 0), 0.0f, false);
     rt_d2h(grads, f->gsum.p, f->nw * sizeof(float), f->s);
     f->losses(1, n_rows, n_rows, out_losses, nullptr);
+  });
+}
+
+extern "C" int ca_fitter_clear_data(ca_fitter *f) {
+  return ft_guard(f, [&] {
+    rt_sync(f->s);
+    f->clear_data();
+  });
+}
+
+extern "C" int ca_fitter_add_samples(ca_fitter *f, const float *state_policy, const float *outcome, int32_t n) {
+  return ft_guard(f, [&] {
+    if (!state_policy || !outcome || n < 0) throw FtError(CA_ERR_ARG, "ca_fitter_add_samples: null or negative");
+    f->reserve(n);
+    rt_h2d(f->sp.p + (size_t)f->ns * FT_SAMPLE_FLOATS, state_policy, (size_t)n * FT_SAMPLE_FLOATS * sizeof(float), f->s);
+    rt_h2d(f->oc.p + f->ns, outcome, (size_t)n * sizeof(float), f->s);
+    rt_sync(f->s);
+    f->added(n);
+  });
+}
+
+/* is p memory of the fitter's device? */
+static void ft_check_device_ptr(const ca_fitter *f, const void *p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    throw FtError(CA_ERR_ARG, "ca_fitter_add_device_samples: not a device pointer");
+  }
+  if (a.type != hipMemoryTypeDevice || a.device != f->device)
+    throw FtError(CA_ERR_ARG, "ca_fitter_add_device_samples: not memory of the fitter's device");
+}
+
+extern "C" int ca_fitter_add_device_samples(ca_fitter *f, const void *d_state_policy, const void *d_outcome, int32_t n) {
+  return ft_guard(f, [&] {
+    if (!d_state_policy || !d_outcome || n < 0) throw FtError(CA_ERR_ARG, "ca_fitter_add_device_samples: null or negative");
+    ft_check_device_ptr(f, d_state_policy);
+    ft_check_device_ptr(f, d_outcome);
+    f->reserve(n);
+    rt_d2d(f->sp.p + (size_t)f->ns * FT_SAMPLE_FLOATS, d_state_policy, (size_t)n * FT_SAMPLE_FLOATS * sizeof(float), f->s);
+    rt_d2d(f->oc.p + f->ns, d_outcome, (size_t)n * sizeof(float), f->s);
+    rt_sync(f->s);
+    f->added(n);
+  });
+}
+
+extern "C" int ca_fitter_add_trainer_samples(ca_fitter *f, ca_trainer *t, int32_t *n_added) {
+  return ft_guard(f, [&] {
+    if (!t || !n_added) throw FtError(CA_ERR_ARG, "ca_fitter_add_trainer_samples: null argument");
+    /* the trainer's own entry points have left their message in ca_last_error */
+    auto ok = [](int rc) {
+      if (rc != CA_OK) throw FtError(rc, ca_last_error());
+    };
+    int32_t dev = -1, count = 0, got = 0;
+    ok(ca_trainer_device(t, &dev));
+    if (dev != f->device) throw FtError(CA_ERR_ARG, "ca_fitter_add_trainer_samples: the trainer is on another device");
+    ok(ca_trainer_num_samples(t, &count));
+    f->reserve(count);
+    rt_sync(f->s); /* the buffers' clears and moves are on the fitter's stream, the pack on the trainer's */
+    ok(ca_trainer_pack_samples_device(t, f->sp.p + (size_t)f->ns * FT_SAMPLE_FLOATS, f->oc.p + f->ns, f->cap - f->ns, &got));
+    f->added(got);
+    *n_added = got;
+  });
+}
+
+extern "C" int ca_fitter_drop_samples(ca_fitter *f, int32_t n_oldest) {
+  return ft_guard(f, [&] {
+    if (f->expanded) throw FtError(CA_ERR_STATE, "ca_fitter_drop_samples: the data set is expanded");
+    if (n_oldest < 0 || n_oldest > f->ns) throw FtError(CA_ERR_ARG, "ca_fitter_drop_samples: more than the set holds");
+    if (n_oldest == 0) return;
+    rt_sync(f->s);
+    if (n_oldest < f->ns) f->slide_samples(n_oldest, f->ns - n_oldest);
+    f->ns -= n_oldest;
+    f->added(0);
+  });
+}
+
+extern "C" int ca_fitter_data_info(ca_fitter *f, int32_t *rows, int32_t *samples) {
+  return ft_guard(f, [&] {
+    if (!rows || !samples) throw FtError(CA_ERR_ARG, "ca_fitter_data_info: null output");
+    *rows = f->n;
+    *samples = f->expanded ? 0 : f->ns;
+  });
+}
+
+extern "C" int ca_fitter_fetch_rows(ca_fitter *f, const int32_t *rows, int32_t n_rows, float *states, float *evals,
+                                    float *probs) {
+  return ft_guard(f, [&] {
+    f->need_data();
+    if (!rows || !states || !evals || !probs || n_rows < 0) throw FtError(CA_ERR_ARG, "ca_fitter_fetch_rows: null or negative");
+    f->check_range(rows, n_rows);
+    f->need_stage();
+    for (int32_t r0 = 0; r0 < n_rows; r0 += f->max_batch) {
+      const int B = n_rows - r0 < f->max_batch ? n_rows - r0 : f->max_batch;
+      rt_h2d(f->bidx.p, rows + r0, (size_t)B * sizeof(int32_t), f->s);
+      f->assemble(f->bidx.p, B);
+      rt_d2h(states + (size_t)r0 * CA_GAME_STATE_SIZE, f->bstates.p, (size_t)B * CA_GAME_STATE_SIZE * sizeof(float), f->s);
+      rt_d2h(evals + r0, f->bevals.p, (size_t)B * sizeof(float), f->s);
+      rt_d2h(probs + (size_t)r0 * CA_NUM_MOVES, f->bprobs.p, (size_t)B * CA_NUM_MOVES * sizeof(float), f->s);
+      rt_sync(f->s);
+    }
   });
 }

@@ -15,16 +15,34 @@ The arrays are what samples_io.samples_for_training returns.  What Keras does an
   * ModelCheckpoint(monitor="val_loss", save_best_only=True): the weights and optimizer state at the end of the first
     epoch whose val_loss is strictly below every earlier one;
   * ReduceLROnPlateau(factor=anneal_factor, patience=patience), min_delta 1e-4, no cooldown, no min_lr.
+
+The samples need not leave the device, nor be held 8 times over.  A Fitter's data set can be PACKED: the un-augmented
+rows of Trainer.export_samples (state_policy [n, 166], outcome [n]), whose 8 n virtual rows -- row v is sample v // 8
+under symmetry v % 8, the row order of Trainer.writeSamples and expand_samples -- are produced batch by batch on the
+device (DESIGN.md "Network training", "The packed data set"):
+
+    fitter = Fitter(max_batch=2048)
+    for generation in ...:
+        trainer.run()
+        fitter.add_trainer_samples(trainer)              # device to device, 668 bytes a sample
+        res = fit_resident(fitter, weights, epochs=10)
+        fitter.drop_samples(...)                         # slide the replay window
+
+fit_samples(w, sp, oc, seed=s) equals fit(w, *expand_samples(sp, oc), seed=s) to the bit, and fit_trainer(w, t) equals
+fit(w, *samples_io.get_samples(t)): the row order is the same, so the validation split and the permutations are, and a
+step on virtual rows reads the floats the expanded arrays hold.
 """
 import ctypes as C
+import inspect
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from . import _lib
 from .nets import GAME_STATE_SIZE, MLP_NUM_WEIGHTS, NUM_MOVES, RESCNN4_NUM_WEIGHTS
-from .trainer import NET_MLP12X100, NET_RESCNN4
+from .trainer import NET_MLP12X100, NET_RESCNN4, Trainer
 
+SAMPLE_FLOATS = GAME_STATE_SIZE + NUM_MOVES  # a packed row: state[70], policy[96]
 MIN_DELTA = 1e-4  # keras.callbacks.ReduceLROnPlateau default
 NETS = {NET_MLP12X100: ("mlp12x100", MLP_NUM_WEIGHTS), NET_RESCNN4: ("rescnn4", RESCNN4_NUM_WEIGHTS)}
 
@@ -47,6 +65,17 @@ def _ptr(a, t=C.c_float):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _packed(state_policy, outcome, who):
+    """the two arrays of a packed sample set, checked"""
+    sp = np.ascontiguousarray(state_policy, dtype=np.float32)
+    if sp.ndim != 2 or sp.shape[1] != SAMPLE_FLOATS:
+        raise ValueError("%s: state_policy must be [n, %d]" % (who, SAMPLE_FLOATS))
+    oc = np.ascontiguousarray(outcome, dtype=np.float32).ravel()
+    if oc.size != sp.shape[0]:
+        raise ValueError("%s: outcome must be [n] for n = %d, got %d" % (who, sp.shape[0], oc.size))
+    return sp, oc
+
+
 class Fitter:
     """One device's fitter of mlp12x100 or rescnn4 (include/corintho_hip.h, "network training").  Losses come back as
     (value + 0.25 policy, value, policy)."""
@@ -57,6 +86,7 @@ class Fitter:
         self._L = _lib.load()
         self._h = C.c_void_p()
         self.max_batch = int(max_batch)
+        self._data = None  # the host arrays of the last set_data, if the set is an expanded one
         _lib.check(self._L, self._L.ca_fitter_create_net(int(device), int(net), self.max_batch, C.byref(self._h)))
 
     def close(self):
@@ -111,6 +141,47 @@ class Fitter:
         self._data = (s, e, p)  # the device copy is taken at once; kept only for the caller's inspection
         self._check(self._L.ca_fitter_set_data(self._h, _ptr(s), _ptr(e), _ptr(p), n))
 
+    # ---- the packed data set (include/corintho_hip.h, "the packed data set") ----
+    def clear_data(self):
+        """empty the data set; the next add_* makes it packed"""
+        self._data = None
+        self._check(self._L.ca_fitter_clear_data(self._h))
+
+    def add_samples(self, state_policy, outcome):
+        """append un-augmented samples (Trainer.export_samples' arrays) from the host"""
+        sp, oc = _packed(state_policy, outcome, "add_samples")
+        self._check(self._L.ca_fitter_add_samples(self._h, _ptr(sp), _ptr(oc), sp.shape[0]))
+
+    def add_device_samples(self, ptr_sp, ptr_oc, n):
+        """append n packed rows from device memory of the fitter's device ([n, 166] and [n] float32 at these addresses,
+        e.g. a tensor's data_ptr()); what produced them must have finished"""
+        self._check(self._L.ca_fitter_add_device_samples(self._h, C.c_void_p(ptr_sp), C.c_void_p(ptr_oc), int(n)))
+
+    def add_trainer_samples(self, trainer):
+        """append the samples of a finished training-mode Trainer, device to device; returns how many"""
+        n = C.c_int32()
+        self._check(self._L.ca_fitter_add_trainer_samples(self._h, trainer._t, C.byref(n)))
+        return n.value
+
+    def drop_samples(self, n):
+        """remove the n oldest samples; the others keep their order"""
+        self._check(self._L.ca_fitter_drop_samples(self._h, int(n)))
+
+    def data_info(self):
+        """(addressable rows, packed samples): (8 n, n) of a packed set, (n, 0) of an expanded one"""
+        rows, samples = C.c_int32(), C.c_int32()
+        self._check(self._L.ca_fitter_data_info(self._h, C.byref(rows), C.byref(samples)))
+        return rows.value, samples.value
+
+    def fetch_rows(self, rows):
+        """(states, evals, probs) of the batch a step on `rows` would read (diagnostic)"""
+        r = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+        s = np.zeros((r.size, GAME_STATE_SIZE), np.float32)
+        e = np.zeros(r.size, np.float32)
+        p = np.zeros((r.size, NUM_MOVES), np.float32)
+        self._check(self._L.ca_fitter_fetch_rows(self._h, _ptr(r, C.c_int32), r.size, _ptr(s), _ptr(e), _ptr(p)))
+        return s, e, p
+
     def train(self, rows, batch_size, learning_rate, batch_losses=False):
         """one epoch over `rows` in that order; returns the three mean losses (and the [batches, 3] per-batch ones)"""
         r = np.ascontiguousarray(rows, dtype=np.int32)
@@ -159,6 +230,123 @@ def epoch_order(rng, n_train, shuffle):
     return rng.permutation(n_train).astype(np.int32) if shuffle else np.arange(n_train, dtype=np.int32)
 
 
+def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed):
+    """the epochs of model.fit on the n rows the backend holds, rows [0, split_at) training; the callbacks' logic"""
+    rng = np.random.default_rng(seed)
+    lr = np.float32(learning_rate)
+    history = {k: [] for k in HISTORY_KEYS}
+    ckpt_best, plateau_best, wait = np.inf, np.inf, 0
+    best = None
+    for epoch in range(epochs):
+        order = epoch_order(rng, split_at, shuffle)
+        loss = be.train(order, batch_size, lr)
+        val = be.evaluate(split_at, n - split_at, batch_size)
+        for k, x in zip(HISTORY_KEYS, tuple(loss) + tuple(val) + (lr,)):
+            history[k].append(float(x))
+        val_loss = val[0]
+        if val_loss < ckpt_best:  # ModelCheckpoint(save_best_only=True): np.less
+            ckpt_best = val_loss
+            best = (be.get_weights(), be.get_optimizer(), epoch)
+        if val_loss < plateau_best - MIN_DELTA:  # ReduceLROnPlateau, mode "min"
+            plateau_best, wait = val_loss, 0
+        else:
+            wait += 1
+            if wait >= patience:
+                lr = np.float32(lr * np.float32(anneal_factor))
+                wait = 0
+    if best is None:  # every val_loss NaN: Keras saves nothing either; report the starting point
+        raise FloatingPointError("fit: no epoch produced a finite val_loss")
+    return FitResult(best_weights=best[0], best_optimizer=best[1], best_epoch=best[2], weights=be.get_weights(),
+                     optimizer=be.get_optimizer(), learning_rate=float(lr), history=history)
+
+
+def _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_factor, patience):
+    if int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError("fit: batch_size must be a positive integer")
+    if int(epochs) != epochs or epochs < 1:
+        raise ValueError("fit: epochs must be a positive integer")
+    if not 0.0 < validation_split < 1.0:
+        raise ValueError("fit: validation_split must lie in (0, 1)")
+    if not learning_rate > 0.0 or not 0.0 < anneal_factor < 1.0 or int(patience) != patience or patience < 0:
+        raise ValueError("fit: learning_rate > 0, anneal_factor in (0, 1) and patience >= 0 are required")
+
+
+def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epochs=1, validation_split=0.3, shuffle=True,
+                 anneal_factor=0.5, patience=3, seed=0, optimizer_state=None):
+    """fit() on whatever data set `fitter` holds -- packed (add_samples, add_device_samples, add_trainer_samples) or
+    expanded (set_data) -- without touching it: the rows are data_info()'s, the split, the permutations, the checkpoint
+    and the plateau logic are fit()'s, and so is the FitResult.  On a packed set of n samples the rows are the 8 n
+    virtual rows, so the result equals fit() on expand_samples of the same samples to the bit.  batch_size may not
+    exceed the fitter's max_batch."""
+    w = _f32(weights).ravel()
+    num_weights = getattr(fitter, "num_weights", w.size)
+    if w.size != num_weights:
+        raise ValueError("fit_resident: the fitter's network has %d floats, got %d" % (num_weights, w.size))
+    _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_factor, patience)
+    n = int(fitter.data_info()[0])
+    split_at = split_index(n, validation_split)
+    if split_at < 1 or split_at >= n:
+        raise ValueError("fit_resident: %d rows leave no training or no validation rows at validation_split=%g"
+                         % (n, validation_split))
+    fitter.set_weights(w)
+    if optimizer_state is None:
+        fitter.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
+    else:
+        m, v, it = optimizer_state
+        fitter.set_optimizer(m, v, it)
+    return _epochs(fitter, n, split_at, learning_rate, int(batch_size), int(epochs), shuffle, anneal_factor, patience,
+                   seed)
+
+
+def fit_samples(weights, state_policy, outcome, *, batch_size=2048, device=0, net=NET_MLP12X100, _backend=None, **kw):
+    """fit() from un-augmented samples (Trainer.export_samples, dist.SampleGather.rows): a packed data set, 668 bytes
+    a sample on the device instead of 5 344.  fit_samples(w, sp, oc, seed=s) equals fit(w, *expand_samples(sp, oc),
+    seed=s) to the bit: the 8 n virtual rows are in expand_samples' row order, so the validation split and every
+    epoch's permutation are the same.  Keywords as fit_resident's."""
+    name, num_weights = net_info(net)
+    if _f32(weights).size != num_weights:
+        raise ValueError("fit_samples: %s weights have %d floats, got %d" % (name, num_weights, _f32(weights).size))
+    sp, oc = _packed(state_policy, outcome, "fit_samples")
+    return _fit_added(lambda be: be.add_samples(sp, oc), weights, batch_size, device, net, _backend, kw)
+
+
+def fit_trainer(weights, trainers, *, batch_size=2048, device=0, net=NET_MLP12X100, _backend=None, **kw):
+    """fit() from the samples of one finished Trainer, or of a sequence of them added in that order, taken device to
+    device (Fitter.add_trainer_samples).  fit_trainer(w, t, seed=s) equals fit(w, *samples_io.get_samples(t), seed=s) to
+    the bit.  Keywords as fit_resident's; the trainers must be on `device`."""
+    ts = [trainers] if isinstance(trainers, Trainer) else list(trainers)
+    if not ts:
+        raise ValueError("fit_trainer: no trainer given")
+    name, num_weights = net_info(net)
+    if _f32(weights).size != num_weights:
+        raise ValueError("fit_trainer: %s weights have %d floats, got %d" % (name, num_weights, _f32(weights).size))
+
+    def add(be):
+        for t in ts:
+            be.add_trainer_samples(t)
+
+    return _fit_added(add, weights, batch_size, device, net, _backend, kw)
+
+
+def _fit_added(add, weights, batch_size, device, net, backend, kw):
+    """a fitter of its own (unless a backend is given), emptied, filled by add(fitter), and fit_resident on it"""
+    # the arguments are checked before a fitter is made, with the defaults of fit_resident's own signature
+    args = inspect.signature(fit_resident).bind(None, weights, batch_size=batch_size, **kw)
+    args.apply_defaults()
+    a = args.arguments
+    _check_fit_args(a["learning_rate"], a["batch_size"], a["epochs"], a["validation_split"], a["anneal_factor"],
+                    a["patience"])
+    own = backend is None
+    be = Fitter(max_batch=int(batch_size), device=device, net=net) if own else backend
+    try:
+        be.clear_data()
+        add(be)
+        return fit_resident(be, weights, batch_size=batch_size, **kw)
+    finally:
+        if own:
+            be.close()
+
+
 def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, batch_size=2048, epochs=1,
         validation_split=0.3, shuffle=True, anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, device=0,
         net=NET_MLP12X100, _backend=None):
@@ -177,14 +365,7 @@ def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, 
     probs = _f32(prob_labels)
     if evals.size != n or probs.shape != (n, NUM_MOVES):
         raise ValueError("fit: eval_labels must be [n] and prob_labels [n, %d] for n = %d" % (NUM_MOVES, n))
-    if int(batch_size) != batch_size or batch_size < 1:
-        raise ValueError("fit: batch_size must be a positive integer")
-    if int(epochs) != epochs or epochs < 1:
-        raise ValueError("fit: epochs must be a positive integer")
-    if not 0.0 < validation_split < 1.0:
-        raise ValueError("fit: validation_split must lie in (0, 1)")
-    if not learning_rate > 0.0 or not 0.0 < anneal_factor < 1.0 or int(patience) != patience or patience < 0:
-        raise ValueError("fit: learning_rate > 0, anneal_factor in (0, 1) and patience >= 0 are required")
+    _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_factor, patience)
     split_at = split_index(n, validation_split)
     if split_at < 1 or split_at >= n:
         raise ValueError("fit: %d rows leave no training or no validation rows at validation_split=%g"
@@ -201,32 +382,7 @@ def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, 
             m, v, it = optimizer_state
             be.set_optimizer(m, v, it)
         be.set_data(states, evals, probs)
-        rng = np.random.default_rng(seed)
-        lr = np.float32(learning_rate)
-        history = {k: [] for k in HISTORY_KEYS}
-        ckpt_best, plateau_best, wait = np.inf, np.inf, 0
-        best = None
-        for epoch in range(epochs):
-            order = epoch_order(rng, split_at, shuffle)
-            loss = be.train(order, batch_size, lr)
-            val = be.evaluate(split_at, n - split_at, batch_size)
-            for k, x in zip(HISTORY_KEYS, tuple(loss) + tuple(val) + (lr,)):
-                history[k].append(float(x))
-            val_loss = val[0]
-            if val_loss < ckpt_best:  # ModelCheckpoint(save_best_only=True): np.less
-                ckpt_best = val_loss
-                best = (be.get_weights(), be.get_optimizer(), epoch)
-            if val_loss < plateau_best - MIN_DELTA:  # ReduceLROnPlateau, mode "min"
-                plateau_best, wait = val_loss, 0
-            else:
-                wait += 1
-                if wait >= patience:
-                    lr = np.float32(lr * np.float32(anneal_factor))
-                    wait = 0
-        if best is None:  # every val_loss NaN: Keras saves nothing either; report the starting point
-            raise FloatingPointError("fit: no epoch produced a finite val_loss")
-        return FitResult(best_weights=best[0], best_optimizer=best[1], best_epoch=best[2], weights=be.get_weights(),
-                         optimizer=be.get_optimizer(), learning_rate=float(lr), history=history)
+        return _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed)
     finally:
         if own:
             be.close()

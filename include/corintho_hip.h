@@ -205,6 +205,8 @@ int ca_trainer_pack_samples_device(ca_trainer *t, void *d_state_policy, void *d_
 /* Start a new generation in the same pool: Trainer::initialize (trainer.cpp:238-256)
  * with a new seed, without reallocating the device buffers. */
 int ca_trainer_reset(ca_trainer *t, int32_t seed);
+/* the HIP device ordinal the trainer was created on (ca_config.device) */
+int ca_trainer_device(ca_trainer *t, int32_t *device);
 int ca_expand_samples(int device, const float *state_policy, const float *outcome, int32_t n, float *game_states,
                       float *eval_samples, float *prob_samples);
 
@@ -327,7 +329,8 @@ int ca_fitter_get_weights(ca_fitter *f, float *weights, size_t n_floats);
 /* Adam's slots and step count (Keras optimizer.iterations); a new fitter starts from zeros */
 int ca_fitter_set_optimizer(ca_fitter *f, const float *m, const float *v, size_t n_floats, int64_t iterations);
 int ca_fitter_get_optimizer(ca_fitter *f, float *m, float *v, size_t n_floats, int64_t *iterations);
-/* the sample set, as samples_io.samples_for_training returns it; copied to the device */
+/* the sample set, as samples_io.samples_for_training returns it; copied to the device.  It replaces whatever set the
+ * fitter held, a packed one included (below), with an expanded one. */
 int ca_fitter_set_data(ca_fitter *f, const float *states /* [n][70] */, const float *evals /* [n] */,
                        const float *probs /* [n][96] */, int32_t n);
 /* one epoch: batches of `batch` rows taken in the order of rows[] (the last one partial), one Adam step each at
@@ -339,6 +342,35 @@ int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows, int32_t b
 int ca_fitter_evaluate(ca_fitter *f, int32_t row0, int32_t n_rows, int32_t batch, double *out_losses);
 /* the gradient of one batch's loss with respect to every weight (0 at the moving statistics); nothing is updated */
 int ca_fitter_gradients(ca_fitter *f, const int32_t *rows, int32_t n_rows, float *grads, double *out_losses);
+
+/* ---- the packed data set: un-augmented samples that stay on the device ----
+ * A fitter's data set has one of two forms.  Expanded (ca_fitter_set_data): the 8 symmetry copies of every sample, as
+ * Trainer::writeSamples lays them out, 5 344 bytes per sample.  Packed (the calls below): state_policy[n][166] and
+ * outcome[n], the rows of ca_trainer_export_samples / ca_trainer_pack_samples_device, 668 bytes per sample.  A packed
+ * set of n samples presents 8 n VIRTUAL rows: row v is sample v / 8 under symmetry v % 8, the row order of
+ * ca_trainer_write_samples and ca_expand_samples.  ca_fitter_train, _evaluate and _gradients take virtual rows then;
+ * the symmetry is applied while a batch is fetched, and every step is the same to the bit as on the expanded set. */
+/* empties the data set, whichever form it has; the next ca_fitter_add_* makes it packed */
+int ca_fitter_clear_data(ca_fitter *f);
+/* appends n packed rows from the host.  On an expanded set: CA_ERR_STATE; more than INT32_MAX virtual rows: CA_ERR_ARG.
+ * The capacity grows geometrically and the rows already there move device to device. */
+int ca_fitter_add_samples(ca_fitter *f, const float *state_policy /* [n][166] */, const float *outcome /* [n] */, int32_t n);
+/* the same from device memory of the fitter's device (the buffers of an RCCL gather, dist.SampleGather(on_device=True));
+ * whatever produced them must have finished.  Copied device to device before the call returns. */
+int ca_fitter_add_device_samples(ca_fitter *f, const void *d_state_policy, const void *d_outcome, int32_t n);
+/* appends the samples of a finished training-mode trainer on the fitter's device, packed by the trainer
+ * (ca_trainer_pack_samples_device) straight into the fitter's buffers; *n_added = ca_trainer_num_samples.  A
+ * testing-mode trainer: that call's error (CA_ERR_STATE); a trainer on another device: CA_ERR_ARG. */
+int ca_fitter_add_trainer_samples(ca_fitter *f, ca_trainer *t, int32_t *n_added);
+/* removes the n_oldest first samples of a packed set (the replay window slides); the others keep their order and
+ * virtual row v becomes v - 8 n_oldest.  More than the set holds: CA_ERR_ARG. */
+int ca_fitter_drop_samples(ca_fitter *f, int32_t n_oldest);
+/* *rows = the rows ca_fitter_train can address, *samples = the packed samples (0 for an expanded set) */
+int ca_fitter_data_info(ca_fitter *f, int32_t *rows, int32_t *samples);
+/* Diagnostic: the batch a step on rows[] would read, copied to the host -- states [n_rows][70], evals [n_rows],
+ * probs [n_rows][96] -- through the kernel that assembles a packed set's batches (for an expanded set, the same
+ * kernel's plain row copy).  n_rows is not bound by max_batch. */
+int ca_fitter_fetch_rows(ca_fitter *f, const int32_t *rows, int32_t n_rows, float *states, float *evals, float *probs);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,18 @@ outside the root) with torch._foreach ops, moving statistics at momentum 0.99.  
 with torch's convolutions and the BatchNorm of the fit (batch mean and biased variance per channel over all rows and
 pixels).  It is the yardstick the HIP step has to beat; torch is not part of the product path.
 
+--packed also times the same step, on the same virtual rows in the same order, on a packed data set of rows / 8
+un-augmented samples (include/corintho_hip.h, "the packed data set"), alternating with the expanded set in the same
+process: what the batch-assembly launch costs.
+
+--handoff measures something else and nothing of the above: the time from a finished fused self-play generation
+(--games, --sims, mlp12x100 at random initial weights) to the data set being ready in a fitter, by the two roads in
+turn, --reps times: samples_io.get_samples + Fitter.set_data (expand on the device, 8x rows to the host and back), and
+Fitter.add_trainer_samples (packed device to device) into an emptied fitter and into one that has the capacity.
+
     python tools/fit_bench.py --torch [--net rescnn4] [--rows 1000000 --batch 2048 --steps 200 --reps 3] [--out file.json]
+    python tools/fit_bench.py --packed [--net rescnn4]
+    python tools/fit_bench.py --handoff [--games 4096 --sims 400]
 """
 import argparse
 import json
@@ -173,6 +184,44 @@ class TorchStepCnn:
         return loss
 
 
+def handoff(a):
+    """one generation, then the two roads to a ready data set in turn; -> the result record"""
+    from corintho_ai_amd import Trainer, samples_io
+
+    t = Trainer(a.games, "", 12345, a.sims, 16, 1.0, 0.25, 0, 1, False, device=a.device, stagger=False)
+    t.set_net(NET_MLP12X100, nets.init_mlp12x100(0, bn_noise=True))
+    t0 = time.perf_counter()
+    if not t.run():
+        raise SystemExit("fit_bench: the generation did not finish")
+    generation_ms = (time.perf_counter() - t0) * 1e3
+    n = t.num_samples()
+    old, new, warm = [], [], []
+    with Fitter(max_batch=a.batch, device=a.device) as fe, Fitter(max_batch=a.batch, device=a.device) as fp:
+        for rep in range(a.reps + 1):  # the first round is the warm-up
+            t0 = time.perf_counter()
+            fe.set_data(*samples_io.get_samples(t))
+            t1 = time.perf_counter()
+            fp.clear_data()
+            got = fp.add_trainer_samples(t)
+            t2 = time.perf_counter()
+            fp.drop_samples(got)  # the window slid: the capacity stays
+            t3 = time.perf_counter()
+            fp.add_trainer_samples(t)
+            t4 = time.perf_counter()
+            assert got == n and fe.data_info() == (8 * n, 0) and fp.data_info() == (8 * n, n)
+            if rep:
+                old.append((t1 - t0) * 1e3)
+                new.append((t2 - t1) * 1e3)
+                warm.append((t4 - t3) * 1e3)
+    t.close()
+    return {"handoff": {"games": a.games, "sims": a.sims, "samples": n, "rows": 8 * n, "generation_ms": generation_ms,
+                        "expanded_bytes": 8 * n * 167 * 4, "packed_bytes": n * 167 * 4,
+                        "get_samples_set_data_ms": min(old), "get_samples_set_data_ms_all": old,
+                        "add_trainer_samples_ms": min(new), "add_trainer_samples_ms_all": new,
+                        "add_trainer_samples_warm_ms": min(warm), "add_trainer_samples_warm_ms_all": warm,
+                        "speedup": min(old) / min(new)}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--net", choices=("mlp12x100", "rescnn4"), default="mlp12x100")
@@ -182,9 +231,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--torch", action="store_true")
+    ap.add_argument("--packed", action="store_true", help="also time the step on a packed set of rows / 8 samples")
+    ap.add_argument("--handoff", action="store_true", help="time generation -> ready data set by both roads instead")
+    ap.add_argument("--games", type=int, default=4096, help="--handoff: games of the generation")
+    ap.add_argument("--sims", type=int, default=400, help="--handoff: searches per move")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.handoff:
+        emit(handoff(a), a.out)
+        return
+    if a.packed and a.rows % 8:
+        raise SystemExit("fit_bench: --packed needs --rows to be a multiple of 8")
     data = samples(a.rows)
     cnn = a.net == "rescnn4"
     w = nets.init_rescnn4(0, bn_noise=True) if cnn else nets.init_mlp12x100(0, bn_noise=True)
@@ -209,12 +267,24 @@ def main():
         for i in range(a.warmup):
             ts.step(torder[i * a.batch:(i + 1) * a.batch])
         torch.cuda.synchronize(ts.dev)
-    hip, tor = [], []
+    fp = None
+    if a.packed:  # the first rows / 8 rows as un-augmented samples: as many virtual rows as the expanded set has rows
+        fp = Fitter(max_batch=a.batch, device=a.device, net=NET_RESCNN4 if cnn else NET_MLP12X100)
+        k = a.rows // 8
+        fp.add_samples(np.concatenate([data[0][:k], data[2][:k]], axis=1), data[1][:k])
+        fp.set_weights(w)
+        fp.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
+        fp.train(order[:a.warmup * a.batch], a.batch, 1e-3)
+    hip, tor, pak = [], [], []
     timed = order[a.warmup * a.batch:]
     for _ in range(a.reps):
         t0 = time.perf_counter()
         f.train(timed, a.batch, 1e-3)
         hip.append((time.perf_counter() - t0) * 1e3 / a.steps)
+        if fp:
+            t0 = time.perf_counter()
+            fp.train(timed, a.batch, 1e-3)
+            pak.append((time.perf_counter() - t0) * 1e3 / a.steps)
         if ts:
             torch.cuda.synchronize(ts.dev)
             t0 = time.perf_counter()
@@ -223,6 +293,8 @@ def main():
             torch.cuda.synchronize(ts.dev)
             tor.append((time.perf_counter() - t0) * 1e3 / a.steps)
     f.close()
+    if fp:
+        fp.close()
 
     def rec(ms):
         best = min(ms)
@@ -236,10 +308,17 @@ def main():
     if tor:
         out["torch"] = rec(tor)
         out["hip_speedup_over_torch"] = min(tor) / min(hip)
+    if pak:
+        out["packed"] = rec(pak)
+        out["packed_over_expanded"] = min(pak) / min(hip)
+    emit(out, a.out)
+
+
+def emit(out, path):
     line = json.dumps(out)
     print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
+    if path:
+        with open(path, "w") as fh:
             fh.write(line + "\n")
 
 
