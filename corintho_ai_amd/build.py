@@ -36,16 +36,22 @@ def needs_build():
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=False, extra=()):
-    if not force and not needs_build():
+def build(force=False, verbose=False, extra=(), out=None, csrc=CSRC):
+    """the product library in the tree; out: a variant (extra flags, or another checkout's csrc) built there instead, always"""
+    if out is None and not force and not needs_build():
         return OUT
-    cmd = [hipcc()] + FLAGS + list(extra) + ["-o", OUT] + [os.path.join(CSRC, s) for s in SOURCES]
+    out = out or OUT
+    cmd = [hipcc()] + FLAGS + list(extra) + ["-o", out] + [os.path.join(csrc, s) for s in SOURCES]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    return OUT
+    return out
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv, verbose=True)
-    print(OUT)
+    # python -m corintho_ai_amd.build [--force] | --out FILE CSRC_DIR [flags ...]
+    if "--out" in sys.argv:
+        i = sys.argv.index("--out")
+        print(build(verbose=True, extra=sys.argv[i + 3:], out=sys.argv[i + 1], csrc=sys.argv[i + 2]))
+    else:
+        print(build(force="--force" in sys.argv, verbose=True))

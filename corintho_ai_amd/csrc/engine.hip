@@ -18,11 +18,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/corintho_hip.h"
-#include "kernels.h"
-#include "nn.h"
 #include "logfmt.h"
-#include "rt.h"
+#include "pools.h"
 
 #ifdef CO_EMU
 thread_local int co_emu_block_idx = 0;
@@ -34,77 +31,9 @@ extern "C" unsigned long long *co_emu_sb_ply(void) { return &co_sb_ply[0][0]; }
 #endif
 #endif
 
-static thread_local std::string g_last_error;
+thread_local std::string g_last_error;
 extern "C" const char *ca_last_error(void) { return g_last_error.c_str(); }
-/* for the entry points of the other sources (nn_train.hip) */
 void co_set_last_error(const std::string &m) { g_last_error = m; }
-
-#define CA_TRY try {
-#define CA_CATCH                          \
-  }                                       \
-  catch (const std::exception &e) {       \
-    g_last_error = e.what();              \
-    return CA_ERR_DEVICE;                 \
-  }
-
-struct EngineError : std::runtime_error {
-  int code;
-  EngineError(int c, const std::string &m) : std::runtime_error(m), code(c) {}
-};
-
-template <typename T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
-  DevBuf &operator=(DevBuf &&o) noexcept { return std::swap(p, o.p), std::swap(n, o.n), *this; }
-  void alloc(size_t count, rt_stream_t s) { /* zeroed, the clear queued on s (rt.h) */
-    release();
-    n = count;
-    rt_malloc((void **)&p, count * sizeof(T), s);
-  }
-  void release() {
-    if (p) rt_free(p);
-    p = nullptr;
-    n = 0;
-  }
-  ~DevBuf() { release(); }
-};
-
-template <typename H, void (*Destroy)(H)>
-struct RtHandle {
-  H h = {};
-  RtHandle() = default;
-  RtHandle(RtHandle &&o) noexcept : h(o.h) { o.h = H{}; }
-  RtHandle &operator=(RtHandle &&o) noexcept { return std::swap(h, o.h), *this; }
-  ~RtHandle() { Destroy(h); }
-  operator H() const { return h; }
-};
-struct Stream : RtHandle<rt_stream_t, rt_stream_destroy> {
-  void create() { rt_stream_create(&h); }
-#ifdef CO_EXP_CU_MASK
-  void create_masked(int p, int n, int mode) { rt_stream_create_masked(&h, p, n, mode); }
-#endif
-};
-struct Event : RtHandle<rt_event_t, rt_event_destroy> {
-  void create() { rt_event_create(&h); }
-};
-template <typename T>
-struct Pinned : RtHandle<void *, rt_host_free> { /* page-locked host memory */
-  void alloc(size_t count) {
-    rt_host_alloc(&h, count * sizeof(T));
-    memset(h, 0, count * sizeof(T));
-  }
-  T &operator[](size_t i) const { return ((T *)h)[i]; }
-};
-
-/* the search kernel (K3) over slots [pool_lo, pool_lo + n) of e */
-static void launch_mcts_step(const EngineParams &e, int n, rt_stream_t s) {
-  RT_LAUNCH(co_k_mcts_step, (n + CO_K3_WAVES - 1) / CO_K3_WAVES, CO_WAVE * CO_K3_WAVES, s, e);
-}
-
-#include "pools.h"
 
 struct ca_trainer {
   ca_config cfg;
@@ -148,15 +77,8 @@ struct ca_trainer {
   bool host_games_valid = false;
   /* fused mode */
   std::unique_ptr<CoNet> nets[2];
-  double mcts_ms = 0, nn_ms = 0, pack_ms = 0;
-  int64_t mcts_launches = 0, nn_launches = 0, nn_rows = 0;
-  /* fused training: the launches that carried timing events (one per pool and window) */
-  double mcts_timed_ms = 0, nn_timed_ms = 0, pack_timed_ms = 0;
-  int64_t timed_launches = 0, nn_timed_rows = 0;
-  int64_t nn_rows_evaluated = 0; /* rows the network kernels worked on (= nn_rows without the evaluation cache) */
-  int64_t steps_cut = 0, step_budget_last = 0; /* ca_config.step_budget: steps of the generation that stopped at their budget; the last budget */
-  bool cache_clean = false;      /* the pools' tables hold nothing of an earlier generation */
-  int64_t cache_clears = 0;
+  RunStats stats;
+  FusedRun fused; /* fused training: the pools, their table and the run (pools.h) */
   /* the evaluation cache serves fused training (and fused analysis): one network, rows packed by the search kernel */
   /* Not for the analysis of caller-given positions (the table's header encoding relies on boards that doMove
    * produced).  Automatic (eval_cache = 0): only for a network whose rows cost more than resolving them -- the 9.65
@@ -181,11 +103,15 @@ struct ca_trainer {
   std::vector<uint32_t> an_seed;  /* [G] */
   std::vector<int32_t> an_pre;    /* [G] Node result of a position that is terminal as given, else 0 */
 
-  CacheTable table; /* fused training with the evaluation cache (entries 0: none) */
-  std::vector<Pool> pools;
   ~ca_trainer() {
     for (auto &r : host_regs) rt_host_unregister(r.first);
   }
+
+  int dev() const { return cfg.device; }
+  /* the one mode whose slots are recycled: its games do not depend on which other games are resident */
+  bool self_play_training() const { return !cfg.testing && !cfg.analyse && !tourney; }
+  /* the device has moved on: what the host knows of the batch and of the games is stale */
+  void invalidate() { scan_valid = host_games_valid = false; }
 
   template <typename T>
   void ensure(DevBuf<T> &b, size_t count) {
@@ -258,7 +184,7 @@ struct ca_trainer {
      * next one (training only: an arena game's trajectory depends on its batch, quirk 12).  0 = automatic: all
      * games resident if their trees fit in 5/8 of the free device memory, else as many slots as fit. */
     R = G;
-    const bool can_recycle = !cfg.testing && !cfg.analyse && !tourney;
+    const bool can_recycle = self_play_training();
     const size_t per_slot = (size_t)2 * ((size_t)cap + CO_ARENA_PAD) * sizeof(uint4) +
                             (size_t)spe * (CO_PATH_MAX * 4 + CO_NUM_MOVES * 4 + 2 * CO_STATE_STRIDE * 4 + CO_GAME_STATE_SIZE * 4 +
                                            CO_NUM_MOVES * 4 + 64) + CO_MT_N * 4 + 512;
@@ -268,7 +194,7 @@ struct ca_trainer {
       const size_t per_game = (size_t)CO_MAX_PLIES * CO_SAMPLE_FLOATS * 4 + sizeof(GameCtl) + 8;
       if ((size_t)G * (per_slot + per_game) > budget) {
         size_t fit = budget > (size_t)G * per_game ? (budget - (size_t)G * per_game) / per_slot : 0;
-        if (fit < 1) throw EngineError(CA_ERR_DEVICE, "not enough device memory for a single resident game");
+        if (fit < 1) throw CaError(CA_ERR_DEVICE, "not enough device memory for a single resident game");
         R = (int)std::min<size_t>(fit, (size_t)G);
         if (R >= 512) R &= ~255; /* whole workgroups of the network kernels' row tiles */
       }
@@ -319,6 +245,11 @@ struct ca_trainer {
     if (!cfg.analyse) reset_games(cfg.seed);
     memset(&P, 0, sizeof P);
     fill_params(cap, cfg.total_games > 0 ? cfg.total_games : G);
+    fused.work_counter = work_counter.p;
+    fused.nn_eval = nn_eval.p;
+    fused.nn_probs = nn_probs.p;
+    fused.stats = &stats;
+    fused.stream = stream;
   }
 
   /* Trainer::initialize (trainer.cpp:238-256): game i is seeded with the i-th
@@ -387,17 +318,13 @@ struct ca_trainer {
     rt_sync(stream);
     iterations = 0;
     trainer_iteration = 0;
-    scan_valid = false;
+    invalidate();
     last_total = 0;
     finished = false;
-    host_games_valid = false;
-    mcts_ms = nn_ms = pack_ms = 0;
-    mcts_launches = nn_launches = nn_rows = 0;
-    mcts_timed_ms = nn_timed_ms = pack_timed_ms = 0;
-    timed_launches = nn_timed_rows = 0;
-    nn_rows_evaluated = 0;
-    steps_cut = step_budget_last = 0;
-    cache_clean = false; /* run_pools empties the tables before the first iteration of the new generation */
+    const int64_t cache_clears = stats.cache_clears; /* (counted over the trainer's life) */
+    stats = RunStats();
+    stats.cache_clears = cache_clears;
+    fused.cache_clean = false; /* the next run empties the tables before the first iteration of the new generation */
     if (logbuf.p) {
       rt_memset(logbuf.p, 0, (size_t)num_logged * CO_LOG_CAP * 4, stream);
       rt_sync(stream);
@@ -408,14 +335,14 @@ struct ca_trainer {
   /* Trainer::initialize, trainer.cpp:243-250: the first num_logged games write `<log_folder>/game_<i>.txt` (i = the game's
    * index in the generation).  Before the first iteration only. */
   void set_logging(const char *folder, int n) {
-    if (tourney || cfg.analyse) throw EngineError(CA_ERR_STATE, "per-game logs belong to Trainer games (self-play or arena)");
-    if (iterations != 0 || trainer_iteration != 0) throw EngineError(CA_ERR_STATE, "ca_trainer_set_logging: the games have started");
-    if (n < 0) throw EngineError(CA_ERR_ARG, "ca_trainer_set_logging: num_logged < 0");
+    if (tourney || cfg.analyse) throw CaError(CA_ERR_STATE, "per-game logs belong to Trainer games (self-play or arena)");
+    if (iterations != 0 || trainer_iteration != 0) throw CaError(CA_ERR_STATE, "ca_trainer_set_logging: the games have started");
+    if (n < 0) throw CaError(CA_ERR_ARG, "ca_trainer_set_logging: num_logged < 0");
     n -= cfg.game_base; /* a shard logs the games of the generation's first num_logged that it owns */
     if (n < 0) n = 0;
     if (n > G) n = G;
     if (n > R) /* logged games start in their own slots (mcts.h): fewer slots than logged games would write fewer files than the reference */
-      throw EngineError(CA_ERR_ARG, "ca_trainer_set_logging: " + std::to_string(n) + " logged games on " + std::to_string(R) +
+      throw CaError(CA_ERR_ARG, "ca_trainer_set_logging: " + std::to_string(n) + " logged games on " + std::to_string(R) +
                                         " resident slots -- a logged game must start in its own slot; raise ca_config.resident");
     std::vector<int> games;
     std::vector<std::string> paths;
@@ -463,13 +390,13 @@ struct ca_trainer {
     for (int k = 0; k < num_logged; ++k) {
       const int32_t *r = rec.data() + (size_t)k * CO_LOG_CAP;
       if (r[0] < 0 || r[0] > CO_LOG_CAP - 1)
-        throw EngineError(CA_ERR_ENGINE, "text log " + log_paths[k] + " does not fit its record (" + std::to_string(r[0]) + " words)");
+        throw CaError(CA_ERR_ENGINE, "text log " + log_paths[k] + " does not fit its record (" + std::to_string(r[0]) + " words)");
       FILE *f = fopen(log_paths[k].c_str(), "w");
       if (!f) continue;
       CoLogWriter wr(f);
       const bool ok = wr.write_game(r + 1, r[0], host_games[log_game[k]].result);
       fclose(f);
-      if (!ok) throw EngineError(CA_ERR_ENGINE, "malformed text-log record for " + log_paths[k]);
+      if (!ok) throw CaError(CA_ERR_ENGINE, "malformed text-log record for " + log_paths[k]);
     }
   }
 
@@ -531,7 +458,7 @@ struct ca_trainer {
      * below -1 (diagnostic): automatic with the factor -n / 16 */
     P.step_budget = cfg.step_budget > 0 ? cfg.step_budget : 0;
     P.step_budget_k16 = cfg.step_budget == 0 ? CO_STEP_BUDGET_K16 : cfg.step_budget < -1 ? -cfg.step_budget : 0;
-    P.work_counter = nullptr; /* a pool's own, set by run_pools */
+    P.work_counter = nullptr; /* a pool's own, set by FusedRun */
     P.pool_lo = 0;
     P.pool_n = R;
     P.pool_row_base = 0;
@@ -609,47 +536,51 @@ struct ca_trainer {
                  (e & CO_ERR_PATH_TOO_DEEP) ? "search path deeper than CO_PATH_MAX; " : "",
                  (e & CO_ERR_TOO_MANY_PLIES) ? "game longer than CO_MAX_PLIES; " : "",
                  (e & CO_ERR_INTERNAL) ? "internal inconsistency; " : "");
-        throw EngineError(CA_ERR_ENGINE, buf);
+        throw CaError(CA_ERR_ENGINE, buf);
       }
     }
   }
 
+  /* one launch of the search kernel on every slot, and what the host has to know afterwards: the batch of model
+   * e.to_play and the games' error bits */
+  void step(const EngineParams &e) {
+    launch_mcts_step(e, R, stream);
+    ++stats.mcts_launches;
+    invalidate();
+    pack(e.to_play);
+    check_errors();
+  }
+
   /* Trainer::doIteration (trainer.cpp:164-236), compat protocol */
   void need_positions() const {
-    if (cfg.analyse && an_pos.empty()) throw EngineError(CA_ERR_STATE, "analysis trainer: ca_trainer_set_positions first");
+    if (cfg.analyse && an_pos.empty()) throw CaError(CA_ERR_STATE, "analysis trainer: ca_trainer_set_positions first");
   }
   bool do_iteration(const float *evals, const float *probs, int to_play) {
     need_positions();
-    if (to_play != 0 && to_play != 1) to_play = -1;
     if (iterations > 0) {
       pack(to_play); /* offsets the reference computes at entry */
       if (last_total > 0) {
-        if (!evals || !probs) throw EngineError(CA_ERR_ARG, "doIteration: null evaluations/probabilities");
+        if (!evals || !probs) throw CaError(CA_ERR_ARG, "doIteration: null evaluations/probabilities");
         rt_h2d(nn_eval.p, evals, (size_t)last_total * 4, stream);
         rt_h2d(nn_probs.p, probs, (size_t)last_total * CO_NUM_MOVES * 4, stream);
       }
     } else {
       rt_memset(req_offset.p, 0, ((size_t)R + 1) * 4, stream);
     }
-    launch_mcts_step(params(to_play), R, stream);
+    const EngineParams e = params(to_play);
     if (to_play == -1) ++trainer_iteration;
     ++iterations;
-    ++mcts_launches;
-    scan_valid = false;
-    host_games_valid = false;
-    pack(to_play);
-    check_errors();
+    step(e);
     return finished;
   }
 
+  /* the requests of model `to_play` (-1: every game; a tournament's model id) */
   int32_t num_requests(int to_play) {
-    if (to_play != 0 && to_play != 1) to_play = -1;
     pack(to_play);
     return last_total;
   }
 
   void write_requests(float *out, int to_play) {
-    if (to_play != 0 && to_play != 1) to_play = -1;
     pack(to_play);
     if (last_total == 0) return;
     /* K4 has laid the rows out as the caller's array holds them: one copy, straight into it */
@@ -658,16 +589,6 @@ struct ca_trainer {
   }
 
   /* ---- Tourney (tourney.cpp) on the same pool: one match per game slot ---- */
-  int32_t tourney_num_requests(int id) {
-    pack(id);
-    return last_total;
-  }
-  void tourney_write_requests(float *out, int id) {
-    pack(id);
-    if (last_total == 0) return;
-    rt_d2h(out, nn_in70.p, (size_t)last_total * CO_GAME_STATE_SIZE * 4, stream);
-    rt_sync(stream);
-  }
   /* Tourney::doIteration (tourney.cpp:53-70).  `rows` = rows of the caller's two arrays: the
    * reference reads them at its own offset table (quirk 10), so the whole arrays travel. */
   void tourney_do_iteration(const float *evals, const float *probs, int32_t rows, int id) {
@@ -679,13 +600,8 @@ struct ca_trainer {
       rt_h2d(nn_eval.p, evals, (size_t)rows * 4, stream);
       rt_h2d(nn_probs.p, probs, (size_t)rows * CO_NUM_MOVES * 4, stream);
     }
-    launch_mcts_step(e, R, stream);
     ++iterations;
-    ++mcts_launches;
-    scan_valid = false;
-    host_games_valid = false;
-    pack(id);
-    check_errors();
+    step(e);
   }
   bool tourney_all_done() {
     fetch_games();
@@ -701,10 +617,10 @@ struct ca_trainer {
     if (id >= 0) {
       RT_LAUNCH(co_k_compact, G, CO_WAVE, stream, e);
       net->forward(nn_in.p, G * spe, req_offset.p + G, nn_eval.p, nn_probs.p, stream);
-      ++nn_launches;
+      ++stats.nn_launches;
     }
     launch_mcts_step(e, G, stream);
-    ++mcts_launches;
+    ++stats.mcts_launches;
     ++iterations;
   }
   /* the all-done flag, refreshed by a scan for model `id` */
@@ -715,6 +631,13 @@ struct ca_trainer {
     rt_sync(stream);
     return d != 0;
   }
+  /* ca_tourney::run is over: the rounds were queued without a look at the games */
+  void tourney_rounds_done() {
+    invalidate();
+    check_errors();
+  }
+  /* a network for the batches of this trainer's games */
+  CoNet *make_net(int kind, const float *weights, size_t n) { return co_net_create(kind, weights, n, (size_t)G * spe, stream); }
 
   int32_t num_samples() {
     fetch_games();
@@ -749,27 +672,29 @@ struct ca_trainer {
     return (float)total / (float)(size_t)G;
   }
 
-  /* ws_off = {sample offsets [G + 1], per game (plies | result << 8) [G]}: the sample kernels work by game, not by slot */
-  void upload_sample_index(const std::vector<int32_t> &off) {
-    std::vector<int32_t> idx(off);
-    idx.resize((size_t)2 * G + 1);
-    for (int g = 0; g < G; ++g) idx[(size_t)G + 1 + g] = host_games[g].n_samples | (host_games[g].result << 8);
+  /* ws_off = {sample offsets [G + 1], per game (plies | result << 8) [G]}: the sample kernels work by game, not by slot.
+   * Returns the number of samples; nothing is uploaded when there are none or more than `cap_rows`. */
+  int32_t upload_sample_index(int32_t cap_rows) {
+    fetch_games();
+    std::vector<int32_t> idx((size_t)2 * G + 1, 0);
+    for (int g = 0; g < G; ++g) {
+      idx[g + 1] = idx[g] + host_games[g].n_samples;
+      idx[(size_t)G + 1 + g] = host_games[g].n_samples | (host_games[g].result << 8);
+    }
+    if (idx[G] == 0 || idx[G] > cap_rows) return idx[G];
+    ensure(ws_off, idx.size());
     rt_h2d(ws_off.p, idx.data(), idx.size() * 4, stream);
     rt_sync(stream); /* idx is a local */
+    return idx[G];
   }
 
   void write_samples(float *gs, float *ev, float *pr) {
-    if (cfg.testing) throw EngineError(CA_ERR_STATE, "writeSamples in testing mode");
-    fetch_games();
-    std::vector<int32_t> off(G + 1, 0);
-    for (int g = 0; g < G; ++g) off[g + 1] = off[g] + host_games[g].n_samples;
-    size_t n = (size_t)off[G];
+    if (cfg.testing) throw CaError(CA_ERR_STATE, "writeSamples in testing mode");
+    const size_t n = (size_t)upload_sample_index(INT32_MAX);
     if (n == 0) return;
-    ensure(ws_off, (size_t)2 * G + 1);
     ensure(ws_gs, n * 8 * CO_GAME_STATE_SIZE);
     ensure(ws_ev, n * 8);
     ensure(ws_pr, n * 8 * CO_NUM_MOVES);
-    upload_sample_index(off);
     RT_LAUNCH(co_k_write_samples, G, CO_WAVE, stream, P, G, (const int32_t *)ws_off.p, (const int32_t *)ws_off.p + G + 1, ws_gs.p,
               ws_ev.p, ws_pr.p);
     rt_d2h(gs, ws_gs.p, n * 8 * CO_GAME_STATE_SIZE * 4, stream);
@@ -779,7 +704,7 @@ struct ca_trainer {
   }
 
   void export_samples(float *state_policy, float *outcome) {
-    if (cfg.testing) throw EngineError(CA_ERR_STATE, "export_samples in testing mode");
+    if (cfg.testing) throw CaError(CA_ERR_STATE, "export_samples in testing mode");
     fetch_games();
     std::vector<float> all((size_t)G * CO_MAX_PLIES * CO_SAMPLE_FLOATS);
     rt_d2h(all.data(), samples.p, all.size() * 4, stream);
@@ -800,18 +725,14 @@ struct ca_trainer {
   /* un-augmented samples packed on the device into caller-owned device memory
    * (the multi-GPU gather hands these straight to RCCL) */
   int32_t pack_samples_device(float *d_state_policy, float *d_outcome, int32_t cap_rows) {
-    if (cfg.testing) throw EngineError(CA_ERR_STATE, "pack_samples in testing mode");
-    fetch_games();
-    std::vector<int32_t> off(G + 1, 0);
-    for (int g = 0; g < G; ++g) off[g + 1] = off[g] + host_games[g].n_samples;
-    if (off[G] > cap_rows) throw EngineError(CA_ERR_ARG, "pack_samples: destination too small");
-    if (off[G] == 0) return 0;
-    ensure(ws_off, (size_t)2 * G + 1);
-    upload_sample_index(off);
+    if (cfg.testing) throw CaError(CA_ERR_STATE, "pack_samples in testing mode");
+    const int32_t n = upload_sample_index(cap_rows);
+    if (n > cap_rows) throw CaError(CA_ERR_ARG, "pack_samples: destination too small");
+    if (n == 0) return 0;
     RT_LAUNCH(co_k_pack_samples, G, CO_WAVE, stream, P, G, (const int32_t *)ws_off.p, (const int32_t *)ws_off.p + G + 1,
               d_state_policy, d_outcome);
     rt_sync(stream);
-    return off[G];
+    return n;
   }
 
   /* Trainer::writeScores (trainer.cpp:115-162) */
@@ -822,7 +743,7 @@ struct ca_trainer {
     for (size_t i = 0; i < n; i += 2) scores[i] = game_score(host_games[i]);
     for (size_t i = 1; i < n; i += 2) scores[i] = (float)(1.0 - (double)game_score(host_games[i]));
     FILE *f = fopen(file, "w");
-    if (!f) throw EngineError(CA_ERR_IO, std::string("cannot open ") + file);
+    if (!f) throw CaError(CA_ERR_IO, std::string("cannot open ") + file);
     const char *who[2] = {"First", "Second"};
     for (int side = 0; side < 2; ++side) {
       int wins = 0, draws = 0;
@@ -841,8 +762,8 @@ struct ca_trainer {
 
   /* ------------------------------------------------------------ analysis mode (DockerMC) */
   void set_positions(const int32_t *boards, const int32_t *to_play, const int32_t *pieces, const int32_t *seeds) {
-    if (!cfg.analyse) throw EngineError(CA_ERR_STATE, "set_positions: not an analysis trainer (ca_config.analyse)");
-    if (iterations > 0) throw EngineError(CA_ERR_STATE, "set_positions after the first iteration");
+    if (!cfg.analyse) throw CaError(CA_ERR_STATE, "set_positions: not an analysis trainer (ca_config.analyse)");
+    if (iterations > 0) throw CaError(CA_ERR_STATE, "set_positions after the first iteration");
     an_pos.assign((size_t)3 * G, 0u);
     an_seed.assign(G, 0u);
     an_pre.assign(G, 0);
@@ -852,16 +773,16 @@ struct ca_trainer {
       uint64_t b = 0;
       for (int i = 0; i < 64; ++i) {
         int v = boards[(size_t)g * 64 + i];
-        if (v != 0 && v != 1) throw EngineError(CA_ERR_ARG, "set_positions: board entries must be 0 or 1");
+        if (v != 0 && v != 1) throw CaError(CA_ERR_ARG, "set_positions: board entries must be 0 or 1");
         if (v) b |= 1ull << i;
       }
       uint32_t meta = 0;
       for (int i = 0; i < 6; ++i) {
         int pc = pieces[(size_t)g * 6 + i];
-        if (pc < 0 || pc > 4) throw EngineError(CA_ERR_ARG, "set_positions: piece counts must be 0..4");
+        if (pc < 0 || pc > 4) throw CaError(CA_ERR_ARG, "set_positions: piece counts must be 0..4");
         meta |= (uint32_t)pc << (3 * i);
       }
-      if (to_play[g] != 0 && to_play[g] != 1) throw EngineError(CA_ERR_ARG, "set_positions: to_play must be 0 or 1");
+      if (to_play[g] != 0 && to_play[g] != 1) throw CaError(CA_ERR_ARG, "set_positions: to_play must be 0 or 1");
       meta |= (uint32_t)to_play[g] << 18;
       an_pos[3 * g] = (uint32_t)b;
       an_pos[3 * g + 1] = (uint32_t)(b >> 32);
@@ -889,7 +810,7 @@ struct ca_trainer {
   }
 
   void analysis(int32_t *out) {
-    if (!cfg.analyse) throw EngineError(CA_ERR_STATE, "not an analysis trainer");
+    if (!cfg.analyse) throw CaError(CA_ERR_STATE, "not an analysis trainer");
     /* the eight result words at the head of each slot's request area (mcts.h co_analyse_finish): one strided copy */
     std::vector<uint32_t> rows((size_t)G * 8);
     rt_d2h_2d(rows.data(), 32, req.p, (size_t)spe * CO_STATE_STRIDE * 4, 32, (size_t)G, stream);
@@ -898,7 +819,7 @@ struct ca_trainer {
     for (int g = 0; g < G; ++g) {
       const uint32_t *r = &rows[(size_t)g * 8];
       int32_t *o = out + (size_t)g * 8;
-      if (!host_games[g].done || r[7] != 1u) throw EngineError(CA_ERR_STATE, "analysis: search of position " + std::to_string(g) + " is not finished");
+      if (!host_games[g].done || r[7] != 1u) throw CaError(CA_ERR_STATE, "analysis: search of position " + std::to_string(g) + " is not finished");
       const int res = (int)r[1];
       o[0] = (int32_t)r[0];
       o[1] = res == CO_RESULT_LOSS || res == CO_RESULT_DRAW;   /* Node::terminal, node.cpp:96-98 */
@@ -916,50 +837,42 @@ struct ca_trainer {
    * chooses on its tree as it stands; evaluations still pending are never received (trainmc.cpp:110-137 does
    * not look at searched_).  Before the first iteration the root is created first, as the constructor does. */
   void finish_analysis() {
-    if (!cfg.analyse) throw EngineError(CA_ERR_STATE, "ca_trainer_finish: not an analysis trainer");
+    if (!cfg.analyse) throw CaError(CA_ERR_STATE, "ca_trainer_finish: not an analysis trainer");
     if (iterations == 0) do_iteration(nullptr, nullptr, -1);
     EngineParams e = params(-1);
     e.force_choose = 1;
-    launch_mcts_step(e, R, stream);
-    ++mcts_launches;
-    scan_valid = false;
-    host_games_valid = false;
-    pack(-1);
-    check_errors();
+    step(e);
   }
 
   /* ------------------------------------------------------------ fused mode */
   void set_net(int slot, int kind, const float *weights, size_t n) {
-    if (slot < 0 || slot > 1) throw EngineError(CA_ERR_ARG, "net slot must be 0 or 1");
+    if (slot < 0 || slot > 1) throw CaError(CA_ERR_ARG, "net slot must be 0 or 1");
     std::unique_ptr<CoNet> fresh;
     try {
       fresh.reset(co_net_create(kind, weights, n, (size_t)R * spe, stream));
     } catch (const std::invalid_argument &e) { /* weights outside the kind's operand range (nn.h range_exceeded) */
-      throw EngineError(CA_ERR_ARG, e.what());
+      throw CaError(CA_ERR_ARG, e.what());
     }
-    if (!fresh) throw EngineError(CA_ERR_ARG, "unknown net kind or bad weight count");
-    if (slot == 0 && !pools.empty()) {
+    if (!fresh) throw CaError(CA_ERR_ARG, "unknown net kind or bad weight count");
+    if (slot == 0 && !fused.pools.empty()) {
       /* Does the new network change whether fused training keeps an evaluation cache?  The tables are part of the
        * pools, and in the middle of a generation the pending leaves point into them (pend_src): refuse that. */
       std::unique_ptr<CoNet> old = std::move(nets[0]);
       nets[0] = std::move(fresh);
-      const bool toggles = (table.entries != 0) != use_cache();
+      const bool toggles = (fused.table.entries != 0) != use_cache();
       if (toggles && iterations > 0 && !finished) {
         nets[0] = std::move(old);
-        throw EngineError(CA_ERR_STATE, "ca_trainer_set_net: this network turns the evaluation cache " +
-                                            std::string(table.entries ? "off" : "on") +
+        throw CaError(CA_ERR_STATE, "ca_trainer_set_net: this network turns the evaluation cache " +
+                                            std::string(fused.table.entries ? "off" : "on") +
                                             " in the middle of a generation; finish or reset the generation first");
       }
-      if (toggles) { /* rebuilt with / without the table */
-        pools.clear();
-        table.release();
-      }
+      if (toggles) fused.release(); /* rebuilt with / without the table */
     } else {
       nets[slot] = std::move(fresh);
     }
     /* entries filled by the previous network must not serve the new one: the next run empties the tables (the value
      * elements the pending leaves point to stay: those rows WERE evaluated by the network in place when they were queued) */
-    if (slot == 0) cache_clean = false;
+    if (slot == 0) fused.cache_clean = false;
   }
 
   /* nn.h range_exceeded: an f16x3 network met an operand beyond fp16's range -- its outputs since are NaN or wrong */
@@ -970,7 +883,7 @@ struct ca_trainer {
      * that every later check (export, score, write samples) raises again until set_net replaces the slot */
     for (int slot = 0; slot < 2; ++slot)
       if (nets[slot] && nets[slot]->range_exceeded(stream))
-        throw EngineError(CA_ERR_ENGINE, std::string("network slot ") + std::to_string(slot) +
+        throw CaError(CA_ERR_ENGINE, std::string("network slot ") + std::to_string(slot) +
                                              ": an activation left the fp16 range of the f16x3 kernels (|x| > 65504); the evaluations "
                                              "are not valid -- use the float32-equivalent x6 kind of the same network");
     net_used = false;
@@ -979,9 +892,9 @@ struct ca_trainer {
   /* host rows in, host results out (ca_trainer_net_forward): persistent device buffers; the rows travel as
    * the caller holds them (70 floats) and are widened to the kernels' 80-float rows on the device */
   void net_forward_host(int slot, const float *states, int32_t n, float *evals, float *probs) {
-    if (slot < 0 || slot > 1 || !nets[slot]) throw EngineError(CA_ERR_STATE, "net slot not set");
+    if (slot < 0 || slot > 1 || !nets[slot]) throw CaError(CA_ERR_STATE, "net slot not set");
     CoNet *net = nets[slot].get();
-    if (n < 0 || (size_t)n > net->max_rows()) throw EngineError(CA_ERR_ARG, "net_forward: more rows than num_games*searches_per_eval");
+    if (n < 0 || (size_t)n > net->max_rows()) throw CaError(CA_ERR_ARG, "net_forward: more rows than num_games*searches_per_eval");
     if (n == 0) return;
     ensure(fw_in70, (size_t)n * CO_GAME_STATE_SIZE);
     ensure(fw_in, (size_t)n * CO_STATE_STRIDE);
@@ -1000,306 +913,127 @@ struct ca_trainer {
     check_net_range();
   }
 
-  void net_forward_rows(int slot, const float *d_in, int32_t rows_cap, const int32_t *d_rows, float *d_eval,
-                        float *d_probs) {
+  /* kernel-only timing of a network on `rows` resident rows (HIP events on the engine's stream);
+   * diagnostics and the per-kernel roofline of bench.py */
+  float net_bench(int slot, const float *states, int32_t rows, int32_t reps) {
+    if (slot < 0 || slot > 1 || !nets[slot]) throw CaError(CA_ERR_STATE, "net slot not set");
+    if ((size_t)rows > nets[slot]->max_rows()) throw CaError(CA_ERR_ARG, "net_bench: too many rows");
+    std::vector<float> pad((size_t)rows * CO_STATE_STRIDE, 0.0f);
+    for (int r = 0; r < rows; ++r)
+      memcpy(&pad[(size_t)r * CO_STATE_STRIDE], states + (size_t)r * CO_GAME_STATE_SIZE, CO_GAME_STATE_SIZE * 4);
+    DevBuf<int32_t> d_n;
+    d_n.alloc(1, stream);
+    rt_h2d(nn_in.p, pad.data(), pad.size() * 4, stream);
+    rt_h2d(d_n.p, &rows, 4, stream);
     net_used = true;
-    nets[slot]->forward(d_in, rows_cap, d_rows, d_eval, d_probs, stream);
-  }
-
-  /* the pools of a fused run (pools.h) and, with the evaluation cache, ONE table for all of them */
-  void pools_create(int npools) {
-    pools.clear();
-    table.release(); /* (before the new table is sized by the free device memory) */
-    pools.resize(npools);
-    for (int p = 0; p < npools; ++p) {
-      Pool &q = pools[p];
-      q.create(p, npools, R, spe);
-      if (use_cache()) {
-        if (p == 0) table.create(cfg.eval_cache, R, spe, q.st);
-        q.attach(table, p, spe);
-      }
-    }
-    cache_clean = true; /* freshly zeroed */
-  }
-
-  /* the pools' work-counter words (EngineParams::work_counter) as the device holds them now */
-  std::vector<unsigned long long> read_work_counters() {
-    std::vector<unsigned long long> wc((size_t)CO_WC_WORDS * CO_MAX_POOLS);
-    rt_d2h(wc.data(), work_counter.p, wc.size() * 8, stream);
+    nets[slot]->forward(nn_in.p, rows, d_n.p, nn_eval.p, nn_probs.p, stream); /* warm */
+    Event e0, e1;
+    e0.create();
+    e1.create();
+    rt_event_record(e0, stream);
+    for (int i = 0; i < reps; ++i) nets[slot]->forward(nn_in.p, rows, d_n.p, nn_eval.p, nn_probs.p, stream);
+    rt_event_record(e1, stream);
     rt_sync(stream);
-    return wc;
+    return rt_event_elapsed_ms(e0, e1) / (float)reps;
   }
 
-  /* device time by kernel family, estimated from the timed launches; with_pack: the fused pools' cache probe too (the
-   * arena books its compaction directly) */
-  void estimate_device_times(bool with_pack) {
-    if (timed_launches == 0) return;
-    mcts_ms = mcts_timed_ms * (double)mcts_launches / (double)timed_launches;
-    nn_ms = nn_timed_ms * (double)nn_launches / (double)timed_launches;
-    if (with_pack) pack_ms = pack_timed_ms * (double)nn_launches / (double)timed_launches;
+  /* diagnostic builds (-DCO_PROF): summed in-kernel cycle stamps, see mcts.h */
+  void read_prof(unsigned long long out[2 * CO_NPROF + 24]) {
+    /* nothing is written to `out` unless this is a stamped build: a caller of the shipped library with a buffer sized for
+     * an earlier round's layout gets the error, not an overflow (ADVICE round 5) */
+    if (!prof.p) throw CaError(CA_ERR_STATE, "not a -DCO_PROF build");
+    for (int i = 0; i < 2 * CO_NPROF + 24; ++i) out[i] = 0;
+    std::vector<unsigned long long> h((size_t)R * CO_NPROF);
+    rt_d2h(h.data(), prof.p, h.size() * 8, stream);
+    rt_sync(stream);
+    for (int g = 0; g < R; ++g)
+      for (int i = 0; i < CO_NPROF; ++i) out[i] += h[(size_t)g * CO_NPROF + i];
+    /* [CO_NPROF ..): clocks, the histogram of wave-step times, then the phase sums of the slow wave-steps alone */
+    rt_d2h(out + CO_NPROF, prof.p + (size_t)R * CO_NPROF, (size_t)(24 + CO_NPROF) * 8, stream);
+    rt_sync(stream);
   }
 
-  /* a run starts: an emptied table when the generation does (or a new network came), the pools' host-side state.
-   * Returns whether the table was emptied here. */
-  bool pools_begin_run() {
-    const bool cache_clean_now = use_cache() && !cache_clean;
-    if (cache_clean_now) {
-      /* a generation starts with an empty table: nothing evaluated in an earlier generation is carried over */
-      table.empty(pools[0].st, true);
-      for (auto &q : pools) {
-        if (iterations == 0) { /* (in mid-generation -- a new network, set_net -- the rows evaluated so far stay counted: ADVICE round 4) */
-          rt_memset(q.count.p, 0, 32, q.st);
-          rt_memset(q.totals.p, 0, 16, q.st);
-        }
-        rt_sync(q.st);
-        q.c_inserted_est = 0;
-      }
-      cache_clean = true;
+  void read_stats(ca_stats *out) {
+    fetch_games();
+    memset(out, 0, sizeof *out);
+    for (int g = 0; g < G; ++g) {
+      out->searches += host_games[g].searches;
+      out->evals += host_games[g].evals;
+      out->nodes += host_games[g].nodes;
+      out->plies += host_games[g].plies;
     }
-    /* the steps cut so far (a run that resumes a generation: not zero), what the first window of each pool is compared with */
-    const std::vector<unsigned long long> wc = read_work_counters();
-    for (auto &q : pools)
-      q.begin_run(wc[CO_WC_WORDS * (&q - &pools[0]) + CO_WC_CUTS], P.stagger_div > 0 ? (P.game_base + q.lo) / P.stagger_div : 0);
-    return cache_clean_now;
+    std::vector<TreeCtl> ht((size_t)2 * R);
+    rt_d2h(ht.data(), trees.p, ht.size() * sizeof(TreeCtl), stream);
+    rt_sync(stream);
+    for (auto &x : ht) out->peak_arena_units = std::max<int64_t>(out->peak_arena_units, x.peak_units);
+    out->iterations = iterations;
+    out->mcts_ms = stats.mcts_ms;
+    out->nn_ms = stats.nn_ms;
+    out->pack_ms = stats.pack_ms;
+    out->mcts_launches = stats.mcts_launches;
+    out->nn_launches = stats.nn_launches;
+    out->nn_rows = stats.nn_rows;
+    out->pools = fused.pools.empty() ? 1 : (int64_t)fused.pools.size();
+    out->resident_slots = R;
+    out->nn_rows_evaluated = stats.nn_rows_evaluated;
+    out->steps_cut = stats.steps_cut;
+    out->step_budget_last = stats.step_budget_last;
+    out->timed_launches = stats.timed_launches;
+    out->nn_timed_rows = stats.nn_timed_rows;
+    out->mcts_timed_ms = stats.mcts_timed_ms;
+    out->nn_timed_ms = stats.nn_timed_ms;
   }
 
-  /* The host never waits for the window it has just queued: at the end of window w it queues
-   * an asynchronous copy of each pool's counter and then reads the copy made at the end of
-   * window w-1, so every stream always holds at least one window of work.  A pool is
-   * therefore seen to be finished one window late; the launches in between find no running
-   * game and no batch row. */
-  void pool_collect(Pool &q, int parity, int poll, std::string &failure) {
-    if (!q.launched[parity]) return;
-    rt_event_sync(q.polled[parity]);
-    unsigned long long c = q.word[parity];
-    const unsigned long long evaluated = q.cache.hdr ? q.word[2 + parity] & 0xFFFFFFFFull : c & 0xFFFFFFFFull;
-    q.running = (int)(c >> 32); /* (bits 32..63: the pool's running games, the low word its rows) */
-    /* steps cut in the window: games held their leaves back (mcts.h co_step_tail), which submits no rows for them */
-    const bool holding = q.word[4 + parity] != q.cuts_seen;
-    q.cuts_seen = q.word[4 + parity];
-    if (q.timed[parity]) {
-      /* one iteration per window is timed (three event records per launch pair cost 1-4 % of
-       * the wall time); its batch size is the counter word just read */
-      mcts_timed_ms += rt_event_elapsed_ms(q.ev[parity][0], q.ev[parity][1]);
-      pack_timed_ms += rt_event_elapsed_ms(q.ev[parity][1], q.ev[parity][2]); /* cache probe (nothing without a cache) */
-      nn_timed_ms += rt_event_elapsed_ms(q.ev[parity][2], q.ev[parity][3]);
-      nn_timed_rows += (int64_t)evaluated; /* rows the network kernel worked on */
-      q.c_inserted_est += (double)evaluated * poll; /* every evaluated row takes a table entry */
-      ++timed_launches;
-      q.timed[parity] = 0;
-    }
-    q.launched[parity] = 0;
-    q.finished = (c >> 32) == 0;
-    if (!q.finished && (c & 0xFFFFFFFFull) == 0 && !holding) {
-      /* main.pyx:161-163 raises when NO game has a request.  A pool whose first game the
-       * staggered start (trainer.cpp:184-186) has not released yet has running games and no
-       * rows by construction: that is not the reference's error condition */
-      /* (an iteration whose games all stopped at their step budget has no rows either -- `holding`, a window in which steps
-       * were cut: that is not it) */
-      if (q.word_iter[parity] > q.first_start && ++q.idle > 16) failure = "No requests during training";
-    } else {
-      q.idle = 0;
+  /* the control block of game (or match) `game`, as the device holds it now */
+  const GameCtl &game(int game, const char *what = "game index out of range") {
+    if (game < 0 || game >= G) throw CaError(CA_ERR_ARG, what);
+    fetch_games();
+    return host_games[game];
+  }
+  /* out[8] = {side to move, done, result, samples, pending requests, error, mate turn, plies} */
+  void game_info(int g, int32_t out[8]) {
+    const GameCtl &gc = game(g);
+    out[0] = gc.to_play; out[1] = gc.done; out[2] = gc.result; out[3] = gc.n_samples;
+    out[4] = gc.done ? 0 : gc.n_pending; out[5] = gc.error; out[6] = gc.mate_turn; out[7] = gc.plies;
+  }
+
+  void read_trace(int g, int32_t *out, int32_t cap, int32_t *n) {
+    if (!cfg.trace) throw CaError(CA_ERR_STATE, "trace not enabled");
+    int32_t len = game(g).trace_len;
+    if (len > CO_TRACE_CAP) throw CaError(CA_ERR_ENGINE, "trace buffer overflow");
+    *n = len;
+    int32_t c = std::min(len, cap);
+    if (out && c > 0) {
+      rt_d2h(out, trace.p + (size_t)g * CO_TRACE_CAP, (size_t)c * 4, stream);
+      rt_sync(stream);
     }
   }
 
-  /* a run is over (its streams are drained): device times from the timed launches, errors, the rows evaluated, the step
-   * budget's statistics */
-  void pools_finish_run(const std::string &failure) {
-    estimate_device_times(true);
-    if (!failure.empty()) throw EngineError(CA_ERR_ENGINE, failure);
+  /* fused training (or N position searches) in `npools` pools: the run is FusedRun's (pools.h); what it leaves is read here */
+  bool run_pools(int64_t max_iterations, int npools) {
+    net_used = true;
+    const int64_t n = fused.run(params(-1), nets[0].get(), npools, use_cache() ? cfg.eval_cache : -1, iterations > 0, max_iterations);
+    trainer_iteration += (int32_t)n;
+    iterations += n;
+    invalidate();
+    /* the run is over (its streams are drained): device times from the timed launches, errors, the rows evaluated, the
+     * step budget's statistics */
+    stats.estimate_device_times(true);
+    if (!fused.failure.empty()) throw CaError(CA_ERR_ENGINE, fused.failure);
     pack(-1); /* refresh the done flag and the batch description */
     check_errors();
     fetch_games();
-    nn_rows = 0;
-    for (int g = 0; g < G; ++g) nn_rows += host_games[g].evals; /* every consumed row was requested once */
-    nn_rows_evaluated = nn_rows;
-    if (use_cache()) {
-      nn_rows_evaluated = 0;
-      for (auto &q : pools) {
-        /* booked by the probe kernels, plus the two iterations whose counters nobody has booked yet (at most one is non-zero) */
-        unsigned long long tot[2] = {0, 0};
-        uint32_t cnt[8] = {0};
-        rt_d2h(tot, q.totals.p, 16, q.st);
-        rt_d2h(cnt, q.count.p, 32, q.st);
-        rt_sync(q.st);
-        nn_rows_evaluated += (int64_t)tot[0] + cnt[0] + cnt[4];
-      }
-    }
-    /* step budget: a pool's word CO_WC_CUTS counts the steps that were cut, CO_WC_BUDGET + {0, 1} hold the last two budgets */
-    const std::vector<unsigned long long> wc = read_work_counters();
-    steps_cut = 0;
-    for (size_t p = 0; p < pools.size(); ++p) steps_cut += (int64_t)wc[CO_WC_WORDS * p + CO_WC_CUTS];
-    step_budget_last = P.step_budget > 0 ? P.step_budget : (int64_t)std::max(wc[CO_WC_BUDGET], wc[CO_WC_BUDGET + 1]) / CO_STEP_UNITS_PER_CONFIG_UNIT;
-  }
-
-  /* The table is half full: start over (returns true).  Between two iterations of EVERY pool, when no entry is pending. */
-  bool cache_empty_when_half_full(int npools) {
-    if (!table.entries) return false;
-    double taken = 0;
-    for (auto &q : pools) taken += q.c_inserted_est;
-    if (taken > 0.5 * (double)table.entries) {
-      /* the table is half full: start over (a long generation asks for far more positions than any table holds;
-       * what is asked for again is mostly recent -- the trees of the games in play).  Between two iterations of
-       * EVERY pool, when no entry is pending: each stream has the same iterations queued at this point; pool 0's
-       * stream waits for the others to get here, empties the table, and the others wait for that. */
-      for (int p = 1; p < npools; ++p) {
-        rt_event_record(pools[p].quiet, pools[p].st);
-        rt_stream_wait(pools[0].st, pools[p].quiet);
-      }
-      table.empty(pools[0].st, false);
-      rt_event_record(pools[0].quiet, pools[0].st);
-      for (int p = 1; p < npools; ++p) rt_stream_wait(pools[p].st, pools[0].quiet);
-      for (auto &q : pools) q.c_inserted_est = 0;
-      ++cache_clears;
-      return true;
-    }
-    return false;
-  }
-
-  /* one iteration of pool p on its stream: the search launch (with the step's share of the engine parameters: the pool's
-   * slice, its counters, the evaluation cache's claim rules) and the network launch behind it; `timed`: with HIP events */
-  void pool_queue_iteration(const EngineParams &run_params, int p, int npools, bool emptied, long long &guard_from, int poll,
-                            int parity, int in_window, bool timed) {
-    Pool &q = pools[p];
-    if (q.finished) return;
-    EngineParams pp = run_params;
-    /* Deferring the new mover's first searches to the next step (mcts.h co_game_step) balances
-     * the waves of a full launch but costs the game one more iteration per ply; once the pool
-     * has thinned out, an iteration is as long as its slowest wave anyway and the number of
-     * iterations of the longest game is what the generation waits for.  Per-game results do
-     * not depend on the choice. */
-    pp.defer_handover = q.running * 2 > q.n ? 1 : 0;
-    pp.pool_lo = q.lo;
-    pp.pool_n = q.n;
-    pp.pool_row_base = q.row_base;
-    pp.pack_counter = pack_counter.p + CO_PACK_STRIDE * p;
-    pp.work_counter = work_counter.p + (size_t)CO_WC_WORDS * p;
-    /* (Measured and not done: no automatic budget for a thin pool -- the last eighth of a pool's games, or a trainer of
-     * 64 -- on the reasoning that stopping the longest game's steps only adds iterations to its chain: 386.4 against 382.6
-     * ms per default generation, 120.7 against 115.3 with the MLP, 95.3 against 93.9 at 64 games.  A thin launch waits for
-     * its slowest wavefront like any other.) */
-    pp.cache = q.cache; /* (hdr null: no cache) */
-    pp.cache.no_claim = emptied ? 1u : 0u;
-    if (emptied) guard_from = trainer_iteration;
-    pp.cache.guard_pools = 0u;
-    if (guard_from >= 0 && trainer_iteration <= guard_from + 2 * poll + 1) {
-      /* (the streams are within two windows of each other: the host waits for window w - 1 before it queues w + 1) */
-      pp.cache.guard_from = (uint32_t)guard_from;
-      /* the OTHER pools only: this pool's own reads of the old contents happened in its launch of iteration
-       * guard_from, which stands in front of this launch in its stream -- with its own bit set, every wavefront
-       * that runs before the launch's first wave has stored done[p] would lose its claims for nothing */
-      for (int p2 = 0; p2 < npools; ++p2)
-        if (p2 != p && !pools[p2].finished) pp.cache.guard_pools |= 1u << p2;
-    }
-    /* The network launch is sized by what the batch can hold: the games still running at the pool's last poll (they
-     * only become fewer) times the searches per evaluation.  In a generation's thin tail the throughput kernel is
-     * then not launched at all and the small-batch kernel's grid shrinks -- a launch whose workgroups all leave at
-     * once still costs their dispatch (for the pixel-major kernel: one 160 KB LDS allocation per 32 rows of capacity). */
-    const int cap_rows = (q.running < q.n ? (q.running > 0 ? q.running : 1) : q.n) * spe;
-    Event *e = q.ev[parity];
-    if (timed) rt_event_record(e[0], q.st);
-    launch_mcts_step(pp, q.n, q.st);
-    if (timed) rt_event_record(e[1], q.st);
-    if (q.cache.hdr) {
-      /* the search kernel has resolved every request row to an element of the cache's value array; the network
-       * evaluates the rows whose position has no entry yet, reading them through in_idx and writing straight to
-       * out_idx */
-      if (timed) rt_event_record(e[2], q.st);
-      CoNetIO io;
-      io.in_idx = q.cache.in_idx;
-      io.out_idx = q.cache.out_idx;
-      io.eval_stride = CO_CACHE_VAL_FLOATS;
-      io.probs_stride = CO_CACHE_VAL_FLOATS;
-      io.alone = npools == 1;
-      net_used = true;
-      nets[0]->forward(req.p, cap_rows, (const int32_t *)(q.cache.count + 4 * (trainer_iteration & 1)), q.cache.val, q.cache.val + 4,
-                       q.st, io);
-      if (timed) rt_event_record(e[3], q.st);
-    } else {
-      if (timed) rt_event_record(e[2], q.st);
-      const int32_t *d_rows = (const int32_t *)(pack_counter.p + CO_PACK_STRIDE * p + (trainer_iteration & 1));
-      CoNetIO io;
-      io.alone = npools == 1;
-      io.in_idx = row_idx.p + q.row_base; /* the rows stay where the games wrote them (co_step_tail) */
-      net_used = true;
-      nets[0]->forward(req.p, cap_rows, d_rows, nn_eval.p + q.row_base, nn_probs.p + (size_t)q.row_base * CO_NUM_MOVES, q.st, io);
-      if (timed) rt_event_record(e[3], q.st);
-    }
-    if (timed) q.timed[parity] = 1;
-    q.launched[parity] = in_window + 1;
-    ++mcts_launches;
-    ++nn_launches;
-  }
-
-  /* Fused training as independent pools of games on separate streams:
-   * every pool runs the loop of main.pyx:142-168 on its own slice of the game arrays and of
-   * the batch buffers; the GPU overlaps one pool's search kernel with another's network
-   * kernel and fills launch tails.  Per-game results do not depend on the pooling. */
-  bool run_pools(int64_t max_iterations, int npools) {
-    const int poll = CO_POOL_POLL;
-    if ((int)pools.size() != npools) pools_create(npools);
-    const bool cache_clean_now = pools_begin_run();
-    rt_sync(stream);
-    EngineParams run_params = params(-1); /* (the iteration: set per launch) */
-    run_params.fused_pack = 1;
-    int64_t it = 0;
-    int in_window = 0, window = 0;
-    bool all_finished = false;
-    std::string failure;
-    /* the table was emptied in mid-generation (a new network, set_net): pending leaves point into its old contents */
-    bool emptied_before_resuming = cache_clean_now && iterations > 0;
-    long long guard_from = -1; /* the no-claim iteration behind the last emptying in mid-generation (EvalCache::guard_from) */
-    while (!all_finished && (max_iterations <= 0 || it < max_iterations)) {
-      const int parity = window & 1;
-      bool emptied = emptied_before_resuming; /* (EvalCache::no_claim) */
-      emptied_before_resuming = false;
-      if (cache_empty_when_half_full(npools)) emptied = true;
-      run_params.iteration = trainer_iteration;
-      for (int p = 0; p < npools; ++p)
-        pool_queue_iteration(run_params, p, npools, emptied, guard_from, poll, parity, in_window,
-                             in_window == poll - 1 || (max_iterations > 0 && it + 1 == max_iterations));
-      const int counter_slot = trainer_iteration & 1;
-      ++trainer_iteration;
-      ++iterations;
-      ++it;
-      ++in_window;
-      if (in_window == poll || (max_iterations > 0 && it == max_iterations)) {
-        for (auto &q : pools) {
-          if (q.finished) continue;
-          rt_d2h(&q.word[parity], pack_counter.p + CO_PACK_STRIDE * (&q - &pools[0]) + counter_slot, 8, q.st);
-          if (q.cache.hdr) rt_d2h(&q.word[2 + parity], q.cache.count + 4 * counter_slot, 4, q.st);
-          rt_d2h(&q.word[4 + parity], work_counter.p + (size_t)CO_WC_WORDS * (&q - &pools[0]) + CO_WC_CUTS, 8, q.st);
-          q.word_iter[parity] = trainer_iteration - 1;
-          rt_event_record(q.polled[parity], q.st);
-        }
-        all_finished = true;
-        for (auto &q : pools) {
-          if (!q.finished) pool_collect(q, parity ^ 1, poll, failure);
-          if (!q.finished) all_finished = false;
-        }
-        in_window = 0;
-        ++window;
-        if (!failure.empty()) break;
-      }
-    }
-    /* drain: read what is still in flight (the last window, or both after an iteration cap).  EVERY pool's stream is
-     * synchronised here, whichever way the loop ended: that is what allows `guard_from` to be a local of this call -- a
-     * later call (an iteration-capped run resumed) starts with no launch of any pool in flight, so no pool can still be
-     * reading elements of a table emptied in an earlier call. */
-    for (auto &q : pools) {
-      rt_sync(q.st);
-      for (int w = 0; w < 2; ++w) pool_collect(q, (window + w) & 1, poll, failure);
-    }
-    host_games_valid = false;
-    scan_valid = false;
-    pools_finish_run(failure);
+    stats.nn_rows = 0;
+    for (int g = 0; g < G; ++g) stats.nn_rows += host_games[g].evals; /* every consumed row was requested once */
+    stats.nn_rows_evaluated = use_cache() ? fused.rows_evaluated() : stats.nn_rows;
+    fused.budget_stats();
     return finished;
   }
 
   bool run(int64_t max_iterations) {
     need_positions();
-    if (!nets[0]) throw EngineError(CA_ERR_STATE, "ca_trainer_run: no network set (ca_trainer_set_net)");
-    if (cfg.testing && !cfg.analyse && !nets[1]) throw EngineError(CA_ERR_STATE, "arena mode needs both networks");
+    if (!nets[0]) throw CaError(CA_ERR_STATE, "ca_trainer_run: no network set (ca_trainer_set_net)");
+    if (cfg.testing && !cfg.analyse && !nets[1]) throw CaError(CA_ERR_STATE, "arena mode needs both networks");
     if (!cfg.testing || cfg.analyse) { /* one network, every slot active: self-play training, or N position searches */
       /* automatic: three pools from 3072 resident games on (round 5, one box, same library, 4096 games x 400: rescnn4 f16x3
        * 417.9 -> 407.6 ms per generation, mlp12x100 f16x3 145.4 -> 138.3 -- with the grouped search a pool's search launch is
@@ -1309,11 +1043,15 @@ struct ca_trainer {
       if (npools > R) npools = R;
       return run_pools(max_iterations, npools);
     }
-    /* arena (main.pyx:142-168 with is_testing): one model is served per iteration and hands over
-     * when its batch comes back empty.  The model to move lives on the device (arena_state, kept
-     * by the two scans of an iteration), both networks are queued every iteration and the idle
-     * one finds a row count of zero, so the host only looks every eighth iteration.  Requests
-     * are packed by K4 in game order (the reference's request order). */
+    return run_arena(max_iterations);
+  }
+
+  /* arena (main.pyx:142-168 with is_testing): one model is served per iteration and hands over
+   * when its batch comes back empty.  The model to move lives on the device (arena_state, kept
+   * by the two scans of an iteration), both networks are queued every iteration and the idle
+   * one finds a row count of zero, so the host only looks every eighth iteration.  Requests
+   * are packed by K4 in game order (the reference's request order). */
+  bool run_arena(int64_t max_iterations) {
     const int poll = 8;
     Event ev[4];
     for (auto &e : ev) e.create();
@@ -1341,19 +1079,19 @@ struct ca_trainer {
       if (timed) rt_event_record(ev[3], stream);
       ++iterations;
       ++it;
-      ++mcts_launches;
-      ++nn_launches;
+      ++stats.mcts_launches;
+      ++stats.nn_launches;
       if (timed) {
         int32_t d = 0;
         rt_d2h(&d, all_done.p, 4, stream);
         rt_d2h(st, arena_state.p, sizeof st, stream);
         rt_sync(stream);
         finished = d != 0;
-        mcts_timed_ms += rt_event_elapsed_ms(ev[0], ev[1]);
-        nn_timed_ms += rt_event_elapsed_ms(ev[2], ev[3]);
-        pack_ms += rt_event_elapsed_ms(ev[1], ev[2]) * poll;
-        nn_timed_rows += st[3] + st[4];
-        ++timed_launches;
+        stats.mcts_timed_ms += rt_event_elapsed_ms(ev[0], ev[1]);
+        stats.nn_timed_ms += rt_event_elapsed_ms(ev[2], ev[3]);
+        stats.pack_ms += rt_event_elapsed_ms(ev[1], ev[2]) * poll;
+        stats.nn_timed_rows += st[3] + st[4];
+        ++stats.timed_launches;
         if (!finished && st[1] > 4) {
           failure = "arena: no model has requests";
           break;
@@ -1363,17 +1101,16 @@ struct ca_trainer {
     rt_sync(stream);
     rt_d2h(st, arena_state.p, sizeof st, stream);
     rt_sync(stream);
-    host_games_valid = false;
-    scan_valid = false;
-    estimate_device_times(false);
-    if (!failure.empty()) throw EngineError(CA_ERR_ENGINE, failure);
+    invalidate();
+    stats.estimate_device_times(false);
+    if (!failure.empty()) throw CaError(CA_ERR_ENGINE, failure);
     pack(st[0]); /* refresh the done flag and the batch description */
     check_errors();
     unsigned long long rows = 0;
     rt_d2h(&rows, row_counter.p, 8, stream);
     rt_sync(stream);
-    nn_rows = (int64_t)rows;
-    nn_rows_evaluated = nn_rows;
+    stats.nn_rows = (int64_t)rows;
+    stats.nn_rows_evaluated = stats.nn_rows;
     return finished;
   }
 };
@@ -1397,6 +1134,7 @@ struct ca_tourney {
   };
   std::map<int, PendingNet> net_specs;         /* fused mode: model id -> network (ca_tourney_set_net) */
   std::map<int, std::unique_ptr<CoNet>> nets;
+  int dev() const { return device; }
   bool exact_offsets = false;                  /* ca_tourney_set_exact_offsets */
 
   /* The loop of rating/tourney.pyx:122-160 with the networks on the GPU: for every model id in
@@ -1417,10 +1155,9 @@ struct ca_tourney {
       if (id < 0) continue;
       if (!nets.count(id)) {
         auto it = net_specs.find(id);
-        if (it == net_specs.end()) throw EngineError(CA_ERR_STATE, "ca_tourney_run: no network for model id " + std::to_string(id));
-        std::unique_ptr<CoNet> n(co_net_create(it->second.kind, it->second.w.data(), it->second.w.size(),
-                                               (size_t)p.G * p.spe, p.stream));
-        if (!n) throw EngineError(CA_ERR_ARG, "unknown net kind or bad weight count");
+        if (it == net_specs.end()) throw CaError(CA_ERR_STATE, "ca_tourney_run: no network for model id " + std::to_string(id));
+        std::unique_ptr<CoNet> n(p.make_net(it->second.kind, it->second.w.data(), it->second.w.size()));
+        if (!n) throw CaError(CA_ERR_ARG, "unknown net kind or bad weight count");
         nets[id] = std::move(n);
       }
     }
@@ -1433,9 +1170,7 @@ struct ca_tourney {
        * finished launches kernels that return at once), so the queue never runs dry in between */
       if ((rounds & 7) == 0 || (max_rounds > 0 && rounds >= max_rounds)) done = p.tourney_poll_done(ids.front());
     }
-    p.scan_valid = false;
-    p.host_games_valid = false;
-    p.check_errors();
+    p.tourney_rounds_done();
     if (done) all_done(); /* (writes the match logs) */
     return done;
   }
@@ -1451,9 +1186,16 @@ struct ca_tourney {
     return done;
   }
 
+  ca_trainer &built_or_state() {
+    try {
+      return built();
+    } catch (const std::exception &e) {
+      throw CaError(CA_ERR_STATE, e.what());
+    }
+  }
   ca_trainer &built() {
     if (pool) return *pool;
-    if (matches.empty()) throw EngineError(CA_ERR_STATE, "tourney without matches");
+    if (matches.empty()) throw CaError(CA_ERR_STATE, "tourney without matches");
     ca_trainer::TourneySetup setup{{}, seeds, exact_offsets};
     ca_config c;
     memset(&c, 0, sizeof c);
@@ -1517,22 +1259,8 @@ extern "C" int ca_device_check(int device) {
 #endif
 }
 
-/* Owners of runtime resources: move-only, null until allocated or created, released once by their destructor */
-#define CA_GUARD(...)                     \
-  try {                                   \
-    __VA_ARGS__;                          \
-    return CA_OK;                         \
-  } catch (const EngineError &e) {        \
-    g_last_error = e.what();              \
-    return e.code;                        \
-  } catch (const std::exception &e) {     \
-    g_last_error = e.what();              \
-    return CA_ERR_DEVICE;                 \
-  }
-
-/* entry points on a trainer select its device first: the caller's thread may have another one current
- * (two trainers on two GPUs in one process; torch.cuda.set_device between calls) */
-#define CA_TGUARD(...) CA_GUARD(rt_set_device(t->cfg.device); __VA_ARGS__)
+/* the reference's to_play: 0 / 1 an arena model, anything else every game */
+static int norm_to_play(int to_play) { return to_play == 0 || to_play == 1 ? to_play : -1; }
 
 extern "C" int ca_trainer_create(const ca_config *cfg, ca_trainer **out) {
   if (!cfg || !out) {
@@ -1550,105 +1278,71 @@ extern "C" int ca_trainer_create(const ca_config *cfg, ca_trainer **out) {
   }
   int rc = ca_device_check(cfg->device);
   if (rc != CA_OK) return rc;
-  ca_trainer *t = nullptr;
-  try {
-    t = new ca_trainer();
+  return co_guard([&] {
+    auto t = std::make_unique<ca_trainer>();
     t->init(*cfg);
-  } catch (const std::exception &e) {
-    g_last_error = e.what();
-    delete t;
-    return CA_ERR_DEVICE;
-  }
-  *out = t;
-  return CA_OK;
+    *out = t.release();
+  });
 }
 
 extern "C" void ca_trainer_destroy(ca_trainer *t) { delete t; }
 
-extern "C" int ca_trainer_num_requests(ca_trainer *t, int to_play, int32_t *out) { CA_TGUARD(*out = t->num_requests(to_play)) }
-extern "C" int ca_trainer_num_samples(ca_trainer *t, int32_t *out) { CA_TGUARD(*out = t->num_samples()) }
-extern "C" int ca_trainer_score(ca_trainer *t, float *out) { CA_TGUARD(*out = t->score()) }
-extern "C" int ca_trainer_avg_mate_length(ca_trainer *t, float *out) { CA_TGUARD(*out = t->avg_mate_length()) }
-extern "C" int ca_trainer_write_requests(ca_trainer *t, float *gs, int to_play) { CA_TGUARD(t->write_requests(gs, to_play)) }
-extern "C" int ca_trainer_write_samples(ca_trainer *t, float *gs, float *ev, float *pr) { CA_TGUARD(t->write_samples(gs, ev, pr)) }
-extern "C" int ca_trainer_write_scores(ca_trainer *t, const char *file) { CA_TGUARD(t->write_scores(file)) }
+extern "C" int ca_trainer_num_requests(ca_trainer *t, int to_play, int32_t *out) {
+  return co_guard(t, [&] { *out = t->num_requests(norm_to_play(to_play)); });
+}
+extern "C" int ca_trainer_num_samples(ca_trainer *t, int32_t *out) { return co_guard(t, [&] { *out = t->num_samples(); }); }
+extern "C" int ca_trainer_score(ca_trainer *t, float *out) { return co_guard(t, [&] { *out = t->score(); }); }
+extern "C" int ca_trainer_avg_mate_length(ca_trainer *t, float *out) { return co_guard(t, [&] { *out = t->avg_mate_length(); }); }
+extern "C" int ca_trainer_write_requests(ca_trainer *t, float *gs, int to_play) {
+  return co_guard(t, [&] { t->write_requests(gs, norm_to_play(to_play)); });
+}
+extern "C" int ca_trainer_write_samples(ca_trainer *t, float *gs, float *ev, float *pr) {
+  return co_guard(t, [&] { t->write_samples(gs, ev, pr); });
+}
+extern "C" int ca_trainer_write_scores(ca_trainer *t, const char *file) { return co_guard(t, [&] { t->write_scores(file); }); }
 extern "C" int ca_trainer_do_iteration(ca_trainer *t, const float *ev, const float *pr, int to_play, int32_t *all_done) {
-  CA_TGUARD(*all_done = t->do_iteration(ev, pr, to_play) ? 1 : 0)
+  return co_guard(t, [&] { *all_done = t->do_iteration(ev, pr, norm_to_play(to_play)) ? 1 : 0; });
 }
-extern "C" int ca_trainer_set_net(ca_trainer *t, int slot, int kind, const float *w, size_t n) { CA_TGUARD(t->set_net(slot, kind, w, n)) }
+extern "C" int ca_trainer_set_net(ca_trainer *t, int slot, int kind, const float *w, size_t n) {
+  return co_guard(t, [&] { t->set_net(slot, kind, w, n); });
+}
 extern "C" int ca_trainer_run(ca_trainer *t, int64_t max_iterations, int32_t *all_done) {
-  CA_TGUARD(*all_done = t->run(max_iterations) ? 1 : 0)
+  return co_guard(t, [&] { *all_done = t->run(max_iterations) ? 1 : 0; });
 }
-extern "C" int ca_trainer_export_samples(ca_trainer *t, float *sp, float *oc) { CA_TGUARD(t->export_samples(sp, oc)) }
+extern "C" int ca_trainer_export_samples(ca_trainer *t, float *sp, float *oc) { return co_guard(t, [&] { t->export_samples(sp, oc); }); }
 extern "C" int ca_trainer_pack_samples_device(ca_trainer *t, void *d_sp, void *d_oc, int32_t cap_rows, int32_t *n_rows) {
-  CA_TGUARD(*n_rows = t->pack_samples_device((float *)d_sp, (float *)d_oc, cap_rows))
+  return co_guard(t, [&] { *n_rows = t->pack_samples_device((float *)d_sp, (float *)d_oc, cap_rows); });
 }
 extern "C" int ca_trainer_pin_host(ca_trainer *t, void *p, size_t bytes, int32_t *pinned) {
-  CA_TGUARD(*pinned = t->pin_host(p, bytes) ? 1 : 0)
+  return co_guard(t, [&] { *pinned = t->pin_host(p, bytes) ? 1 : 0; });
 }
-extern "C" int ca_trainer_unpin_host(ca_trainer *t, void *p) { CA_TGUARD(t->unpin_host(p)) }
+extern "C" int ca_trainer_unpin_host(ca_trainer *t, void *p) { return co_guard(t, [&] { t->unpin_host(p); }); }
 extern "C" int ca_trainer_set_positions(ca_trainer *t, const int32_t *boards, const int32_t *to_play, const int32_t *pieces,
                                         const int32_t *seeds) {
-  CA_TGUARD(t->set_positions(boards, to_play, pieces, seeds))
+  return co_guard(t, [&] { t->set_positions(boards, to_play, pieces, seeds); });
 }
-extern "C" int ca_trainer_analysis(ca_trainer *t, int32_t *out) { CA_TGUARD(t->analysis(out)) }
-extern "C" int ca_trainer_finish(ca_trainer *t) { CA_TGUARD(t->finish_analysis()) }
+extern "C" int ca_trainer_analysis(ca_trainer *t, int32_t *out) { return co_guard(t, [&] { t->analysis(out); }); }
+extern "C" int ca_trainer_finish(ca_trainer *t) { return co_guard(t, [&] { t->finish_analysis(); }); }
 extern "C" int ca_trainer_set_logging(ca_trainer *t, const char *log_folder, int32_t num_logged) {
-  CA_TGUARD(t->set_logging(log_folder, num_logged))
+  return co_guard(t, [&] { t->set_logging(log_folder, num_logged); });
 }
-extern "C" int ca_trainer_reset(ca_trainer *t, int32_t seed) { CA_TGUARD(t->reset_games(seed)) }
+extern "C" int ca_trainer_reset(ca_trainer *t, int32_t seed) { return co_guard(t, [&] { t->reset_games(seed); }); }
 extern "C" int ca_trainer_device(ca_trainer *t, int32_t *device) {
-  CA_GUARD({
-    if (!t || !device) throw EngineError(CA_ERR_ARG, "ca_trainer_device: null argument");
-    *device = t->cfg.device;
-  })
+  return co_guard(t, [&] {
+    if (!device) throw CaError(CA_ERR_ARG, "ca_trainer_device: null argument");
+    *device = t->dev();
+  });
 }
-/* diagnostic builds (-DCO_PROF): summed in-kernel cycle stamps, see mcts.h; not in the public header */
+/* diagnostic builds (-DCO_PROF), see ca_trainer::read_prof; not in the public header */
 extern "C" int ca_trainer_prof(ca_trainer *t, unsigned long long out[2 * CO_NPROF + 24]) {
-  CA_TGUARD({
-    /* nothing is written to `out` unless this is a stamped build: a caller of the shipped library with a buffer sized for
-     * an earlier round's layout gets the error, not an overflow (ADVICE round 5) */
-    if (!t->prof.p) throw EngineError(CA_ERR_STATE, "not a -DCO_PROF build");
-    for (int i = 0; i < 2 * CO_NPROF + 24; ++i) out[i] = 0;
-    std::vector<unsigned long long> h((size_t)t->R * CO_NPROF);
-    rt_d2h(h.data(), t->prof.p, h.size() * 8, t->stream);
-    rt_sync(t->stream);
-    for (int g = 0; g < t->R; ++g)
-      for (int i = 0; i < CO_NPROF; ++i) out[i] += h[(size_t)g * CO_NPROF + i];
-    /* [CO_NPROF ..): clocks, the histogram of wave-step times, then the phase sums of the slow wave-steps alone */
-    rt_d2h(out + CO_NPROF, t->prof.p + (size_t)t->R * CO_NPROF, (size_t)(24 + CO_NPROF) * 8, t->stream);
-    rt_sync(t->stream);
-  })
+  return co_guard(t, [&] { t->read_prof(out); });
 }
 
 extern "C" int ca_trainer_net_forward(ca_trainer *t, int slot, const float *states, int32_t n, float *evals, float *probs) {
-  CA_TGUARD(t->net_forward_host(slot, states, n, evals, probs))
+  return co_guard(t, [&] { t->net_forward_host(slot, states, n, evals, probs); });
 }
-
-/* kernel-only timing of a network on `rows` resident rows (HIP events on the engine's stream);
- * diagnostics and the per-kernel roofline of bench.py */
 extern "C" int ca_trainer_net_bench(ca_trainer *t, int slot, const float *states, int32_t rows, int32_t reps, float *ms_per_call) {
-  CA_TGUARD({
-    if (slot < 0 || slot > 1 || !t->nets[slot]) throw EngineError(CA_ERR_STATE, "net slot not set");
-    if ((size_t)rows > t->nets[slot]->max_rows()) throw EngineError(CA_ERR_ARG, "net_bench: too many rows");
-    std::vector<float> pad((size_t)rows * CO_STATE_STRIDE, 0.0f);
-    for (int r = 0; r < rows; ++r)
-      memcpy(&pad[(size_t)r * CO_STATE_STRIDE], states + (size_t)r * CO_GAME_STATE_SIZE, CO_GAME_STATE_SIZE * 4);
-    DevBuf<int32_t> d_n;
-    d_n.alloc(1, t->stream);
-    rt_h2d(t->nn_in.p, pad.data(), pad.size() * 4, t->stream);
-    rt_h2d(d_n.p, &rows, 4, t->stream);
-    t->net_used = true;
-    t->nets[slot]->forward(t->nn_in.p, rows, d_n.p, t->nn_eval.p, t->nn_probs.p, t->stream); /* warm */
-    Event e0, e1;
-    e0.create();
-    e1.create();
-    rt_event_record(e0, t->stream);
-    for (int i = 0; i < reps; ++i) t->nets[slot]->forward(t->nn_in.p, rows, d_n.p, t->nn_eval.p, t->nn_probs.p, t->stream);
-    rt_event_record(e1, t->stream);
-    rt_sync(t->stream);
-    *ms_per_call = rt_event_elapsed_ms(e0, e1) / (float)reps;
-  })
+  return co_guard(t, [&] { *ms_per_call = t->net_bench(slot, states, rows, reps); });
 }
 
 extern "C" int ca_expand_samples(int device, const float *state_policy, const float *outcome, int32_t n, float *gs, float *ev,
@@ -1672,85 +1366,32 @@ extern "C" int ca_expand_samples(int device, const float *state_policy, const fl
   return CA_OK;
 }
 
-extern "C" int ca_trainer_stats(ca_trainer *t, ca_stats *out) {
-  CA_TGUARD({
-    t->fetch_games();
-    memset(out, 0, sizeof *out);
-    for (int g = 0; g < t->G; ++g) {
-      out->searches += t->host_games[g].searches;
-      out->evals += t->host_games[g].evals;
-      out->nodes += t->host_games[g].nodes;
-      out->plies += t->host_games[g].plies;
-    }
-    std::vector<TreeCtl> ht((size_t)2 * t->R);
-    rt_d2h(ht.data(), t->trees.p, ht.size() * sizeof(TreeCtl), t->stream);
-    rt_sync(t->stream);
-    for (auto &x : ht) out->peak_arena_units = std::max<int64_t>(out->peak_arena_units, x.peak_units);
-    out->iterations = t->iterations;
-    out->mcts_ms = t->mcts_ms;
-    out->nn_ms = t->nn_ms;
-    out->pack_ms = t->pack_ms;
-    out->mcts_launches = t->mcts_launches;
-    out->nn_launches = t->nn_launches;
-    out->nn_rows = t->nn_rows;
-    out->pools = t->pools.empty() ? 1 : (int64_t)t->pools.size();
-    out->resident_slots = t->R;
-    out->nn_rows_evaluated = t->nn_rows_evaluated;
-    out->steps_cut = t->steps_cut;
-    out->step_budget_last = t->step_budget_last;
-    out->timed_launches = t->timed_launches;
-    out->nn_timed_rows = t->nn_timed_rows;
-    out->mcts_timed_ms = t->mcts_timed_ms;
-    out->nn_timed_ms = t->nn_timed_ms;
-  })
-}
-
-extern "C" int ca_trainer_game_info(ca_trainer *t, int game, int32_t out[8]) {
-  CA_TGUARD({
-    if (game < 0 || game >= t->G) throw EngineError(CA_ERR_ARG, "game index out of range");
-    t->fetch_games();
-    const GameCtl &gc = t->host_games[game];
-    out[0] = gc.to_play; out[1] = gc.done; out[2] = gc.result; out[3] = gc.n_samples;
-    out[4] = gc.done ? 0 : gc.n_pending; out[5] = gc.error; out[6] = gc.mate_turn; out[7] = gc.plies;
-  })
-}
-
+extern "C" int ca_trainer_stats(ca_trainer *t, ca_stats *out) { return co_guard(t, [&] { t->read_stats(out); }); }
+extern "C" int ca_trainer_game_info(ca_trainer *t, int game, int32_t out[8]) { return co_guard(t, [&] { t->game_info(game, out); }); }
 extern "C" int ca_trainer_trace(ca_trainer *t, int game, int32_t *out, int32_t cap, int32_t *n) {
-  CA_TGUARD({
-    if (!t->cfg.trace) throw EngineError(CA_ERR_STATE, "trace not enabled");
-    if (game < 0 || game >= t->G) throw EngineError(CA_ERR_ARG, "game index out of range");
-    t->fetch_games();
-    int32_t len = t->host_games[game].trace_len;
-    if (len > CO_TRACE_CAP) throw EngineError(CA_ERR_ENGINE, "trace buffer overflow");
-    *n = len;
-    int32_t c = std::min(len, cap);
-    if (out && c > 0) {
-      rt_d2h(out, t->trace.p + (size_t)game * CO_TRACE_CAP, (size_t)c * 4, t->stream);
-      rt_sync(t->stream);
-    }
-  })
+  return co_guard(t, [&] { t->read_trace(game, out, cap, n); });
 }
 
 /* ---- Tourney C ABI */
 extern "C" int ca_tourney_create(int device, uint32_t arena_units, int trace, ca_tourney **out) {
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
-  CA_GUARD({
-    if (!out) throw EngineError(CA_ERR_ARG, "null output pointer");
+  return co_guard([&] {
+    if (!out) throw CaError(CA_ERR_ARG, "null output pointer");
     auto t = std::make_unique<ca_tourney>();
     t->device = device;
     t->arena_units = arena_units;
     t->trace = trace;
     *out = t.release();
-  })
+  });
 }
 extern "C" void ca_tourney_destroy(ca_tourney *t) { delete t; }
 
 extern "C" int ca_tourney_add_player(ca_tourney *t, int32_t player_id, int32_t model_id, int32_t max_searches,
                                      int32_t searches_per_eval, float c_puct, float epsilon, int32_t random) {
-  CA_GUARD({
-    if (t->pool) throw EngineError(CA_ERR_STATE, "addPlayer after the tournament has started");
-    if (!random && (max_searches <= 0 || searches_per_eval <= 0)) throw EngineError(CA_ERR_ARG, "addPlayer: bad search settings");
+  return co_guard(t, [&] {
+    if (t->pool) throw CaError(CA_ERR_STATE, "addPlayer after the tournament has started");
+    if (!random && (max_searches <= 0 || searches_per_eval <= 0)) throw CaError(CA_ERR_ARG, "addPlayer: bad search settings");
     PlayerCfg p;
     memset(&p, 0, sizeof p);
     p.player_id = player_id;
@@ -1761,67 +1402,64 @@ extern "C" int ca_tourney_add_player(ca_tourney *t, int32_t player_id, int32_t m
     p.epsilon = epsilon;
     p.random = random ? 1 : 0;
     t->players[player_id] = p;
-  })
+  });
 }
 
 extern "C" int ca_tourney_add_match(ca_tourney *t, int32_t player1, int32_t player2, int32_t logging) {
-  CA_GUARD({
-    if (t->pool) throw EngineError(CA_ERR_STATE, "addMatch after the tournament has started");
-    if (!t->players.count(player1) || !t->players.count(player2)) throw EngineError(CA_ERR_ARG, "addMatch: unknown player");
+  return co_guard(t, [&] {
+    if (t->pool) throw CaError(CA_ERR_STATE, "addMatch after the tournament has started");
+    if (!t->players.count(player1) || !t->players.count(player2)) throw CaError(CA_ERR_ARG, "addMatch: unknown player");
     if (t->players[player1].random && t->players[player2].random)
-      throw EngineError(CA_ERR_ARG, "addMatch: at most one random player per match (match.cpp:72)");
+      throw CaError(CA_ERR_ARG, "addMatch: at most one random player per match (match.cpp:72)");
     t->matches.emplace_back(player1, player2);
     t->match_logging.push_back(logging ? 1 : 0);
     t->seeds.push_back((uint32_t)t->generator()); /* tourney.cpp:86 */
-  })
+  });
 }
 extern "C" int ca_tourney_set_log_folder(ca_tourney *t, const char *log_folder) {
-  CA_GUARD({
-    if (t->pool) throw EngineError(CA_ERR_STATE, "set_log_folder after the tournament has started");
+  return co_guard(t, [&] {
+    if (t->pool) throw CaError(CA_ERR_STATE, "set_log_folder after the tournament has started");
     t->log_folder = log_folder ? log_folder : "";
-  })
+  });
 }
 
 extern "C" int ca_tourney_set_net(ca_tourney *t, int32_t model_id, int32_t kind, const float *weights, size_t n_floats) {
-  CA_GUARD({
-    if (model_id < 0) throw EngineError(CA_ERR_ARG, "negative model ids are the dummy ids of random players");
-    if (!weights || n_floats == 0) throw EngineError(CA_ERR_ARG, "ca_tourney_set_net: no weights");
+  return co_guard(t, [&] {
+    if (model_id < 0) throw CaError(CA_ERR_ARG, "negative model ids are the dummy ids of random players");
+    if (!weights || n_floats == 0) throw CaError(CA_ERR_ARG, "ca_tourney_set_net: no weights");
     ca_tourney::PendingNet spec;
     spec.kind = kind;
     spec.w.assign(weights, weights + n_floats);
     t->net_specs[model_id] = std::move(spec);
     t->nets.erase(model_id);
-  })
+  });
 }
 extern "C" int ca_tourney_set_exact_offsets(ca_tourney *t, int32_t on) {
-  CA_GUARD({
-    if (t->pool) throw EngineError(CA_ERR_STATE, "set_exact_offsets after the tournament has started");
+  return co_guard(t, [&] {
+    if (t->pool) throw CaError(CA_ERR_STATE, "set_exact_offsets after the tournament has started");
     t->exact_offsets = on != 0;
-  })
+  });
 }
 extern "C" int ca_tourney_run(ca_tourney *t, int64_t max_rounds, int32_t *all_done) {
-  CA_GUARD(rt_set_device(t->device); *all_done = t->run(max_rounds) ? 1 : 0)
+  return co_guard(t, [&] { *all_done = t->run(max_rounds) ? 1 : 0; });
 }
-extern "C" int ca_tourney_all_done(ca_tourney *t, int32_t *out) { CA_GUARD(*out = t->all_done() ? 1 : 0) }
+extern "C" int ca_tourney_all_done(ca_tourney *t, int32_t *out) { return co_guard(t, [&] { *out = t->all_done() ? 1 : 0; }); }
 extern "C" int ca_tourney_num_requests(ca_tourney *t, int32_t id, int32_t *out) {
-  CA_GUARD(rt_set_device(t->device); *out = t->built().tourney_num_requests(id))
+  return co_guard(t, [&] { *out = t->built().num_requests(id); });
 }
 extern "C" int ca_tourney_write_requests(ca_tourney *t, float *game_states, int32_t id) {
-  CA_GUARD(rt_set_device(t->device); t->built().tourney_write_requests(game_states, id))
+  return co_guard(t, [&] { t->built().write_requests(game_states, id); });
 }
 extern "C" int ca_tourney_do_iteration(ca_tourney *t, const float *evaluations, const float *probabilities,
                                        int32_t rows, int32_t id) {
-  CA_GUARD(rt_set_device(t->device); t->built().tourney_do_iteration(evaluations, probabilities, rows, id))
+  return co_guard(t, [&] { t->built().tourney_do_iteration(evaluations, probabilities, rows, id); });
 }
-extern "C" int ca_tourney_num_matches(ca_tourney *t, int32_t *out) { CA_GUARD(*out = (int32_t)t->matches.size()) }
+extern "C" int ca_tourney_num_matches(ca_tourney *t, int32_t *out) { return co_guard(t, [&] { *out = (int32_t)t->matches.size(); }); }
 /* out[8] = {player id 1, player id 2, done, result (util.h:57-64, first player's view), side to move, pending
  * requests, plies, error} */
 extern "C" int ca_tourney_match_info(ca_tourney *t, int32_t match, int32_t out[8]) {
-  CA_GUARD({
-    ca_trainer &p = t->built();
-    if (match < 0 || match >= p.G) throw EngineError(CA_ERR_ARG, "match index out of range");
-    p.fetch_games();
-    const GameCtl &gc = p.host_games[match];
+  return co_guard(t, [&] {
+    const GameCtl &gc = t->built().game(match, "match index out of range");
     out[0] = t->matches[match].first;
     out[1] = t->matches[match].second;
     out[2] = gc.done;
@@ -1830,47 +1468,31 @@ extern "C" int ca_tourney_match_info(ca_tourney *t, int32_t match, int32_t out[8
     out[5] = gc.done ? 0 : gc.n_pending;
     out[6] = gc.plies;
     out[7] = gc.error;
-  })
+  });
 }
 extern "C" int ca_tourney_match_score(ca_tourney *t, int32_t match, float *out) {
-  CA_GUARD({
-    ca_trainer &p = t->built();
-    if (match < 0 || match >= p.G) throw EngineError(CA_ERR_ARG, "match index out of range");
-    p.fetch_games();
-    *out = ca_trainer::game_score(p.host_games[match]); /* Match::score, match.cpp:52-58 */
-  })
+  return co_guard(t, [&] {
+    *out = ca_trainer::game_score(t->built().game(match, "match index out of range")); /* Match::score, match.cpp:52-58 */
+  });
 }
 /* Tourney::writeScores, tourney.cpp:33-41: "id1 id2 score" per finished match */
 extern "C" int ca_tourney_write_scores(ca_tourney *t, const char *filename) {
-  CA_GUARD({
+  return co_guard(t, [&] {
     ca_trainer &p = t->built();
-    p.fetch_games();
     std::ofstream f(filename);
-    if (!f) throw EngineError(CA_ERR_ARG, std::string("cannot open ") + filename);
-    for (int g = 0; g < p.G; ++g)
-      if (p.host_games[g].done)
-        f << t->matches[g].first << ' ' << t->matches[g].second << ' ' << ca_trainer::game_score(p.host_games[g]) << '\n';
-  })
+    if (!f) throw CaError(CA_ERR_ARG, std::string("cannot open ") + filename);
+    for (int g = 0; g < (int)t->matches.size(); ++g) {
+      const GameCtl &gc = p.game(g);
+      if (gc.done) f << t->matches[g].first << ' ' << t->matches[g].second << ' ' << ca_trainer::game_score(gc) << '\n';
+    }
+  });
 }
+/* the trace and the statistics of the tournament's trainer; a tournament that cannot be built is CA_ERR_STATE here */
 extern "C" int ca_tourney_trace(ca_tourney *t, int32_t match, int32_t *out, int32_t cap, int32_t *n_out) {
-  ca_trainer *p = nullptr;
-  try {
-    p = &t->built();
-  } catch (const std::exception &e) {
-    g_last_error = e.what();
-    return CA_ERR_STATE;
-  }
-  return ca_trainer_trace(p, match, out, cap, n_out);
+  return co_guard(t, [&] { t->built_or_state().read_trace(match, out, cap, n_out); });
 }
 extern "C" int ca_tourney_stats(ca_tourney *t, ca_stats *out) {
-  ca_trainer *p = nullptr;
-  try {
-    p = &t->built();
-  } catch (const std::exception &e) {
-    g_last_error = e.what();
-    return CA_ERR_STATE;
-  }
-  return ca_trainer_stats(p, out);
+  return co_guard(t, [&] { t->built_or_state().read_stats(out); });
 }
 
 /* ---- stand-alone test entry points, each on a stream of its own */
@@ -1885,7 +1507,7 @@ extern "C" int ca_rules_legal_moves(int device, const uint64_t *boards, const ui
                                     int32_t *is_lines) {
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
-  CA_GUARD({
+  return co_guard([&] {
     const Stream ts = device_stream(device);
     DevBuf<uint64_t> b;
     DevBuf<uint32_t> m, mk;
@@ -1897,13 +1519,13 @@ extern "C" int ca_rules_legal_moves(int device, const uint64_t *boards, const ui
     rt_d2h(masks, mk.p, (size_t)n * 12, ts);
     rt_d2h(is_lines, ln.p, (size_t)n * 4, ts);
     rt_sync(ts);
-  })
+  });
 }
 
 extern "C" int ca_rules_do_move(int device, uint64_t *boards, uint32_t *metas, const int32_t *moves, int32_t n, float *states) {
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
-  CA_GUARD({
+  return co_guard([&] {
     const Stream ts = device_stream(device);
     DevBuf<uint64_t> b;
     DevBuf<uint32_t> m;
@@ -1921,13 +1543,13 @@ extern "C" int ca_rules_do_move(int device, uint64_t *boards, uint32_t *metas, c
     rt_sync(ts);
     for (int i = 0; i < n; ++i)
       memcpy(states + (size_t)i * CO_GAME_STATE_SIZE, &tmp[(size_t)i * CO_STATE_STRIDE], CO_GAME_STATE_SIZE * 4);
-  })
+  });
 }
 
 extern "C" int ca_rules_rows(int device, uint64_t *boards, uint32_t *metas, const int32_t *moves, int32_t n, uint32_t *masks) {
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
-  CA_GUARD({
+  return co_guard([&] {
     const Stream ts = device_stream(device);
     DevBuf<uint64_t> b;
     DevBuf<uint32_t> m, mk;
@@ -1941,14 +1563,14 @@ extern "C" int ca_rules_rows(int device, uint64_t *boards, uint32_t *metas, cons
     rt_d2h(metas, m.p, (size_t)n * 4, ts);
     rt_d2h(masks, mk.p, (size_t)n * 12, ts);
     rt_sync(ts);
-  })
+  });
 }
 
 extern "C" int ca_rng_draw(int device, uint32_t seed, int32_t n, int32_t chunk, uint32_t *out) {
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
-  CA_GUARD({
-    if (chunk < 1 || chunk > CO_WAVE) throw EngineError(CA_ERR_ARG, "chunk must be 1..64");
+  return co_guard([&] {
+    if (chunk < 1 || chunk > CO_WAVE) throw CaError(CA_ERR_ARG, "chunk must be 1..64");
     const Stream ts = device_stream(device);
     std::vector<uint32_t> x(CO_MT_N);
     x[0] = seed;
@@ -1962,13 +1584,13 @@ extern "C" int ca_rng_draw(int device, uint32_t seed, int32_t n, int32_t chunk, 
     RT_LAUNCH(co_k_rng_draw, 1, CO_WAVE, ts, mt.p, idx.p, n, chunk, o.p);
     rt_d2h(out, o.p, (size_t)n * 4, ts);
     rt_sync(ts);
-  })
+  });
 }
 
 extern "C" int ca_fp_probe(int device, const float *in, int32_t n, float *out) {
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
-  CA_GUARD({
+  return co_guard([&] {
     const Stream ts = device_stream(device);
     DevBuf<float> di, dout;
     di.alloc((size_t)n * 8, ts); dout.alloc((size_t)n * 8, ts);
@@ -1976,5 +1598,5 @@ extern "C" int ca_fp_probe(int device, const float *in, int32_t n, float *out) {
     RT_LAUNCH(co_k_fp_probe, (n + CO_WAVE - 1) / CO_WAVE, CO_WAVE, ts, (const float *)di.p, n, dout.p);
     rt_d2h(out, dout.p, (size_t)n * 32, ts);
     rt_sync(ts);
-  })
+  });
 }

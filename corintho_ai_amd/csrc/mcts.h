@@ -42,15 +42,11 @@ CO_CONST uint32_t CO_GAMMA_BITS[CO_NUM_GAMMA] = CO_GAMMA_BITS_INIT;
     w.pacc[slot] += now_ - w.tph;                 \
     w.tph = now_;                                 \
   } while (0)
-#ifdef CO_PROF_LIGHT /* stamps that wait for nothing: a phase is charged the waits the PRODUCT has in it */
-#define CO_PH_MEM(slot) CO_PH(slot)
-#else
 #define CO_PH_MEM(slot)                                               \
   do {                                                                \
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");       \
     CO_PH(slot);                                                      \
   } while (0)
-#endif
 #else
 #define CO_CLK() 0ull
 #define CO_PROF_ADD(w, slot, v) ((void)0)
@@ -63,7 +59,7 @@ CO_CONST uint32_t CO_GAMMA_BITS[CO_NUM_GAMMA] = CO_GAMMA_BITS_INIT;
  * (depth, terminal leaves and their propagation, a SIMD shared with another pool's kernel) -- and the emulation build, which
  * has no clock and must stay deterministic, counts PUCT scans (1 scan ~ 1.6 us).  Either way ONE scalar lives across the
  * step: the deadline (device) or the scans so far minus the budget (emulation). */
-#if !defined(CO_EMU) && !defined(CO_BUDGET_SCANS)
+#ifndef CO_EMU
 #define CO_STEP_CLOCK() ((uint32_t)__builtin_amdgcn_s_memrealtime())
 #define CO_STEP_UNITS_PER_CONFIG_UNIT 100 /* ca_config.step_budget > 0 is in microseconds */
 #define CO_STEP_WORK(w, n) ((void)0)
@@ -1028,16 +1024,9 @@ CO_COLD2 void co_search(CoWave &w, CoTree &t, CoRoot &rc) {
  * leaf, a node wider than the wavefront, a path beyond CO_SB_DEPTH, a full arena) ends the group in front of it: the
  * simulations before it are committed, it is run by co_search on the committed tree, the ones behind it are selected
  * again in the next group (their selection is discarded -- nothing was written). */
-#ifndef CO_SB_PE_ONE
 #define CO_SB_PE_ONE 96
-#endif
-#ifndef CO_SB_PE_TWO
 #define CO_SB_PE_TWO 40
-#endif
 #define CO_SB_DEPTH 12 /* levels a grouped simulation may pass (a level = a lane of its row when it commits: at most 16) */
-#if CO_SB != 1 && CO_SB != 4
-#error "CO_SB: 1 (one simulation after another) or 4 (one per row of the wavefront)"
-#endif
 
 #if defined(CO_SB_STATS) && defined(CO_EMU)
 /* emulation-build counters of the grouped search (tools/sb_stats.py): 0 groups, 1 simulations asked for, 2 committed,
@@ -1053,7 +1042,6 @@ extern unsigned long long co_sb_ply[8][8]; /* by game progress (plies / 4): grou
 #define CO_SBP(w, i, v) ((void)0)
 #endif
 
-#if CO_SB > 1
 /* m = simulations that are certainly due (1 < m <= CO_SB = 4: each adds one pending leaf and one search).  Returns how
  * many were committed; fewer than m: the next one takes co_search.
  *
@@ -1848,7 +1836,6 @@ CO_DEV int co_search_rows(CoWave &w, CoTree &t, CoRoot &rc, int m) {
    * simulation that is neither ordinary nor a terminal leaf -- the caller's next simulation takes co_search */
   return done | (term >= 0 || dead_end ? 0x100 : 0) | (term < 0 && !dead_end && done < m ? 0x200 : 0);
 }
-#endif
 
 /* the root asks for its own evaluation (trainmc.cpp:143-167, 198-202) */
 CO_DEV void co_request_root(CoWave &w, CoTree &t) {
@@ -1900,13 +1887,11 @@ CO_DEV int co_mc_do_iteration(CoWave &w, CoTree &t, const float *eval, const flo
   rc.ev = root_ev;
   rc.e0 = 0u;
   rc.ne = 0u;
-#if CO_SB > 1
   /* How many to select together follows from how the position's simulations have been ending: everything behind one that
    * is not ordinary is selected in vain (endgames of a trained network: every second simulation a terminal leaf or a
    * dead end, ten levels down).  pe = running share of such simulations in 1/256 (seven eighths of the old estimate per
    * simulation, kept with the game from step to step): above 3/8 they run one after the other, above 5/32 two at a time. */
   int pe = w.gc.sb_cap > 0 && w.gc.sb_cap <= 256 ? w.gc.sb_cap : 0;
-#endif
   /* (bit 2 of gc.held: this call has run a simulation.  A step whose budget is spent before its first one -- a deadline
    * already behind the receive phase -- still makes progress: else it would stop again and again, for ever.  In the
    * game's record because one more scalar kept across the loop costs the kernel 200 spilled registers.) */
@@ -1923,7 +1908,6 @@ CO_DEV int co_mc_do_iteration(CoWave &w, CoTree &t, const float *eval, const flo
       break;
     }
     CO_PH_MEM(20);
-#if CO_SB > 1
     int counted = 0;
     {
       const int cap = pe > CO_SB_PE_ONE ? 1 : pe > CO_SB_PE_TWO ? 2 : CO_SB;
@@ -1942,22 +1926,17 @@ CO_DEV int co_mc_do_iteration(CoWave &w, CoTree &t, const float *eval, const flo
       }
     }
     const int pending_before = w.gc.n_pending;
-#endif
     CO_SBS(8, 1);
     CO_SBP(w, 6, 1);
     co_search(w, t, rc);
     w.gc.held |= 4;
     CO_PROF_ADD(w, 5, 1ull);
-#if CO_SB > 1
     if (!counted) {
       if (w.gc.n_pending > pending_before) pe -= pe >> 3; /* (it queued a leaf: ordinary) */
       else pe += (256 - pe) >> 3;
     }
-#endif
   }
-#if CO_SB > 1
   w.gc.sb_cap = pe > 0 ? pe : 0;
-#endif
   /* (the root's slot only when the answer depends on it: with leaves pending -- nearly every step -- it does not) */
   if (w.gc.n_pending != 0 || (w.gc.held & 1)) return 0;
   if (t.tc.searches_done == w.max_searches) return 1;

@@ -29,7 +29,7 @@
 #include <vector>
 
 #include "engine_defs.h"
-#include "nn.h"
+#include "host.h"
 
 #define MLP_TILES 7               /* 7 x 16 = 112 >= 100 features */
 #define MLP_STEPS 28              /* 7 tiles x 4 k-steps */
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256, 1) void co_k_mlp_forward(const float *__restri
 
 /* ------------------------------------------------------------------ host */
 struct MlpNet : CoNet {
-  float *d_wfrag = nullptr, *d_bias = nullptr, *d_a = nullptr, *d_b = nullptr;
+  DevBuf<float> d_wfrag, d_bias, d_a, d_b;
   size_t cap;
   MlpNet(const float *w, size_t max_rows, rt_stream_t s) : cap(max_rows) {
     std::vector<float> wf((size_t)MLP_NLAYERS * MLP_LAYER_FLOATS, 0.0f);
@@ -201,13 +201,8 @@ struct MlpNet : CoNet {
       const float *K = p, *b = K + (size_t)in_dim * 100, *ga = b + 100, *be = ga + 100, *mu = be + 100, *va = mu + 100;
       for (int k = 0; k < in_dim; ++k)
         for (int o = 0; o < 100; ++o) put(l, k, o, K[(size_t)k * 100 + o]);
-      for (int o = 0; o < 100; ++o) {
-        bias[(size_t)l * MLP_PADW + o] = b[o];
-        /* BatchNormalization inference: gamma (x - mean) / sqrt(var + eps) + beta */
-        float a = (float)((double)ga[o] / sqrt((double)va[o] + CO_BN_EPS));
-        ba[(size_t)l * MLP_PADW + o] = a;
-        bb[(size_t)l * MLP_PADW + o] = (float)((double)be[o] - (double)mu[o] * (double)a);
-      }
+      for (int o = 0; o < 100; ++o) bias[(size_t)l * MLP_PADW + o] = b[o];
+      bn_fold(ga, be, mu, va, 100, &ba[(size_t)l * MLP_PADW], &bb[(size_t)l * MLP_PADW]);
       p = va + 100;
       in_dim = 100;
     }
@@ -218,23 +213,13 @@ struct MlpNet : CoNet {
     }
     for (int o = 0; o < 96; ++o) bias[(size_t)12 * MLP_PADW + o] = bp[o];
     bias[(size_t)12 * MLP_PADW + 96] = bv[0];
-    rt_malloc((void **)&d_wfrag, wf.size() * 4, s);
-    rt_malloc((void **)&d_bias, bias.size() * 4, s);
-    rt_malloc((void **)&d_a, ba.size() * 4, s);
-    rt_malloc((void **)&d_b, bb.size() * 4, s);
-    rt_h2d(d_wfrag, wf.data(), wf.size() * 4, s);
-    rt_h2d(d_bias, bias.data(), bias.size() * 4, s);
-    rt_h2d(d_a, ba.data(), ba.size() * 4, s);
-    rt_h2d(d_b, bb.data(), bb.size() * 4, s);
+    d_wfrag.upload(wf.data(), wf.size(), s);
+    d_bias.upload(bias.data(), bias.size(), s);
+    d_a.upload(ba.data(), ba.size(), s);
+    d_b.upload(bb.data(), bb.size(), s);
     rt_sync(s);
     RT_CHECK(hipFuncSetAttribute((const void *)co_k_mlp_forward, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  2 * MLP_LAYER_FLOATS * (int)sizeof(float)));
-  }
-  ~MlpNet() override {
-    rt_free(d_wfrag);
-    rt_free(d_bias);
-    rt_free(d_a);
-    rt_free(d_b);
   }
   size_t max_rows() const override { return cap; }
   int kind() const override { return CO_NET_MLP12X100; }
@@ -243,9 +228,8 @@ struct MlpNet : CoNet {
                rt_stream_t s, const CoNetIO &io = CoNetIO()) override {
     int grid = (rows_cap + MLP_ROWS_PER_WG - 1) / MLP_ROWS_PER_WG;
     if (grid < 1) return;
-    hipLaunchKernelGGL(co_k_mlp_forward, dim3(grid), dim3(256), 2 * MLP_LAYER_FLOATS * sizeof(float), s, d_in, d_rows, (const float *)d_wfrag,
-                       (const float *)d_bias, (const float *)d_a, (const float *)d_b, d_eval, d_probs, io);
-    RT_CHECK(hipGetLastError());
+    RT_LAUNCH_LDS(co_k_mlp_forward, grid, 256, 2 * MLP_LAYER_FLOATS * sizeof(float), s, d_in, d_rows, (const float *)d_wfrag.p,
+                  (const float *)d_bias.p, (const float *)d_a.p, (const float *)d_b.p, d_eval, d_probs, io);
   }
 };
 

@@ -45,8 +45,8 @@
 #include <vector>
 
 #include "engine_defs.h"
+#include "host.h"
 #include "lds_dma.h"
-#include "nn.h"
 
 typedef float m3_f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 m3_bf16x8 __attribute__((ext_vector_type(8)));
@@ -311,34 +311,9 @@ __global__ __launch_bounds__(256, 1) void co_k_mlp_forward_split_t(const float *
 #define co_k_mlp_forward_h3 co_k_mlp_forward_split_t<2, true>
 
 /* ------------------------------------------------------------------ host */
-static inline uint16_t m3_bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static inline float m3_bf16_to_f(uint16_t b) {
-  uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-static inline uint16_t m3_f16_rne(float f) {
-  _Float16 h = (_Float16)f;
-  uint16_t u;
-  memcpy(&u, &h, 2);
-  return u;
-}
-static inline float m3_f16_to_f(uint16_t u) {
-  _Float16 h;
-  memcpy(&h, &u, 2);
-  return (float)h;
-}
-
 struct MlpSplitNet : CoNet {
-  uint32_t *d_w = nullptr;
-  uint32_t *d_range = nullptr; /* f16: the kernels' out-of-range flag */
+  DevBuf<uint32_t> d_w;
+  RangeFlag range; /* f16: the kernels' out-of-range flag */
   size_t cap;
   int nt;
   bool f16;
@@ -370,14 +345,11 @@ struct MlpSplitNet : CoNet {
       B[l].assign(128, 0.0);
       kin[l] = in_dim;
       fold(l, kern, b, in_dim, 100, 0);
-      a_prev.assign(100, 0.0);
-      c_prev.assign(100, 0.0);
-      for (int o = 0; o < 100; ++o) {
-        /* the float32 constants K5 applies (BatchNormalization inference, eps 1e-3) */
-        float a = (float)((double)ga[o] / sqrt((double)va[o] + CO_BN_EPS));
-        a_prev[o] = a;
-        c_prev[o] = (float)((double)be[o] - (double)mu[o] * (double)a);
-      }
+      /* the float32 constants K5 applies (BatchNormalization inference, eps 1e-3) */
+      float a[100], c[100];
+      bn_fold(ga, be, mu, va, 100, a, c);
+      a_prev.assign(a, a + 100);
+      c_prev.assign(c, c + 100);
       p = va + 100;
       in_dim = 100;
     }
@@ -407,11 +379,10 @@ struct MlpSplitNet : CoNet {
                   throw std::invalid_argument("mlp12x100h3: a weight of layer " + std::to_string(l) + " is " + std::to_string(v) +
                                               " after the BatchNorm fold, beyond the fp16 range of the f16x3 kernels: use mlp12x100x6");
                 size_t lane = 32 * h + i;
-                for (int t = 0; t < nt; ++t) {
-                  uint16_t term = f16 ? m3_f16_rne(v) : m3_bf16_rne(v);
-                  v = v - (f16 ? m3_f16_to_f(term) : m3_bf16_to_f(term));
-                  buf[off + (((size_t)to * nt + t) * 64 + lane) * 4 + j / 2] |= (uint32_t)term << (16 * (j & 1));
-                }
+                uint16_t term[3];
+                split_terms(v, nt, f16, term);
+                for (int t = 0; t < nt; ++t)
+                  buf[off + (((size_t)to * nt + t) * 64 + lane) * 4 + j / 2] |= (uint32_t)term[t] << (16 * (j & 1));
               }
       }
       for (int o = 0; o < 128; ++o) {
@@ -419,9 +390,8 @@ struct MlpSplitNet : CoNet {
         memcpy(&buf[(size_t)2 * l * chunk_words + 4 * step_words + o], &b, 4);
       }
     }
-    rt_malloc((void **)&d_w, buf.size() * 4, s);
-    rt_h2d(d_w, buf.data(), buf.size() * 4, s);
-    if (f16) rt_malloc((void **)&d_range, 4, s);
+    d_w.upload(buf.data(), buf.size(), s);
+    if (f16) range.alloc(s);
     rt_sync(s);
     if (f16)
       RT_CHECK(hipFuncSetAttribute((const void *)co_k_mlp_forward_h3, hipFuncAttributeMaxDynamicSharedMemorySize, M3_LDS_BYTES(2)));
@@ -430,17 +400,7 @@ struct MlpSplitNet : CoNet {
     else
       RT_CHECK(hipFuncSetAttribute((const void *)co_k_mlp_forward_x6, hipFuncAttributeMaxDynamicSharedMemorySize, M3_LDS_BYTES(3)));
   }
-  ~MlpSplitNet() override {
-    rt_free(d_w);
-    rt_free(d_range);
-  }
-  bool range_exceeded(rt_stream_t s) override {
-    if (!d_range) return false;
-    uint32_t flag = 0;
-    rt_d2h(&flag, d_range, 4, s);
-    rt_sync(s);
-    return flag != 0;
-  }
+  bool range_exceeded(rt_stream_t s) override { return range.read(s); }
   size_t max_rows() const override { return cap; }
   int kind() const override { return f16 ? CO_NET_MLP12X100_H3 : nt == 2 ? CO_NET_MLP12X100_X3 : CO_NET_MLP12X100_X6; }
   double flop_per_row() const override { return 2.0 * (70 * 100 + 11 * 100 * 100 + 100 + 100 * 96); }
@@ -449,15 +409,14 @@ struct MlpSplitNet : CoNet {
     int grid = (rows_cap + M3_ROWS_PER_WG - 1) / M3_ROWS_PER_WG;
     if (grid < 1) return;
     if (f16)
-      hipLaunchKernelGGL(co_k_mlp_forward_h3, dim3(grid), dim3(256), M3_LDS_BYTES(2), s, d_in, d_rows, (const uint32_t *)d_w, d_eval,
-                         d_probs, io, d_range);
+      RT_LAUNCH_LDS(co_k_mlp_forward_h3, grid, 256, M3_LDS_BYTES(2), s, d_in, d_rows, (const uint32_t *)d_w.p, d_eval, d_probs, io,
+                    range.ptr());
     else if (nt == 2)
-      hipLaunchKernelGGL(co_k_mlp_forward_x3, dim3(grid), dim3(256), M3_LDS_BYTES(2), s, d_in, d_rows, (const uint32_t *)d_w, d_eval,
-                         d_probs, io, d_range);
+      RT_LAUNCH_LDS(co_k_mlp_forward_x3, grid, 256, M3_LDS_BYTES(2), s, d_in, d_rows, (const uint32_t *)d_w.p, d_eval, d_probs, io,
+                    range.ptr());
     else
-      hipLaunchKernelGGL(co_k_mlp_forward_x6, dim3(grid), dim3(256), M3_LDS_BYTES(3), s, d_in, d_rows, (const uint32_t *)d_w, d_eval,
-                         d_probs, io, d_range);
-    RT_CHECK(hipGetLastError());
+      RT_LAUNCH_LDS(co_k_mlp_forward_x6, grid, 256, M3_LDS_BYTES(3), s, d_in, d_rows, (const uint32_t *)d_w.p, d_eval, d_probs, io,
+                    range.ptr());
   }
 };
 

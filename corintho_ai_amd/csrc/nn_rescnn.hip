@@ -33,8 +33,8 @@
 #include <vector>
 
 #include "engine_defs.h"
+#include "host.h"
 #include "lds_dma.h"
-#include "nn.h"
 
 #define RC_NB 4
 #define RC_POS_PER_WG 16
@@ -304,9 +304,7 @@ __device__ __forceinline__ void rc_dense_value(const RcParams &P, const float *w
   if (q == 0 && pos < rows && c < ncols) P.eval[rc_out_row(P, pos) * (size_t)P.io.eval_stride] = tanhf(v2[0] + P.bv2[0]);
 }
 
-#ifndef CO_RC_F32_BLOCKS
 #define CO_RC_F32_BLOCKS 2
-#endif
 __global__ __launch_bounds__(256, CO_RC_F32_BLOCKS) void co_k_rescnn_forward(RcParams P) {
   __shared__ __attribute__((aligned(16))) float lds_w[2 * RC_CONV_CHUNK];
   __shared__ float lds_feat[4][RC_NB][96];
@@ -387,9 +385,7 @@ __global__ __launch_bounds__(256, CO_RC_F32_BLOCKS) void co_k_rescnn_forward(RcP
  * runs hundreds of such iterations, each as long as its slowest kernel).  NT = 3: 1 (three packed
  * operand sets + three weight fragment sets leave no registers for a second pair at two waves per
  * SIMD; the MFMA work per weight byte is that of NT = 2, NP = 2 again). */
-#ifndef RC3_SMALL_ROWS
 #define RC3_SMALL_ROWS 4096 /* NT = 2: batches up to this size take the small-batch kernel: <= 256 workgroups */
-#endif
 #define RC6_THIN_ROWS 2048  /* NT = 3: batches up to this size take the four-wave kernel: <= 256 workgroups of 8 positions */
 #define RCS_STEM_CHUNK(NT) (512 * (NT))  /* u32: 1 k-step x 2 out tiles x NT terms x 64 lanes x 4 */
 #define RCS_CONV_CHUNK(NT) (2048 * (NT)) /* u32: 4 k-steps ... = 8 KB per term */
@@ -924,12 +920,6 @@ __global__ __launch_bounds__(512, 2) void co_k_rescnn_forward_x6(Rc3Params Q) {
 /* The f16x3 kernels (see above rcs_forward): throughput kernel, 32 positions per workgroup; _small: batches up to
  * RC3_SMALL_ROWS rows, 16 positions per workgroup, and up to RC6_THIN_ROWS rows on the four-wave thin path (one wave per
  * SIMD, 8 positions per workgroup, waves 4..7 leave at once; see co_k_rescnn_forward_x6). */
-#ifndef CO_RESCNN_PIXMAJOR_DEFAULT
-#define CO_RESCNN_PIXMAJOR_DEFAULT 1 /* 0: a diagnostic build whose batches beyond RC3_SMALL_ROWS take the (position, pixel)-column kernel (tools/exp/pixmajor_ab.py) */
-#endif
-#if !CO_RESCNN_PIXMAJOR_DEFAULT
-__global__ __launch_bounds__(512, 2) void co_k_rescnn_forward_h3(Rc3Params Q) { rcs_forward<2, 2, 8, true>(Q); }
-#endif
 __global__ __launch_bounds__(512, 2) void co_k_rescnn_forward_h3_small(Rc3Params Q) {
   const int rows = *Q.base.d_rows, rbase = rcp_small_begin(Q, rows);
   if (rows - rbase <= 0) return; /* the whole batch is the throughput kernel's */
@@ -940,8 +930,6 @@ __global__ __launch_bounds__(512, 2) void co_k_rescnn_forward_h3_small(Rc3Params
     rcs_forward<1, 2, 8, true>(Q, rbase);
   }
 }
-#define RCH_LDS_WORDS(NP) RCS_LDS_WORDS(2, NP)
-#define RCH_THREADS 512
 
 /* ======================================================================
  * K6p: the f16x3 throughput kernel in PIXEL-MAJOR form (round 4).
@@ -1295,27 +1283,19 @@ __global__ __launch_bounds__(512, 2) void co_k_rescnn_forward_h3p(Rc3Params Q) {
 
 /* ------------------------------------------------------------------ host */
 struct ResCnnNet : CoNet {
-  std::vector<float *> bufs;
+  std::vector<DevBuf<float>> bufs;
   RcParams P;
   size_t cap;
 
   float *upload(const std::vector<float> &h, rt_stream_t s) {
-    float *d = nullptr;
-    rt_malloc((void **)&d, h.size() * 4, s);
-    rt_h2d(d, h.data(), h.size() * 4, s);
-    bufs.push_back(d);
-    return d;
+    bufs.emplace_back();
+    bufs.back().upload(h.data(), h.size(), s);
+    return bufs.back().p;
   }
 
   ResCnnNet(const float *w, size_t max_rows, rt_stream_t s) : cap(max_rows) {
     const float *p = w;
     std::vector<float> trunk(RC_TRUNK_FLOATS, 0.0f), epi((size_t)RC_NUM_CONVS * 192, 0.0f);
-    auto bn_fold = [](const float *ga, const float *be, const float *mu, const float *va, int n, float *a, float *c) {
-      for (int i = 0; i < n; ++i) {
-        a[i] = (float)((double)ga[i] / sqrt((double)va[i] + CO_BN_EPS));
-        c[i] = (float)((double)be[i] - (double)mu[i] * (double)a[i]);
-      }
-    };
     size_t off = 0;
     for (int cv = 0; cv < RC_NUM_CONVS; ++cv) {
       const int cin = cv == 0 ? 10 : 64;
@@ -1380,9 +1360,6 @@ struct ResCnnNet : CoNet {
     P.bv2 = upload(bv2, s);
     rt_sync(s);
   }
-  ~ResCnnNet() override {
-    for (float *d : bufs) rt_free(d);
-  }
   size_t max_rows() const override { return cap; }
   int kind() const override { return CO_NET_RESCNN4; }
   double flop_per_row() const override {
@@ -1398,57 +1375,17 @@ struct ResCnnNet : CoNet {
     p.d_rows = d_rows;
     p.eval = d_eval;
     p.probs = d_probs;
-    hipLaunchKernelGGL(co_k_rescnn_forward, dim3(grid), dim3(256), 0, s, p);
-    RT_CHECK(hipGetLastError());
+    RT_LAUNCH(co_k_rescnn_forward, grid, 256, s, p);
   }
 };
-
-static inline uint16_t rc_bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40); /* NaN */
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static inline float rc_bf16_to_f(uint16_t h) {
-  uint32_t u = (uint32_t)h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-/* float -> IEEE binary16, round to nearest even, subnormals kept (what v_cvt_f16_f32 gives) */
-static inline uint16_t rc_f16_rne(float f) {
-  _Float16 h = (_Float16)f;
-  uint16_t u;
-  memcpy(&u, &h, 2);
-  return u;
-}
-static inline float rc_f16_to_f(uint16_t u) {
-  _Float16 h;
-  memcpy(&h, &u, 2);
-  return (float)h;
-}
-/* v -> nt 16-bit terms: bf16(v) (f16: fp16(v)), the same of the remainder, ... (the device's rcs_split) */
-static inline void rc_bf16_terms(float v, int nt, uint16_t *t, bool f16 = false) {
-  if (f16 && !(fabsf(v) <= CO_F16_MAX))
-    throw std::invalid_argument("rescnn4h3: a convolution weight is " + std::to_string(v) +
-                                ", beyond the fp16 range of the f16x3 kernels: use rescnn4x6");
-  for (int i = 0; i < nt; ++i) {
-    t[i] = f16 ? rc_f16_rne(v) : rc_bf16_rne(v);
-    v = v - (f16 ? rc_f16_to_f(t[i]) : rc_bf16_to_f(t[i]));
-  }
-}
 
 /* the split-precision kernels: NT = 2 (bf16x3) or 3 (bf16x6, float32-equivalent) */
 struct ResCnnSplitNet : ResCnnNet {
   int nt;
-  bool f16;
-  bool pixmajor = false; /* f16: batches beyond RC3_SMALL_ROWS on the pixel-major kernel (K6p) */
-  int num_cus = 256;     /* (a pass of that kernel = one workgroup per CU) */
-  uint32_t *d_trunk3 = nullptr;
-  uint32_t *d_whead3 = nullptr;
-  uint32_t *d_epi3 = nullptr;
-  uint32_t *d_range = nullptr; /* f16: the kernels' out-of-range flag */
+  bool f16;          /* fp16 terms; batches beyond RC3_SMALL_ROWS on the pixel-major kernel (K6p) */
+  int num_cus = 256; /* (a pass of that kernel = one workgroup per CU) */
+  DevBuf<uint32_t> d_trunk3, d_whead3, d_epi3;
+  RangeFlag range; /* f16: the kernels' out-of-range flag */
   ResCnnSplitNet(const float *w, size_t max_rows, rt_stream_t s, int nterms, bool fp16 = false)
       : ResCnnNet(w, max_rows, s), nt(nterms), f16(fp16) {
     const size_t stem_chunk = (size_t)512 * nt, conv_chunk = (size_t)2048 * nt;
@@ -1456,6 +1393,13 @@ struct ResCnnSplitNet : ResCnnNet {
     const float *p = w;
     size_t off = 0;
     uint16_t tv[3];
+    /* v -> tv: its nt terms (the device's rcs_split) */
+    auto terms = [&](float v) {
+      if (f16 && !(fabsf(v) <= CO_F16_MAX))
+        throw std::invalid_argument("rescnn4h3: a convolution weight is " + std::to_string(v) +
+                                    ", beyond the fp16 range of the f16x3 kernels: use rescnn4x6");
+      split_terms(v, nt, f16, tv);
+    };
     for (int cv = 0; cv < RC_NUM_CONVS; ++cv) {
       const int cin = cv == 0 ? 10 : 64;
       const int cs = cv == 0 ? 1 : 4;
@@ -1472,7 +1416,7 @@ struct ResCnnSplitNet : ResCnnNet {
                   int ci = 32 * T + 4 * h + 8 * (2 * a + (j >> 2)) + (j & 3);
                   int co = 32 * to + i;
                   float v = ci < cin ? K[((size_t)tap * cin + ci) * 64 + co] : 0.0f;
-                  rc_bf16_terms(v, nt, tv, f16);
+                  terms(v);
                   size_t lane = 32 * h + i;
                   for (int t = 0; t < nt; ++t) {
                     size_t wd = off + (size_t)tap * chunk + ((((size_t)st * 2 + to) * nt + t) * 64 + lane) * 4 + j / 2;
@@ -1494,40 +1438,34 @@ struct ResCnnSplitNet : ResCnnNet {
             int T = st >> 1, a = st & 1;
             int k = 32 * T + 4 * h + 8 * (2 * a + (j >> 2)) + (j & 3);
             float v = i < 4 ? pk[k * 4 + i] : i < 6 ? vk[k * 2 + (i - 4)] : 0.0f;
-            rc_bf16_terms(v, nt, tv, f16);
+            terms(v);
             size_t lane = 32 * h + i;
             for (int t = 0; t < nt; ++t)
               wh3[(((size_t)st * nt + t) * 64 + lane) * 4 + j / 2] |= (uint32_t)tv[t] << (16 * (j & 1));
           }
-    rt_malloc((void **)&d_trunk3, tr.size() * 4, s);
-    rt_h2d(d_trunk3, tr.data(), tr.size() * 4, s);
-    rt_malloc((void **)&d_whead3, head_words * 4, s);
-    rt_h2d(d_whead3, wh3.data(), wh3.size() * 4, s);
-    rt_d2d(d_whead3 + frag1, P.wpol, 6144 * 4, s); /* the dense weights in the base class's MFMA order */
-    rt_d2d(d_whead3 + frag1 + 6144, P.wv1, 2048 * 4, s);
-    rt_d2d(d_whead3 + frag1 + 6144 + 2048, P.wv2, 1024 * 4, s);
-    if (f16) rt_malloc((void **)&d_range, 4, s);
-    rt_malloc((void **)&d_epi3, (size_t)RC3_EPI_WORDS * 4, s); /* zero-filled: the padding is staged too */
-    rt_d2d(d_epi3, P.epi, (size_t)RC_NUM_CONVS * 192 * 4, s);
+    d_trunk3.upload(tr.data(), tr.size(), s);
+    d_whead3.alloc(head_words, s);
+    rt_h2d(d_whead3.p, wh3.data(), wh3.size() * 4, s);
+    rt_d2d(d_whead3.p + frag1, P.wpol, 6144 * 4, s); /* the dense weights in the base class's MFMA order */
+    rt_d2d(d_whead3.p + frag1 + 6144, P.wv1, 2048 * 4, s);
+    rt_d2d(d_whead3.p + frag1 + 6144 + 2048, P.wv2, 1024 * 4, s);
+    if (f16) range.alloc(s);
+    d_epi3.alloc(RC3_EPI_WORDS, s); /* zero-filled: the padding is staged too */
+    rt_d2d(d_epi3.p, P.epi, (size_t)RC_NUM_CONVS * 192 * 4, s);
     if (nt == 2) {
       RT_CHECK(hipFuncSetAttribute((const void *)co_k_rescnn_forward_x3, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    RCS_LDS_WORDS(2, 2) * 4));
       RT_CHECK(hipFuncSetAttribute((const void *)co_k_rescnn_forward_x3_small, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    RCS_LDS_WORDS(2, 1) * 4));
-#if !CO_RESCNN_PIXMAJOR_DEFAULT
-      RT_CHECK(hipFuncSetAttribute((const void *)co_k_rescnn_forward_h3, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   RCH_LDS_WORDS(2) * 4));
-#endif
       RT_CHECK(hipFuncSetAttribute((const void *)co_k_rescnn_forward_h3p, hipFuncAttributeMaxDynamicSharedMemorySize, RCP_LDS_WORDS * 4));
       {
-        pixmajor = f16 && CO_RESCNN_PIXMAJOR_DEFAULT != 0;
         int dev = 0;
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
           num_cus = prop.multiProcessorCount;
       }
       RT_CHECK(hipFuncSetAttribute((const void *)co_k_rescnn_forward_h3_small, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   RCH_LDS_WORDS(1) * 4));
+                                   RCS_LDS_WORDS(2, 1) * 4));
     } else {
       RT_CHECK(hipFuncSetAttribute((const void *)co_k_rescnn_forward_x6, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    RCS_LDS_WORDS(3, 1) * 4));
@@ -1535,19 +1473,7 @@ struct ResCnnSplitNet : ResCnnNet {
     }
     rt_sync(s);
   }
-  ~ResCnnSplitNet() override {
-    rt_free(d_trunk3);
-    rt_free(d_whead3);
-    rt_free(d_epi3);
-    rt_free(d_range);
-  }
-  bool range_exceeded(rt_stream_t s) override {
-    if (!d_range) return false;
-    uint32_t flag = 0;
-    rt_d2h(&flag, d_range, 4, s);
-    rt_sync(s);
-    return flag != 0;
-  }
+  bool range_exceeded(rt_stream_t s) override { return range.read(s); }
   int kind() const override { return f16 ? CO_NET_RESCNN4_H3 : nt == 2 ? CO_NET_RESCNN4_X3 : CO_NET_RESCNN4_X6; }
   void forward(const float *d_in, int32_t rows_cap, const int32_t *d_rows, float *d_eval, float *d_probs,
                rt_stream_t s, const CoNetIO &io = CoNetIO()) override {
@@ -1559,11 +1485,11 @@ struct ResCnnSplitNet : ResCnnNet {
     q.base.d_rows = d_rows;
     q.base.eval = d_eval;
     q.base.probs = d_probs;
-    q.wtrunk = d_trunk3;
-    q.whead3 = d_whead3;
-    q.epi3 = d_epi3;
-    q.range_flag = d_range;
-    q.pass_rows = pixmajor && io.alone ? 32 * num_cus : 0;
+    q.wtrunk = d_trunk3.p;
+    q.whead3 = d_whead3.p;
+    q.epi3 = d_epi3.p;
+    q.range_flag = range.ptr();
+    q.pass_rows = f16 && io.alone ? 32 * num_cus : 0;
     if (nt == 2) {
       /* both kernels are queued; the row count on the device decides which one works (the other's
        * workgroups return at once).  Batches that can exceed RC3_SMALL_ROWS need the throughput kernel. */
@@ -1571,25 +1497,19 @@ struct ResCnnSplitNet : ResCnnNet {
       /* enough workgroups for either path of the f16 kernel: 16 positions each, or 8 on its thin path (<= RC6_THIN_ROWS rows) */
       const int thin_rows = rows_cap < RC6_THIN_ROWS ? rows_cap : RC6_THIN_ROWS;
       const int small_grid = f16 && (thin_rows + 7) / 8 > (small_rows + 15) / 16 ? (thin_rows + 7) / 8 : (small_rows + 15) / 16;
-      hipLaunchKernelGGL(f16 ? co_k_rescnn_forward_h3_small : co_k_rescnn_forward_x3_small, dim3(small_grid), dim3(512),
-                         (f16 ? RCH_LDS_WORDS(1) : RCS_LDS_WORDS(2, 1)) * 4, s, q);
+      RT_LAUNCH_LDS(f16 ? co_k_rescnn_forward_h3_small : co_k_rescnn_forward_x3_small, small_grid, 512, RCS_LDS_WORDS(2, 1) * 4, s, q);
       if (rows_cap > RC3_SMALL_ROWS) {
-        if (pixmajor)
-          hipLaunchKernelGGL(co_k_rescnn_forward_h3p, dim3((rows_cap + 31) / 32), dim3(512), RCP_LDS_WORDS * 4, s, q);
-#if !CO_RESCNN_PIXMAJOR_DEFAULT
-        else if (f16)
-          hipLaunchKernelGGL(co_k_rescnn_forward_h3, dim3((rows_cap + 31) / 32), dim3(RCH_THREADS), RCH_LDS_WORDS(2) * 4, s, q);
-#endif
+        if (f16)
+          RT_LAUNCH_LDS(co_k_rescnn_forward_h3p, (rows_cap + 31) / 32, 512, RCP_LDS_WORDS * 4, s, q);
         else
-          hipLaunchKernelGGL(co_k_rescnn_forward_x3, dim3((rows_cap + 31) / 32), dim3(512), RCS_LDS_WORDS(2, 2) * 4, s, q);
+          RT_LAUNCH_LDS(co_k_rescnn_forward_x3, (rows_cap + 31) / 32, 512, RCS_LDS_WORDS(2, 2) * 4, s, q);
       }
     } else {
       /* enough workgroups for either path: 16 positions each in the throughput path, 8 in the thin one (<= 2048 rows) */
       const int thin_rows = rows_cap < RC6_THIN_ROWS ? rows_cap : RC6_THIN_ROWS;
       const int grid = (rows_cap + 15) / 16 > (thin_rows + 7) / 8 ? (rows_cap + 15) / 16 : (thin_rows + 7) / 8;
-      hipLaunchKernelGGL(co_k_rescnn_forward_x6, dim3(grid), dim3(512), RCS_LDS_WORDS(3, 1) * 4, s, q);
+      RT_LAUNCH_LDS(co_k_rescnn_forward_x6, grid, 512, RCS_LDS_WORDS(3, 1) * 4, s, q);
     }
-    RT_CHECK(hipGetLastError());
   }
 };
 

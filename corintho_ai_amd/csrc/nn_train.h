@@ -6,12 +6,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <stdexcept>
 #include <string>
 #include <vector>
 
-#include "../../include/corintho_hip.h"
-#include "nn.h"
+#include "host.h"
 
 #define FT_PADW 112  /* row stride of the heads' outputs H and their gradients Hd (and of the MLP's activations): 7 tiles of 16 */
 #define FT_NSPLIT 16 /* at most this many row chunks per weight gradient (partials of ft_k_gemm) */
@@ -21,40 +19,6 @@
 #define FT_SPLIT0 -1
 #define FT_SPLIT1 -2
 #define FT_WHOLE -3
-
-#define FT_LAUNCH(kernel, grid, block, stream, ...)                             \
-  do {                                                                          \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__); \
-    RT_CHECK(hipGetLastError());                                                \
-  } while (0)
-
-template <typename T>
-struct FtBuf {
-  T *p = nullptr;
-  FtBuf() = default;
-  FtBuf(const FtBuf &) = delete;
-  FtBuf &operator=(const FtBuf &) = delete;
-  ~FtBuf() { rt_free(p); }
-  void alloc(size_t n, rt_stream_t s) {
-    rt_free(p);
-    p = nullptr;
-    rt_malloc((void **)&p, n * sizeof(T), s);
-  }
-  void release() {
-    rt_free(p);
-    p = nullptr;
-  }
-  void swap(FtBuf &o) {
-    T *t = p;
-    p = o.p;
-    o.p = t;
-  }
-};
-
-struct FtError : std::runtime_error {
-  int code;
-  FtError(int c, const std::string &m) : std::runtime_error(m), code(c) {}
-};
 
 /* C[m][n] (+)= sum_k A[m][k] B[k][n] over one chunk of k, every operand addressed through strides (so a transpose is
  * free).  One wave per 16x16 output tile and chunk; chunk s writes C + s * c_split.  Loads outside [0,M) x [k0,k1) and

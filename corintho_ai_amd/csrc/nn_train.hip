@@ -30,8 +30,6 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-void co_set_last_error(const std::string &m);
-
 /* the strided product that FtGemm (nn_train.h) describes */
 __global__ __launch_bounds__(256) void ft_k_gemm(FtGemm g) {
   const int lane = threadIdx.x & 63;
@@ -224,11 +222,11 @@ __global__ __launch_bounds__(256) void ft_k_update(float *__restrict__ w, float 
 void ft_gemm(rt_stream_t s, const FtGemm &a) {
   const int tiles = ((a.M + 15) / 16) * ((a.N + 15) / 16) * ((a.K + a.kchunk - 1) / a.kchunk);
   if (tiles == 0) return;
-  FT_LAUNCH(ft_k_gemm, (tiles + 3) / 4, 256, s, a);
+  RT_LAUNCH(ft_k_gemm, (tiles + 3) / 4, 256, s, a);
 }
 
 void ft_relu_bwd(rt_stream_t s, float *dA, const float *A, int B, int ld, int ncol, float *gbias) {
-  FT_LAUNCH(ft_k_relu_bwd, (ncol + 15) / 16, 1024, s, dA, A, B, ld, ncol, gbias);
+  RT_LAUNCH(ft_k_relu_bwd, (ncol + 15) / 16, 1024, s, dA, A, B, ld, ncol, gbias);
 }
 
 FtNet *ft_net_create(int kind, int max_batch, rt_stream_t s) {
@@ -245,11 +243,12 @@ struct ca_fitter {
   int32_t ns = 0, cap = 0;    /* packed samples, and how many sp and oc have room for */
   rt_stream_t s = nullptr;
   std::unique_ptr<FtNet> net;
-  FtBuf<float> w, m, v, g, gsum, stat, h, hd, loss;
-  FtBuf<float> states, evals, probs; /* the expanded set */
-  FtBuf<float> sp, oc;               /* the packed set: state_policy[cap][166], outcome[cap] */
-  FtBuf<float> bstates, bevals, bprobs; /* one batch of a packed set as ft_k_assemble wrote it: max_batch rows */
-  FtBuf<int32_t> sidx, idx, ident, bidx; /* ident[r] = r, the rows of an assembled batch; bidx: ca_fitter_fetch_rows */
+  int dev() const { return device; }
+  DevBuf<float> w, m, v, g, gsum, stat, h, hd, loss;
+  DevBuf<float> states, evals, probs; /* the expanded set */
+  DevBuf<float> sp, oc;               /* the packed set: state_policy[cap][166], outcome[cap] */
+  DevBuf<float> bstates, bevals, bprobs; /* one batch of a packed set as ft_k_assemble wrote it: max_batch rows */
+  DevBuf<int32_t> sidx, idx, ident, bidx; /* ident[r] = r, the rows of an assembled batch; bidx: ca_fitter_fetch_rows */
   std::vector<float> hloss;
 
   void init(int dev, int kind, int mb) {
@@ -283,7 +282,7 @@ struct ca_fitter {
   };
   FtSource source() const { return FtSource{expanded ? nullptr : sp.p, oc.p, states.p, evals.p, probs.p}; }
   void assemble(const int32_t *rows, int B) {
-    FT_LAUNCH(ft_k_assemble, (B * FT_SAMPLE_FLOATS + 255) / 256, 256, s, source(), rows, B, bstates.p, bevals.p, bprobs.p);
+    RT_LAUNCH(ft_k_assemble, (B * FT_SAMPLE_FLOATS + 255) / 256, 256, s, source(), rows, B, bstates.p, bevals.p, bprobs.p);
   }
   /* the batch of rows[0..B) (a device pointer): the expanded set itself, or a packed set's rows assembled */
   Batch batch(const int32_t *rows, int B) {
@@ -295,8 +294,8 @@ struct ca_fitter {
 
   /* loss terms of the batch (and the logit / value gradients in Hd); loss sums to loss.p[2 * slot] */
   void loss_terms(const Batch &b, int B, bool grads, int slot) {
-    FT_LAUNCH(ft_k_loss, (B + 255) / 256, 256, s, (const float *)h.p, b.rows, B, b.evals, b.probs, hd.p);
-    FT_LAUNCH(ft_k_head_reduce, FT_PADW / 16, 1024, s, (const float *)hd.p, B, grads ? g.p : (float *)nullptr,
+    RT_LAUNCH(ft_k_loss, (B + 255) / 256, 256, s, (const float *)h.p, b.rows, B, b.evals, b.probs, hd.p);
+    RT_LAUNCH(ft_k_head_reduce, FT_PADW / 16, 1024, s, (const float *)hd.p, B, grads ? g.p : (float *)nullptr,
               net->policy_bias(), net->value_bias(), loss.p + 2 * slot);
   }
 
@@ -312,12 +311,12 @@ struct ca_fitter {
   /* the end of a step on the partials gradient() left: Adam and the moving statistics, or (apply = false) the
    * summed gradient to gsum only */
   void update(FtSplits ns, float lr_t, bool apply) {
-    FT_LAUNCH(ft_k_update, (nw + 255) / 256, 256, s, w.p, m.p, v.p, (const float *)g.p, nw, ns.rows, ns.pixels,
+    RT_LAUNCH(ft_k_update, (nw + 255) / 256, 256, s, w.p, m.p, v.p, (const float *)g.p, nw, ns.rows, ns.pixels,
               (const int32_t *)sidx.p, (const float *)stat.p, lr_t, apply ? 1 : 0, gsum.p);
   }
 
   void need_data() {
-    if (n <= 0) throw FtError(CA_ERR_STATE, "ca_fitter: no data (ca_fitter_set_data, ca_fitter_add_samples)");
+    if (n <= 0) throw CaError(CA_ERR_STATE, "ca_fitter: no data (ca_fitter_set_data, ca_fitter_add_samples)");
   }
   /* room in idx for the nr rows of a call: an expanded set has it from ca_fitter_set_data, a packed one takes what its
    * largest call asked for, not a share of its capacity */
@@ -361,22 +360,22 @@ struct ca_fitter {
   }
   /* the packed rows [first, first + count) to the front of new buffers with room for new_cap samples, device to device */
   void move_samples(int32_t first, int32_t count, int32_t new_cap) {
-    FtBuf<float> nsp, noc;
+    DevBuf<float> nsp, noc;
     nsp.alloc((size_t)new_cap * FT_SAMPLE_FLOATS, s);
     noc.alloc((size_t)new_cap, s);
     rt_d2d(nsp.p, sp.p + (size_t)first * FT_SAMPLE_FLOATS, (size_t)count * FT_SAMPLE_FLOATS * sizeof(float), s);
     rt_d2d(noc.p, oc.p + first, (size_t)count * sizeof(float), s);
     rt_sync(s); /* before the old buffers are freed */
-    sp.swap(nsp);
-    oc.swap(noc);
+    std::swap(sp, nsp);
+    std::swap(oc, noc);
     cap = new_cap;
   }
   /* room for `add` more packed samples behind the ns there are; capacity grows geometrically */
   void reserve(int32_t add) {
-    if (expanded) throw FtError(CA_ERR_STATE, "ca_fitter: the data set is expanded (ca_fitter_clear_data first)");
-    if (add < 0) throw FtError(CA_ERR_ARG, "ca_fitter: negative sample count");
+    if (expanded) throw CaError(CA_ERR_STATE, "ca_fitter: the data set is expanded (ca_fitter_clear_data first)");
+    if (add < 0) throw CaError(CA_ERR_ARG, "ca_fitter: negative sample count");
     const int64_t need = (int64_t)ns + add, most = INT32_MAX / CA_NUM_SYMMETRIES;
-    if (need > most) throw FtError(CA_ERR_ARG, "ca_fitter: more than INT32_MAX virtual rows");
+    if (need > most) throw CaError(CA_ERR_ARG, "ca_fitter: more than INT32_MAX virtual rows");
     need_stage();
     if (need <= cap) return;
     int64_t nc = 2 * (int64_t)cap > need ? 2 * (int64_t)cap : need;
@@ -389,18 +388,18 @@ struct ca_fitter {
   }
   void check_n(size_t n_floats) {
     if (n_floats != (size_t)nw)
-      throw FtError(CA_ERR_ARG, std::string("ca_fitter: ") + net->name() + " has " + std::to_string(nw) + " floats");
+      throw CaError(CA_ERR_ARG, std::string("ca_fitter: ") + net->name() + " has " + std::to_string(nw) + " floats");
   }
   void check_rows(const int32_t *rows, int32_t nr) {
-    if (nr < 0 || nr > n) throw FtError(CA_ERR_ARG, "ca_fitter: more rows than the data set holds");
+    if (nr < 0 || nr > n) throw CaError(CA_ERR_ARG, "ca_fitter: more rows than the data set holds");
     check_range(rows, nr);
   }
   void check_range(const int32_t *rows, int32_t nr) {
     for (int32_t i = 0; i < nr; ++i)
-      if (rows[i] < 0 || rows[i] >= n) throw FtError(CA_ERR_ARG, "ca_fitter: row index out of range");
+      if (rows[i] < 0 || rows[i] >= n) throw CaError(CA_ERR_ARG, "ca_fitter: row index out of range");
   }
   void check_batch(int32_t batch) {
-    if (batch < 1 || batch > max_batch) throw FtError(CA_ERR_ARG, "ca_fitter: batch must be in [1, max_batch]");
+    if (batch < 1 || batch > max_batch) throw CaError(CA_ERR_ARG, "ca_fitter: batch must be in [1, max_batch]");
   }
   void ensure_loss(int slots) {
     if ((int)hloss.size() < 2 * slots) {
@@ -432,23 +431,6 @@ struct ca_fitter {
   }
 };
 
-/* the body of an entry point on the fitter's device; what it throws becomes the return code and ca_last_error */
-template <class F>
-static int ft_guard(ca_fitter *f, F &&body) {
-  try {
-    if (!f) throw FtError(CA_ERR_ARG, "ca_fitter: null handle");
-    rt_set_device(f->device);
-    body();
-    return CA_OK;
-  } catch (const FtError &e) {
-    co_set_last_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    co_set_last_error(e.what());
-    return CA_ERR_DEVICE;
-  }
-}
-
 extern "C" int ca_fitter_create(int device, int32_t max_batch, ca_fitter **out) {
   return ca_fitter_create_net(device, CA_NET_MLP12X100, max_batch, out);
 }
@@ -465,17 +447,11 @@ extern "C" int ca_fitter_create_net(int device, int32_t net, int32_t max_batch, 
   *out = nullptr;
   int rc = ca_device_check(device);
   if (rc != CA_OK) return rc;
-  ca_fitter *f = nullptr;
-  try {
-    f = new ca_fitter();
+  return co_guard([&] {
+    auto f = std::make_unique<ca_fitter>();
     f->init(device, net, max_batch);
-  } catch (const std::exception &e) {
-    co_set_last_error(e.what());
-    delete f;
-    return CA_ERR_DEVICE;
-  }
-  *out = f;
-  return CA_OK;
+    *out = f.release();
+  });
 }
 
 extern "C" void ca_fitter_destroy(ca_fitter *f) {
@@ -489,27 +465,27 @@ extern "C" void ca_fitter_destroy(ca_fitter *f) {
 }
 
 extern "C" int ca_fitter_set_weights(ca_fitter *f, const float *weights, size_t n_floats) {
-  return ft_guard(f, [&] {
+  return co_guard(f, [&] {
     f->check_n(n_floats);
-    if (!weights) throw FtError(CA_ERR_ARG, "null weights");
+    if (!weights) throw CaError(CA_ERR_ARG, "null weights");
     rt_h2d(f->w.p, weights, f->nw * sizeof(float), f->s);
     rt_sync(f->s);
   });
 }
 
 extern "C" int ca_fitter_get_weights(ca_fitter *f, float *weights, size_t n_floats) {
-  return ft_guard(f, [&] {
+  return co_guard(f, [&] {
     f->check_n(n_floats);
-    if (!weights) throw FtError(CA_ERR_ARG, "null weights");
+    if (!weights) throw CaError(CA_ERR_ARG, "null weights");
     rt_d2h(weights, f->w.p, f->nw * sizeof(float), f->s);
     rt_sync(f->s);
   });
 }
 
 extern "C" int ca_fitter_set_optimizer(ca_fitter *f, const float *m, const float *v, size_t n_floats, int64_t iterations) {
-  return ft_guard(f, [&] {
+  return co_guard(f, [&] {
     f->check_n(n_floats);
-    if (!m || !v || iterations < 0) throw FtError(CA_ERR_ARG, "null slots or negative iterations");
+    if (!m || !v || iterations < 0) throw CaError(CA_ERR_ARG, "null slots or negative iterations");
     rt_h2d(f->m.p, m, f->nw * sizeof(float), f->s);
     rt_h2d(f->v.p, v, f->nw * sizeof(float), f->s);
     rt_sync(f->s);
@@ -518,9 +494,9 @@ extern "C" int ca_fitter_set_optimizer(ca_fitter *f, const float *m, const float
 }
 
 extern "C" int ca_fitter_get_optimizer(ca_fitter *f, float *m, float *v, size_t n_floats, int64_t *iterations) {
-  return ft_guard(f, [&] {
+  return co_guard(f, [&] {
     f->check_n(n_floats);
-    if (!m || !v || !iterations) throw FtError(CA_ERR_ARG, "null output");
+    if (!m || !v || !iterations) throw CaError(CA_ERR_ARG, "null output");
     rt_d2h(m, f->m.p, f->nw * sizeof(float), f->s);
     rt_d2h(v, f->v.p, f->nw * sizeof(float), f->s);
     rt_sync(f->s);
@@ -529,8 +505,8 @@ extern "C" int ca_fitter_get_optimizer(ca_fitter *f, float *m, float *v, size_t 
 }
 
 extern "C" int ca_fitter_set_data(ca_fitter *f, const float *states, const float *evals, const float *probs, int32_t n) {
-  return ft_guard(f, [&] {
-    if (n < 1 || !states || !evals || !probs) throw FtError(CA_ERR_ARG, "ca_fitter_set_data: empty or null");
+  return co_guard(f, [&] {
+    if (n < 1 || !states || !evals || !probs) throw CaError(CA_ERR_ARG, "ca_fitter_set_data: empty or null");
     f->clear_data(); /* no data while the buffers are being replaced: a failure below leaves the fitter without, not with half */
     f->expanded = true;
     f->states.alloc((size_t)n * CA_GAME_STATE_SIZE, f->s);
@@ -548,10 +524,10 @@ extern "C" int ca_fitter_set_data(ca_fitter *f, const float *states, const float
 
 extern "C" int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows, int32_t batch, float learning_rate,
                                double *out_losses, float *batch_losses) {
-  return ft_guard(f, [&] {
+  return co_guard(f, [&] {
     f->need_data();
     f->check_batch(batch);
-    if (!rows || n_rows < 1) throw FtError(CA_ERR_ARG, "ca_fitter_train: no rows");
+    if (!rows || n_rows < 1) throw CaError(CA_ERR_ARG, "ca_fitter_train: no rows");
     f->check_rows(rows, n_rows);
     f->need_idx(n_rows);
     const int nb = (n_rows + batch - 1) / batch;
@@ -571,11 +547,11 @@ extern "C" int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows
 }
 
 extern "C" int ca_fitter_evaluate(ca_fitter *f, int32_t row0, int32_t n_rows, int32_t batch, double *out_losses) {
-  return ft_guard(f, [&] {
+  return co_guard(f, [&] {
     f->need_data();
     f->check_batch(batch);
     if (n_rows < 1 || row0 < 0 || (int64_t)row0 + n_rows > f->n)
-      throw FtError(CA_ERR_ARG, "ca_fitter_evaluate: rows out of range");
+      throw CaError(CA_ERR_ARG, "ca_fitter_evaluate: rows out of range");
     f->need_idx(n_rows);
     std::vector<int32_t> rows(n_rows);
     for (int32_t i = 0; i < n_rows; ++i) rows[i] = row0 + i;
@@ -593,10 +569,10 @@ extern "C" int ca_fitter_evaluate(ca_fitter *f, int32_t row0, int32_t n_rows, in
 }
 
 extern "C" int ca_fitter_gradients(ca_fitter *f, const int32_t *rows, int32_t n_rows, float *grads, double *out_losses) {
-  return ft_guard(f, [&] {
+  return co_guard(f, [&] {
     f->need_data();
     f->check_batch(n_rows);
-    if (!rows || !grads) throw FtError(CA_ERR_ARG, "null argument");
+    if (!rows || !grads) throw CaError(CA_ERR_ARG, "null argument");
     f->check_rows(rows, n_rows);
     f->need_idx(n_rows);
     f->ensure_loss(1);
@@ -608,15 +584,15 @@ extern "C" int ca_fitter_gradients(ca_fitter *f, const int32_t *rows, int32_t n_
 }
 
 extern "C" int ca_fitter_clear_data(ca_fitter *f) {
-  return ft_guard(f, [&] {
+  return co_guard(f, [&] {
     rt_sync(f->s);
     f->clear_data();
   });
 }
 
 extern "C" int ca_fitter_add_samples(ca_fitter *f, const float *state_policy, const float *outcome, int32_t n) {
-  return ft_guard(f, [&] {
-    if (!state_policy || !outcome || n < 0) throw FtError(CA_ERR_ARG, "ca_fitter_add_samples: null or negative");
+  return co_guard(f, [&] {
+    if (!state_policy || !outcome || n < 0) throw CaError(CA_ERR_ARG, "ca_fitter_add_samples: null or negative");
     f->reserve(n);
     rt_h2d(f->sp.p + (size_t)f->ns * FT_SAMPLE_FLOATS, state_policy, (size_t)n * FT_SAMPLE_FLOATS * sizeof(float), f->s);
     rt_h2d(f->oc.p + f->ns, outcome, (size_t)n * sizeof(float), f->s);
@@ -630,15 +606,15 @@ static void ft_check_device_ptr(const ca_fitter *f, const void *p) {
   hipPointerAttribute_t a;
   if (hipPointerGetAttributes(&a, p) != hipSuccess) {
     (void)hipGetLastError();
-    throw FtError(CA_ERR_ARG, "ca_fitter_add_device_samples: not a device pointer");
+    throw CaError(CA_ERR_ARG, "ca_fitter_add_device_samples: not a device pointer");
   }
   if (a.type != hipMemoryTypeDevice || a.device != f->device)
-    throw FtError(CA_ERR_ARG, "ca_fitter_add_device_samples: not memory of the fitter's device");
+    throw CaError(CA_ERR_ARG, "ca_fitter_add_device_samples: not memory of the fitter's device");
 }
 
 extern "C" int ca_fitter_add_device_samples(ca_fitter *f, const void *d_state_policy, const void *d_outcome, int32_t n) {
-  return ft_guard(f, [&] {
-    if (!d_state_policy || !d_outcome || n < 0) throw FtError(CA_ERR_ARG, "ca_fitter_add_device_samples: null or negative");
+  return co_guard(f, [&] {
+    if (!d_state_policy || !d_outcome || n < 0) throw CaError(CA_ERR_ARG, "ca_fitter_add_device_samples: null or negative");
     ft_check_device_ptr(f, d_state_policy);
     ft_check_device_ptr(f, d_outcome);
     f->reserve(n);
@@ -650,15 +626,15 @@ extern "C" int ca_fitter_add_device_samples(ca_fitter *f, const void *d_state_po
 }
 
 extern "C" int ca_fitter_add_trainer_samples(ca_fitter *f, ca_trainer *t, int32_t *n_added) {
-  return ft_guard(f, [&] {
-    if (!t || !n_added) throw FtError(CA_ERR_ARG, "ca_fitter_add_trainer_samples: null argument");
+  return co_guard(f, [&] {
+    if (!t || !n_added) throw CaError(CA_ERR_ARG, "ca_fitter_add_trainer_samples: null argument");
     /* the trainer's own entry points have left their message in ca_last_error */
     auto ok = [](int rc) {
-      if (rc != CA_OK) throw FtError(rc, ca_last_error());
+      if (rc != CA_OK) throw CaError(rc, ca_last_error());
     };
     int32_t dev = -1, count = 0, got = 0;
     ok(ca_trainer_device(t, &dev));
-    if (dev != f->device) throw FtError(CA_ERR_ARG, "ca_fitter_add_trainer_samples: the trainer is on another device");
+    if (dev != f->device) throw CaError(CA_ERR_ARG, "ca_fitter_add_trainer_samples: the trainer is on another device");
     ok(ca_trainer_num_samples(t, &count));
     f->reserve(count);
     rt_sync(f->s); /* the buffers' clears and moves are on the fitter's stream, the pack on the trainer's */
@@ -669,9 +645,9 @@ extern "C" int ca_fitter_add_trainer_samples(ca_fitter *f, ca_trainer *t, int32_
 }
 
 extern "C" int ca_fitter_drop_samples(ca_fitter *f, int32_t n_oldest) {
-  return ft_guard(f, [&] {
-    if (f->expanded) throw FtError(CA_ERR_STATE, "ca_fitter_drop_samples: the data set is expanded");
-    if (n_oldest < 0 || n_oldest > f->ns) throw FtError(CA_ERR_ARG, "ca_fitter_drop_samples: more than the set holds");
+  return co_guard(f, [&] {
+    if (f->expanded) throw CaError(CA_ERR_STATE, "ca_fitter_drop_samples: the data set is expanded");
+    if (n_oldest < 0 || n_oldest > f->ns) throw CaError(CA_ERR_ARG, "ca_fitter_drop_samples: more than the set holds");
     if (n_oldest == 0) return;
     rt_sync(f->s);
     if (n_oldest < f->ns) f->slide_samples(n_oldest, f->ns - n_oldest);
@@ -681,8 +657,8 @@ extern "C" int ca_fitter_drop_samples(ca_fitter *f, int32_t n_oldest) {
 }
 
 extern "C" int ca_fitter_data_info(ca_fitter *f, int32_t *rows, int32_t *samples) {
-  return ft_guard(f, [&] {
-    if (!rows || !samples) throw FtError(CA_ERR_ARG, "ca_fitter_data_info: null output");
+  return co_guard(f, [&] {
+    if (!rows || !samples) throw CaError(CA_ERR_ARG, "ca_fitter_data_info: null output");
     *rows = f->n;
     *samples = f->expanded ? 0 : f->ns;
   });
@@ -690,9 +666,9 @@ extern "C" int ca_fitter_data_info(ca_fitter *f, int32_t *rows, int32_t *samples
 
 extern "C" int ca_fitter_fetch_rows(ca_fitter *f, const int32_t *rows, int32_t n_rows, float *states, float *evals,
                                     float *probs) {
-  return ft_guard(f, [&] {
+  return co_guard(f, [&] {
     f->need_data();
-    if (!rows || !states || !evals || !probs || n_rows < 0) throw FtError(CA_ERR_ARG, "ca_fitter_fetch_rows: null or negative");
+    if (!rows || !states || !evals || !probs || n_rows < 0) throw CaError(CA_ERR_ARG, "ca_fitter_fetch_rows: null or negative");
     f->check_range(rows, n_rows);
     f->need_stage();
     for (int32_t r0 = 0; r0 < n_rows; r0 += f->max_batch) {

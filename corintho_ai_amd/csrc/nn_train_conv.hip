@@ -315,12 +315,12 @@ static inline int fc_bn_rpc(int R) { return 128 * ((R + 128 * FC_BN_CHUNKS - 1) 
 
 /* x0[B * 16][16] = rescnn4's input planes of states[rows[r]] (nets.rescnn4_input_planes), channels 10..15 zero */
 static void fc_planes(rt_stream_t s, const float *states, const int32_t *rows, int B, float *x0) {
-  FT_LAUNCH(fc_k_planes, (unsigned)(((long)B * 16 * FC_IN_LD + 255) / 256), 256, s, states, rows, B, x0);
+  RT_LAUNCH(fc_k_planes, (unsigned)(((long)B * 16 * FC_IN_LD + 255) / 256), 256, s, states, rows, B, x0);
 }
 
 /* wt[l][tap][co][ci] = w[first + l * stride][8 - tap][ci][co] for the n 64 -> 64 kernels: the operand of backward-data */
 static void fc_wtrans(rt_stream_t s, const float *w, int first, int stride, int n, float *wt) {
-  FT_LAUNCH(fc_k_wtrans, (n * FC_WG_FLOATS + 255) / 256, 256, s, w, first, stride, n, wt);
+  RT_LAUNCH(fc_k_wtrans, (n * FC_WG_FLOATS + 255) / 256, 256, s, w, first, stride, n, wt);
 }
 
 /* out[row][co] (+)= bias[co] + sum over taps and ci of X[row shifted by the tap][ci] W[tap][ci][co]; cin = 10 reads X
@@ -329,9 +329,9 @@ static void fc_conv3(rt_stream_t s, const float *X, int cin, const float *W, con
                      int accumulate) {
   const int grid = (B + FC_POS - 1) / FC_POS;
   if (cin == FC_C)
-    FT_LAUNCH(fc_k_conv3<FC_C>, grid, 256, s, X, W, cin, bias, out, B, accumulate);
+    RT_LAUNCH(fc_k_conv3<FC_C>, grid, 256, s, X, W, cin, bias, out, B, accumulate);
   else
-    FT_LAUNCH(fc_k_conv3<FC_IN_LD>, grid, 256, s, X, W, cin, bias, out, B, accumulate);
+    RT_LAUNCH(fc_k_conv3<FC_IN_LD>, grid, 256, s, X, W, cin, bias, out, B, accumulate);
 }
 
 /* dW[tap][ci][co] = sum over rows of X[row shifted by the tap][ci] dZ[row][co]: per-chunk partials into part
@@ -341,10 +341,10 @@ static void fc_conv3_wgrad(rt_stream_t s, const float *X, int cin, const float *
   ppc = ppc < 16 ? 16 : (ppc + 3) / 4 * 4;
   const int nchunk = (B + ppc - 1) / ppc, n = 9 * cin * FC_C;
   if (cin == FC_C)
-    FT_LAUNCH(fc_k_wgrad<FC_C>, dim3(nchunk, 3), 3 * FC_C * 4, s, X, dZ, B, ppc, cin, part);
+    RT_LAUNCH(fc_k_wgrad<FC_C>, dim3(nchunk, 3), 3 * FC_C * 4, s, X, dZ, B, ppc, cin, part);
   else
-    FT_LAUNCH(fc_k_wgrad<FC_IN_LD>, dim3(nchunk, 3), 3 * FC_IN_LD * 4, s, X, dZ, B, ppc, cin, part);
-  FT_LAUNCH(fc_k_wgrad_sum, (n + 255) / 256, 256, s, (const float *)part, nchunk, n, dW);
+    RT_LAUNCH(fc_k_wgrad<FC_IN_LD>, dim3(nchunk, 3), 3 * FC_IN_LD * 4, s, X, dZ, B, ppc, cin, part);
+  RT_LAUNCH(fc_k_wgrad_sum, (n + 255) / 256, 256, s, (const float *)part, nchunk, n, dW);
 }
 
 /* BatchNorm over the R rows of Z[R][C] (C in {64, 4, 2}), then + res (or null), then ReLU -> out.  bn = gamma, beta,
@@ -357,11 +357,11 @@ static void fc_bn_fwd(rt_stream_t s, const float *Z, const float *res, float *ou
   const float *mean = bn + 2 * C, *var = bn + 3 * C;
   if (train) {
     const int rpc = fc_bn_rpc(R), nch = (R + rpc - 1) / rpc;
-    FT_LAUNCH(fc_k_bn_part, nch, 256, s, Z, R, C, rpc, part);
-    FT_LAUNCH(fc_k_bn_final, 1, 64, s, (const float *)part, nch, R, rpc, C, stat);
+    RT_LAUNCH(fc_k_bn_part, nch, 256, s, Z, R, C, rpc, part);
+    RT_LAUNCH(fc_k_bn_final, 1, 64, s, (const float *)part, nch, R, rpc, C, stat);
     mean = stat, var = stat + 64;
   }
-  FT_LAUNCH(fc_k_bn_apply, (unsigned)((n + 4095) / 4096), 256, s, Z, res, out, n, C, bn, mean, var);
+  RT_LAUNCH(fc_k_bn_apply, (unsigned)((n + 4095) / 4096), 256, s, Z, res, out, n, C, bn, mean, var);
 }
 
 /* backward of the same: dOut is the gradient at `out`; dY = dOut where out > 0 (written back to dOut when keep: the
@@ -370,10 +370,10 @@ static void fc_bn_bwd(rt_stream_t s, float *dOut, const float *out, const float 
                       const float *stat, int keep, float *part, float *g) {
   const long n = (long)R * C;
   const int rpc = fc_bn_rpc(R), nch = (R + rpc - 1) / rpc;
-  FT_LAUNCH(fc_k_bnb_part, nch, 256, s, dOut, out, Z, R, C, rpc, stat, keep, (double *)part);
+  RT_LAUNCH(fc_k_bnb_part, nch, 256, s, dOut, out, Z, R, C, rpc, stat, keep, (double *)part);
   double *dpart = (double *)part, *fin = dpart + FC_BN_PART; /* the backward partials are float64 */
-  FT_LAUNCH(fc_k_bnb_final, 1, 64, s, (const double *)dpart, nch, C, R, g, fin);
-  FT_LAUNCH(fc_k_bnb_apply, (unsigned)((n + 4095) / 4096), 256, s, (const float *)dOut, out, Z, dZ, n, C, bn, stat,
+  RT_LAUNCH(fc_k_bnb_final, 1, 64, s, (const double *)dpart, nch, C, R, g, fin);
+  RT_LAUNCH(fc_k_bnb_apply, (unsigned)((n + 4095) / 4096), 256, s, (const float *)dOut, out, Z, dZ, n, C, bn, stat,
             (const double *)fin);
 }
 
@@ -420,7 +420,7 @@ struct FcCarver {
 struct FtResCnn : FtNet {
   const FcLayout L;
   const size_t rows; /* max_batch rounded up to whole 16-row tiles */
-  FtBuf<float> x0, act, wt, wpart, bnpart;
+  DevBuf<float> x0, act, wt, wpart, bnpart;
   /* pieces of act: activations are [rows * 16][C]; the heads' [rows * 16][4] and [rows * 16][2] are [rows][64] and
    * [rows][32] once flattened (pixel * C + channel) */
   float *Z[9], *X[5], *T[4];  /* convolution l's output before its BatchNorm; the stem's (0) and block b - 1's output;

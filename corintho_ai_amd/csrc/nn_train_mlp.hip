@@ -120,7 +120,7 @@ __global__ __launch_bounds__(1024) void ft_k_bn_bwd(const float *__restrict__ dY
 
 struct FtMlp : FtNet {
   size_t rows_ld; /* floats of one layer's activations: max_batch rounded up to whole tiles x FT_PADW */
-  FtBuf<float> x0, act, y, dy, dz;
+  DevBuf<float> x0, act, y, dy, dz;
 
   FtMlp(int max_batch, rt_stream_t s) : rows_ld((size_t)((max_batch + 15) / 16 * 16) * FT_PADW) {
     x0.alloc(rows_ld / FT_PADW * FT_IN_LD, s);
@@ -149,13 +149,13 @@ struct FtMlp : FtNet {
   static long x_ld(int l) { return l == 0 ? FT_IN_LD : FT_PADW; }
 
   void forward(const FtShared &sh, const int32_t *rows, int B, bool train) override {
-    FT_LAUNCH(ft_k_gather, (B * CA_GAME_STATE_SIZE + 255) / 256, 256, sh.s, sh.states, rows, B, x0.p);
+    RT_LAUNCH(ft_k_gather, (B * CA_GAME_STATE_SIZE + 255) / 256, 256, sh.s, sh.states, rows, B, x0.p);
     for (int l = 0; l < CO_MLP_LAYERS; ++l) {
       FtGemm a = mk(X(l), x_ld(l), 1, sh.w + ML.kernel(l), 100, 1, A(l), FT_PADW, 1, B, CO_MLP_WIDTH, ML.in_dim(l));
       a.bias = sh.w + ML.bias(l);
       a.relu = 1;
       ft_gemm(sh.s, a);
-      FT_LAUNCH(ft_k_bn_fwd, FT_PADW / 16, 1024, sh.s, (const float *)A(l), Y(l), B, (const float *)sh.w, ML.gamma(l),
+      RT_LAUNCH(ft_k_bn_fwd, FT_PADW / 16, 1024, sh.s, (const float *)A(l), Y(l), B, (const float *)sh.w, ML.gamma(l),
                 train ? 1 : 0, sh.stat + l * FT_STAT_LD);
     }
     FtGemm p = mk(Y(11), FT_PADW, 1, sh.w + ML.kp, CA_NUM_MOVES, 1, sh.h, FT_PADW, 1, B, CA_NUM_MOVES, CO_MLP_WIDTH);
@@ -181,7 +181,7 @@ struct FtMlp : FtNet {
     a.accumulate = 1;
     ft_gemm(sh.s, a);
     for (int l = CO_MLP_LAYERS - 1; l >= 0; --l) {
-      FT_LAUNCH(ft_k_bn_bwd, FT_PADW / 16, 1024, sh.s, (const float *)dy.p, (const float *)A(l), dz.p, B,
+      RT_LAUNCH(ft_k_bn_bwd, FT_PADW / 16, 1024, sh.s, (const float *)dy.p, (const float *)A(l), dz.p, B,
                 (const float *)sh.w, ML.bias(l), (const float *)(sh.stat + l * FT_STAT_LD), sh.g);
       a = mk(X(l), 1, x_ld(l), dz.p, FT_PADW, 1, sh.g + ML.kernel(l), CO_MLP_WIDTH, 1, ML.in_dim(l), CO_MLP_WIDTH, B);
       a.kchunk = kch, a.c_split = ML.nw;

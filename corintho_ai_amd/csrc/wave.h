@@ -27,11 +27,9 @@
 
 #define CO_WAVE 64
 
-/* Simulations of a step selected together by the search kernel (mcts.h co_search_rows): 4 = one per row of the
- * wavefront, 1 = one after another (rounds 1-4). */
-#ifndef CO_SB
+/* Simulations of a step selected together by the search kernel (mcts.h co_search_rows): one per row of the wavefront
+ * (rounds 1-4: one after another, what co_search still does for a simulation that ends its group). */
 #define CO_SB 4
-#endif
 
 #ifdef CO_EMU
 // ------------------------------------------------------------------ emulation

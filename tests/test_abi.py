@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 from corintho_ai_amd import _lib
+from tests.engines import cdll
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -92,3 +93,25 @@ def test_cpp_tourney_wrapper_compiles_and_links(tmp_path):
     subprocess.check_call(["g++", "-std=c++17", "-o", str(exe), str(src), "-L" + os.path.dirname(_lib.LIB_PATH),
                            "-lcorintho_hip", "-Wl,-rpath," + os.path.dirname(_lib.LIB_PATH)])
     subprocess.check_call([str(exe)])
+
+
+# one entry point of each family; the emulation build has no fitter
+_FAMILIES = ["ca_trainer_num_requests", "ca_trainer_stats", "ca_tourney_all_done"]
+_NULL_CASES = [pytest.param("emu", e, id="emu-" + e) for e in _FAMILIES] + [
+    pytest.param("hip", e, id="hip-" + e, marks=pytest.mark.gpu) for e in _FAMILIES + ["ca_fitter_data_info"]]
+
+
+@pytest.mark.parametrize("engine,entry", _NULL_CASES)
+def test_a_null_handle_is_an_argument_error(engine, entry):
+    """every entry point on a handle goes through one guard (csrc/host.h co_guard): a null trainer, tourney or fitter is
+    CA_ERR_ARG with a message, not a crash.  No kernel runs."""
+    L = cdll(engine)
+    i32 = C.c_int32()
+    rc = {
+        "ca_trainer_num_requests": lambda: L.ca_trainer_num_requests(None, -1, C.byref(i32)),
+        "ca_trainer_stats": lambda: L.ca_trainer_stats(None, C.byref(_lib.CaStats())),
+        "ca_tourney_all_done": lambda: L.ca_tourney_all_done(None, C.byref(i32)),
+        "ca_fitter_data_info": lambda: L.ca_fitter_data_info(None, C.byref(i32), C.byref(C.c_int32())),
+    }[entry]()
+    assert rc == -1  # CA_ERR_ARG
+    assert L.ca_last_error()

@@ -41,6 +41,7 @@ for spec in libs:
         del os.environ[kv.split("=")[0]]
 acc = [[0.0, 0.0, 0.0] for _ in libs]
 extra = ["" for _ in libs]
+walls = [[] for _ in libs]
 for r in range(reps):
     for i, t in enumerate(ts):
         t.reset(100 + r)
@@ -49,10 +50,12 @@ for r in range(reps):
         dt = time.perf_counter() - t0
         st = t.stats()
         acc[i][0] += dt * 1e3
+        walls[i].append(dt * 1e3)
         acc[i][1] += st["mcts_ms"]
         acc[i][2] += st["nn_ms"]
         acc[i].append(st.get("nn_rows_evaluated", 0) / max(st.get("nn_rows", 1), 1))
         extra[i] = "iterations %d, steps cut %d, last budget %d" % (st["iterations"], st.get("steps_cut", 0), st.get("step_budget_last", 0))
-for path, a, x in zip(libs, acc, extra):
+for path, a, x, wl in zip(libs, acc, extra, walls):
     print("%-44s wall %.1f ms  search %.1f ms  network %.1f ms   (%d games, %s, %d pool(s), mean of %d; rows evaluated %.4f of the requested; %s)" %
           (os.path.basename(path), a[0] / reps, a[1] / reps, a[2] / reps, G, net, pools, reps, sum(a[3:]) / max(len(a[3:]), 1), x))
+    print("%-44s wall by repetition: %s ms" % ("", " ".join("%.1f" % v for v in wl)))

@@ -26,7 +26,7 @@ ALL = ("cfg1", "cfg4", "cfg5", "tourney", "compat")
 
 def rooflines(st, wall_s, net_name):
     """roofline objects of a finished run from the engine's own statistics: device time per kernel family is estimated
-    from the HIP-event durations of the timed launches (engine.hip run_pools), as in bench.py"""
+    from the HIP-event durations of the timed launches (pools.h FusedRun), as in bench.py"""
     flop = nets.rescnn4_flop_per_row()
     rows = st.get("nn_rows_evaluated", 0) or st.get("evals", 0)
     timed = st["nn_ms"] > 0 and st["mcts_ms"] > 0  # (the tournament's fused loop carries no events: wall level only)

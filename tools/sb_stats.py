@@ -14,9 +14,9 @@ sys.path.insert(0, ROOT)
 LIB = "/tmp/libcorintho_emu_sbstats.so"
 
 
-def build(sb):
+def build():
     csrc = os.path.join(ROOT, "corintho_ai_amd", "csrc")
-    cmd = ["g++", "-O2", "-std=c++17", "-DCO_EMU", "-DCO_SB_STATS", "-DCO_SB=%d" % sb, "-ffp-contract=off", "-fno-fast-math",
+    cmd = ["g++", "-O2", "-std=c++17", "-DCO_EMU", "-DCO_SB_STATS", "-ffp-contract=off", "-fno-fast-math",
            "-fopenmp", "-fPIC", "-Wno-unknown-pragmas", "-shared", "-o", LIB, "-x", "c++", os.path.join(csrc, "engine.hip"),
            "-x", "c++", os.path.join(ROOT, "tests", "emu", "nn_emu.cpp"), "-lm"]
     subprocess.check_call(cmd)
@@ -26,8 +26,7 @@ def main():
     games = int(sys.argv[1]) if len(sys.argv) > 1 else 64
     sims = int(sys.argv[2]) if len(sys.argv) > 2 else 400
     net = sys.argv[3] if len(sys.argv) > 3 else "mlp"
-    sb = int(sys.argv[4]) if len(sys.argv) > 4 else 4
-    build(sb)
+    build()
     os.environ["CO_EMU_LIB"] = LIB
     import numpy as np
 
@@ -47,7 +46,7 @@ def main():
     s = [int(L.co_emu_sb_stats()[i]) for i in range(32)]
     st = t.stats()
     tot = s[2] + s[8]
-    print("games %d, sims/move %d, net %s, CO_SB %d: %d simulations (engine counts %d)" % (games, sims, net, sb, tot, st["searches"]))
+    print("games %d, sims/move %d, net %s: %d simulations (engine counts %d)" % (games, sims, net, tot, st["searches"]))
     print("  groups %d, asked %d, committed in groups %d (%.1f %%), sequential %d (%.1f %%)" %
           (s[0], s[1], s[2], 100.0 * s[2] / tot, s[8], 100.0 * s[8] / tot))
     print("  group ended by: nothing searchable %d, terminal child %d, wide node %d, too deep %d, terminal leaf %d" %
@@ -64,7 +63,7 @@ def main():
         if g:
             print("    plies %2d-%2d: %7d groups, %.2f committed, %4.1f %% terminal, %4.1f %% sequential, %d sequential simulations" %
                   (4 * b, 4 * b + 3, g, pl[8 * b + 2] / g, 100.0 * pl[8 * b + 3] / g, 100.0 * pl[8 * b + 4] / g, pl[8 * b + 6]))
-    print("  groups by simulations committed: " + ", ".join("%d: %d" % (k, s[12 + k]) for k in range(sb + 1)))
+    print("  groups by simulations committed: " + ", ".join("%d: %d" % (k, s[12 + k]) for k in range(5)))  # CO_SB = 4 (wave.h)
 
 
 if __name__ == "__main__":
