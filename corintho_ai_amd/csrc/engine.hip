@@ -89,6 +89,13 @@ struct ca_trainer {
     return nets[0] && nets[0]->flop_per_row() >= 1e6;
   }
 
+  /* host-driven protocol with the evaluation cache (ca_trainer_set_host_cache): fused training on one pool, stepped one
+   * iteration per doIteration, the caller as its network (pools.h HostNet) */
+  bool host_cache = false;
+  int host_cache_log2 = -1; /* the table: 0 sized automatically, else 2^n entries */
+  int32_t host_rows = 0;    /* rows handed to the caller by the last iteration: the cache's count word */
+  HostNet host_net;
+
   /* tournament mode (ca_tourney): per-match players, per-match seeds, the reference's read offsets */
   bool tourney = false, exact_offsets = false;
   std::vector<PlayerCfg> host_pcfg; /* [2G] */
@@ -320,6 +327,7 @@ struct ca_trainer {
     trainer_iteration = 0;
     invalidate();
     last_total = 0;
+    host_rows = 0;
     finished = false;
     const int64_t cache_clears = stats.cache_clears; /* (counted over the trainer's life) */
     stats = RunStats();
@@ -557,6 +565,7 @@ struct ca_trainer {
   }
   bool do_iteration(const float *evals, const float *probs, int to_play) {
     need_positions();
+    if (host_cache) return host_cache_iteration(evals, probs, to_play);
     if (iterations > 0) {
       pack(to_play); /* offsets the reference computes at entry */
       if (last_total > 0) {
@@ -576,16 +585,103 @@ struct ca_trainer {
 
   /* the requests of model `to_play` (-1: every game; a tournament's model id) */
   int32_t num_requests(int to_play) {
+    if (host_cache) return host_cache_all_games(to_play), host_rows;
     pack(to_play);
     return last_total;
   }
 
   void write_requests(float *out, int to_play) {
+    if (host_cache) {
+      host_cache_all_games(to_play);
+      /* HostNet::forward has laid the rows out as the caller's array holds them, and the iteration's run has drained */
+      rt_d2h(out, nn_in70.p, (size_t)host_rows * CO_GAME_STATE_SIZE * 4, stream);
+      rt_sync(stream);
+      return;
+    }
     pack(to_play);
     if (last_total == 0) return;
     /* K4 has laid the rows out as the caller's array holds them: one copy, straight into it */
     rt_d2h(out, nn_in70.p, (size_t)last_total * CO_GAME_STATE_SIZE * 4, stream);
     rt_sync(stream);
+  }
+
+  /* ---- the host-driven protocol with the evaluation cache ---- */
+  /* log2_entries < 0 off, 0 a table sized automatically, 6..30 2^n entries; at a generation boundary only */
+  void set_host_cache(int32_t log2_entries) {
+    if ((log2_entries >= 1 && log2_entries <= 5) || log2_entries > 30)
+      throw CaError(CA_ERR_ARG, "ca_trainer_set_host_cache: log2_entries must be negative (off), 0 (automatic) or 6..30, not " +
+                                        std::to_string(log2_entries));
+    const bool on = log2_entries >= 0;
+    if (on && !self_play_training()) /* (as use_cache(): the table's keys are positions that self-play reached) */
+      throw CaError(CA_ERR_STATE, "ca_trainer_set_host_cache: the evaluation cache serves self-play training only, not a testing, "
+                                  "analysis or tournament trainer");
+    if (!on && !host_cache) return;
+    if (iterations != 0)
+      throw CaError(CA_ERR_STATE, "ca_trainer_set_host_cache: in the middle of a generation; switch before the first "
+                                  "ca_trainer_do_iteration or after ca_trainer_reset");
+    /* the pool and its table are built for this mode (and, switched off, rebuilt by the next ca_trainer_run for its own) */
+    fused.release();
+    host_cache = on;
+    host_cache_log2 = log2_entries;
+    fused.host_stepped = on;
+    host_rows = 0;
+    if (!on) return;
+    if (!pend_key.p) { /* (a trainer created with ca_config.eval_cache < 0 has none yet) */
+      pend_key.alloc((size_t)R * spe, stream);
+      pend_src.alloc((size_t)R * spe, stream);
+      P.pend_key = pend_key.p;
+      P.pend_src = pend_src.p;
+      rt_sync(stream);
+    }
+    fused.spe = spe;
+    fused.create(1, R, log2_entries);
+    fused.cache_clean = false; /* (the first iteration starts the generation: counters cleared with the table) */
+    /* the caller's rows and answers pass through the plain protocol's own staging arrays, which this mode leaves idle */
+    host_net.rows_cap = (size_t)R * spe;
+    host_net.rows70 = nn_in70.p;
+    host_net.ev_in = nn_eval.p;
+    host_net.pr_in = nn_probs.p;
+    host_net.d_ctl = ctl.p;
+    host_net.h_ctl = &h_ctl[0];
+    host_net.out_idx = nullptr;
+  }
+  void host_cache_all_games(int to_play) const {
+    if (to_play != -1) throw CaError(CA_ERR_ARG, "host-driven protocol with the evaluation cache: to_play must be -1 (training)");
+  }
+  /* Trainer::doIteration with the cache: the answers to the rows handed out go where a network kernel would have written
+   * them, then one iteration of fused training on one pool -- the search launch resolves its request rows against the
+   * table and HostNet gathers the ones left over.  No step budget and no deferred hand-over: either would add round trips. */
+  bool host_cache_iteration(const float *evals, const float *probs, int to_play) {
+    host_cache_all_games(to_play);
+    rt_stream_t st = fused.pools[0].st;
+    if (host_rows > 0) {
+      if (!evals || !probs) throw CaError(CA_ERR_ARG, "doIteration: null evaluations/probabilities");
+      host_net.receive(evals, probs, host_rows, st);
+      host_rows = 0;
+    }
+    EngineParams e = params(-1);
+    e.step_budget = 0;
+    e.step_budget_k16 = 0;
+    host_net.scan_params = e;
+    const int64_t n = fused.run(e, &host_net, 1, host_cache_log2, iterations > 0, 1);
+    trainer_iteration += (int32_t)n;
+    iterations += n;
+    invalidate();
+    stats.estimate_device_times(true);
+    if (!fused.failure.empty()) throw CaError(CA_ERR_ENGINE, fused.failure);
+    /* what the run's drain has brought: the protocol's flags and the pool's words of this iteration */
+    last_total = h_ctl[0];
+    finished = h_ctl[1] != 0;
+    any_error = h_ctl[2] != 0;
+    scan_valid_for = -1;
+    scan_valid = true;
+    const Pool &q = fused.pools[0];
+    host_rows = (int32_t)std::min<unsigned long long>(q.word[2] & 0xFFFFFFFFull, (unsigned long long)R * spe);
+    stats.nn_rows += (int64_t)(q.word[0] & 0xFFFFFFFFull); /* rows the games requested */
+    stats.nn_rows_evaluated += host_rows;                   /* ... and the ones the caller gets */
+    check_errors();
+    if (finished) maybe_write_logs();
+    return finished;
   }
 
   /* ---- Tourney (tourney.cpp) on the same pool: one match per game slot ---- */
@@ -854,7 +950,7 @@ struct ca_trainer {
       throw CaError(CA_ERR_ARG, e.what());
     }
     if (!fresh) throw CaError(CA_ERR_ARG, "unknown net kind or bad weight count");
-    if (slot == 0 && !fused.pools.empty()) {
+    if (slot == 0 && !fused.pools.empty() && !host_cache) { /* (host_cache: the pool and its table are that mode's, whatever the network) */
       /* Does the new network change whether fused training keeps an evaluation cache?  The tables are part of the
        * pools, and in the middle of a generation the pending leaves point into them (pend_src): refuse that. */
       std::unique_ptr<CoNet> old = std::move(nets[0]);
@@ -1032,6 +1128,9 @@ struct ca_trainer {
 
   bool run(int64_t max_iterations) {
     need_positions();
+    if (host_cache)
+      throw CaError(CA_ERR_STATE, "ca_trainer_run: the host-driven protocol drives this trainer's generations with the evaluation "
+                                  "cache; switch it off first (ca_trainer_set_host_cache with a negative size)");
     if (!nets[0]) throw CaError(CA_ERR_STATE, "ca_trainer_run: no network set (ca_trainer_set_net)");
     if (cfg.testing && !cfg.analyse && !nets[1]) throw CaError(CA_ERR_STATE, "arena mode needs both networks");
     if (!cfg.testing || cfg.analyse) { /* one network, every slot active: self-play training, or N position searches */
@@ -1305,6 +1404,9 @@ extern "C" int ca_trainer_do_iteration(ca_trainer *t, const float *ev, const flo
 }
 extern "C" int ca_trainer_set_net(ca_trainer *t, int slot, int kind, const float *w, size_t n) {
   return co_guard(t, [&] { t->set_net(slot, kind, w, n); });
+}
+extern "C" int ca_trainer_set_host_cache(ca_trainer *t, int32_t log2_entries) {
+  return co_guard(t, [&] { t->set_host_cache(log2_entries); });
 }
 extern "C" int ca_trainer_run(ca_trainer *t, int64_t max_iterations, int32_t *all_done) {
   return co_guard(t, [&] { *all_done = t->run(max_iterations) ? 1 : 0; });

@@ -160,6 +160,38 @@ CO_KERNEL co_k_expand_rows(const float *in70, float *out80, int rows, int nblock
   }
 }
 
+/* ---- host-driven protocol with the evaluation cache (pools.h HostNet): the rows the cache could not resolve travel to
+ * the caller and its answers come back.  One thread per float, so a wavefront reads and writes 64 consecutive floats;
+ * no LDS, no atomics.  Float e belongs to wavefront e / 64 of the launch: */
+#define CO_HOST_ROWS_FLOAT ((CO_BLOCK_IDX * CO_WAVES_PER_BLOCK + CO_WAVE_IN_BLOCK) * CO_WAVE + lane)
+/* out70[r][0..70) = request row in_idx[r] of `req` for r < count[0], the cache's count word of this iteration (and
+ * r < cap_rows, the rows out70 holds: the launch is sized by them); threads beyond leave */
+CO_KERNEL co_k_host_rows_out(const float *req, const int32_t *in_idx, const uint32_t *count, int cap_rows, float *out70) {
+  const uint32_t have = count[0];
+  const int total = (int)(have < (uint32_t)cap_rows ? have : (uint32_t)cap_rows) * CO_GAME_STATE_SIZE;
+  FOR_LANES {
+    const int e = CO_HOST_ROWS_FLOAT;
+    if (e < total) {
+      const int r = e / CO_GAME_STATE_SIZE, c = e - r * CO_GAME_STATE_SIZE;
+      out70[e] = req[(size_t)in_idx[r] * CO_STATE_STRIDE + c];
+    }
+  }
+}
+/* evals[r], probs[r][96] -> element out_idx[r] of the cache's value array {value, 3 pad, 96 priors}, r < rows: where a
+ * network kernel writes through CoNetIO */
+CO_KERNEL co_k_host_rows_in(const float *evals, const float *probs, const int32_t *out_idx, int rows, float *val) {
+  const int total = rows * (1 + CO_NUM_MOVES);
+  FOR_LANES {
+    const int e = CO_HOST_ROWS_FLOAT;
+    if (e < total) {
+      const int r = e / (1 + CO_NUM_MOVES), c = e - r * (1 + CO_NUM_MOVES);
+      float *dst = val + (size_t)out_idx[r] * CO_CACHE_VAL_FLOATS;
+      if (c == 0) dst[0] = evals[r];
+      else dst[4 + c - 1] = probs[(size_t)r * CO_NUM_MOVES + c - 1];
+    }
+  }
+}
+
 /* one wavefront per GAME (not slot); sample_offset[g] = number of plies of games < g, meta[g] = plies | result << 8 */
 CO_KERNEL co_k_write_samples(EngineParams P, int n_games, const int32_t *sample_offset, const int32_t *meta, float *game_states,
                              float *eval_samples, float *prob_samples) {

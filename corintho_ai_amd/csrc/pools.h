@@ -147,6 +147,51 @@ struct Pool {
   }
 };
 
+/* The "network" of the host-driven protocol with the evaluation cache (ca_trainer_set_host_cache): its forward pass is
+ * the round trip to the caller.  forward() -- FusedRun queues it behind the search launch like any network -- gathers the
+ * rows the cache could not resolve into a dense [n][70] array for Trainer::writeRequests and has the protocol's flags
+ * (co_k_scan: all done, any error) copied to the host with them; receive(), queued in front of the NEXT search launch,
+ * scatters the caller's answers to the elements of the cache's value array a network kernel would have written. */
+struct HostNet : CoNet {
+  /* the trainer's, set once */
+  size_t rows_cap = 0;
+  float *rows70 = nullptr;               /* [rows_cap][70] the rows to hand out */
+  float *ev_in = nullptr, *pr_in = nullptr; /* [rows_cap], [rows_cap][96] the caller's answers on the device */
+  int32_t *d_ctl = nullptr, *h_ctl = nullptr; /* EngineParams::ctl and its page-locked copy */
+  EngineParams scan_params = {};         /* the games, for co_k_scan */
+  /* of the last forward(): where the answers go */
+  const int32_t *out_idx = nullptr;
+  float *val = nullptr;
+
+  /* one thread per float */
+  static int blocks(size_t floats) { return (int)((floats + CO_WAVE * CO_WAVES_PER_BLOCK - 1) / (CO_WAVE * CO_WAVES_PER_BLOCK)); }
+  size_t max_rows() const override { return rows_cap; }
+  int kind() const override { return 0; }
+  double flop_per_row() const override { return 0.0; }
+  void forward(const float *d_in, int32_t cap, const int32_t *d_rows, float *d_eval, float *, rt_stream_t s,
+               const CoNetIO &io = CoNetIO()) override {
+    if (!io.in_idx || !io.out_idx || io.eval_stride != CO_CACHE_VAL_FLOATS || io.probs_stride != CO_CACHE_VAL_FLOATS)
+      throw CaError(CA_ERR_STATE, "HostNet: rows that did not come through the evaluation cache");
+    if (cap < 0 || (size_t)cap > rows_cap) cap = (int32_t)rows_cap;
+    out_idx = io.out_idx;
+    val = d_eval;
+    if (cap > 0)
+      RT_LAUNCH(co_k_host_rows_out, blocks((size_t)cap * CO_GAME_STATE_SIZE), CO_WAVE * CO_WAVES_PER_BLOCK, s, d_in, io.in_idx,
+                (const uint32_t *)d_rows, (int)cap, rows70);
+    RT_LAUNCH(co_k_scan, 1, CO_WAVE, s, scan_params);
+    rt_d2h(h_ctl, d_ctl, 16, s);
+  }
+  /* evals[n], probs[n][96]: the answers to the n rows of the last forward(), in its order */
+  void receive(const float *evals, const float *probs, int32_t n, rt_stream_t s) {
+    if (n <= 0) return;
+    if ((size_t)n > rows_cap || !out_idx) throw CaError(CA_ERR_STATE, "HostNet: answers to rows that were not handed out");
+    rt_h2d(ev_in, evals, (size_t)n * 4, s);
+    rt_h2d(pr_in, probs, (size_t)n * CO_NUM_MOVES * 4, s);
+    RT_LAUNCH(co_k_host_rows_in, blocks((size_t)n * (1 + CO_NUM_MOVES)), CO_WAVE * CO_WAVES_PER_BLOCK, s, (const float *)ev_in,
+              (const float *)pr_in, out_idx, (int)n, val);
+  }
+};
+
 /* Fused training as independent pools of games on separate streams:
  * every pool runs the loop of main.pyx:142-168 on its own slice of the game arrays and of
  * the batch buffers; the GPU overlaps one pool's search kernel with another's network
@@ -158,6 +203,7 @@ struct FusedRun {
   CacheTable table; /* fused training with the evaluation cache (entries 0: none) */
   std::vector<Pool> pools;
   bool cache_clean = false; /* the pools' tables hold nothing of an earlier generation */
+  bool host_stepped = false; /* the caller evaluates the rows (HostNet): one pool, one iteration per run */
 
   /* what the trainer hands a run */
   EngineParams run_params;          /* its parameters for every game, fused_pack set (the iteration: set per launch) */
@@ -248,7 +294,9 @@ struct FusedRun {
       stats->pack_timed_ms += rt_event_elapsed_ms(q.ev[parity][1], q.ev[parity][2]); /* cache probe (nothing without a cache) */
       stats->nn_timed_ms += rt_event_elapsed_ms(q.ev[parity][2], q.ev[parity][3]);
       stats->nn_timed_rows += (int64_t)evaluated; /* rows the network kernel worked on */
-      q.c_inserted_est += (double)evaluated * poll; /* every evaluated row takes a table entry */
+      /* every evaluated row takes a table entry; the timed iteration stands for its window, whose length is what was
+       * queued in it (a full window: poll; a run capped at one iteration, HostNet: that one) */
+      q.c_inserted_est += (double)evaluated * q.launched[parity];
       ++stats->timed_launches;
       q.timed[parity] = 0;
     }
@@ -301,7 +349,8 @@ struct FusedRun {
      * has thinned out, an iteration is as long as its slowest wave anyway and the number of
      * iterations of the longest game is what the generation waits for.  Per-game results do
      * not depend on the choice. */
-    pp.defer_handover = q.running * 2 > q.n ? 1 : 0;
+    /* (stepped by the host, HostNet: an iteration more is a round trip to the caller more -- never deferred) */
+    pp.defer_handover = !host_stepped && q.running * 2 > q.n ? 1 : 0;
     pp.pool_lo = q.lo;
     pp.pool_n = q.n;
     pp.pool_row_base = q.row_base;

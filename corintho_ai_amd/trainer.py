@@ -134,6 +134,14 @@ class Trainer:
         _lib.check(self._L, self._L.ca_trainer_run(self._t, max_iterations, C.byref(done)))
         return bool(done.value)
 
+    def set_host_cache(self, on):
+        """The reference protocol with the evaluation cache (training only, at a generation boundary): num_requests /
+        writeRequests then hand out only the rows whose position has no stored evaluation in this generation, in
+        unspecified order, and doIteration takes the answers to exactly those rows.  `on`: True (table sized
+        automatically), False / None (off) or a table size log2 in 6..30.  The caller's network must give a row the same
+        outputs in whatever batch it stands; num_requests() == 0 with games still running means "all served"."""
+        _lib.check(self._L, self._L.ca_trainer_set_host_cache(self._t, _eval_cache_cfg(on)))
+
     def pin(self, *arrays):
         """Page-lock caller arrays (the evals / probs / game_states of the play loop, main.pyx:132-134) for
         direct DMA.  They must outlive the trainer or be passed to unpin() first.  -> all pinned?"""

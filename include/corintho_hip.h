@@ -130,6 +130,28 @@ int ca_trainer_write_scores(ca_trainer *t, const char *file);
 int ca_trainer_do_iteration(ca_trainer *t, const float *evaluations, const float *probabilities, int to_play,
                             int32_t *all_done);
 
+/* Host-driven protocol with the evaluation cache (training mode only).  log2_entries: 0 = table sized
+ * automatically (as ca_config.eval_cache = 0 sizes it), 6..30 = 2^n entries, negative = off (the default).
+ * Allowed only at a generation boundary: before the first ca_trainer_do_iteration, or after ca_trainer_reset.
+ *
+ * With it on the three protocol calls above keep their signatures and hand the caller only the request rows whose
+ * position has no stored evaluation in this generation (to_play must be -1):
+ *   ca_trainer_num_requests   n = the positions to evaluate: the request rows the cache could resolve neither to an
+ *                             earlier row of this generation nor to another row of this batch.  n may be 0 while games
+ *                             are still running (every row was served from the table): that is not the reference's
+ *                             "No requests during training" condition, just call ca_trainer_do_iteration again.
+ *   ca_trainer_write_requests writes those n rows, [n][70], densely.  Their ORDER IS UNSPECIFIED: a game reserves its
+ *                             rows with an atomic, so it is not the reference's game order and may differ between runs.
+ *   ca_trainer_do_iteration   evaluations[n], probabilities[n][96] answer exactly those rows in that order.
+ * all_done, num_samples, write_samples, score, write_scores, the game logs and the traces are unchanged.
+ * PRECONDITION: the caller's network gives a row the same outputs in whatever batch it stands.  Then every game's
+ * results equal the plain protocol's bit for bit; a network that is not batch-invariant gets "evaluated once, reused".
+ * The number of iterations of a generation may differ from the plain protocol's.  ca_stats: nn_rows = rows the games
+ * requested, nn_rows_evaluated = rows handed to the caller, iterations = ca_trainer_do_iteration calls.
+ * CA_ERR_STATE: a testing, analysis or tournament trainer; switching in mid-generation; ca_trainer_run while it is on.
+ * CA_ERR_ARG: log2_entries in 1..5 or above 30; to_play other than -1 in the three calls while it is on. */
+int ca_trainer_set_host_cache(ca_trainer *t, int32_t log2_entries);
+
 /* Optional, for the reference protocol above: page-lock a caller-owned array (the three arrays the
  * reference's play loop allocates once and passes to every call, main.pyx:132-134) so that the
  * per-iteration copies from / to it are direct DMA at PCIe speed instead of staged copies from
