@@ -13,6 +13,9 @@ f32p = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int32)
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
+# ca_net_fn: int fn(void *user, int32_t row0, int32_t cap_rows, const int32_t *d_rows, void *stream)
+NET_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p)
+CA_ERR_CALLBACK = -6
 
 
 class CaConfig(C.Structure):
@@ -83,7 +86,10 @@ EXPORTS = [
     "ca_fitter_get_optimizer", "ca_fitter_set_data", "ca_fitter_train", "ca_fitter_evaluate", "ca_fitter_gradients",
     "ca_trainer_device", "ca_fitter_clear_data", "ca_fitter_add_samples", "ca_fitter_add_device_samples",
     "ca_fitter_add_trainer_samples", "ca_fitter_drop_samples", "ca_fitter_data_info", "ca_fitter_fetch_rows",
+    "ca_trainer_request_rows", "ca_trainer_set_net_fn", "ca_tourney_set_net_fn", "ca_net_create", "ca_net_forward_device",
+    "ca_net_destroy",
 ]
+NET_FN_EXPORTS = EXPORTS[-6:]  # the caller-supplied network: set_net_fn, ca_net_*
 
 
 def declare(L):
@@ -145,6 +151,15 @@ def declare(L):
     L.ca_tourney_match_score.argtypes = [vp, C.c_int32, f32p]
     L.ca_tourney_trace.argtypes = [vp, C.c_int32, i32p, C.c_int32, i32p]
     L.ca_tourney_stats.argtypes = [vp, C.POINTER(CaStats)]
+    net_fn = hasattr(L, "ca_trainer_set_net_fn")  # an earlier build of the library (tools/ab.py compares against them) has none
+    if net_fn:
+        L.ca_trainer_request_rows.argtypes = [vp, i32p]
+        L.ca_trainer_set_net_fn.argtypes = [vp, C.c_int, NET_FN, vp, vp, vp, vp, C.c_int32, C.c_double]
+        L.ca_tourney_set_net_fn.argtypes = [vp, C.c_int32, NET_FN, vp, vp, vp, vp, C.c_int32, C.c_double]
+        L.ca_net_create.argtypes = [C.c_int, C.c_int, f32p, C.c_size_t, C.c_int32, C.POINTER(vp)]
+        L.ca_net_forward_device.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp]
+        L.ca_net_destroy.argtypes = [vp]
+        L.ca_net_destroy.restype = None
     f64p = C.POINTER(C.c_double)
     fitter = hasattr(L, "ca_fitter_create")  # the emulation build of the engine (tests/emu) has no training kernels
     if fitter:
@@ -152,8 +167,10 @@ def declare(L):
     for name in EXPORTS:
         if name.startswith("ca_fitter_") and not fitter:
             continue
+        if name in NET_FN_EXPORTS and not net_fn:
+            continue
         fn = getattr(L, name)
-        if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy"):
+        if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy", "ca_net_destroy"):
             fn.restype = C.c_int
     return L
 
@@ -204,3 +221,34 @@ def check(L, rc):
     if rc != 0:
         msg = L.ca_last_error()
         raise EngineError("corintho_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
+
+
+class NetCallback:
+    """A Python function fn(row0, cap_rows, d_rows_ptr, stream_ptr) as a ca_net_fn.  Whatever fn raises is kept in
+    `error` and reported to the library as a failure (return 1); the object must live as long as the slot it serves."""
+
+    def __init__(self, fn):
+        self.fn = fn
+        self.error = None
+
+        def call(_user, row0, cap_rows, d_rows, stream):
+            try:
+                fn(row0, cap_rows, d_rows or 0, stream or 0)
+                return 0
+            except BaseException as e:  # noqa: B902 -- nothing may unwind through the C frames above
+                self.error = e
+                return 1
+
+        self.c = NET_FN(call)
+
+
+def check_callbacks(L, rc, callbacks):
+    """check() for a call that may have run caller-supplied network functions: CA_ERR_CALLBACK re-raises what the
+    function raised, chained to the library's error"""
+    if rc == CA_ERR_CALLBACK:
+        for cb in callbacks:
+            if cb.error is not None:
+                err, cb.error = cb.error, None
+                msg = L.ca_last_error()
+                raise err from EngineError("corintho_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
+    check(L, rc)

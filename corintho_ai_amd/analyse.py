@@ -23,6 +23,7 @@ class Analyser:
         b = np.ascontiguousarray(boards, dtype=np.int32).reshape(-1, 64)
         self.n = b.shape[0]
         self.searches_per_eval = searches_per_eval
+        self.device = device
         self._t = T.Trainer(self.n, "", 0, max_searches, searches_per_eval, c_puct, epsilon, 0, 1, True, device=device,
                             stagger=False, arena_units=arena_units, analyse=True, _cdll=_cdll)
         self._t.set_positions(b, to_play, pieces, seeds)
@@ -40,6 +41,13 @@ class Analyser:
     # fused
     def set_net(self, kind, weights):
         self._t.set_net(kind, weights)
+
+    def request_rows(self):
+        return self._t.request_rows()
+
+    def set_net_fn(self, fn, d_states_ptr, d_evals_ptr, d_probs_ptr, max_rows, flop_per_row=0.0):
+        """your own network inside run() (Trainer.set_net_fn)"""
+        self._t.set_net_fn(fn, d_states_ptr, d_evals_ptr, d_probs_ptr, max_rows, 0, flop_per_row)
 
     def run(self, max_iterations=0):
         return self._t.run(max_iterations)

@@ -77,6 +77,8 @@ struct ca_trainer {
   bool host_games_valid = false;
   /* fused mode */
   std::unique_ptr<CoNet> nets[2];
+  bool in_callback = false;     /* inside a caller-supplied network function (ExternalNet): entry points are refused (host.h co_guard) */
+  bool callback_failed = false; /* ... and one returned non-zero: the generation is unusable until ca_trainer_reset */
   RunStats stats;
   FusedRun fused; /* fused training: the pools, their table and the run (pools.h) */
   /* the evaluation cache serves fused training (and fused analysis): one network, rows packed by the search kernel */
@@ -333,6 +335,9 @@ struct ca_trainer {
     stats = RunStats();
     stats.cache_clears = cache_clears;
     fused.cache_clean = false; /* the next run empties the tables before the first iteration of the new generation */
+    callback_failed = false;
+    for (auto &n : nets)
+      if (n) n->clear_failure();
     if (logbuf.p) {
       rt_memset(logbuf.p, 0, (size_t)num_logged * CO_LOG_CAP * 4, stream);
       rt_sync(stream);
@@ -565,6 +570,7 @@ struct ca_trainer {
   }
   bool do_iteration(const float *evals, const float *probs, int to_play) {
     need_positions();
+    need_no_failed_callback("ca_trainer_do_iteration");
     if (host_cache) return host_cache_iteration(evals, probs, to_play);
     if (iterations > 0) {
       pack(to_play); /* offsets the reference computes at entry */
@@ -726,6 +732,11 @@ struct ca_trainer {
     rt_d2h(&d, all_done.p, 4, stream);
     rt_sync(stream);
     return d != 0;
+  }
+  /* everything queued on the trainer's stream has run; what the host knew of the games is stale */
+  void drain() {
+    rt_sync(stream);
+    invalidate();
   }
   /* ca_tourney::run is over: the rounds were queued without a look at the games */
   void tourney_rounds_done() {
@@ -950,6 +961,24 @@ struct ca_trainer {
       throw CaError(CA_ERR_ARG, e.what());
     }
     if (!fresh) throw CaError(CA_ERR_ARG, "unknown net kind or bad weight count");
+    install_net(slot, std::move(fresh), "ca_trainer_set_net");
+  }
+
+  /* the caller's own network as slot `slot` (pools.h ExternalNet) */
+  void set_net_fn(int slot, ca_net_fn fn, void *user, float *d_states, float *d_evals, float *d_probs, int32_t max_rows,
+                  double flop_per_row) {
+    if (slot < 0 || slot > 1) throw CaError(CA_ERR_ARG, "net slot must be 0 or 1");
+    if (!fn || !d_states || !d_evals || !d_probs) throw CaError(CA_ERR_ARG, "ca_trainer_set_net_fn: null function or buffer");
+    if (max_rows < R * spe)
+      throw CaError(CA_ERR_ARG, "ca_trainer_set_net_fn: buffers of " + std::to_string(max_rows) + " rows, this trainer asks for up to " +
+                                        std::to_string(R * spe) + " (ca_trainer_request_rows)");
+    if (!(flop_per_row >= 0.0)) throw CaError(CA_ERR_ARG, "ca_trainer_set_net_fn: flop_per_row must be 0 (unknown) or positive");
+    install_net(slot, std::make_unique<ExternalNet>(fn, user, d_states, d_evals, d_probs, (size_t)max_rows, flop_per_row, &in_callback),
+                "ca_trainer_set_net_fn");
+  }
+
+  /* a new network takes its slot: the one path of set_net and set_net_fn */
+  void install_net(int slot, std::unique_ptr<CoNet> fresh, const char *who) {
     if (slot == 0 && !fused.pools.empty() && !host_cache) { /* (host_cache: the pool and its table are that mode's, whatever the network) */
       /* Does the new network change whether fused training keeps an evaluation cache?  The tables are part of the
        * pools, and in the middle of a generation the pending leaves point into them (pend_src): refuse that. */
@@ -958,7 +987,7 @@ struct ca_trainer {
       const bool toggles = (fused.table.entries != 0) != use_cache();
       if (toggles && iterations > 0 && !finished) {
         nets[0] = std::move(old);
-        throw CaError(CA_ERR_STATE, "ca_trainer_set_net: this network turns the evaluation cache " +
+        throw CaError(CA_ERR_STATE, std::string(who) + ": this network turns the evaluation cache " +
                                             std::string(fused.table.entries ? "off" : "on") +
                                             " in the middle of a generation; finish or reset the generation first");
       }
@@ -969,6 +998,22 @@ struct ca_trainer {
     /* entries filled by the previous network must not serve the new one: the next run empties the tables (the value
      * elements the pending leaves point to stay: those rows WERE evaluated by the network in place when they were queued) */
     if (slot == 0) fused.cache_clean = false;
+  }
+
+  /* A caller-supplied network function returned non-zero (ExternalNet): the run that saw it has left through its drain;
+   * the games hold evaluations that were never written, so the generation is over until ca_trainer_reset. */
+  void check_callback() {
+    for (int slot = 0; slot < 2; ++slot)
+      if (nets[slot] && nets[slot]->callback_failed()) {
+        callback_failed = true;
+        invalidate();
+        throw CaError(CA_ERR_CALLBACK, "the caller-supplied network function of slot " + std::to_string(slot) + " returned non-zero");
+      }
+  }
+  void need_no_failed_callback(const char *who) const {
+    if (callback_failed)
+      throw CaError(CA_ERR_STATE, std::string(who) + ": a caller-supplied network function failed in this generation; it cannot go on -- "
+                                                     "start a new one with ca_trainer_reset");
   }
 
   /* nn.h range_exceeded: an f16x3 network met an operand beyond fp16's range -- its outputs since are NaN or wrong */
@@ -989,6 +1034,7 @@ struct ca_trainer {
    * the caller holds them (70 floats) and are widened to the kernels' 80-float rows on the device */
   void net_forward_host(int slot, const float *states, int32_t n, float *evals, float *probs) {
     if (slot < 0 || slot > 1 || !nets[slot]) throw CaError(CA_ERR_STATE, "net slot not set");
+    need_no_failed_callback("ca_trainer_net_forward");
     CoNet *net = nets[slot].get();
     if (n < 0 || (size_t)n > net->max_rows()) throw CaError(CA_ERR_ARG, "net_forward: more rows than num_games*searches_per_eval");
     if (n == 0) return;
@@ -1003,6 +1049,10 @@ struct ca_trainer {
     RT_LAUNCH(co_k_expand_rows, nb, CO_WAVE, stream, (const float *)fw_in70.p, fw_in.p, (int)n, nb);
     net_used = true;
     net->forward(fw_in.p, n, fw_rows.p, fw_ev.p, fw_pr.p, stream);
+    if (net->callback_failed()) {
+      rt_sync(stream);
+      check_callback();
+    }
     rt_d2h(evals, fw_ev.p, (size_t)n * 4, stream);
     rt_d2h(probs, fw_pr.p, (size_t)n * CO_NUM_MOVES * 4, stream);
     rt_sync(stream);
@@ -1115,6 +1165,7 @@ struct ca_trainer {
     /* the run is over (its streams are drained): device times from the timed launches, errors, the rows evaluated, the
      * step budget's statistics */
     stats.estimate_device_times(true);
+    check_callback();
     if (!fused.failure.empty()) throw CaError(CA_ERR_ENGINE, fused.failure);
     pack(-1); /* refresh the done flag and the batch description */
     check_errors();
@@ -1128,6 +1179,7 @@ struct ca_trainer {
 
   bool run(int64_t max_iterations) {
     need_positions();
+    need_no_failed_callback("ca_trainer_run");
     if (host_cache)
       throw CaError(CA_ERR_STATE, "ca_trainer_run: the host-driven protocol drives this trainer's generations with the evaluation "
                                   "cache; switch it off first (ca_trainer_set_host_cache with a negative size)");
@@ -1175,6 +1227,7 @@ struct ca_trainer {
       net_used = true;
       for (int slot = 0; slot < 2; ++slot) /* get_predictions, main.pyx:74-81 */
         nets[slot]->forward(nn_in.p, R * spe, arena_state.p + 3 + slot, nn_eval.p, nn_probs.p, stream);
+      if (nets[0]->callback_failed() || nets[1]->callback_failed()) break; /* (a caller-supplied network: nothing more is queued) */
       if (timed) rt_event_record(ev[3], stream);
       ++iterations;
       ++it;
@@ -1202,6 +1255,7 @@ struct ca_trainer {
     rt_sync(stream);
     invalidate();
     stats.estimate_device_times(false);
+    check_callback();
     if (!failure.empty()) throw CaError(CA_ERR_ENGINE, failure);
     pack(st[0]); /* refresh the done flag and the batch description */
     check_errors();
@@ -1227,10 +1281,17 @@ struct ca_tourney {
   std::mt19937 generator;                      /* default constructed: seed 5489 (tourney.h:43) */
   std::vector<uint32_t> seeds;
   std::unique_ptr<ca_trainer> pool;            /* built at the first query after the last addMatch */
-  struct PendingNet {
-    int kind;
+  struct PendingNet { /* either weights of one of the library's kinds or the caller's function (ca_tourney_set_net_fn) */
+    int kind = 0;
     std::vector<float> w;
+    ca_net_fn fn = nullptr;
+    void *user = nullptr;
+    float *d_states = nullptr, *d_evals = nullptr, *d_probs = nullptr;
+    int32_t max_rows = 0;
+    double flop_per_row = 0.0;
   };
+  bool in_callback = false;     /* inside a caller-supplied network function: entry points are refused (host.h co_guard) */
+  bool callback_failed = false; /* ... and one returned non-zero: the tournament cannot go on */
   std::map<int, PendingNet> net_specs;         /* fused mode: model id -> network (ca_tourney_set_net) */
   std::map<int, std::unique_ptr<CoNet>> nets;
   int dev() const { return device; }
@@ -1242,6 +1303,8 @@ struct ca_tourney {
    * table).  The evaluation arrays persist between rounds like the driver's, so the result is the
    * one the compat protocol gives with the same networks. */
   bool run(int64_t max_rounds) {
+    if (callback_failed)
+      throw CaError(CA_ERR_STATE, "ca_tourney_run: a caller-supplied network function failed; this tournament cannot go on");
     ca_trainer &p = built();
     std::vector<int> ids;
     for (auto &m : matches)
@@ -1255,19 +1318,42 @@ struct ca_tourney {
       if (!nets.count(id)) {
         auto it = net_specs.find(id);
         if (it == net_specs.end()) throw CaError(CA_ERR_STATE, "ca_tourney_run: no network for model id " + std::to_string(id));
-        std::unique_ptr<CoNet> n(p.make_net(it->second.kind, it->second.w.data(), it->second.w.size()));
+        const PendingNet &spec = it->second;
+        std::unique_ptr<CoNet> n;
+        if (spec.fn) {
+          if (spec.max_rows < p.G * p.spe)
+            throw CaError(CA_ERR_ARG, "ca_tourney_set_net_fn: buffers of " + std::to_string(spec.max_rows) + " rows for model id " +
+                                              std::to_string(id) + ", this tournament asks for up to " + std::to_string(p.G * p.spe));
+          n = std::make_unique<ExternalNet>(spec.fn, spec.user, spec.d_states, spec.d_evals, spec.d_probs, (size_t)spec.max_rows,
+                                            spec.flop_per_row, &in_callback);
+        } else {
+          n.reset(p.make_net(spec.kind, spec.w.data(), spec.w.size()));
+        }
         if (!n) throw CaError(CA_ERR_ARG, "unknown net kind or bad weight count");
         nets[id] = std::move(n);
       }
     }
     int64_t rounds = 0;
     bool done = p.tourney_all_done();
+    int failed_id = -1;
     while (!done && (max_rounds <= 0 || rounds < max_rounds)) {
-      for (int id : ids) p.tourney_round(id, id >= 0 ? nets[id].get() : nullptr);
+      for (int id : ids) {
+        p.tourney_round(id, id >= 0 ? nets[id].get() : nullptr);
+        if (id >= 0 && nets[id]->callback_failed()) { /* (a caller-supplied network: nothing more is queued) */
+          failed_id = id;
+          break;
+        }
+      }
+      if (failed_id >= 0) break;
       ++rounds;
       /* the host looks at the all-done flag every eighth round only (a round that finds every match
        * finished launches kernels that return at once), so the queue never runs dry in between */
       if ((rounds & 7) == 0 || (max_rounds > 0 && rounds >= max_rounds)) done = p.tourney_poll_done(ids.front());
+    }
+    if (failed_id >= 0) {
+      callback_failed = true;
+      p.drain();
+      throw CaError(CA_ERR_CALLBACK, "the caller-supplied network function of model id " + std::to_string(failed_id) + " returned non-zero");
     }
     p.tourney_rounds_done();
     if (done) all_done(); /* (writes the match logs) */
@@ -1405,6 +1491,16 @@ extern "C" int ca_trainer_do_iteration(ca_trainer *t, const float *ev, const flo
 extern "C" int ca_trainer_set_net(ca_trainer *t, int slot, int kind, const float *w, size_t n) {
   return co_guard(t, [&] { t->set_net(slot, kind, w, n); });
 }
+extern "C" int ca_trainer_set_net_fn(ca_trainer *t, int slot, ca_net_fn fn, void *user, float *d_states, float *d_evals,
+                                     float *d_probs, int32_t max_rows, double flop_per_row) {
+  return co_guard(t, [&] { t->set_net_fn(slot, fn, user, d_states, d_evals, d_probs, max_rows, flop_per_row); });
+}
+extern "C" int ca_trainer_request_rows(ca_trainer *t, int32_t *rows) {
+  return co_guard(t, [&] {
+    if (!rows) throw CaError(CA_ERR_ARG, "ca_trainer_request_rows: null argument");
+    *rows = t->R * t->spe;
+  });
+}
 extern "C" int ca_trainer_set_host_cache(ca_trainer *t, int32_t log2_entries) {
   return co_guard(t, [&] { t->set_host_cache(log2_entries); });
 }
@@ -1536,6 +1632,24 @@ extern "C" int ca_tourney_set_net(ca_tourney *t, int32_t model_id, int32_t kind,
     t->nets.erase(model_id);
   });
 }
+extern "C" int ca_tourney_set_net_fn(ca_tourney *t, int32_t model_id, ca_net_fn fn, void *user, float *d_states, float *d_evals,
+                                     float *d_probs, int32_t max_rows, double flop_per_row) {
+  return co_guard(t, [&] {
+    if (model_id < 0) throw CaError(CA_ERR_ARG, "negative model ids are the dummy ids of random players");
+    if (!fn || !d_states || !d_evals || !d_probs) throw CaError(CA_ERR_ARG, "ca_tourney_set_net_fn: null function or buffer");
+    if (max_rows <= 0 || !(flop_per_row >= 0.0)) throw CaError(CA_ERR_ARG, "ca_tourney_set_net_fn: max_rows must be positive, flop_per_row 0 or positive");
+    ca_tourney::PendingNet spec;
+    spec.fn = fn;
+    spec.user = user;
+    spec.d_states = d_states;
+    spec.d_evals = d_evals;
+    spec.d_probs = d_probs;
+    spec.max_rows = max_rows;
+    spec.flop_per_row = flop_per_row;
+    t->net_specs[model_id] = std::move(spec);
+    t->nets.erase(model_id);
+  });
+}
 extern "C" int ca_tourney_set_exact_offsets(ca_tourney *t, int32_t on) {
   return co_guard(t, [&] {
     if (t->pool) throw CaError(CA_ERR_STATE, "set_exact_offsets after the tournament has started");
@@ -1596,6 +1710,68 @@ extern "C" int ca_tourney_trace(ca_tourney *t, int32_t match, int32_t *out, int3
 extern "C" int ca_tourney_stats(ca_tourney *t, ca_stats *out) {
   return co_guard(t, [&] { t->built_or_state().read_stats(out); });
 }
+
+/* ---- the library's own network kernels on device memory, without a trainer (ca_net_*): a CoNet and the 80-float rows the
+ * kernels read, i.e. ca_trainer::net_forward_host without its copies */
+struct ca_net {
+  int device = 0;
+  Stream stream;
+  std::unique_ptr<CoNet> net;
+  DevBuf<float> rows80; /* [max_rows][CO_STATE_STRIDE] */
+  /* ONE row buffer: a call on another stream than the last one (the pools of a fused run) starts behind that one's kernels */
+  Event used;
+  rt_stream_t used_on = {};
+  bool used_once = false;
+  int dev() const { return device; }
+
+  void forward_device(const float *d_states, int32_t rows_cap, const int32_t *d_rows, float *d_evals, float *d_probs, void *stream_arg) {
+    if (!d_states || !d_rows || !d_evals || !d_probs) throw CaError(CA_ERR_ARG, "ca_net_forward_device: null buffer");
+    if (rows_cap < 0 || (size_t)rows_cap > net->max_rows()) throw CaError(CA_ERR_ARG, "ca_net_forward_device: more rows than the net's max_rows");
+    if (rows_cap == 0) return;
+    const rt_stream_t s = stream_arg ? (rt_stream_t)(intptr_t)stream_arg : (rt_stream_t)stream;
+    if (used_once && used_on != s) rt_stream_wait(s, used);
+    const int nb = rows_cap * CO_STATE_STRIDE / CO_WAVE + 1 < 1024 ? rows_cap * CO_STATE_STRIDE / CO_WAVE + 1 : 1024;
+    RT_LAUNCH(co_k_expand_rows, nb, CO_WAVE, s, d_states, rows80.p, (int)rows_cap, nb);
+    net->forward(rows80.p, rows_cap, d_rows, d_evals, d_probs, s);
+    rt_event_record(used, s);
+    used_on = s;
+    used_once = true;
+    if (!stream_arg) {
+      rt_sync(s);
+      if (net->range_exceeded(s))
+        throw CaError(CA_ERR_ENGINE, "ca_net_forward_device: an activation left the fp16 range of the f16x3 kernels (|x| > 65504); the "
+                                     "evaluations are not valid -- use the float32-equivalent x6 kind of the same network");
+    }
+  }
+};
+
+extern "C" int ca_net_create(int device, int kind, const float *weights, size_t n_floats, int32_t max_rows, ca_net **out) {
+  int rc = ca_device_check(device);
+  if (rc != CA_OK) return rc;
+  return co_guard([&] {
+    if (!out || !weights || max_rows <= 0) throw CaError(CA_ERR_ARG, "ca_net_create: null argument or max_rows < 1");
+    *out = nullptr;
+    rt_set_device(device);
+    auto n = std::make_unique<ca_net>();
+    n->device = device;
+    n->stream.create();
+    n->used.create();
+    try {
+      n->net.reset(co_net_create(kind, weights, n_floats, (size_t)max_rows, n->stream));
+    } catch (const std::invalid_argument &e) { /* weights outside the kind's operand range (nn.h range_exceeded) */
+      throw CaError(CA_ERR_ARG, e.what());
+    }
+    if (!n->net) throw CaError(CA_ERR_ARG, "unknown net kind or bad weight count");
+    n->rows80.alloc((size_t)max_rows * CO_STATE_STRIDE, n->stream);
+    rt_sync(n->stream);
+    *out = n.release();
+  });
+}
+extern "C" int ca_net_forward_device(ca_net *n, const float *d_states, int32_t rows_cap, const int32_t *d_rows, float *d_evals,
+                                     float *d_probs, void *stream) {
+  return co_guard(n, [&] { n->forward_device(d_states, rows_cap, d_rows, d_evals, d_probs, stream); });
+}
+extern "C" void ca_net_destroy(ca_net *n) { delete n; }
 
 /* ---- stand-alone test entry points, each on a stream of its own */
 static Stream device_stream(int device) {

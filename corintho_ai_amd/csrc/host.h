@@ -88,12 +88,20 @@ int co_guard(F &&body) {
     return CA_ERR_DEVICE;
   }
 }
+/* is the handle inside a caller-supplied network function (ca_net_fn)?  Handles without such a flag: never */
+template <class H>
+auto co_in_callback(const H *h, int) -> decltype((bool)h->in_callback) { return h->in_callback; }
+template <class H>
+bool co_in_callback(const H *, long) { return false; }
+
 /* ... of an entry point on a handle (trainer, tourney, fitter).  Its device is selected first: the caller's thread may
  * have another one current (two trainers on two GPUs in one process; torch.cuda.set_device between calls) */
 template <class H, class F>
 int co_guard(H *h, F &&body) {
   return co_guard([&] {
     if (!h) throw CaError(CA_ERR_ARG, "null handle");
+    if (co_in_callback(h, 0))
+      throw CaError(CA_ERR_STATE, "called from inside a caller-supplied network function (ca_net_fn) of the same handle");
     rt_set_device(h->dev());
     body();
   });

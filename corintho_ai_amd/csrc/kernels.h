@@ -160,34 +160,40 @@ CO_KERNEL co_k_expand_rows(const float *in70, float *out80, int rows, int nblock
   }
 }
 
-/* ---- host-driven protocol with the evaluation cache (pools.h HostNet): the rows the cache could not resolve travel to
- * the caller and its answers come back.  One thread per float, so a wavefront reads and writes 64 consecutive floats;
- * no LDS, no atomics.  Float e belongs to wavefront e / 64 of the launch: */
+/* ---- request rows for a caller and the caller's answers back: the host-driven protocol with the evaluation cache
+ * (pools.h HostNet, the caller on the host) and a caller-supplied network inside the run (pools.h ExternalNet, the caller's
+ * function on the device).  One thread per float, so a wavefront reads and writes 64 consecutive floats; no LDS, no
+ * atomics.  Float e belongs to wavefront e / 64 of the launch: */
 #define CO_HOST_ROWS_FLOAT ((CO_BLOCK_IDX * CO_WAVES_PER_BLOCK + CO_WAVE_IN_BLOCK) * CO_WAVE + lane)
-/* out70[r][0..70) = request row in_idx[r] of `req` for r < count[0], the cache's count word of this iteration (and
- * r < cap_rows, the rows out70 holds: the launch is sized by them); threads beyond leave */
+/* out70[r][0..70) = request row in_idx[r] (null: row r) of `req` for r < count[0], the device's row count of this
+ * iteration, and ZERO for count[0] <= r < cap_rows, the rows out70 holds (the launch is sized by them): a caller that
+ * evaluates all cap_rows rows never reads an earlier iteration's rows.  Threads beyond leave. */
 CO_KERNEL co_k_host_rows_out(const float *req, const int32_t *in_idx, const uint32_t *count, int cap_rows, float *out70) {
   const uint32_t have = count[0];
-  const int total = (int)(have < (uint32_t)cap_rows ? have : (uint32_t)cap_rows) * CO_GAME_STATE_SIZE;
+  const int rows = (int)(have < (uint32_t)cap_rows ? have : (uint32_t)cap_rows);
+  const int total = cap_rows * CO_GAME_STATE_SIZE;
   FOR_LANES {
     const int e = CO_HOST_ROWS_FLOAT;
     if (e < total) {
       const int r = e / CO_GAME_STATE_SIZE, c = e - r * CO_GAME_STATE_SIZE;
-      out70[e] = req[(size_t)in_idx[r] * CO_STATE_STRIDE + c];
+      out70[e] = r < rows ? req[(size_t)(in_idx ? in_idx[r] : r) * CO_STATE_STRIDE + c] : 0.0f;
     }
   }
 }
-/* evals[r], probs[r][96] -> element out_idx[r] of the cache's value array {value, 3 pad, 96 priors}, r < rows: where a
- * network kernel writes through CoNetIO */
-CO_KERNEL co_k_host_rows_in(const float *evals, const float *probs, const int32_t *out_idx, int rows, float *val) {
-  const int total = rows * (1 + CO_NUM_MOVES);
+/* evals[r], probs[r][96] -> d_eval[o * eval_stride], d_probs[o * probs_stride + m] with o = out_idx[r] (null: r), for
+ * r < rows and r < count[0] (null: no device count): where a network kernel writes through CoNetIO -- the reference
+ * layout {1, 96}, or an element {value, 3 pad, 96 priors} of the cache's value array */
+CO_KERNEL co_k_host_rows_in(const float *evals, const float *probs, const int32_t *out_idx, const uint32_t *count, int rows,
+                            float *d_eval, float *d_probs, int eval_stride, int probs_stride) {
+  const uint32_t have = count ? count[0] : (uint32_t)rows;
+  const int total = (int)(have < (uint32_t)rows ? have : (uint32_t)rows) * (1 + CO_NUM_MOVES);
   FOR_LANES {
     const int e = CO_HOST_ROWS_FLOAT;
     if (e < total) {
       const int r = e / (1 + CO_NUM_MOVES), c = e - r * (1 + CO_NUM_MOVES);
-      float *dst = val + (size_t)out_idx[r] * CO_CACHE_VAL_FLOATS;
-      if (c == 0) dst[0] = evals[r];
-      else dst[4 + c - 1] = probs[(size_t)r * CO_NUM_MOVES + c - 1];
+      const size_t o = (size_t)(out_idx ? out_idx[r] : r);
+      if (c == 0) d_eval[o * (size_t)eval_stride] = evals[r];
+      else d_probs[o * (size_t)probs_stride + c - 1] = probs[(size_t)r * CO_NUM_MOVES + c - 1];
     }
   }
 }

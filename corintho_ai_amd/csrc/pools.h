@@ -147,6 +147,9 @@ struct Pool {
   }
 };
 
+/* one thread per float (kernels.h co_k_host_rows_out / _in) */
+static int host_rows_blocks(size_t floats) { return (int)((floats + CO_WAVE * CO_WAVES_PER_BLOCK - 1) / (CO_WAVE * CO_WAVES_PER_BLOCK)); }
+
 /* The "network" of the host-driven protocol with the evaluation cache (ca_trainer_set_host_cache): its forward pass is
  * the round trip to the caller.  forward() -- FusedRun queues it behind the search launch like any network -- gathers the
  * rows the cache could not resolve into a dense [n][70] array for Trainer::writeRequests and has the protocol's flags
@@ -163,8 +166,6 @@ struct HostNet : CoNet {
   const int32_t *out_idx = nullptr;
   float *val = nullptr;
 
-  /* one thread per float */
-  static int blocks(size_t floats) { return (int)((floats + CO_WAVE * CO_WAVES_PER_BLOCK - 1) / (CO_WAVE * CO_WAVES_PER_BLOCK)); }
   size_t max_rows() const override { return rows_cap; }
   int kind() const override { return 0; }
   double flop_per_row() const override { return 0.0; }
@@ -176,7 +177,7 @@ struct HostNet : CoNet {
     out_idx = io.out_idx;
     val = d_eval;
     if (cap > 0)
-      RT_LAUNCH(co_k_host_rows_out, blocks((size_t)cap * CO_GAME_STATE_SIZE), CO_WAVE * CO_WAVES_PER_BLOCK, s, d_in, io.in_idx,
+      RT_LAUNCH(co_k_host_rows_out, host_rows_blocks((size_t)cap * CO_GAME_STATE_SIZE), CO_WAVE * CO_WAVES_PER_BLOCK, s, d_in, io.in_idx,
                 (const uint32_t *)d_rows, (int)cap, rows70);
     RT_LAUNCH(co_k_scan, 1, CO_WAVE, s, scan_params);
     rt_d2h(h_ctl, d_ctl, 16, s);
@@ -187,8 +188,59 @@ struct HostNet : CoNet {
     if ((size_t)n > rows_cap || !out_idx) throw CaError(CA_ERR_STATE, "HostNet: answers to rows that were not handed out");
     rt_h2d(ev_in, evals, (size_t)n * 4, s);
     rt_h2d(pr_in, probs, (size_t)n * CO_NUM_MOVES * 4, s);
-    RT_LAUNCH(co_k_host_rows_in, blocks((size_t)n * (1 + CO_NUM_MOVES)), CO_WAVE * CO_WAVES_PER_BLOCK, s, (const float *)ev_in,
-              (const float *)pr_in, out_idx, (int)n, val);
+    RT_LAUNCH(co_k_host_rows_in, host_rows_blocks((size_t)n * (1 + CO_NUM_MOVES)), CO_WAVE * CO_WAVES_PER_BLOCK, s,
+              (const float *)ev_in, (const float *)pr_in, out_idx, (const uint32_t *)nullptr, (int)n, val, val + 4,
+              (int)CO_CACHE_VAL_FLOATS, (int)CO_CACHE_VAL_FLOATS);
+  }
+};
+
+/* The caller's own network inside a run (ca_trainer_set_net_fn, ca_tourney_set_net_fn): forward() lays the launch's request
+ * rows out densely in the caller's DEVICE buffer -- 70 floats each, the rows beyond the device's count zeroed -- calls the
+ * caller's function on the launch's stream, and scatters the answers it leaves in the caller's two output buffers to where
+ * a network kernel would have written them (CoNetIO).  Nothing comes back to the host: the function is handed the
+ * capacity of the launch and a device pointer to the count.  The pools of a fused run call forward() on their own
+ * streams without waiting for each other; each works in rows [io.row_base, io.row_base + rows_cap) of the buffers. */
+struct ExternalNet : CoNet {
+  ca_net_fn fn = nullptr;
+  void *user = nullptr;
+  float *states = nullptr, *evals = nullptr, *probs = nullptr; /* the caller's: [rows_cap][70], [rows_cap], [rows_cap][96] */
+  size_t rows_cap = 0;
+  double flops = 0.0;
+  bool *in_callback = nullptr; /* the owner's guard flag: an entry point called from inside fn is refused (host.h co_guard) */
+  bool failed = false;
+
+  ExternalNet(ca_net_fn f, void *u, float *d_states, float *d_evals, float *d_probs, size_t max_rows, double flop_per_row,
+              bool *guard)
+      : fn(f), user(u), states(d_states), evals(d_evals), probs(d_probs), rows_cap(max_rows), flops(flop_per_row), in_callback(guard) {}
+  size_t max_rows() const override { return rows_cap; }
+  int kind() const override { return 0; }
+  double flop_per_row() const override { return flops; }
+  bool callback_failed() const override { return failed; }
+  void clear_failure() override { failed = false; }
+  void forward(const float *d_in, int32_t cap, const int32_t *d_rows, float *d_eval, float *d_probs, rt_stream_t s,
+               const CoNetIO &io = CoNetIO()) override {
+    if (failed || cap <= 0) return;
+    const size_t row0 = (size_t)io.row_base;
+    if (io.row_base < 0 || row0 + (size_t)cap > rows_cap)
+      throw CaError(CA_ERR_STATE, "caller-supplied network: rows " + std::to_string(row0) + " .. " + std::to_string(row0 + (size_t)cap) +
+                                          " are beyond the " + std::to_string(rows_cap) + " rows of its buffers");
+    RT_LAUNCH(co_k_host_rows_out, host_rows_blocks((size_t)cap * CO_GAME_STATE_SIZE), CO_WAVE * CO_WAVES_PER_BLOCK, s, d_in, io.in_idx,
+              (const uint32_t *)d_rows, (int)cap, states + row0 * CO_GAME_STATE_SIZE);
+    *in_callback = true;
+    int rc;
+    try {
+      rc = fn(user, (int32_t)row0, cap, d_rows, (void *)(intptr_t)s);
+    } catch (...) { /* (a function that throws through a C boundary has already broken its contract) */
+      rc = -1;
+    }
+    *in_callback = false;
+    if (rc != 0) {
+      failed = true;
+      return;
+    }
+    RT_LAUNCH(co_k_host_rows_in, host_rows_blocks((size_t)cap * (1 + CO_NUM_MOVES)), CO_WAVE * CO_WAVES_PER_BLOCK, s,
+              (const float *)(evals + row0), (const float *)(probs + row0 * CO_NUM_MOVES), io.out_idx, (const uint32_t *)d_rows, (int)cap,
+              d_eval, d_probs, (int)io.eval_stride, (int)io.probs_stride);
   }
 };
 
@@ -385,6 +437,7 @@ struct FusedRun {
     if (timed) rt_event_record(e[2], q.st);
     CoNetIO io;
     io.alone = npools == 1;
+    io.row_base = q.row_base; /* (a caller-supplied network's slice of its buffers, ExternalNet) */
     const int32_t *d_rows;
     float *d_eval, *d_probs;
     if (q.cache.hdr) {
@@ -439,6 +492,7 @@ struct FusedRun {
       run_params.iteration = iteration;
       for (int p = 0; p < npools; ++p)
         queue_iteration(p, emptied, in_window == poll - 1 || (max_iterations > 0 && it + 1 == max_iterations));
+      if (net->callback_failed()) break; /* nothing more is queued; the drain below, as on any other exit */
       const int counter_slot = iteration & 1;
       ++iteration;
       ++it;

@@ -25,6 +25,7 @@ class Tourney:
     def __init__(self, num_threads=1, log_folder="", *, device=0, arena_units=0, trace=False, _cdll=None):
         self._L = _cdll if _cdll is not None else _lib.load()
         self._t = C.c_void_p()
+        self._net_fns = {}  # model id -> _lib.NetCallback, alive as long as the model holds it
         _lib.check(self._L, self._L.ca_tourney_create(device, arena_units, int(bool(trace)), C.byref(self._t)))
         if log_folder:  # tourney.h:46: matches added with logging=True write <log_folder>/match_<p1>_<p2>_<index>.txt
             _lib.check(self._L, self._L.ca_tourney_set_log_folder(self._t, str(log_folder).encode()))
@@ -74,6 +75,15 @@ class Tourney:
     def set_net(self, model_id, kind, weights):
         w = np.ascontiguousarray(weights, dtype=np.float32)
         _lib.check(self._L, self._L.ca_tourney_set_net(self._t, model_id, kind, _f32(w, "weights"), w.size))
+        self._net_fns.pop(model_id, None)
+
+    def set_net_fn(self, model_id, fn, d_states_ptr, d_evals_ptr, d_probs_ptr, max_rows, flop_per_row=0.0):
+        """your own network for model `model_id` (Trainer.set_net_fn); max_rows >= matches x the largest searches_per_eval"""
+        cb = _lib.NetCallback(fn)
+        _lib.check(self._L, self._L.ca_tourney_set_net_fn(self._t, model_id, cb.c, None, C.c_void_p(d_states_ptr),
+                                                          C.c_void_p(d_evals_ptr), C.c_void_p(d_probs_ptr), int(max_rows),
+                                                          float(flop_per_row)))
+        self._net_fns[model_id] = cb
 
     def set_exact_offsets(self, on=True):
         """diagnostic: matches read their own rows instead of the reference's offset table (tourney.cpp:55-62)"""
@@ -81,7 +91,7 @@ class Tourney:
 
     def run(self, max_rounds=0):
         done = C.c_int32()
-        _lib.check(self._L, self._L.ca_tourney_run(self._t, max_rounds, C.byref(done)))
+        _lib.check_callbacks(self._L, self._L.ca_tourney_run(self._t, max_rounds, C.byref(done)), self._net_fns.values())
         return bool(done.value)
 
     # ---- introspection

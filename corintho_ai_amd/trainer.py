@@ -67,6 +67,8 @@ class Trainer:
         self.num_games = num_games
         self.searches_per_eval = searches_per_eval
         self.testing = bool(testing)
+        self.device = device
+        self._net_fns = {}  # slot -> _lib.NetCallback, alive as long as the slot holds it
         _lib.check(self._L, self._L.ca_trainer_create(C.byref(cfg), C.byref(self._t)))
         if num_logged:  # trainer.cpp:243-250: the first num_logged games write log_folder/game_<i>.txt
             _lib.check(self._L, self._L.ca_trainer_set_logging(self._t, str(log_folder).encode(), int(num_logged)))
@@ -128,10 +130,31 @@ class Trainer:
     def set_net(self, kind, weights, slot=0):
         w = np.ascontiguousarray(weights, dtype=np.float32)
         _lib.check(self._L, self._L.ca_trainer_set_net(self._t, slot, kind, _f32(w, "weights"), w.size))
+        self._net_fns.pop(slot, None)
+
+    def request_rows(self):
+        """rows a network of this trainer must be able to take: resident slots x searches_per_eval"""
+        out = C.c_int32()
+        _lib.check(self._L, self._L.ca_trainer_request_rows(self._t, C.byref(out)))
+        return out.value
+
+    def set_net_fn(self, fn, d_states_ptr, d_evals_ptr, d_probs_ptr, max_rows, slot=0, flop_per_row=0.0):
+        """Your own network as slot `slot` of fused mode (ca_trainer_set_net_fn).  The three device buffers
+        ([max_rows][70], [max_rows], [max_rows][96] float32, max_rows >= request_rows()) are yours and must outlive the
+        slot.  fn(row0, cap_rows, d_rows_ptr, stream_ptr) is called inside run(): rows [row0, row0 + cap_rows) of the
+        states are ready on the HIP stream `stream_ptr`; it enqueues work there that leaves the answers in the same rows
+        of the other two buffers.  It evaluates all cap_rows rows (those from the device count *d_rows_ptr on are zero
+        and their answers ignored) and must not call this trainer.  What it raises ends the run and is re-raised by
+        run(); the generation then needs reset()."""
+        cb = _lib.NetCallback(fn)
+        _lib.check(self._L, self._L.ca_trainer_set_net_fn(self._t, slot, cb.c, None, C.c_void_p(d_states_ptr),
+                                                          C.c_void_p(d_evals_ptr), C.c_void_p(d_probs_ptr), int(max_rows),
+                                                          float(flop_per_row)))
+        self._net_fns[slot] = cb
 
     def run(self, max_iterations=0):
         done = C.c_int32()
-        _lib.check(self._L, self._L.ca_trainer_run(self._t, max_iterations, C.byref(done)))
+        _lib.check_callbacks(self._L, self._L.ca_trainer_run(self._t, max_iterations, C.byref(done)), self._net_fns.values())
         return bool(done.value)
 
     def set_host_cache(self, on):
@@ -181,8 +204,8 @@ class Trainer:
             raise ValueError("net_forward: out_probs must be [>= %d][%d], got %s" % (n, NUM_MOVES, pr.shape))
         if n == 0:
             return ev, pr
-        _lib.check(self._L, self._L.ca_trainer_net_forward(self._t, slot, _f32(s, "states"), n, _f32(ev, "ev"),
-                                                           _f32(pr, "pr")))
+        _lib.check_callbacks(self._L, self._L.ca_trainer_net_forward(self._t, slot, _f32(s, "states"), n, _f32(ev, "ev"),
+                                                                     _f32(pr, "pr")), self._net_fns.values())
         return ev, pr
 
     def net_bench(self, states, reps=20, slot=0):

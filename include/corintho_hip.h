@@ -35,6 +35,7 @@ extern "C" {
 #define CA_ERR_ENGINE -3   /* a game reported an engine error (arena full, ...) */
 #define CA_ERR_STATE -4    /* call made in the wrong state */
 #define CA_ERR_IO -5
+#define CA_ERR_CALLBACK -6 /* a caller-supplied network function returned non-zero */
 
 typedef struct ca_trainer ca_trainer;
 
@@ -206,6 +207,44 @@ int ca_trainer_finish(ca_trainer *t);
 /* slot 0 = best model (training, and arena `to_play == 1`), slot 1 = new model (arena
  * `to_play == 0`), as get_predictions chooses them (main.pyx:70-83) */
 int ca_trainer_set_net(ca_trainer *t, int slot, int kind, const float *weights, size_t n_floats);
+/* ---- the caller's own network in fused mode ----
+ * rows a network of this trainer must be able to take: resident slots x searches_per_eval */
+int ca_trainer_request_rows(ca_trainer *t, int32_t *rows);
+/* The caller's network as slot `slot` of fused mode.  The three DEVICE buffers are the caller's, on the trainer's device,
+ * of max_rows rows (>= ca_trainer_request_rows), and stay allocated until the slot is replaced or the trainer destroyed:
+ *   d_states [max_rows][70]   written by the library: request rows, the reference's layout (writeRequests)
+ *   d_evals  [max_rows]       written by fn
+ *   d_probs  [max_rows][96]   written by fn
+ * fn(user, row0, cap_rows, d_rows, stream): rows [row0, row0 + cap_rows) of d_states are ready on `stream` (a
+ * hipStream_t); the first *d_rows of them (a device int32, <= cap_rows; the host does not know it) are positions, the
+ * rest are zero.  fn enqueues, on `stream` or ordered against it, work that leaves the answers in the same rows of
+ * d_evals / d_probs, and returns 0; it need not synchronise.  Answers to rows beyond *d_rows are ignored.
+ *
+ * The caller evaluates cap_rows rows, not *d_rows: that is the price of never asking the host.  A fused training run
+ * shrinks cap_rows to (games still running) x searches_per_eval as a pool thins out.  The arena queues both models in
+ * every iteration and the idle one finds a count of 0: its function is asked for cap_rows zero rows.
+ *
+ * The contract of fn:
+ *   - It is called on the thread that called ca_trainer_run / ca_trainer_net_forward / ca_tourney_run, never
+ *     concurrently and never after that call has returned.
+ *   - It must not call an entry point on the same trainer (tourney): that call returns CA_ERR_STATE.
+ *   - Fused training calls it once per pool and iteration, with that pool's row0.  The pools' row ranges are disjoint,
+ *     so work enqueued for one pool may still be running when fn is called for the next.  The arena, tournaments,
+ *     ca_trainer_net_forward and ca_trainer_net_bench call it with row0 = 0.
+ *   - PRECONDITION of the evaluation cache (ca_config.eval_cache), as for ca_trainer_set_host_cache: the caller's network
+ *     gives a row the same outputs in whatever batch it stands.  Then every game's results equal the built-in path's bit
+ *     for bit; a network that is not batch-invariant gets "evaluated once, reused".
+ *   - flop_per_row is what the automatic rule of ca_config.eval_cache = 0 reads (a cache from 1e6 on): 0 = unknown, then
+ *     no automatic cache; ca_config.eval_cache > 0 still forces one.
+ * A non-zero return of fn ends the run: nothing more is queued, every stream is drained as on any other exit, and the
+ * call returns CA_ERR_CALLBACK with the slot (model id) in ca_last_error().  The generation is unusable until
+ * ca_trainer_reset: ca_trainer_run, ca_trainer_do_iteration and ca_trainer_net_forward return CA_ERR_STATE and say so (a
+ * tournament has no reset: ca_tourney_run keeps returning CA_ERR_STATE).
+ * CA_ERR_ARG: a slot other than 0 / 1, a null function or buffer, max_rows below ca_trainer_request_rows.  CA_ERR_STATE:
+ * a replacement that would turn the evaluation cache on or off in mid-generation, as ca_trainer_set_net. */
+typedef int (*ca_net_fn)(void *user, int32_t row0, int32_t cap_rows, const int32_t *d_rows, void *stream);
+int ca_trainer_set_net_fn(ca_trainer *t, int slot, ca_net_fn fn, void *user, float *d_states, float *d_evals,
+                          float *d_probs, int32_t max_rows, double flop_per_row);
 /* Run the whole generation on the device.  max_iterations 0 = until done. */
 int ca_trainer_run(ca_trainer *t, int64_t max_iterations, int32_t *all_done);
 /* One network evaluation of host rows through the device kernels (numerics tests):
@@ -301,6 +340,10 @@ int ca_tourney_do_iteration(ca_tourney *t, const float *evaluations, const float
  * ca_tourney_run plays the loop of rating/tourney.pyx:122-160 on the device, model ids in
  * ascending order, until every match is done or `max_rounds` rounds have run (0 = no limit). */
 int ca_tourney_set_net(ca_tourney *t, int32_t model_id, int32_t kind, const float *weights, size_t n_floats);
+/* the caller's own network for model `model_id` (see ca_trainer_set_net_fn); max_rows is checked against matches x the
+ * largest searches_per_eval when the tournament is built (CA_ERR_ARG from ca_tourney_run) */
+int ca_tourney_set_net_fn(ca_tourney *t, int32_t model_id, ca_net_fn fn, void *user, float *d_states, float *d_evals,
+                          float *d_probs, int32_t max_rows, double flop_per_row);
 int ca_tourney_run(ca_tourney *t, int64_t max_rounds, int32_t *all_done);
 /* Diagnostic (not in the reference): 1 = every match reads its evaluations at the rows Tourney::writeRequests
  * gave it, instead of through Tourney::doIteration's own offset table (tourney.cpp:55-62, SURVEY 8a quirk 10,
@@ -315,6 +358,18 @@ int ca_tourney_match_info(ca_tourney *t, int32_t match, int32_t out[8]);
 int ca_tourney_match_score(ca_tourney *t, int32_t match, float *out);
 int ca_tourney_trace(ca_tourney *t, int32_t match, int32_t *out, int32_t cap, int32_t *n);
 int ca_tourney_stats(ca_tourney *t, ca_stats *out);
+
+/* ---- The library's own network kernels on device memory, without a trainer (what ca_trainer_net_forward does after its
+ * upload): d_states [rows_cap][70], *d_rows valid rows (a device int32), -> d_evals [rows_cap], d_probs [rows_cap][96]; rows
+ * from *d_rows on are left untouched.  Queued on `stream` (a hipStream_t; NULL: the net's own stream, synchronised before
+ * the call returns, and an f16x3 kind's range flag checked: CA_ERR_ENGINE).  Kinds and weight layouts as
+ * ca_trainer_set_net; rows_cap <= max_rows.  A net holds one staging buffer: a call on another stream than the previous
+ * one starts behind the previous call's kernels.  This is what a ca_net_fn calls to run one of the library's networks. */
+typedef struct ca_net ca_net;
+int ca_net_create(int device, int kind, const float *weights, size_t n_floats, int32_t max_rows, ca_net **out);
+int ca_net_forward_device(ca_net *n, const float *d_states, int32_t rows_cap, const int32_t *d_rows, float *d_evals,
+                          float *d_probs, void *stream);
+void ca_net_destroy(ca_net *n);
 
 /* rule layer on a batch of positions (one wavefront each): legal-move masks + is_lines */
 int ca_rules_legal_moves(int device, const uint64_t *boards, const uint32_t *metas, int32_t n, uint32_t *masks /* [n][3] */,
