@@ -1,4 +1,5 @@
-// engine.hip -- host side of the self-play pool and the C ABI (include/corintho_hip.h).
+// engine.hip -- host side of the self-play pool and the C ABI (include/corintho_hip.h); networks come in through
+// net_host.h, fused training runs in pools.h, the words host and kernels pass each other are named in engine_defs.h.
 //
 // Mirrors the reference Trainer (corintho_ai/cpp/src/trainer.cpp) method by
 // method; the per-game work of every method runs in the kernels of kernels.h.
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "logfmt.h"
+#include "net_host.h"
 #include "pools.h"
 
 #ifdef CO_EMU
@@ -61,7 +63,7 @@ struct ca_trainer {
   DevBuf<GameCtl> results;   /* [G] finished games by index (recycling pools) */
   DevBuf<uint32_t> seeds_dev; /* [G] per-game generator seeds (recycling pools) */
   DevBuf<int32_t> ctl;
-  Pinned<int32_t> h_ctl; /* {batch rows, all done, any error, games not done} of the last scan */
+  Pinned<int32_t> h_ctl; /* EngineParams::ctl of the last scan (read_ctl) */
   /* buffers of the host-facing calls, kept (and grown on demand) instead of allocated per call */
   DevBuf<int32_t> ws_off, fw_rows;
   DevBuf<float> ws_gs, ws_ev, ws_pr, fw_in70, fw_in, fw_ev, fw_pr;
@@ -73,12 +75,14 @@ struct ca_trainer {
   int scan_valid_for = 0;      /* to_play / model id the current req_offset/nn_in describe (if scan_valid) */
   int32_t last_total = 0;
   bool finished = false;
+  bool any_error = false; /* the last scan saw an error bit in some game */
+  bool net_used = false;  /* a network launch has been queued since the range flags were last read */
   std::vector<GameCtl> host_games;
   bool host_games_valid = false;
   /* fused mode */
   std::unique_ptr<CoNet> nets[2];
-  bool in_callback = false;     /* inside a caller-supplied network function (ExternalNet): entry points are refused (host.h co_guard) */
-  bool callback_failed = false; /* ... and one returned non-zero: the generation is unusable until ca_trainer_reset */
+  /* a caller-supplied network function (ExternalNet) that returned non-zero: the generation is unusable until ca_trainer_reset */
+  CallbackState callback{false, false, " in this generation; it cannot go on -- start a new one with ca_trainer_reset"};
   RunStats stats;
   FusedRun fused; /* fused training: the pools, their table and the run (pools.h) */
   /* the evaluation cache serves fused training (and fused analysis): one network, rows packed by the search kernel */
@@ -92,7 +96,7 @@ struct ca_trainer {
   }
 
   /* host-driven protocol with the evaluation cache (ca_trainer_set_host_cache): fused training on one pool, stepped one
-   * iteration per doIteration, the caller as its network (pools.h HostNet) */
+   * iteration per doIteration, the caller as its network (net_host.h HostNet) */
   bool host_cache = false;
   int host_cache_log2 = -1; /* the table: 0 sized automatically, else 2^n entries */
   int32_t host_rows = 0;    /* rows handed to the caller by the last iteration: the cache's count word */
@@ -132,13 +136,8 @@ struct ca_trainer {
    * bounce buffers.  The buffer must stay allocated until it is unpinned or the trainer destroyed. */
   bool pin_host(void *p, size_t bytes) {
     for (auto &r : host_regs)
-      if (r.first == p) {
-        if (r.second >= bytes) return true;
-        rt_host_unregister(p);
-        r = host_regs.back();
-        host_regs.pop_back();
-        break;
-      }
+      if (r.first == p && r.second >= bytes) return true;
+    unpin_host(p); /* (registered with fewer bytes) */
     if (!rt_host_register(p, bytes)) return false;
     host_regs.emplace_back(p, bytes);
     return true;
@@ -228,8 +227,8 @@ struct ca_trainer {
     nn_in.alloc((size_t)R * spe * CO_STATE_STRIDE, stream);
     row_idx.alloc((size_t)R * spe, stream);
     nn_in70.alloc((size_t)R * spe * CO_GAME_STATE_SIZE, stream);
-    ctl.alloc(4, stream);
-    h_ctl.alloc(4);
+    ctl.alloc(CO_CTL_WORDS, stream);
+    h_ctl.alloc(CO_CTL_WORDS);
     nn_eval.alloc((size_t)R * spe, stream);
     nn_probs.alloc((size_t)R * spe * CO_NUM_MOVES, stream);
     if (!cfg.testing) samples.alloc((size_t)G * CO_MAX_PLIES * CO_SAMPLE_FLOATS, stream); /* by game */
@@ -243,7 +242,7 @@ struct ca_trainer {
     row_counter.alloc(1, stream);
     pack_counter.alloc((size_t)CO_PACK_STRIDE * CO_MAX_POOLS, stream); /* a 128-byte line per pool: every wavefront of a launch adds to its pool's words */
     work_counter.alloc((size_t)CO_WC_WORDS * CO_MAX_POOLS, stream);
-    arena_state.alloc(8, stream);
+    arena_state.alloc(CO_AS_WORDS, stream);
     if (tourney) {
       pcfg.alloc(host_pcfg.size(), stream);
       rt_h2d(pcfg.p, host_pcfg.data(), host_pcfg.size() * sizeof(PlayerCfg), stream);
@@ -323,7 +322,7 @@ struct ca_trainer {
     rt_memset(row_counter.p, 0, 8, stream);
     rt_memset(pack_counter.p, 0, (size_t)8 * CO_PACK_STRIDE * CO_MAX_POOLS, stream);
     rt_memset(work_counter.p, 0, (size_t)8 * CO_WC_WORDS * CO_MAX_POOLS, stream);
-    rt_memset(arena_state.p, 0, 32, stream);
+    rt_memset(arena_state.p, 0, CO_AS_WORDS * 4, stream);
     rt_sync(stream);
     iterations = 0;
     trainer_iteration = 0;
@@ -335,7 +334,7 @@ struct ca_trainer {
     stats = RunStats();
     stats.cache_clears = cache_clears;
     fused.cache_clean = false; /* the next run empties the tables before the first iteration of the new generation */
-    callback_failed = false;
+    callback.failed = false;
     for (auto &n : nets)
       if (n) n->clear_failure();
     if (logbuf.p) {
@@ -493,20 +492,23 @@ struct ca_trainer {
     return e;
   }
 
+  /* h_ctl holds what a scan for model `to_play` wrote: the batch and the flags the host goes by */
+  void read_ctl(int to_play) {
+    last_total = h_ctl[CO_CTL_ROWS];
+    finished = h_ctl[CO_CTL_ALL_DONE] != 0;
+    any_error = h_ctl[CO_CTL_ANY_ERROR] != 0;
+    scan_valid_for = to_play;
+    scan_valid = true;
+  }
   /* offsets + compact batch for model `to_play` (K4); ONE host synchronisation, on 16 bytes */
-  bool any_error = false;
   void pack(int to_play) {
     if (scan_valid && scan_valid_for == to_play) return;
     const EngineParams e = params(to_play);
     RT_LAUNCH(co_k_scan, 1, CO_WAVE, stream, e);
     RT_LAUNCH(co_k_compact, R, CO_WAVE, stream, e);
-    rt_d2h(h_ctl, ctl.p, 16, stream);
+    rt_d2h(h_ctl, ctl.p, CO_CTL_WORDS * 4, stream);
     rt_sync(stream);
-    last_total = h_ctl[0];
-    finished = h_ctl[1] != 0;
-    any_error = h_ctl[2] != 0;
-    scan_valid_for = to_play;
-    scan_valid = true;
+    read_ctl(to_play);
     if (finished && !any_error) maybe_write_logs();
   }
 
@@ -570,7 +572,7 @@ struct ca_trainer {
   }
   bool do_iteration(const float *evals, const float *probs, int to_play) {
     need_positions();
-    need_no_failed_callback("ca_trainer_do_iteration");
+    callback.need_none_failed("ca_trainer_do_iteration");
     if (host_cache) return host_cache_iteration(evals, probs, to_play);
     if (iterations > 0) {
       pack(to_play); /* offsets the reference computes at entry */
@@ -597,17 +599,11 @@ struct ca_trainer {
   }
 
   void write_requests(float *out, int to_play) {
-    if (host_cache) {
-      host_cache_all_games(to_play);
-      /* HostNet::forward has laid the rows out as the caller's array holds them, and the iteration's run has drained */
-      rt_d2h(out, nn_in70.p, (size_t)host_rows * CO_GAME_STATE_SIZE * 4, stream);
-      rt_sync(stream);
-      return;
-    }
-    pack(to_play);
-    if (last_total == 0) return;
-    /* K4 has laid the rows out as the caller's array holds them: one copy, straight into it */
-    rt_d2h(out, nn_in70.p, (size_t)last_total * CO_GAME_STATE_SIZE * 4, stream);
+    const int32_t n = num_requests(to_play);
+    if (n == 0) return;
+    /* K4 (with the evaluation cache: HostNet::forward, and the iteration's run has drained) has laid the rows out as the
+     * caller's array holds them: one copy, straight into it */
+    rt_d2h(out, nn_in70.p, (size_t)n * CO_GAME_STATE_SIZE * 4, stream);
     rt_sync(stream);
   }
 
@@ -676,14 +672,10 @@ struct ca_trainer {
     stats.estimate_device_times(true);
     if (!fused.failure.empty()) throw CaError(CA_ERR_ENGINE, fused.failure);
     /* what the run's drain has brought: the protocol's flags and the pool's words of this iteration */
-    last_total = h_ctl[0];
-    finished = h_ctl[1] != 0;
-    any_error = h_ctl[2] != 0;
-    scan_valid_for = -1;
-    scan_valid = true;
-    const Pool &q = fused.pools[0];
-    host_rows = (int32_t)std::min<unsigned long long>(q.word[2] & 0xFFFFFFFFull, (unsigned long long)R * spe);
-    stats.nn_rows += (int64_t)(q.word[0] & 0xFFFFFFFFull); /* rows the games requested */
+    read_ctl(-1);
+    const Pool::Seen &seen = fused.pools[0].seen[0]; /* (one iteration: the window of parity 0) */
+    host_rows = (int32_t)std::min<size_t>(seen.evaluated, (size_t)R * spe);
+    stats.nn_rows += (int64_t)co_pack_rows(seen.pack); /* rows the games requested */
     stats.nn_rows_evaluated += host_rows;                   /* ... and the ones the caller gets */
     check_errors();
     if (finished) maybe_write_logs();
@@ -743,9 +735,6 @@ struct ca_trainer {
     invalidate();
     check_errors();
   }
-  /* a network for the batches of this trainer's games */
-  CoNet *make_net(int kind, const float *weights, size_t n) { return co_net_create(kind, weights, n, (size_t)G * spe, stream); }
-
   int32_t num_samples() {
     fetch_games();
     int32_t n = 0;
@@ -795,51 +784,47 @@ struct ca_trainer {
     return idx[G];
   }
 
+  /* the guard of the three ways samples leave (`what` names the one): their number, the index of them uploaded */
+  int32_t need_samples(const char *what, int32_t cap_rows = INT32_MAX) {
+    if (cfg.testing) throw CaError(CA_ERR_STATE, std::string(what) + " in testing mode");
+    return upload_sample_index(cap_rows);
+  }
+  const int32_t *ws_meta() const { return ws_off.p + G + 1; }
+
   void write_samples(float *gs, float *ev, float *pr) {
-    if (cfg.testing) throw CaError(CA_ERR_STATE, "writeSamples in testing mode");
-    const size_t n = (size_t)upload_sample_index(INT32_MAX);
+    const size_t n = (size_t)need_samples("writeSamples");
     if (n == 0) return;
     ensure(ws_gs, n * 8 * CO_GAME_STATE_SIZE);
     ensure(ws_ev, n * 8);
     ensure(ws_pr, n * 8 * CO_NUM_MOVES);
-    RT_LAUNCH(co_k_write_samples, G, CO_WAVE, stream, P, G, (const int32_t *)ws_off.p, (const int32_t *)ws_off.p + G + 1, ws_gs.p,
-              ws_ev.p, ws_pr.p);
+    RT_LAUNCH(co_k_write_samples, G, CO_WAVE, stream, P, G, (const int32_t *)ws_off.p, ws_meta(), ws_gs.p, ws_ev.p, ws_pr.p);
     rt_d2h(gs, ws_gs.p, n * 8 * CO_GAME_STATE_SIZE * 4, stream);
     rt_d2h(ev, ws_ev.p, n * 8 * 4, stream);
     rt_d2h(pr, ws_pr.p, n * 8 * CO_NUM_MOVES * 4, stream);
     rt_sync(stream);
   }
 
-  void export_samples(float *state_policy, float *outcome) {
-    if (cfg.testing) throw CaError(CA_ERR_STATE, "export_samples in testing mode");
-    fetch_games();
-    std::vector<float> all((size_t)G * CO_MAX_PLIES * CO_SAMPLE_FLOATS);
-    rt_d2h(all.data(), samples.p, all.size() * 4, stream);
-    rt_sync(stream);
-    size_t row = 0;
-    for (int g = 0; g < G; ++g) {
-      int n = host_games[g].n_samples;
-      for (int i = 0; i < n; ++i, ++row) {
-        memcpy(state_policy + row * CO_SAMPLE_FLOATS, &all[((size_t)g * CO_MAX_PLIES + i) * CO_SAMPLE_FLOATS],
-               CO_SAMPLE_FLOATS * 4);
-        float e = host_games[g].result == CO_RESULT_DRAW ? 0.0f : 1.0f;
-        if ((n - 1 - i) & 1) e = (float)((double)e * -1.0);
-        outcome[row] = e;
-      }
-    }
+  /* un-augmented samples packed on the device into device memory: the caller's (the multi-GPU gather hands these
+   * straight to RCCL), or export_samples' staging buffers */
+  void pack_samples(float *d_state_policy, float *d_outcome) {
+    RT_LAUNCH(co_k_pack_samples, G, CO_WAVE, stream, P, G, (const int32_t *)ws_off.p, ws_meta(), d_state_policy, d_outcome);
   }
-
-  /* un-augmented samples packed on the device into caller-owned device memory
-   * (the multi-GPU gather hands these straight to RCCL) */
   int32_t pack_samples_device(float *d_state_policy, float *d_outcome, int32_t cap_rows) {
-    if (cfg.testing) throw CaError(CA_ERR_STATE, "pack_samples in testing mode");
-    const int32_t n = upload_sample_index(cap_rows);
+    const int32_t n = need_samples("pack_samples", cap_rows);
     if (n > cap_rows) throw CaError(CA_ERR_ARG, "pack_samples: destination too small");
-    if (n == 0) return 0;
-    RT_LAUNCH(co_k_pack_samples, G, CO_WAVE, stream, P, G, (const int32_t *)ws_off.p, (const int32_t *)ws_off.p + G + 1,
-              d_state_policy, d_outcome);
+    if (n > 0) pack_samples(d_state_policy, d_outcome);
     rt_sync(stream);
     return n;
+  }
+  void export_samples(float *state_policy, float *outcome) {
+    const size_t n = (size_t)need_samples("export_samples");
+    if (n == 0) return;
+    ensure(ws_gs, n * CO_SAMPLE_FLOATS);
+    ensure(ws_ev, n);
+    pack_samples(ws_gs.p, ws_ev.p);
+    rt_d2h(state_policy, ws_gs.p, n * CO_SAMPLE_FLOATS * 4, stream);
+    rt_d2h(outcome, ws_ev.p, n * 4, stream);
+    rt_sync(stream);
   }
 
   /* Trainer::writeScores (trainer.cpp:115-162) */
@@ -902,9 +887,7 @@ struct ca_trainer {
     DevBuf<uint64_t> db;
     DevBuf<uint32_t> dm, dk;
     DevBuf<int32_t> dl;
-    db.alloc(G, stream); dm.alloc(G, stream); dk.alloc((size_t)G * 3, stream); dl.alloc(G, stream);
-    rt_h2d(db.p, hb.data(), (size_t)G * 8, stream);
-    rt_h2d(dm.p, hm.data(), (size_t)G * 4, stream);
+    db.upload(hb.data(), G, stream); dm.upload(hm.data(), G, stream); dk.alloc((size_t)G * 3, stream); dl.alloc(G, stream);
     RT_LAUNCH(co_k_rules_batch, G, CO_WAVE, stream, (const uint64_t *)db.p, (const uint32_t *)dm.p, G, dk.p, dl.p);
     std::vector<uint32_t> mk((size_t)G * 3);
     std::vector<int32_t> ln(G);
@@ -952,32 +935,13 @@ struct ca_trainer {
   }
 
   /* ------------------------------------------------------------ fused mode */
-  void set_net(int slot, int kind, const float *weights, size_t n) {
+  /* the network `spec` names as slot `slot` (net_host.h NetSpec: weights of a kind, or the caller's own function) */
+  void set_net(int slot, const NetSpec &spec, const char *who) {
     if (slot < 0 || slot > 1) throw CaError(CA_ERR_ARG, "net slot must be 0 or 1");
-    std::unique_ptr<CoNet> fresh;
-    try {
-      fresh.reset(co_net_create(kind, weights, n, (size_t)R * spe, stream));
-    } catch (const std::invalid_argument &e) { /* weights outside the kind's operand range (nn.h range_exceeded) */
-      throw CaError(CA_ERR_ARG, e.what());
-    }
-    if (!fresh) throw CaError(CA_ERR_ARG, "unknown net kind or bad weight count");
-    install_net(slot, std::move(fresh), "ca_trainer_set_net");
+    install_net(slot, spec.make((size_t)R * spe, stream, &callback, ", this trainer", " (ca_trainer_request_rows)"), who);
   }
 
-  /* the caller's own network as slot `slot` (pools.h ExternalNet) */
-  void set_net_fn(int slot, ca_net_fn fn, void *user, float *d_states, float *d_evals, float *d_probs, int32_t max_rows,
-                  double flop_per_row) {
-    if (slot < 0 || slot > 1) throw CaError(CA_ERR_ARG, "net slot must be 0 or 1");
-    if (!fn || !d_states || !d_evals || !d_probs) throw CaError(CA_ERR_ARG, "ca_trainer_set_net_fn: null function or buffer");
-    if (max_rows < R * spe)
-      throw CaError(CA_ERR_ARG, "ca_trainer_set_net_fn: buffers of " + std::to_string(max_rows) + " rows, this trainer asks for up to " +
-                                        std::to_string(R * spe) + " (ca_trainer_request_rows)");
-    if (!(flop_per_row >= 0.0)) throw CaError(CA_ERR_ARG, "ca_trainer_set_net_fn: flop_per_row must be 0 (unknown) or positive");
-    install_net(slot, std::make_unique<ExternalNet>(fn, user, d_states, d_evals, d_probs, (size_t)max_rows, flop_per_row, &in_callback),
-                "ca_trainer_set_net_fn");
-  }
-
-  /* a new network takes its slot: the one path of set_net and set_net_fn */
+  /* a new network takes its slot */
   void install_net(int slot, std::unique_ptr<CoNet> fresh, const char *who) {
     if (slot == 0 && !fused.pools.empty() && !host_cache) { /* (host_cache: the pool and its table are that mode's, whatever the network) */
       /* Does the new network change whether fused training keeps an evaluation cache?  The tables are part of the
@@ -1004,29 +968,14 @@ struct ca_trainer {
    * the games hold evaluations that were never written, so the generation is over until ca_trainer_reset. */
   void check_callback() {
     for (int slot = 0; slot < 2; ++slot)
-      if (nets[slot] && nets[slot]->callback_failed()) {
-        callback_failed = true;
-        invalidate();
-        throw CaError(CA_ERR_CALLBACK, "the caller-supplied network function of slot " + std::to_string(slot) + " returned non-zero");
-      }
-  }
-  void need_no_failed_callback(const char *who) const {
-    if (callback_failed)
-      throw CaError(CA_ERR_STATE, std::string(who) + ": a caller-supplied network function failed in this generation; it cannot go on -- "
-                                                     "start a new one with ca_trainer_reset");
+      if (nets[slot] && nets[slot]->callback_failed()) invalidate(), callback.check(nets[slot].get(), "slot " + std::to_string(slot));
   }
 
-  /* nn.h range_exceeded: an f16x3 network met an operand beyond fp16's range -- its outputs since are NaN or wrong */
-  bool net_used = false; /* a network launch has been queued since the range flags were last read */
   void check_net_range() {
     if (!net_used) return; /* (no copy and stream wait per slot when nothing ran) */
     /* the device flag is sticky for the life of the network object: net_used is cleared only when every slot is clean, so
      * that every later check (export, score, write samples) raises again until set_net replaces the slot */
-    for (int slot = 0; slot < 2; ++slot)
-      if (nets[slot] && nets[slot]->range_exceeded(stream))
-        throw CaError(CA_ERR_ENGINE, std::string("network slot ") + std::to_string(slot) +
-                                             ": an activation left the fp16 range of the f16x3 kernels (|x| > 65504); the evaluations "
-                                             "are not valid -- use the float32-equivalent x6 kind of the same network");
+    for (int slot = 0; slot < 2; ++slot) ::check_net_range(nets[slot].get(), stream, "network slot " + std::to_string(slot));
     net_used = false;
   }
 
@@ -1034,7 +983,7 @@ struct ca_trainer {
    * the caller holds them (70 floats) and are widened to the kernels' 80-float rows on the device */
   void net_forward_host(int slot, const float *states, int32_t n, float *evals, float *probs) {
     if (slot < 0 || slot > 1 || !nets[slot]) throw CaError(CA_ERR_STATE, "net slot not set");
-    need_no_failed_callback("ca_trainer_net_forward");
+    callback.need_none_failed("ca_trainer_net_forward");
     CoNet *net = nets[slot].get();
     if (n < 0 || (size_t)n > net->max_rows()) throw CaError(CA_ERR_ARG, "net_forward: more rows than num_games*searches_per_eval");
     if (n == 0) return;
@@ -1045,8 +994,7 @@ struct ca_trainer {
     ensure(fw_rows, 1);
     rt_h2d(fw_in70.p, states, (size_t)n * CO_GAME_STATE_SIZE * 4, stream);
     rt_h2d(fw_rows.p, &n, 4, stream);
-    const int nb = n * CO_STATE_STRIDE / CO_WAVE + 1 < 1024 ? n * CO_STATE_STRIDE / CO_WAVE + 1 : 1024;
-    RT_LAUNCH(co_k_expand_rows, nb, CO_WAVE, stream, (const float *)fw_in70.p, fw_in.p, (int)n, nb);
+    expand_rows(fw_in70.p, fw_in.p, n, stream);
     net_used = true;
     net->forward(fw_in.p, n, fw_rows.p, fw_ev.p, fw_pr.p, stream);
     if (net->callback_failed()) {
@@ -1063,14 +1011,13 @@ struct ca_trainer {
    * diagnostics and the per-kernel roofline of bench.py */
   float net_bench(int slot, const float *states, int32_t rows, int32_t reps) {
     if (slot < 0 || slot > 1 || !nets[slot]) throw CaError(CA_ERR_STATE, "net slot not set");
-    if ((size_t)rows > nets[slot]->max_rows()) throw CaError(CA_ERR_ARG, "net_bench: too many rows");
-    std::vector<float> pad((size_t)rows * CO_STATE_STRIDE, 0.0f);
-    for (int r = 0; r < rows; ++r)
-      memcpy(&pad[(size_t)r * CO_STATE_STRIDE], states + (size_t)r * CO_GAME_STATE_SIZE, CO_GAME_STATE_SIZE * 4);
+    if ((size_t)rows > std::min(nets[slot]->max_rows(), (size_t)R * spe)) throw CaError(CA_ERR_ARG, "net_bench: too many rows");
     DevBuf<int32_t> d_n;
     d_n.alloc(1, stream);
-    rt_h2d(nn_in.p, pad.data(), pad.size() * 4, stream);
+    ensure(fw_in70, (size_t)rows * CO_GAME_STATE_SIZE); /* (not nn_in70: the protocols hand that one to the caller) */
+    rt_h2d(fw_in70.p, states, (size_t)rows * CO_GAME_STATE_SIZE * 4, stream);
     rt_h2d(d_n.p, &rows, 4, stream);
+    expand_rows(fw_in70.p, nn_in.p, rows, stream);
     net_used = true;
     nets[slot]->forward(nn_in.p, rows, d_n.p, nn_eval.p, nn_probs.p, stream); /* warm */
     Event e0, e1;
@@ -1179,7 +1126,7 @@ struct ca_trainer {
 
   bool run(int64_t max_iterations) {
     need_positions();
-    need_no_failed_callback("ca_trainer_run");
+    callback.need_none_failed("ca_trainer_run");
     if (host_cache)
       throw CaError(CA_ERR_STATE, "ca_trainer_run: the host-driven protocol drives this trainer's generations with the evaluation "
                                   "cache; switch it off first (ca_trainer_set_host_cache with a negative size)");
@@ -1210,7 +1157,7 @@ struct ca_trainer {
     e.arena_state = arena_state.p;
     e.row_counter = row_counter.p;
     int64_t it = 0;
-    int32_t st[5] = {0, 0, 0, 0, 0};
+    int32_t st[CO_AS_WORDS] = {};
     std::string failure;
     while (!finished && (max_iterations <= 0 || it < max_iterations)) {
       const bool timed = (it % poll) == poll - 1 || (max_iterations > 0 && it + 1 == max_iterations);
@@ -1226,7 +1173,7 @@ struct ca_trainer {
       if (timed) rt_event_record(ev[2], stream);
       net_used = true;
       for (int slot = 0; slot < 2; ++slot) /* get_predictions, main.pyx:74-81 */
-        nets[slot]->forward(nn_in.p, R * spe, arena_state.p + 3 + slot, nn_eval.p, nn_probs.p, stream);
+        nets[slot]->forward(nn_in.p, R * spe, arena_state.p + CO_AS_ROWS + slot, nn_eval.p, nn_probs.p, stream);
       if (nets[0]->callback_failed() || nets[1]->callback_failed()) break; /* (a caller-supplied network: nothing more is queued) */
       if (timed) rt_event_record(ev[3], stream);
       ++iterations;
@@ -1242,9 +1189,9 @@ struct ca_trainer {
         stats.mcts_timed_ms += rt_event_elapsed_ms(ev[0], ev[1]);
         stats.nn_timed_ms += rt_event_elapsed_ms(ev[2], ev[3]);
         stats.pack_ms += rt_event_elapsed_ms(ev[1], ev[2]) * poll;
-        stats.nn_timed_rows += st[3] + st[4];
+        stats.nn_timed_rows += st[CO_AS_ROWS] + st[CO_AS_ROWS + 1];
         ++stats.timed_launches;
-        if (!finished && st[1] > 4) {
+        if (!finished && st[CO_AS_EMPTY] > 4) {
           failure = "arena: no model has requests";
           break;
         }
@@ -1257,7 +1204,7 @@ struct ca_trainer {
     stats.estimate_device_times(false);
     check_callback();
     if (!failure.empty()) throw CaError(CA_ERR_ENGINE, failure);
-    pack(st[0]); /* refresh the done flag and the batch description */
+    pack(st[CO_AS_MODEL]); /* refresh the done flag and the batch description */
     check_errors();
     unsigned long long rows = 0;
     rt_d2h(&rows, row_counter.p, 8, stream);
@@ -1281,18 +1228,8 @@ struct ca_tourney {
   std::mt19937 generator;                      /* default constructed: seed 5489 (tourney.h:43) */
   std::vector<uint32_t> seeds;
   std::unique_ptr<ca_trainer> pool;            /* built at the first query after the last addMatch */
-  struct PendingNet { /* either weights of one of the library's kinds or the caller's function (ca_tourney_set_net_fn) */
-    int kind = 0;
-    std::vector<float> w;
-    ca_net_fn fn = nullptr;
-    void *user = nullptr;
-    float *d_states = nullptr, *d_evals = nullptr, *d_probs = nullptr;
-    int32_t max_rows = 0;
-    double flop_per_row = 0.0;
-  };
-  bool in_callback = false;     /* inside a caller-supplied network function: entry points are refused (host.h co_guard) */
-  bool callback_failed = false; /* ... and one returned non-zero: the tournament cannot go on */
-  std::map<int, PendingNet> net_specs;         /* fused mode: model id -> network (ca_tourney_set_net) */
+  CallbackState callback{false, false, "; this tournament cannot go on"}; /* a caller-supplied network function that failed */
+  std::map<int, NetSpec> net_specs;            /* fused mode: model id -> network (ca_tourney_set_net, _set_net_fn) */
   std::map<int, std::unique_ptr<CoNet>> nets;
   int dev() const { return device; }
   bool exact_offsets = false;                  /* ca_tourney_set_exact_offsets */
@@ -1303,8 +1240,7 @@ struct ca_tourney {
    * table).  The evaluation arrays persist between rounds like the driver's, so the result is the
    * one the compat protocol gives with the same networks. */
   bool run(int64_t max_rounds) {
-    if (callback_failed)
-      throw CaError(CA_ERR_STATE, "ca_tourney_run: a caller-supplied network function failed; this tournament cannot go on");
+    callback.need_none_failed("ca_tourney_run");
     ca_trainer &p = built();
     std::vector<int> ids;
     for (auto &m : matches)
@@ -1318,19 +1254,7 @@ struct ca_tourney {
       if (!nets.count(id)) {
         auto it = net_specs.find(id);
         if (it == net_specs.end()) throw CaError(CA_ERR_STATE, "ca_tourney_run: no network for model id " + std::to_string(id));
-        const PendingNet &spec = it->second;
-        std::unique_ptr<CoNet> n;
-        if (spec.fn) {
-          if (spec.max_rows < p.G * p.spe)
-            throw CaError(CA_ERR_ARG, "ca_tourney_set_net_fn: buffers of " + std::to_string(spec.max_rows) + " rows for model id " +
-                                              std::to_string(id) + ", this tournament asks for up to " + std::to_string(p.G * p.spe));
-          n = std::make_unique<ExternalNet>(spec.fn, spec.user, spec.d_states, spec.d_evals, spec.d_probs, (size_t)spec.max_rows,
-                                            spec.flop_per_row, &in_callback);
-        } else {
-          n.reset(p.make_net(spec.kind, spec.w.data(), spec.w.size()));
-        }
-        if (!n) throw CaError(CA_ERR_ARG, "unknown net kind or bad weight count");
-        nets[id] = std::move(n);
+        nets[id] = it->second.make((size_t)p.G * p.spe, p.stream, &callback, " for model id " + std::to_string(id) + ", this tournament");
       }
     }
     int64_t rounds = 0;
@@ -1351,9 +1275,8 @@ struct ca_tourney {
       if ((rounds & 7) == 0 || (max_rounds > 0 && rounds >= max_rounds)) done = p.tourney_poll_done(ids.front());
     }
     if (failed_id >= 0) {
-      callback_failed = true;
       p.drain();
-      throw CaError(CA_ERR_CALLBACK, "the caller-supplied network function of model id " + std::to_string(failed_id) + " returned non-zero");
+      callback.check(nets[failed_id].get(), "model id " + std::to_string(failed_id));
     }
     p.tourney_rounds_done();
     if (done) all_done(); /* (writes the match logs) */
@@ -1444,6 +1367,27 @@ extern "C" int ca_device_check(int device) {
 #endif
 }
 
+/* An entry point without a handle (the *_create calls, the stand-alone test entry points): the device checked and made
+ * current, then the body under the guard ... */
+template <class F>
+static int on_device(int device, F &&body) {
+  const int rc = ca_device_check(device);
+  if (rc != CA_OK) return rc;
+  return co_guard([&] {
+    rt_set_device(device);
+    body();
+  });
+}
+/* ... with a stream of its own */
+template <class F>
+static int on_device_stream(int device, F &&body) {
+  return on_device(device, [&] {
+    Stream s;
+    s.create();
+    body(s);
+  });
+}
+
 /* the reference's to_play: 0 / 1 an arena model, anything else every game */
 static int norm_to_play(int to_play) { return to_play == 0 || to_play == 1 ? to_play : -1; }
 
@@ -1461,9 +1405,7 @@ extern "C" int ca_trainer_create(const ca_config *cfg, ca_trainer **out) {
     g_last_error = "ca_trainer_create: invalid configuration (num_logged must be 0 on device)";
     return CA_ERR_ARG;
   }
-  int rc = ca_device_check(cfg->device);
-  if (rc != CA_OK) return rc;
-  return co_guard([&] {
+  return on_device(cfg->device, [&] {
     auto t = std::make_unique<ca_trainer>();
     t->init(*cfg);
     *out = t.release();
@@ -1489,11 +1431,13 @@ extern "C" int ca_trainer_do_iteration(ca_trainer *t, const float *ev, const flo
   return co_guard(t, [&] { *all_done = t->do_iteration(ev, pr, norm_to_play(to_play)) ? 1 : 0; });
 }
 extern "C" int ca_trainer_set_net(ca_trainer *t, int slot, int kind, const float *w, size_t n) {
-  return co_guard(t, [&] { t->set_net(slot, kind, w, n); });
+  return co_guard(t, [&] { t->set_net(slot, NetSpec(kind, w, n), "ca_trainer_set_net"); });
 }
 extern "C" int ca_trainer_set_net_fn(ca_trainer *t, int slot, ca_net_fn fn, void *user, float *d_states, float *d_evals,
                                      float *d_probs, int32_t max_rows, double flop_per_row) {
-  return co_guard(t, [&] { t->set_net_fn(slot, fn, user, d_states, d_evals, d_probs, max_rows, flop_per_row); });
+  return co_guard(t, [&] {
+    t->set_net(slot, NetSpec("ca_trainer_set_net_fn", {fn, user, d_states, d_evals, d_probs, max_rows, flop_per_row}), "ca_trainer_set_net_fn");
+  });
 }
 extern "C" int ca_trainer_request_rows(ca_trainer *t, int32_t *rows) {
   return co_guard(t, [&] {
@@ -1572,9 +1516,7 @@ extern "C" int ca_trainer_trace(ca_trainer *t, int game, int32_t *out, int32_t c
 
 /* ---- Tourney C ABI */
 extern "C" int ca_tourney_create(int device, uint32_t arena_units, int trace, ca_tourney **out) {
-  int rc = ca_device_check(device);
-  if (rc != CA_OK) return rc;
-  return co_guard([&] {
+  return on_device(device, [&] {
     if (!out) throw CaError(CA_ERR_ARG, "null output pointer");
     auto t = std::make_unique<ca_tourney>();
     t->device = device;
@@ -1621,33 +1563,22 @@ extern "C" int ca_tourney_set_log_folder(ca_tourney *t, const char *log_folder) 
   });
 }
 
+/* the network of model `model_id`, made when the tournament next runs (NetSpec::make) */
+static void tourney_set_net(ca_tourney *t, int32_t model_id, NetSpec spec) {
+  if (model_id < 0) throw CaError(CA_ERR_ARG, "negative model ids are the dummy ids of random players");
+  t->net_specs[model_id] = std::move(spec);
+  t->nets.erase(model_id);
+}
 extern "C" int ca_tourney_set_net(ca_tourney *t, int32_t model_id, int32_t kind, const float *weights, size_t n_floats) {
   return co_guard(t, [&] {
-    if (model_id < 0) throw CaError(CA_ERR_ARG, "negative model ids are the dummy ids of random players");
     if (!weights || n_floats == 0) throw CaError(CA_ERR_ARG, "ca_tourney_set_net: no weights");
-    ca_tourney::PendingNet spec;
-    spec.kind = kind;
-    spec.w.assign(weights, weights + n_floats);
-    t->net_specs[model_id] = std::move(spec);
-    t->nets.erase(model_id);
+    tourney_set_net(t, model_id, NetSpec(kind, weights, n_floats).keep());
   });
 }
 extern "C" int ca_tourney_set_net_fn(ca_tourney *t, int32_t model_id, ca_net_fn fn, void *user, float *d_states, float *d_evals,
                                      float *d_probs, int32_t max_rows, double flop_per_row) {
   return co_guard(t, [&] {
-    if (model_id < 0) throw CaError(CA_ERR_ARG, "negative model ids are the dummy ids of random players");
-    if (!fn || !d_states || !d_evals || !d_probs) throw CaError(CA_ERR_ARG, "ca_tourney_set_net_fn: null function or buffer");
-    if (max_rows <= 0 || !(flop_per_row >= 0.0)) throw CaError(CA_ERR_ARG, "ca_tourney_set_net_fn: max_rows must be positive, flop_per_row 0 or positive");
-    ca_tourney::PendingNet spec;
-    spec.fn = fn;
-    spec.user = user;
-    spec.d_states = d_states;
-    spec.d_evals = d_evals;
-    spec.d_probs = d_probs;
-    spec.max_rows = max_rows;
-    spec.flop_per_row = flop_per_row;
-    t->net_specs[model_id] = std::move(spec);
-    t->nets.erase(model_id);
+    tourney_set_net(t, model_id, NetSpec("ca_tourney_set_net_fn", {fn, user, d_states, d_evals, d_probs, max_rows, flop_per_row}));
   });
 }
 extern "C" int ca_tourney_set_exact_offsets(ca_tourney *t, int32_t on) {
@@ -1730,38 +1661,27 @@ struct ca_net {
     if (rows_cap == 0) return;
     const rt_stream_t s = stream_arg ? (rt_stream_t)(intptr_t)stream_arg : (rt_stream_t)stream;
     if (used_once && used_on != s) rt_stream_wait(s, used);
-    const int nb = rows_cap * CO_STATE_STRIDE / CO_WAVE + 1 < 1024 ? rows_cap * CO_STATE_STRIDE / CO_WAVE + 1 : 1024;
-    RT_LAUNCH(co_k_expand_rows, nb, CO_WAVE, s, d_states, rows80.p, (int)rows_cap, nb);
+    expand_rows(d_states, rows80.p, rows_cap, s);
     net->forward(rows80.p, rows_cap, d_rows, d_evals, d_probs, s);
     rt_event_record(used, s);
     used_on = s;
     used_once = true;
     if (!stream_arg) {
       rt_sync(s);
-      if (net->range_exceeded(s))
-        throw CaError(CA_ERR_ENGINE, "ca_net_forward_device: an activation left the fp16 range of the f16x3 kernels (|x| > 65504); the "
-                                     "evaluations are not valid -- use the float32-equivalent x6 kind of the same network");
+      check_net_range(net.get(), s, "ca_net_forward_device");
     }
   }
 };
 
 extern "C" int ca_net_create(int device, int kind, const float *weights, size_t n_floats, int32_t max_rows, ca_net **out) {
-  int rc = ca_device_check(device);
-  if (rc != CA_OK) return rc;
-  return co_guard([&] {
+  return on_device_stream(device, [&](Stream &s) {
     if (!out || !weights || max_rows <= 0) throw CaError(CA_ERR_ARG, "ca_net_create: null argument or max_rows < 1");
     *out = nullptr;
-    rt_set_device(device);
     auto n = std::make_unique<ca_net>();
     n->device = device;
-    n->stream.create();
+    n->stream = std::move(s);
     n->used.create();
-    try {
-      n->net.reset(co_net_create(kind, weights, n_floats, (size_t)max_rows, n->stream));
-    } catch (const std::invalid_argument &e) { /* weights outside the kind's operand range (nn.h range_exceeded) */
-      throw CaError(CA_ERR_ARG, e.what());
-    }
-    if (!n->net) throw CaError(CA_ERR_ARG, "unknown net kind or bad weight count");
+    n->net = NetSpec(kind, weights, n_floats).make((size_t)max_rows, n->stream, nullptr);
     n->rows80.alloc((size_t)max_rows * CO_STATE_STRIDE, n->stream);
     rt_sync(n->stream);
     *out = n.release();
@@ -1774,25 +1694,14 @@ extern "C" int ca_net_forward_device(ca_net *n, const float *d_states, int32_t r
 extern "C" void ca_net_destroy(ca_net *n) { delete n; }
 
 /* ---- stand-alone test entry points, each on a stream of its own */
-static Stream device_stream(int device) {
-  rt_set_device(device);
-  Stream s;
-  s.create();
-  return s;
-}
 
 extern "C" int ca_rules_legal_moves(int device, const uint64_t *boards, const uint32_t *metas, int32_t n, uint32_t *masks,
                                     int32_t *is_lines) {
-  int rc = ca_device_check(device);
-  if (rc != CA_OK) return rc;
-  return co_guard([&] {
-    const Stream ts = device_stream(device);
+  return on_device_stream(device, [&](Stream &ts) {
     DevBuf<uint64_t> b;
     DevBuf<uint32_t> m, mk;
     DevBuf<int32_t> ln;
-    b.alloc(n, ts); m.alloc(n, ts); mk.alloc((size_t)n * 3, ts); ln.alloc(n, ts);
-    rt_h2d(b.p, boards, (size_t)n * 8, ts);
-    rt_h2d(m.p, metas, (size_t)n * 4, ts);
+    b.upload(boards, n, ts); m.upload(metas, n, ts); mk.alloc((size_t)n * 3, ts); ln.alloc(n, ts);
     RT_LAUNCH(co_k_rules_batch, n, CO_WAVE, ts, (const uint64_t *)b.p, (const uint32_t *)m.p, n, mk.p, ln.p);
     rt_d2h(masks, mk.p, (size_t)n * 12, ts);
     rt_d2h(is_lines, ln.p, (size_t)n * 4, ts);
@@ -1801,18 +1710,12 @@ extern "C" int ca_rules_legal_moves(int device, const uint64_t *boards, const ui
 }
 
 extern "C" int ca_rules_do_move(int device, uint64_t *boards, uint32_t *metas, const int32_t *moves, int32_t n, float *states) {
-  int rc = ca_device_check(device);
-  if (rc != CA_OK) return rc;
-  return co_guard([&] {
-    const Stream ts = device_stream(device);
+  return on_device_stream(device, [&](Stream &ts) {
     DevBuf<uint64_t> b;
     DevBuf<uint32_t> m;
     DevBuf<int32_t> mv;
     DevBuf<float> st;
-    b.alloc(n, ts); m.alloc(n, ts); mv.alloc(n, ts); st.alloc((size_t)n * CO_STATE_STRIDE, ts);
-    rt_h2d(b.p, boards, (size_t)n * 8, ts);
-    rt_h2d(m.p, metas, (size_t)n * 4, ts);
-    rt_h2d(mv.p, moves, (size_t)n * 4, ts);
+    b.upload(boards, n, ts); m.upload(metas, n, ts); mv.upload(moves, n, ts); st.alloc((size_t)n * CO_STATE_STRIDE, ts);
     RT_LAUNCH(co_k_domove_batch, n, CO_WAVE, ts, b.p, m.p, (const int32_t *)mv.p, n, st.p);
     std::vector<float> tmp((size_t)n * CO_STATE_STRIDE);
     rt_d2h(boards, b.p, (size_t)n * 8, ts);
@@ -1825,17 +1728,11 @@ extern "C" int ca_rules_do_move(int device, uint64_t *boards, uint32_t *metas, c
 }
 
 extern "C" int ca_rules_rows(int device, uint64_t *boards, uint32_t *metas, const int32_t *moves, int32_t n, uint32_t *masks) {
-  int rc = ca_device_check(device);
-  if (rc != CA_OK) return rc;
-  return co_guard([&] {
-    const Stream ts = device_stream(device);
+  return on_device_stream(device, [&](Stream &ts) {
     DevBuf<uint64_t> b;
     DevBuf<uint32_t> m, mk;
     DevBuf<int32_t> mv;
-    b.alloc(n, ts); m.alloc(n, ts); mk.alloc((size_t)n * 3, ts); mv.alloc(n, ts);
-    rt_h2d(b.p, boards, (size_t)n * 8, ts);
-    rt_h2d(m.p, metas, (size_t)n * 4, ts);
-    rt_h2d(mv.p, moves, (size_t)n * 4, ts);
+    b.upload(boards, n, ts); m.upload(metas, n, ts); mv.upload(moves, n, ts); mk.alloc((size_t)n * 3, ts);
     RT_LAUNCH(co_k_rules_rows, (n + 3) / 4, CO_WAVE, ts, b.p, m.p, (const int32_t *)mv.p, n, mk.p);
     rt_d2h(boards, b.p, (size_t)n * 8, ts);
     rt_d2h(metas, m.p, (size_t)n * 4, ts);
@@ -1845,20 +1742,15 @@ extern "C" int ca_rules_rows(int device, uint64_t *boards, uint32_t *metas, cons
 }
 
 extern "C" int ca_rng_draw(int device, uint32_t seed, int32_t n, int32_t chunk, uint32_t *out) {
-  int rc = ca_device_check(device);
-  if (rc != CA_OK) return rc;
-  return co_guard([&] {
+  return on_device_stream(device, [&](Stream &ts) {
     if (chunk < 1 || chunk > CO_WAVE) throw CaError(CA_ERR_ARG, "chunk must be 1..64");
-    const Stream ts = device_stream(device);
     std::vector<uint32_t> x(CO_MT_N);
     x[0] = seed;
     for (int i = 1; i < CO_MT_N; ++i) x[i] = 1812433253u * (x[i - 1] ^ (x[i - 1] >> 30)) + (uint32_t)i;
     DevBuf<uint32_t> mt, o;
     DevBuf<int32_t> idx;
-    mt.alloc(CO_MT_N, ts); o.alloc(n, ts); idx.alloc(1, ts);
-    int32_t i0 = CO_MT_N;
-    rt_h2d(mt.p, x.data(), CO_MT_N * 4, ts);
-    rt_h2d(idx.p, &i0, 4, ts);
+    const int32_t i0 = CO_MT_N;
+    mt.upload(x.data(), CO_MT_N, ts); idx.upload(&i0, 1, ts); o.alloc(n, ts);
     RT_LAUNCH(co_k_rng_draw, 1, CO_WAVE, ts, mt.p, idx.p, n, chunk, o.p);
     rt_d2h(out, o.p, (size_t)n * 4, ts);
     rt_sync(ts);
@@ -1866,13 +1758,9 @@ extern "C" int ca_rng_draw(int device, uint32_t seed, int32_t n, int32_t chunk, 
 }
 
 extern "C" int ca_fp_probe(int device, const float *in, int32_t n, float *out) {
-  int rc = ca_device_check(device);
-  if (rc != CA_OK) return rc;
-  return co_guard([&] {
-    const Stream ts = device_stream(device);
+  return on_device_stream(device, [&](Stream &ts) {
     DevBuf<float> di, dout;
-    di.alloc((size_t)n * 8, ts); dout.alloc((size_t)n * 8, ts);
-    rt_h2d(di.p, in, (size_t)n * 32, ts);
+    di.upload(in, (size_t)n * 8, ts); dout.alloc((size_t)n * 8, ts);
     RT_LAUNCH(co_k_fp_probe, (n + CO_WAVE - 1) / CO_WAVE, CO_WAVE, ts, (const float *)di.p, n, dout.p);
     rt_d2h(out, dout.p, (size_t)n * 32, ts);
     rt_sync(ts);

@@ -78,6 +78,27 @@
 #define CO_WC_MEAN 18   /* [2] the smoothed mean, in 1/256 scans */
 #define CO_WC_CUTS 32   /* steps cut (ca_stats.steps_cut) */
 
+/* ---- The words host and kernels pass each other, by name */
+/* EngineParams::ctl, written by co_k_scan: batch rows, all done, OR of the games' error bits (as 0 / 1), games not done */
+enum { CO_CTL_ROWS, CO_CTL_ALL_DONE, CO_CTL_ANY_ERROR, CO_CTL_NOT_DONE, CO_CTL_WORDS };
+/* EngineParams::arena_state: model of this iteration, consecutive empty batches, model of the next iteration (committed
+ * by the next entry scan), [2] batch rows for network slot 0 / 1 (the idle network's count is 0) */
+enum { CO_AS_MODEL, CO_AS_EMPTY, CO_AS_NEXT, CO_AS_ROWS, CO_AS_WORDS = CO_AS_ROWS + 2 };
+/* a word of EngineParams::pack_counter: (games still running << 32) | rows of the iteration's batch */
+#define CO_PACK_ONE_RUNNING (1ull << 32) /* what a running game adds */
+CO_HD uint32_t co_pack_rows(unsigned long long c) { return (uint32_t)(c & 0xFFFFFFFFull); }
+CO_HD uint32_t co_pack_running(unsigned long long c) { return (uint32_t)(c >> 32); }
+/* EvalCache::count is [2][CO_CACHE_COUNT_STRIDE] by iteration parity, EvalCache::totals [CO_CACHE_TOTALS] */
+#define CO_CACHE_COUNT_STRIDE 4
+#define CO_CACHE_TOTALS 2
+/* the outcome of sample i of a game of `plies` samples (selfplayer.cpp:79-113): the last mover wins unless the game is
+ * drawn; the sign alternates backwards */
+CO_HD float co_sample_outcome(int result, int plies, int i) {
+  float e = result == CO_RESULT_DRAW ? 0.0f : 1.0f;
+  if ((plies - 1 - i) & 1) e = (float)((double)e * -1.0);
+  return e;
+}
+
 struct GameCtl {
   int32_t to_play;    /* SelfPlayer::to_play_ */
   int32_t done;       /* Trainer::is_done_[i] */
@@ -161,8 +182,8 @@ struct EvalCache {
                         * (stored by the first wave of p's next search launch, which stream order puts behind them) */
   int32_t *in_idx;     /* [pool rows] request rows the network evaluates this iteration, compact ... */
   int32_t *out_idx;    /* ... and the element of val each one writes */
-  uint32_t *count;     /* [2][4] by iteration parity: {rows to evaluate, 0, 0, 0} */
-  unsigned long long *totals; /* [2] rows evaluated in earlier iterations, - */
+  uint32_t *count;     /* [2][CO_CACHE_COUNT_STRIDE] by iteration parity: {rows to evaluate, 0, 0, 0} */
+  unsigned long long *totals; /* [CO_CACHE_TOTALS] rows evaluated in earlier iterations, - */
 };
 
 struct EngineParams {
@@ -194,9 +215,7 @@ struct EngineParams {
   int32_t *read_offset;
   /* fused arena (Trainer test mode with both networks on the device): the model to move lives on
    * the device so that the host need not look at every iteration (main.pyx:150-154 flips it when
-   * its batch comes back empty).  [0] model of this iteration, [1] consecutive empty batches,
-   * [2] model of the next iteration (committed by the next entry scan), [3], [4] batch rows for
-   * network slot 0 / 1 (the idle network's count is 0).  Null: `to_play` is the host's. */
+   * its batch comes back empty): the words CO_AS_*.  Null: `to_play` is the host's. */
   int32_t *arena_state;
   int32_t scan_phase; /* co_k_scan: 0 = offsets at entry of an iteration, 1 = batch after the search */
   /* pool */
@@ -224,7 +243,7 @@ struct EngineParams {
   int32_t *row_idx;       /* [rows] fused training: batch row m of this iteration is request row row_idx[m] of `req`
                            * (= slot * searches_per_eval + pending leaf); the network kernels gather through it (nn.h CoNetIO) */
   float *nn_in70;         /* [rows][70] the same rows as Trainer::writeRequests lays them out (compat mode), or null */
-  int32_t *ctl;           /* [4] written by co_k_scan: batch rows, all done, OR of the games' error bits, games not done */
+  int32_t *ctl;           /* [CO_CTL_WORDS] written by co_k_scan */
   float *samples;       /* [G][CO_MAX_PLIES][166] */
   int32_t *trace;       /* [G][CO_TRACE_CAP] or null */
   /* per-game text logs (Trainer's num_logged, trainer.cpp:243-250): the first num_logged games record what the
@@ -235,9 +254,9 @@ struct EngineParams {
   const int32_t *log_index; /* tournament: record of match i, or -1 (addMatch's `logging`); null = games 0 .. num_logged - 1 */
   int32_t *all_done;    /* [1] */
   unsigned long long *row_counter; /* [1] rows handed to the network so far */
-  /* fused training mode: K3 packs its own requests.  pack_counter[iteration & 1] =
-   * (games still running << 32) | rows of this iteration's batch; the other one is
-   * cleared for the next iteration.  The network kernels read the low word. */
+  /* fused training mode: K3 packs its own requests.  pack_counter[iteration & 1] is this iteration's word
+   * (co_pack_rows, co_pack_running); the other one is cleared for the next iteration.  The network kernels
+   * read the low word. */
   int32_t fused_pack;
   int32_t defer_handover; /* fused mode: end a game's step at the hand-over (see mcts.h co_choose_move_and_continue) */
   /* fused training: a game's step stops selecting after this many PUCT scans and carries on in the next launch, its

@@ -88,9 +88,10 @@ int co_guard(F &&body) {
     return CA_ERR_DEVICE;
   }
 }
-/* is the handle inside a caller-supplied network function (ca_net_fn)?  Handles without such a flag: never */
+/* is the handle inside a caller-supplied network function (ca_net_fn)?  Handles without that state (net_host.h
+ * CallbackState): never */
 template <class H>
-auto co_in_callback(const H *h, int) -> decltype((bool)h->in_callback) { return h->in_callback; }
+auto co_in_callback(const H *h, int) -> decltype((bool)h->callback.in_callback) { return h->callback.in_callback; }
 template <class H>
 bool co_in_callback(const H *, long) { return false; }
 

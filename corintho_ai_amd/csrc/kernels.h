@@ -41,7 +41,7 @@ CO_DEV int co_game_active(const EngineParams &P, int g, const GameCtl &gc, int t
 CO_KERNEL co_k_scan(EngineParams P) {
   int G = P.num_games;
   /* fused arena: the entry scan works for the model staged by the previous iteration */
-  const int tp = P.arena_state ? P.arena_state[P.scan_phase == 0 ? 2 : 0] : P.to_play;
+  const int tp = P.arena_state ? P.arena_state[P.scan_phase == 0 ? CO_AS_NEXT : CO_AS_MODEL] : P.to_play;
   int chunk = (G + CO_WAVE - 1) / CO_WAVE;
   LV(int, csum);
   LV(int, nd);
@@ -101,25 +101,25 @@ CO_KERNEL co_k_scan(EngineParams P) {
       P.req_offset[G] = run;
       P.all_done[0] = not_done == 0;
       if (P.ctl) {
-        P.ctl[0] = run;
-        P.ctl[1] = not_done == 0;
-        P.ctl[2] = any_error;
-        P.ctl[3] = not_done;
+        P.ctl[CO_CTL_ROWS] = run;
+        P.ctl[CO_CTL_ALL_DONE] = not_done == 0;
+        P.ctl[CO_CTL_ANY_ERROR] = any_error;
+        P.ctl[CO_CTL_NOT_DONE] = not_done;
       }
       if (P.row_counter && (!P.arena_state || P.scan_phase == 1)) P.row_counter[0] += (unsigned long long)run;
       if (P.arena_state) {
         if (P.scan_phase == 0) {
-          P.arena_state[0] = tp; /* commit: the search, the compaction and the network of this iteration see it */
+          P.arena_state[CO_AS_MODEL] = tp; /* commit: the search, the compaction and the network of this iteration see it */
         } else {
-          P.arena_state[3 + (tp == 0 ? 1 : 0)] = run; /* get_predictions, main.pyx:74-81: slot 1 serves model 0 */
-          P.arena_state[3 + (tp == 0 ? 0 : 1)] = 0;
+          P.arena_state[CO_AS_ROWS + (tp == 0 ? 1 : 0)] = run; /* get_predictions, main.pyx:74-81: slot 1 serves model 0 */
+          P.arena_state[CO_AS_ROWS + (tp == 0 ? 0 : 1)] = 0;
           /* main.pyx:150-154: a model without requests hands over to the other one */
           if (not_done != 0 && run == 0) {
-            P.arena_state[2] = 1 - tp;
-            P.arena_state[1] += 1;
+            P.arena_state[CO_AS_NEXT] = 1 - tp;
+            P.arena_state[CO_AS_EMPTY] += 1;
           } else {
-            P.arena_state[2] = tp;
-            P.arena_state[1] = 0;
+            P.arena_state[CO_AS_NEXT] = tp;
+            P.arena_state[CO_AS_EMPTY] = 0;
           }
         }
       }
@@ -131,7 +131,7 @@ CO_KERNEL co_k_compact(EngineParams P) {
   int g = CO_BLOCK_IDX;
   if (g >= P.num_games) return;
   GameCtl gc = P.games[g];
-  if (!co_game_active(P, g, gc, P.arena_state ? P.arena_state[0] : P.to_play)) return;
+  if (!co_game_active(P, g, gc, P.arena_state ? P.arena_state[CO_AS_MODEL] : P.to_play)) return;
   int n = gc.n_pending;
   const float *src = P.req + (size_t)g * P.searches_per_eval * CO_STATE_STRIDE;
   float *dst = P.nn_in + (size_t)P.req_offset[g] * CO_STATE_STRIDE;
@@ -161,7 +161,7 @@ CO_KERNEL co_k_expand_rows(const float *in70, float *out80, int rows, int nblock
 }
 
 /* ---- request rows for a caller and the caller's answers back: the host-driven protocol with the evaluation cache
- * (pools.h HostNet, the caller on the host) and a caller-supplied network inside the run (pools.h ExternalNet, the caller's
+ * (net_host.h HostNet, the caller on the host) and a caller-supplied network inside the run (net_host.h ExternalNet, the caller's
  * function on the device).  One thread per float, so a wavefront reads and writes 64 consecutive floats; no LDS, no
  * atomics.  Float e belongs to wavefront e / 64 of the launch: */
 #define CO_HOST_ROWS_FLOAT ((CO_BLOCK_IDX * CO_WAVES_PER_BLOCK + CO_WAVE_IN_BLOCK) * CO_WAVE + lane)
@@ -207,9 +207,7 @@ CO_KERNEL co_k_write_samples(EngineParams P, int n_games, const int32_t *sample_
   size_t off = (size_t)sample_offset[g];
   const float *smp = P.samples + (size_t)g * CO_MAX_PLIES * CO_SAMPLE_FLOATS;
   for (int i = n - 1; i >= 0; --i) {
-    /* the last mover wins unless the game is drawn; sign alternates backwards */
-    float evaluation = result == CO_RESULT_DRAW ? 0.0f : 1.0f;
-    if ((n - 1 - i) & 1) evaluation = (float)((double)evaluation * -1.0);
+    const float evaluation = co_sample_outcome(result, n, i);
     const float *st = smp + (size_t)i * CO_SAMPLE_FLOATS;
     const float *pol = st + CO_GAME_STATE_SIZE;
     for (int k = 0; k < CO_NUM_SYMMETRIES; ++k) {
@@ -238,11 +236,7 @@ CO_KERNEL co_k_pack_samples(EngineParams P, int n_games, const int32_t *sample_o
   int total = n * CO_SAMPLE_FLOATS;
   FOR_LANES {
     for (int i = lane; i < total; i += CO_WAVE) state_policy[off * CO_SAMPLE_FLOATS + i] = smp[i];
-    for (int i = lane; i < n; i += CO_WAVE) {
-      float e = result == CO_RESULT_DRAW ? 0.0f : 1.0f;
-      if ((n - 1 - i) & 1) e = (float)((double)e * -1.0);
-      outcome[off + i] = e;
-    }
+    for (int i = lane; i < n; i += CO_WAVE) outcome[off + i] = co_sample_outcome(result, n, i);
   }
 }
 

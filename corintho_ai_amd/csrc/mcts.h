@@ -2495,7 +2495,7 @@ CO_DEV int co_game_step(CoWave &w, const float *eval, const float *probs) {
  * (trainer.cpp:176-196 training, :216-229 arena, tourney.cpp:63-72) */
 CO_DEV int co_step_gate(const EngineParams &P, int g, const GameCtl &gc) {
   if (gc.done || gc.error) return 0;
-  const int tp = P.arena_state ? P.arena_state[0] : P.to_play;
+  const int tp = P.arena_state ? P.arena_state[CO_AS_MODEL] : P.to_play;
   if (P.pcfg) {
     if (P.pcfg[2 * g + gc.to_play].model_id != tp) return 0; /* tourney.cpp:66 */
   } else if (tp == 0 || tp == 1) {
@@ -2604,7 +2604,7 @@ CO_DEV void co_cache_resolve(const EngineParams &P, CoWave &w, int g, int n, int
   const uint64_t nm = WAVE_BALLOT(need);
   const uint32_t cnt = (uint32_t)co_popc64(nm);
   uint32_t base = 0u;
-  if (cnt) base = co_atomic_add_u32(C.count + 4 * par, cnt);
+  if (cnt) base = co_atomic_add_u32(C.count + CO_CACHE_COUNT_STRIDE * par, cnt);
   int32_t *psrc = P.pend_src + (size_t)g * P.searches_per_eval;
   FOR_LANES {
     if (lane < n) {
@@ -2662,8 +2662,8 @@ CO_DEV void co_pool_housekeeping(const EngineParams &P, int g) {
           /* the other parity's counter of rows to evaluate was the previous iteration's (its network launch is
            * over): book it, clear it for the next iteration */
           const int op = (P.iteration & 1) ^ 1;
-          P.cache.totals[0] += P.cache.count[4 * op];
-          P.cache.count[4 * op] = 0u;
+          P.cache.totals[0] += P.cache.count[CO_CACHE_COUNT_STRIDE * op];
+          P.cache.count[CO_CACHE_COUNT_STRIDE * op] = 0u;
           /* this launch stands behind the pool's network launch of iteration - 1 in its stream: entries the pool
            * claimed in iterations < iteration (stamps <= iteration) hold their outputs -- tell the other pools */
           co_lane_store_coherent_u32(P.cache.done + (P.cache.pool_bits >> CO_CACHE_POOL_SHIFT), (uint32_t)P.iteration);
@@ -2796,18 +2796,18 @@ CO_DEV void co_step_tail(const EngineParams &P, CoWave &w, int g, int done) {
     /* (still running, no rows.  A held game is counted in the pool's CO_WC_CUTS word only, which the host copies with this
      * one at every poll to tell a window without rows from "no game has a request"; a count of held games in bits 56.. of
      * this word was 8 bits wide and read 256 of them as none) */
-    co_atomic_add_u64_noret(P.pack_counter + (P.iteration & 1), 1ull << 32);
+    co_atomic_add_u64_noret(P.pack_counter + (P.iteration & 1), CO_PACK_ONE_RUNNING);
     if (P.work_counter) co_atomic_add_u64_noret(P.work_counter + CO_WC_CUTS, 1ull); /* (ca_stats.steps_cut) */
     w.gc.noise_held = w.noise_words;
     return;
   }
-  if (packs) old = co_atomic_add_u64(P.pack_counter + (P.iteration & 1), (1ull << 32) | (unsigned long long)w.gc.n_pending);
+  if (packs) old = co_atomic_add_u64(P.pack_counter + (P.iteration & 1), CO_PACK_ONE_RUNNING | (unsigned long long)w.gc.n_pending);
   CO_PH_MEM(26);
   if (!done && !w.gc.error && w.gc.n_pending > 0) co_capture_noise(w);
   CO_PH_MEM(27);
   if (packs) {
     const int n = w.gc.n_pending;
-    const int base = P.pool_row_base + (int)(unsigned)(old & 0xFFFFFFFFull);
+    const int base = P.pool_row_base + (int)co_pack_rows(old);
     w.gc.row_off = base;
     /* the rows stay in the game's request area; the network kernels read them through an index array (nn.h CoNetIO):
      * with the evaluation cache the rows it has to evaluate (co_cache_resolve), else every row of the batch.  (Until
@@ -2844,7 +2844,7 @@ CO_DEV void co_mcts_step_wave(const EngineParams &P, int g) {
   const TreeCtl tc0 = P.trees[2 * g], tc1 = P.trees[2 * g + 1];
   const int gate = co_step_gate(P, g, gc);
   if (gate != 1) {
-    if (gate == 2 && P.fused_pack) co_atomic_add_u64(P.pack_counter + (P.iteration & 1), 1ull << 32); /* still running */
+    if (gate == 2 && P.fused_pack) co_atomic_add_u64(P.pack_counter + (P.iteration & 1), CO_PACK_ONE_RUNNING); /* still running */
     return;
   }
   CoWave w;

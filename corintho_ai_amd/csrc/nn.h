@@ -50,7 +50,7 @@ struct CoNetIO {
    * the other pools' search and network kernels): a kernel family may then choose for throughput per CU rather than for
    * the latency of this launch (nn_rescnn.hip rcp_small_begin). */
   int32_t alone = 1;
-  /* First row of the launch in the buffers of a caller-supplied network (pools.h ExternalNet): each pool of a fused run
+  /* First row of the launch in the buffers of a caller-supplied network (net_host.h ExternalNet): each pool of a fused run
    * works in its own slice of them.  Every other network ignores it. */
   int32_t row_base = 0;
 };
@@ -71,7 +71,7 @@ struct CoNet {
    * net was created left the range, its outputs are not to be trusted -- the engine turns that into an error and names
    * the float32-equivalent x6 kind.  Kinds with float32's exponent range never report. */
   virtual bool range_exceeded(rt_stream_t) { return false; }
-  /* A caller-supplied network (pools.h ExternalNet) whose function returned non-zero: its forward() queues nothing any
+  /* A caller-supplied network (net_host.h ExternalNet) whose function returned non-zero: its forward() queues nothing any
    * more, and whoever drives a run looks here after queueing and leaves.  clear_failure(): a new generation. */
   virtual bool callback_failed() const { return false; }
   virtual void clear_failure() {}

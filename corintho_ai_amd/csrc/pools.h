@@ -88,9 +88,12 @@ struct Pool {
   int word_iter[2] = {0, 0}; /* Trainer::searches_done_ of the iteration whose counter word was copied */
   int first_start = 0;       /* iteration at which the stagger releases the pool's first game (trainer.cpp:184-186) */
   int timed[2] = {0, 0};     /* the window's last iteration carries the events */
-  Pinned<unsigned long long> word; /* [parity] counter word copied at the end of window parity 0 / 1, [2 + parity] rows the
-                             * network evaluated in that iteration (evaluation cache), [4 + parity] the pool's steps cut so far
-                             * (work_counter[CO_WC_CUTS]) */
+  struct Seen { /* what the end of a window copies from the device, for its last iteration */
+    unsigned long long pack; /* the pool's counter word (co_pack_rows, co_pack_running) */
+    unsigned long long cuts; /* the pool's steps cut so far (work_counter[CO_WC_CUTS]) */
+    uint32_t evaluated;      /* rows the network evaluated (evaluation cache) */
+  };
+  Pinned<Seen> seen; /* [window parity], page-locked */
   unsigned long long cuts_seen = 0; /* that count at the last window collected (at the start of the run: read when it began) */
   /* the pool's own arrays of the evaluation cache, and its view of them and of the shared table (hdr null: no cache) */
   DevBuf<int32_t> in_idx, out_idx;
@@ -110,7 +113,7 @@ struct Pool {
       for (auto &e : ev[w]) e.create();
       polled[w].create();
     }
-    word.alloc(6);
+    seen.alloc(2);
     quiet.create();
   }
 
@@ -119,8 +122,8 @@ struct Pool {
     const size_t rows = (size_t)n * spe;
     in_idx.alloc(rows, st);
     out_idx.alloc(rows, st);
-    count.alloc(8, st);
-    totals.alloc(2, st);
+    count.alloc(2 * CO_CACHE_COUNT_STRIDE, st);
+    totals.alloc(CO_CACHE_TOTALS, st);
     cache.hdr = table.hdr.p;
     cache.val = table.val.p;
     cache.mask = (uint32_t)(table.entries - 1);
@@ -144,103 +147,6 @@ struct Pool {
     timed[0] = timed[1] = 0;
     word_iter[0] = word_iter[1] = 0;
     first_start = first;
-  }
-};
-
-/* one thread per float (kernels.h co_k_host_rows_out / _in) */
-static int host_rows_blocks(size_t floats) { return (int)((floats + CO_WAVE * CO_WAVES_PER_BLOCK - 1) / (CO_WAVE * CO_WAVES_PER_BLOCK)); }
-
-/* The "network" of the host-driven protocol with the evaluation cache (ca_trainer_set_host_cache): its forward pass is
- * the round trip to the caller.  forward() -- FusedRun queues it behind the search launch like any network -- gathers the
- * rows the cache could not resolve into a dense [n][70] array for Trainer::writeRequests and has the protocol's flags
- * (co_k_scan: all done, any error) copied to the host with them; receive(), queued in front of the NEXT search launch,
- * scatters the caller's answers to the elements of the cache's value array a network kernel would have written. */
-struct HostNet : CoNet {
-  /* the trainer's, set once */
-  size_t rows_cap = 0;
-  float *rows70 = nullptr;               /* [rows_cap][70] the rows to hand out */
-  float *ev_in = nullptr, *pr_in = nullptr; /* [rows_cap], [rows_cap][96] the caller's answers on the device */
-  int32_t *d_ctl = nullptr, *h_ctl = nullptr; /* EngineParams::ctl and its page-locked copy */
-  EngineParams scan_params = {};         /* the games, for co_k_scan */
-  /* of the last forward(): where the answers go */
-  const int32_t *out_idx = nullptr;
-  float *val = nullptr;
-
-  size_t max_rows() const override { return rows_cap; }
-  int kind() const override { return 0; }
-  double flop_per_row() const override { return 0.0; }
-  void forward(const float *d_in, int32_t cap, const int32_t *d_rows, float *d_eval, float *, rt_stream_t s,
-               const CoNetIO &io = CoNetIO()) override {
-    if (!io.in_idx || !io.out_idx || io.eval_stride != CO_CACHE_VAL_FLOATS || io.probs_stride != CO_CACHE_VAL_FLOATS)
-      throw CaError(CA_ERR_STATE, "HostNet: rows that did not come through the evaluation cache");
-    if (cap < 0 || (size_t)cap > rows_cap) cap = (int32_t)rows_cap;
-    out_idx = io.out_idx;
-    val = d_eval;
-    if (cap > 0)
-      RT_LAUNCH(co_k_host_rows_out, host_rows_blocks((size_t)cap * CO_GAME_STATE_SIZE), CO_WAVE * CO_WAVES_PER_BLOCK, s, d_in, io.in_idx,
-                (const uint32_t *)d_rows, (int)cap, rows70);
-    RT_LAUNCH(co_k_scan, 1, CO_WAVE, s, scan_params);
-    rt_d2h(h_ctl, d_ctl, 16, s);
-  }
-  /* evals[n], probs[n][96]: the answers to the n rows of the last forward(), in its order */
-  void receive(const float *evals, const float *probs, int32_t n, rt_stream_t s) {
-    if (n <= 0) return;
-    if ((size_t)n > rows_cap || !out_idx) throw CaError(CA_ERR_STATE, "HostNet: answers to rows that were not handed out");
-    rt_h2d(ev_in, evals, (size_t)n * 4, s);
-    rt_h2d(pr_in, probs, (size_t)n * CO_NUM_MOVES * 4, s);
-    RT_LAUNCH(co_k_host_rows_in, host_rows_blocks((size_t)n * (1 + CO_NUM_MOVES)), CO_WAVE * CO_WAVES_PER_BLOCK, s,
-              (const float *)ev_in, (const float *)pr_in, out_idx, (const uint32_t *)nullptr, (int)n, val, val + 4,
-              (int)CO_CACHE_VAL_FLOATS, (int)CO_CACHE_VAL_FLOATS);
-  }
-};
-
-/* The caller's own network inside a run (ca_trainer_set_net_fn, ca_tourney_set_net_fn): forward() lays the launch's request
- * rows out densely in the caller's DEVICE buffer -- 70 floats each, the rows beyond the device's count zeroed -- calls the
- * caller's function on the launch's stream, and scatters the answers it leaves in the caller's two output buffers to where
- * a network kernel would have written them (CoNetIO).  Nothing comes back to the host: the function is handed the
- * capacity of the launch and a device pointer to the count.  The pools of a fused run call forward() on their own
- * streams without waiting for each other; each works in rows [io.row_base, io.row_base + rows_cap) of the buffers. */
-struct ExternalNet : CoNet {
-  ca_net_fn fn = nullptr;
-  void *user = nullptr;
-  float *states = nullptr, *evals = nullptr, *probs = nullptr; /* the caller's: [rows_cap][70], [rows_cap], [rows_cap][96] */
-  size_t rows_cap = 0;
-  double flops = 0.0;
-  bool *in_callback = nullptr; /* the owner's guard flag: an entry point called from inside fn is refused (host.h co_guard) */
-  bool failed = false;
-
-  ExternalNet(ca_net_fn f, void *u, float *d_states, float *d_evals, float *d_probs, size_t max_rows, double flop_per_row,
-              bool *guard)
-      : fn(f), user(u), states(d_states), evals(d_evals), probs(d_probs), rows_cap(max_rows), flops(flop_per_row), in_callback(guard) {}
-  size_t max_rows() const override { return rows_cap; }
-  int kind() const override { return 0; }
-  double flop_per_row() const override { return flops; }
-  bool callback_failed() const override { return failed; }
-  void clear_failure() override { failed = false; }
-  void forward(const float *d_in, int32_t cap, const int32_t *d_rows, float *d_eval, float *d_probs, rt_stream_t s,
-               const CoNetIO &io = CoNetIO()) override {
-    if (failed || cap <= 0) return;
-    const size_t row0 = (size_t)io.row_base;
-    if (io.row_base < 0 || row0 + (size_t)cap > rows_cap)
-      throw CaError(CA_ERR_STATE, "caller-supplied network: rows " + std::to_string(row0) + " .. " + std::to_string(row0 + (size_t)cap) +
-                                          " are beyond the " + std::to_string(rows_cap) + " rows of its buffers");
-    RT_LAUNCH(co_k_host_rows_out, host_rows_blocks((size_t)cap * CO_GAME_STATE_SIZE), CO_WAVE * CO_WAVES_PER_BLOCK, s, d_in, io.in_idx,
-              (const uint32_t *)d_rows, (int)cap, states + row0 * CO_GAME_STATE_SIZE);
-    *in_callback = true;
-    int rc;
-    try {
-      rc = fn(user, (int32_t)row0, cap, d_rows, (void *)(intptr_t)s);
-    } catch (...) { /* (a function that throws through a C boundary has already broken its contract) */
-      rc = -1;
-    }
-    *in_callback = false;
-    if (rc != 0) {
-      failed = true;
-      return;
-    }
-    RT_LAUNCH(co_k_host_rows_in, host_rows_blocks((size_t)cap * (1 + CO_NUM_MOVES)), CO_WAVE * CO_WAVES_PER_BLOCK, s,
-              (const float *)(evals + row0), (const float *)(probs + row0 * CO_NUM_MOVES), io.out_idx, (const uint32_t *)d_rows, (int)cap,
-              d_eval, d_probs, (int)io.eval_stride, (int)io.probs_stride);
   }
 };
 
@@ -309,8 +215,8 @@ struct FusedRun {
       table.empty(pools[0].st, true);
       for (auto &q : pools) {
         if (!mid_generation) { /* (in mid-generation -- a new network, set_net -- the rows evaluated so far stay counted: ADVICE round 4) */
-          rt_memset(q.count.p, 0, 32, q.st);
-          rt_memset(q.totals.p, 0, 16, q.st);
+          rt_memset(q.count.p, 0, 2 * CO_CACHE_COUNT_STRIDE * 4, q.st);
+          rt_memset(q.totals.p, 0, CO_CACHE_TOTALS * 8, q.st);
         }
         rt_sync(q.st);
         q.c_inserted_est = 0;
@@ -333,12 +239,12 @@ struct FusedRun {
   void collect(Pool &q, int parity) {
     if (!q.launched[parity]) return;
     rt_event_sync(q.polled[parity]);
-    unsigned long long c = q.word[parity];
-    const unsigned long long evaluated = q.cache.hdr ? q.word[2 + parity] & 0xFFFFFFFFull : c & 0xFFFFFFFFull;
-    q.running = (int)(c >> 32); /* (bits 32..63: the pool's running games, the low word its rows) */
+    const Pool::Seen &w = q.seen[parity];
+    const uint32_t evaluated = q.cache.hdr ? w.evaluated : co_pack_rows(w.pack);
+    q.running = (int)co_pack_running(w.pack);
     /* steps cut in the window: games held their leaves back (mcts.h co_step_tail), which submits no rows for them */
-    const bool holding = q.word[4 + parity] != q.cuts_seen;
-    q.cuts_seen = q.word[4 + parity];
+    const bool holding = w.cuts != q.cuts_seen;
+    q.cuts_seen = w.cuts;
     if (q.timed[parity]) {
       /* one iteration per window is timed (three event records per launch pair cost 1-4 % of
        * the wall time); its batch size is the counter word just read */
@@ -353,8 +259,8 @@ struct FusedRun {
       q.timed[parity] = 0;
     }
     q.launched[parity] = 0;
-    q.finished = (c >> 32) == 0;
-    if (!q.finished && (c & 0xFFFFFFFFull) == 0 && !holding) {
+    q.finished = q.running == 0;
+    if (!q.finished && co_pack_rows(w.pack) == 0 && !holding) {
       /* main.pyx:161-163 raises when NO game has a request.  A pool whose first game the
        * staggered start (trainer.cpp:184-186) has not released yet has running games and no
        * rows by construction: that is not the reference's error condition */
@@ -448,7 +354,7 @@ struct FusedRun {
       io.out_idx = q.cache.out_idx;
       io.eval_stride = CO_CACHE_VAL_FLOATS;
       io.probs_stride = CO_CACHE_VAL_FLOATS;
-      d_rows = (const int32_t *)(q.cache.count + 4 * (iteration & 1));
+      d_rows = (const int32_t *)(q.cache.count + CO_CACHE_COUNT_STRIDE * (iteration & 1));
       d_eval = q.cache.val;
       d_probs = q.cache.val + 4;
     } else {
@@ -501,9 +407,10 @@ struct FusedRun {
         for (auto &q : pools) {
           if (q.finished) continue;
           const size_t p = &q - &pools[0];
-          rt_d2h(&q.word[parity], run_params.pack_counter + CO_PACK_STRIDE * p + counter_slot, 8, q.st);
-          if (q.cache.hdr) rt_d2h(&q.word[2 + parity], q.cache.count + 4 * counter_slot, 4, q.st);
-          rt_d2h(&q.word[4 + parity], work_counter + (size_t)CO_WC_WORDS * p + CO_WC_CUTS, 8, q.st);
+          Pool::Seen &w = q.seen[parity];
+          rt_d2h(&w.pack, run_params.pack_counter + CO_PACK_STRIDE * p + counter_slot, 8, q.st);
+          if (q.cache.hdr) rt_d2h(&w.evaluated, q.cache.count + CO_CACHE_COUNT_STRIDE * counter_slot, 4, q.st);
+          rt_d2h(&w.cuts, work_counter + (size_t)CO_WC_WORDS * p + CO_WC_CUTS, 8, q.st);
           q.word_iter[parity] = iteration - 1;
           rt_event_record(q.polled[parity], q.st);
         }
@@ -533,12 +440,12 @@ struct FusedRun {
     int64_t rows = 0;
     for (auto &q : pools) {
       /* booked by the probe kernels, plus the two iterations whose counters nobody has booked yet (at most one is non-zero) */
-      unsigned long long tot[2] = {0, 0};
-      uint32_t cnt[8] = {0};
-      rt_d2h(tot, q.totals.p, 16, q.st);
-      rt_d2h(cnt, q.count.p, 32, q.st);
+      unsigned long long tot = 0;
+      uint32_t cnt[2 * CO_CACHE_COUNT_STRIDE] = {0};
+      rt_d2h(&tot, q.totals.p, 8, q.st);
+      rt_d2h(cnt, q.count.p, sizeof cnt, q.st);
       rt_sync(q.st);
-      rows += (int64_t)tot[0] + cnt[0] + cnt[4];
+      rows += (int64_t)tot + cnt[0] + cnt[CO_CACHE_COUNT_STRIDE];
     }
     return rows;
   }

@@ -43,6 +43,7 @@ static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
   return v;
 }
 #define CO_DEV static inline
+#define CO_HD static inline /* host and device (engine_defs.h: the decoders of the shared words) */
 #define CO_COLD static /* the product build keeps these out of line (see below) */
 #define CO_COLD2 static
 #define CO_KERNEL static void
@@ -186,6 +187,7 @@ extern thread_local int co_emu_block_idx;
 // ------------------------------------------------------------------- gfx950
 #include <hip/hip_runtime.h>
 #define CO_DEV __device__ __forceinline__
+#define CO_HD __host__ __device__ __forceinline__
 /* once-per-ply and rare paths (move choice, the sequential simulation, slot recycling).  Round 5 measured them as real calls
  * (-DCO_COLD_NOINLINE: the search kernel's spills go from 328 scalar + 36 vector registers to 54 + 58, its scratch from
  * 240 to 1208 bytes per lane): a generation of 4096 games with the reference's network takes 262 ms instead of 181 --

@@ -338,7 +338,10 @@ int ca_tourney_do_iteration(ca_tourney *t, const float *evaluations, const float
 /* Fused mode (not in the reference): the networks run on the GPU too.  ca_tourney_set_net
  * gives model `model_id` its network (kinds and weight layouts as ca_trainer_set_net);
  * ca_tourney_run plays the loop of rating/tourney.pyx:122-160 on the device, model ids in
- * ascending order, until every match is done or `max_rounds` rounds have run (0 = no limit). */
+ * ascending order, until every match is done or `max_rounds` rounds have run (0 = no limit).
+ * The network is built when ca_tourney_run first needs it, and what is wrong with it is reported
+ * there as ca_trainer_set_net reports it: CA_ERR_ARG for an unknown kind, a bad weight count or
+ * f16x3 weights beyond fp16's range. */
 int ca_tourney_set_net(ca_tourney *t, int32_t model_id, int32_t kind, const float *weights, size_t n_floats);
 /* the caller's own network for model `model_id` (see ca_trainer_set_net_fn); max_rows is checked against matches x the
  * largest searches_per_eval when the tournament is built (CA_ERR_ARG from ca_tourney_run) */

@@ -1,0 +1,197 @@
+// engine_host_driver.cpp -- TEST: the host side of the engine driven through the C ABI (include/corintho_hip.h) by a
+// plain program, linked with the emulation build of engine.hip (tests/emu) so that it runs on the CPU under the host
+// compiler's sanitizers (tests/emu/sanitize.mk, target host_driver) with nothing loaded into an interpreter.  It walks
+// the paths that build networks, pass the protocol's words between "device" and host, and move samples: a fused
+// generation, the host-driven protocol with the evaluation cache, a caller-supplied network that works and one that
+// fails, a tournament, the three sample exits and a stand-alone network.  Exit status 0: every call returned what it
+// should and the sample exits agree.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../include/corintho_hip.h"
+
+namespace {
+constexpr int GS = 70, NM = 96, NSYM = 8, MLP = 1;
+
+#define EXPECT(rc, call)                                                                              \
+  do {                                                                                                \
+    const int got_ = (call);                                                                          \
+    if (got_ != (rc)) {                                                                               \
+      fprintf(stderr, "%s:%d: %s returned %d, expected %d (%s)\n", __FILE__, __LINE__, #call, got_, (rc), ca_last_error()); \
+      exit(1);                                                                                        \
+    }                                                                                                 \
+  } while (0)
+#define OK(call) EXPECT(CA_OK, call)
+#define REQUIRE(cond)                                                     \
+  do {                                                                    \
+    if (!(cond)) {                                                        \
+      fprintf(stderr, "%s:%d: %s does not hold\n", __FILE__, __LINE__, #cond); \
+      exit(1);                                                            \
+    }                                                                     \
+  } while (0)
+
+// mlp12x100 in the flat layout of nn.h: small pseudo-random kernels, BatchNorm at identity
+std::vector<float> mlp_weights(uint32_t seed) {
+  std::vector<float> w;
+  auto next = [&] {
+    seed = seed * 1664525u + 1013904223u;
+    return ((float)(seed >> 8) / (float)(1 << 24) - 0.5f) * 0.2f;
+  };
+  for (int l = 0; l < 12; ++l) {
+    for (int i = 0; i < (l == 0 ? GS : 100) * 100; ++i) w.push_back(next());
+    for (float c : {0.0f, 1.0f, 0.0f, 0.0f, 1.0f})  // bias, gamma, beta, moving mean, moving variance
+      w.insert(w.end(), 100, c);
+  }
+  for (int i = 0; i < 100; ++i) w.push_back(next());
+  w.push_back(0.0f);
+  for (int i = 0; i < 100 * NM; ++i) w.push_back(next());
+  w.insert(w.end(), NM, 0.0f);
+  return w;
+}
+
+ca_config config(int games, int searches, int spe) {
+  ca_config c;
+  memset(&c, 0, sizeof c);
+  c.num_games = games;
+  c.seed = 11;
+  c.max_searches = searches;
+  c.searches_per_eval = spe;
+  c.c_puct = 1.0f;
+  c.epsilon = 0.25f;
+  c.no_stagger = 1;
+  return c;
+}
+
+// a caller's network: value 0, uniform priors, for every row of the launch; fails from call `fail_at` on (0: never)
+struct UniformNet {
+  std::vector<float> states, evals, probs;
+  int calls = 0, fail_at = 0;
+  explicit UniformNet(int rows) : states((size_t)rows * GS), evals(rows), probs((size_t)rows * NM) {}
+};
+int uniform_net(void *user, int32_t row0, int32_t cap_rows, const int32_t *d_rows, void *) {
+  UniformNet *n = (UniformNet *)user;
+  if (n->fail_at && ++n->calls >= n->fail_at) return 1;
+  if (*d_rows > cap_rows) return 2;
+  for (int r = row0; r < row0 + cap_rows; ++r) {
+    n->evals[r] = 0.0f;
+    for (int m = 0; m < NM; ++m) n->probs[(size_t)r * NM + m] = 1.0f / NM;
+  }
+  return 0;
+}
+
+void fused_generation_and_sample_exits(const std::vector<float> &w) {
+  ca_config c = config(8, 24, 8);
+  c.resident = 4;
+  ca_trainer *t = nullptr;
+  OK(ca_trainer_create(&c, &t));
+  OK(ca_trainer_set_net(t, 0, MLP, w.data(), w.size()));
+  EXPECT(CA_ERR_ARG, ca_trainer_set_net(t, 0, 99, w.data(), w.size()));
+  int32_t done = 0, n = 0, packed = 0;
+  OK(ca_trainer_run(t, 0, &done));
+  REQUIRE(done == 1);
+  OK(ca_trainer_num_samples(t, &n));
+  REQUIRE(n > 0);
+  // writeSamples, export + expand, pack into "device" memory: the same rows
+  std::vector<float> gs((size_t)n * NSYM * GS), ev((size_t)n * NSYM), pr((size_t)n * NSYM * NM);
+  OK(ca_trainer_write_samples(t, gs.data(), ev.data(), pr.data()));
+  std::vector<float> sp((size_t)n * (GS + NM)), oc(n), dsp(sp.size()), doc(n);
+  OK(ca_trainer_export_samples(t, sp.data(), oc.data()));
+  EXPECT(CA_ERR_ARG, ca_trainer_pack_samples_device(t, dsp.data(), doc.data(), n - 1, &packed));
+  OK(ca_trainer_pack_samples_device(t, dsp.data(), doc.data(), n, &packed));
+  REQUIRE(packed == n && sp == dsp && oc == doc);
+  std::vector<float> gs2(gs.size()), ev2(ev.size()), pr2(pr.size());
+  OK(ca_expand_samples(0, sp.data(), oc.data(), n, gs2.data(), ev2.data(), pr2.data()));
+  REQUIRE(gs == gs2 && ev == ev2 && pr == pr2);
+  // net_forward and net_bench widen the caller's 70-float rows
+  std::vector<float> e(5), p(5 * NM);
+  float ms = 0;
+  OK(ca_trainer_net_forward(t, 0, gs.data(), 5, e.data(), p.data()));
+  OK(ca_trainer_net_bench(t, 0, gs.data(), 5, 1, &ms));
+  ca_trainer_destroy(t);
+}
+
+void host_cache_iterations() {
+  ca_config c = config(8, 24, 8);
+  ca_trainer *t = nullptr;
+  OK(ca_trainer_create(&c, &t));
+  OK(ca_trainer_set_host_cache(t, 0));
+  std::vector<float> states((size_t)64 * GS), evals(64, 0.0f), probs((size_t)64 * NM, 1.0f / NM);
+  for (int it = 0; it < 3; ++it) {
+    int32_t done = 0, n = 0;
+    OK(ca_trainer_do_iteration(t, evals.data(), probs.data(), -1, &done));
+    OK(ca_trainer_num_requests(t, -1, &n));
+    REQUIRE(!done && n > 0 && n <= 64);
+    OK(ca_trainer_write_requests(t, states.data(), -1));
+  }
+  ca_trainer_destroy(t);
+}
+
+void caller_supplied_network() {
+  ca_config c = config(8, 24, 8);
+  ca_trainer *t = nullptr;
+  OK(ca_trainer_create(&c, &t));
+  int32_t rows = 0, done = 0;
+  OK(ca_trainer_request_rows(t, &rows));
+  UniformNet net(rows);
+  EXPECT(CA_ERR_ARG, ca_trainer_set_net_fn(t, 0, nullptr, &net, net.states.data(), net.evals.data(), net.probs.data(), rows, 0.0));
+  EXPECT(CA_ERR_ARG, ca_trainer_set_net_fn(t, 0, uniform_net, &net, net.states.data(), net.evals.data(), net.probs.data(), rows - 1, 0.0));
+  OK(ca_trainer_set_net_fn(t, 0, uniform_net, &net, net.states.data(), net.evals.data(), net.probs.data(), rows, 0.0));
+  OK(ca_trainer_run(t, 0, &done));
+  REQUIRE(done == 1);
+  // the same generation again with a function that gives up at its third call
+  OK(ca_trainer_reset(t, 12));
+  net.fail_at = 3;
+  EXPECT(CA_ERR_CALLBACK, ca_trainer_run(t, 0, &done));
+  EXPECT(CA_ERR_STATE, ca_trainer_run(t, 0, &done));
+  net.fail_at = 0;
+  OK(ca_trainer_reset(t, 12));
+  OK(ca_trainer_run(t, 4, &done));
+  ca_trainer_destroy(t);
+}
+
+void tournament(const std::vector<float> &w0, const std::vector<float> &w1) {
+  ca_tourney *t = nullptr;
+  OK(ca_tourney_create(0, 0, 0, &t));
+  OK(ca_tourney_add_player(t, 0, 0, 16, 4, 1.0f, 0.25f, 0));
+  OK(ca_tourney_add_player(t, 1, 1, 12, 4, 1.0f, 0.25f, 0));
+  OK(ca_tourney_add_match(t, 0, 1, 0));
+  OK(ca_tourney_add_match(t, 1, 0, 0));
+  int32_t done = 0;
+  OK(ca_tourney_set_net(t, 0, MLP, w0.data(), w0.size()));
+  EXPECT(CA_ERR_STATE, ca_tourney_run(t, 0, &done));  // no network for model 1
+  OK(ca_tourney_set_net(t, 1, 99, w1.data(), w1.size()));
+  EXPECT(CA_ERR_ARG, ca_tourney_run(t, 0, &done));  // an unknown kind, as a trainer reports it
+  OK(ca_tourney_set_net(t, 1, MLP, w1.data(), w1.size()));
+  OK(ca_tourney_run(t, 0, &done));
+  REQUIRE(done == 1);
+  ca_tourney_destroy(t);
+}
+
+void stand_alone_network(const std::vector<float> &w) {
+  ca_net *n = nullptr;
+  EXPECT(CA_ERR_ARG, ca_net_create(0, 99, w.data(), w.size(), 16, &n));
+  OK(ca_net_create(0, MLP, w.data(), w.size(), 16, &n));
+  std::vector<float> states((size_t)16 * GS, 0.25f), evals(16), probs((size_t)16 * NM);
+  const int32_t rows = 9;
+  OK(ca_net_forward_device(n, states.data(), 16, &rows, evals.data(), probs.data(), nullptr));
+  EXPECT(CA_ERR_ARG, ca_net_forward_device(n, states.data(), 17, &rows, evals.data(), probs.data(), nullptr));
+  float sum = 0;
+  for (int m = 0; m < NM; ++m) sum += probs[(size_t)8 * NM + m];
+  REQUIRE(sum > 0.99f && sum < 1.01f);
+  ca_net_destroy(n);
+}
+}  // namespace
+
+int main() {
+  const std::vector<float> w0 = mlp_weights(1), w1 = mlp_weights(2);
+  fused_generation_and_sample_exits(w0);
+  host_cache_iterations();
+  caller_supplied_network();
+  tournament(w0, w1);
+  stand_alone_network(w0);
+  puts("engine_host_driver: ok");
+  return 0;
+}
