@@ -1,6 +1,7 @@
 // host.h -- the host plumbing every source shares: owners of runtime resources, the error type and the guard of the C
-// ABI's entry points, and what the inference networks' constructors have in common (16-bit operand terms, the f16
-// range flag, the folded BatchNorm constants).  Builds on rt.h, so it compiles under -DCO_EMU too.
+// ABI's entry points, and what the inference networks' constructors have in common (the f16 range flag, the folded
+// BatchNorm constants; the 16-bit operand terms of the split-precision kinds: nn_split.h).  Builds on rt.h, so it
+// compiles under -DCO_EMU too.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -108,67 +109,6 @@ int co_guard(H *h, F &&body) {
   });
 }
 
-/* ---- 16-bit operand terms of the split-precision kernels, as the host packs them */
-inline uint16_t bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  const uint32_t a = u & 0x7fffffffu;
-  if (a > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40); /* NaN: the rounding add could carry a full mantissa into a finite number */
-  if (a >= 0x7f7f8000u && a < 0x7f800000u) return (uint16_t)(u >> 16); /* ... or a finite one to infinity: the largest bf16, the next term takes the rest */
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-inline float bf16_to_f(uint16_t h) {
-  uint32_t u = (uint32_t)h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-/* float -> IEEE binary16, round to nearest even, subnormals kept (what v_cvt_f16_f32 gives); in integer arithmetic, so
- * that a host compiler without a 16-bit float type gives the same bits */
-inline uint16_t f16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  const uint32_t sign = (u >> 16) & 0x8000u;
-  u &= 0x7fffffffu;
-  if (u > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((u >> 13) & 0x1ffu)); /* NaN */
-  if (u >= 0x47800000u) return (uint16_t)(sign | 0x7c00u);                        /* 2^16 and beyond, infinity */
-  uint32_t r, rem, half;
-  if (u < 0x38800000u) { /* below 2^-14: a multiple of fp16's subnormal quantum 2^-24 */
-    if (u <= 0x33000000u) return (uint16_t)sign; /* up to 2^-25, the tie included: zero */
-    const int shift = 126 - (int)(u >> 23);      /* 14 .. 24 */
-    const uint32_t m = (u & 0x7fffffu) | 0x800000u;
-    r = m >> shift;
-    rem = m & ((1u << shift) - 1u);
-    half = 1u << (shift - 1);
-  } else {
-    r = (u - 0x38000000u) >> 13; /* exponent rebiased; a carry out of the mantissa below is the next exponent (65520: infinity) */
-    rem = u & 0x1fffu;
-    half = 0x1000u;
-  }
-  if (rem > half || (rem == half && (r & 1u))) ++r;
-  return (uint16_t)(sign | r);
-}
-inline float f16_to_f(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-  float f;
-  if (e == 0) { /* zero or subnormal: m quanta of 2^-24, exact */
-    f = (float)m * 5.9604644775390625e-8f;
-    return sign ? -f : f;
-  }
-  const uint32_t u = sign | (e == 31 ? 0x7f800000u : (e + 112u) << 23) | (m << 13);
-  memcpy(&f, &u, 4);
-  return f;
-}
-/* v -> nt 16-bit terms: bf16(v) (f16: fp16(v)), the same of the remainder, ... (the device's m3_split / rcs_split).  An
- * f16 caller checks |v| <= CO_F16_MAX first. */
-inline void split_terms(float v, int nt, bool f16, uint16_t *out) {
-  for (int i = 0; i < nt; ++i) {
-    out[i] = f16 ? f16_rne(v) : bf16_rne(v);
-    v = v - (f16 ? f16_to_f(out[i]) : bf16_to_f(out[i]));
-  }
-}
-
 /* the kernels' out-of-range flag of an f16x3 network (nn.h range_exceeded); never allocated: never raised */
 struct RangeFlag {
   DevBuf<uint32_t> flag;
@@ -189,4 +129,9 @@ inline void bn_fold(const float *gamma, const float *beta, const float *mean, co
     a[i] = (float)((double)gamma[i] / sqrt((double)var[i] + CO_BN_EPS));
     c[i] = (float)((double)beta[i] - (double)mean[i] * (double)a[i]);
   }
+}
+/* ... BatchNorm j (n channels) of the flat weights w with layout L (nn_layout.h) */
+template <class L>
+void bn_fold(const float *w, const L &lay, int j, int n, float *a, float *c) {
+  bn_fold(w + lay.gamma(j), w + lay.beta(j), w + lay.mean(j), w + lay.var(j), n, a, c);
 }

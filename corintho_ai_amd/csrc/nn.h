@@ -12,6 +12,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "nn_layout.h"
 #include "rt.h"
 
 #define CO_NET_NUM_MOVES 96
@@ -20,13 +21,35 @@
 #define CO_NET_RESCNN4_X3 3 /* same network and weights, convolutions at bf16x3 split precision */
 #define CO_NET_MLP12X100_X3 4 /* mlp12x100, same weights, dense layers at bf16x3 split precision */
 /* float32-equivalent arithmetic on the bf16 matrix pipe: both operands as three bf16 terms (their sum is the
- * float32 value), six MFMA products -- everything down to 2^-24 of a product is kept (nn_rescnn.hip) */
+ * float32 value), six MFMA products -- everything down to 2^-24 of a product is kept (nn_rescnn_split.h) */
 #define CO_NET_RESCNN4_X6 5
 #define CO_NET_MLP12X100_X6 6
 /* two fp16 terms per operand (22 significand bits), three MFMA products: float32-class arithmetic at the cost of bf16x3 */
 #define CO_NET_RESCNN4_H3 8
 #define CO_NET_MLP12X100_H3 9
 /* (7 was round 2's Winograd experiment, git 22960a5:tools/exp/archive, removed from the tree in round 6) */
+/* what a kind is: the network, the terms per operand of its matrix products (0: fp32 MFMA) and whether they are fp16 */
+enum CoNetFamily { CO_FAMILY_MLP12X100, CO_FAMILY_RESCNN4 };
+struct CoNetKind {
+  int kind, family, terms;
+  bool f16;
+};
+inline constexpr CoNetKind CO_NET_KINDS[] = {
+    {CO_NET_MLP12X100, CO_FAMILY_MLP12X100, 0, false},    {CO_NET_RESCNN4, CO_FAMILY_RESCNN4, 0, false},
+    {CO_NET_MLP12X100_X3, CO_FAMILY_MLP12X100, 2, false}, {CO_NET_RESCNN4_X3, CO_FAMILY_RESCNN4, 2, false},
+    {CO_NET_MLP12X100_X6, CO_FAMILY_MLP12X100, 3, false}, {CO_NET_RESCNN4_X6, CO_FAMILY_RESCNN4, 3, false},
+    {CO_NET_MLP12X100_H3, CO_FAMILY_MLP12X100, 2, true},  {CO_NET_RESCNN4_H3, CO_FAMILY_RESCNN4, 2, true},
+};
+inline const CoNetKind *co_net_kind(int kind) {
+  for (const CoNetKind &k : CO_NET_KINDS)
+    if (k.kind == kind) return &k;
+  return nullptr;
+}
+inline int co_net_kind_of(int family, int terms, bool f16) {
+  for (const CoNetKind &k : CO_NET_KINDS)
+    if (k.family == family && k.terms == terms && k.f16 == f16) return k.kind;
+  return 0;
+}
 
 /* mlp12x100 flat weight layout (float32), matching Keras get_weights() order of
  * wrapper.py:256-271:
@@ -37,6 +60,18 @@
 #define CO_MLP_WIDTH 100
 #define CO_MLP_NUM_WEIGHTS (70 * 100 + 500 + 11 * (100 * 100 + 500) + 100 + 1 + 100 * 96 + 96)
 #define CO_BN_EPS 1e-3
+/* rescnn4 flat weight layout (float32; specification: nets.py "rescnn4"), in order:
+ *   stem: kernel[3,3,10,64] (HWIO), bias[64], gamma, beta, mean, var [64 each]
+ *   blocks b = 0..3: conv1 (kernel[3,3,64,64], bias, gamma, beta, mean, var), conv2 (same)
+ *   policy: kernel[64,4], bias[4], gamma, beta, mean, var [4 each], dense kernel[64,96], bias[96]
+ *   value:  kernel[64,2], bias[2], gamma, beta, mean, var [2 each], dense1 kernel[32,64], bias[64],
+ *           dense2 kernel[64,1], bias[1] */
+#define CO_RESCNN4_NUM_WEIGHTS \
+  ((9 * 10 + 5) * 64 + 8 * (9 * 64 + 5) * 64 + (64 + 5) * 4 + 64 * 96 + 96 + (64 + 5) * 2 + 32 * 64 + 64 + 64 + 1)
+/* both layouts by name: nn_layout.h */
+static_assert(MlpLayout().nw == CO_MLP_NUM_WEIGHTS && MlpLayout::LAYERS == CO_MLP_LAYERS && MlpLayout::W == CO_MLP_WIDTH,
+              "MlpLayout is not the mlp12x100 layout above");
+static_assert(ResCnnLayout().nw == CO_RESCNN4_NUM_WEIGHTS && CO_RESCNN4_NUM_WEIGHTS == 312383, "ResCnnLayout is not the rescnn4 layout above");
 
 /* Optional indirection of a network launch (the evaluation cache of fused training): row r of the launch is read
  * from input row in_idx[r] and its outputs go to element out_idx[r] of arrays with the given strides (floats per
@@ -48,7 +83,7 @@ struct CoNetIO {
   int32_t probs_stride = CO_NET_NUM_MOVES;
   /* Does this launch have the GPU to itself?  False when other streams keep it busy too (fused training in several pools:
    * the other pools' search and network kernels): a kernel family may then choose for throughput per CU rather than for
-   * the latency of this launch (nn_rescnn.hip rcp_small_begin). */
+   * the latency of this launch (nn_rescnn_split.h rcp_small_begin). */
   int32_t alone = 1;
   /* First row of the launch in the buffers of a caller-supplied network (net_host.h ExternalNet): each pool of a fused run
    * works in its own slice of them.  Every other network ignores it. */

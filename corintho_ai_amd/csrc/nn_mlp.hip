@@ -189,24 +189,21 @@ struct MlpNet : CoNet {
     std::vector<float> wf((size_t)MLP_NLAYERS * MLP_LAYER_FLOATS, 0.0f);
     std::vector<float> bias((size_t)MLP_NLAYERS * MLP_PADW, 0.0f), ba((size_t)12 * MLP_PADW, 0.0f),
         bb((size_t)12 * MLP_PADW, 0.0f);
-    const float *p = w;
-    int in_dim = 70;
+    constexpr MlpLayout ML;
     auto put = [&](int l, int k, int o, float v) {
       /* wfrag[l][step = 4*tt + r][tile][lane = 16*q + i] = W[k = 16tt + 4q + r][o = 16*tile + i] */
       int tt = k / 16, q = (k % 16) / 4, r = k % 4;
       int tile = o / 16, i = o % 16;
       wf[(size_t)l * MLP_LAYER_FLOATS + ((size_t)(4 * tt + r) * MLP_TILES + tile) * 64 + 16 * q + i] = v;
     };
-    for (int l = 0; l < 12; ++l) {
-      const float *K = p, *b = K + (size_t)in_dim * 100, *ga = b + 100, *be = ga + 100, *mu = be + 100, *va = mu + 100;
-      for (int k = 0; k < in_dim; ++k)
+    for (int l = 0; l < ML.LAYERS; ++l) {
+      const float *K = w + ML.kernel(l), *b = w + ML.bias(l);
+      for (int k = 0; k < ML.in_dim(l); ++k)
         for (int o = 0; o < 100; ++o) put(l, k, o, K[(size_t)k * 100 + o]);
       for (int o = 0; o < 100; ++o) bias[(size_t)l * MLP_PADW + o] = b[o];
-      bn_fold(ga, be, mu, va, 100, &ba[(size_t)l * MLP_PADW], &bb[(size_t)l * MLP_PADW]);
-      p = va + 100;
-      in_dim = 100;
+      bn_fold(w, ML, l, 100, &ba[(size_t)l * MLP_PADW], &bb[(size_t)l * MLP_PADW]);
     }
-    const float *Kv = p, *bv = Kv + 100, *Kp = bv + 1, *bp = Kp + 9600;
+    const float *Kv = w + ML.kv, *bv = w + ML.bv, *Kp = w + ML.kp, *bp = w + ML.bp;
     for (int k = 0; k < 100; ++k) {
       for (int o = 0; o < 96; ++o) put(12, k, o, Kp[(size_t)k * 96 + o]);
       put(12, k, 96, Kv[k]);
@@ -218,12 +215,11 @@ struct MlpNet : CoNet {
     d_a.upload(ba.data(), ba.size(), s);
     d_b.upload(bb.data(), bb.size(), s);
     rt_sync(s);
-    RT_CHECK(hipFuncSetAttribute((const void *)co_k_mlp_forward, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 2 * MLP_LAYER_FLOATS * (int)sizeof(float)));
+    rt_max_dynamic_lds(co_k_mlp_forward, 2 * MLP_LAYER_FLOATS * sizeof(float));
   }
   size_t max_rows() const override { return cap; }
-  int kind() const override { return CO_NET_MLP12X100; }
-  double flop_per_row() const override { return 2.0 * (70 * 100 + 11 * 100 * 100 + 100 + 100 * 96); }
+  int kind() const override { return co_net_kind_of(CO_FAMILY_MLP12X100, 0, false); }
+  double flop_per_row() const override { return MlpLayout().flop_per_row(); }
   void forward(const float *d_in, int32_t rows_cap, const int32_t *d_rows, float *d_eval, float *d_probs,
                rt_stream_t s, const CoNetIO &io = CoNetIO()) override {
     int grid = (rows_cap + MLP_ROWS_PER_WG - 1) / MLP_ROWS_PER_WG;
@@ -238,13 +234,10 @@ CoNet *co_rescnn_split_create(const float *weights, size_t n_floats, size_t max_
 CoNet *co_mlp_split_create(const float *weights, size_t n_floats, size_t max_rows, rt_stream_t s, int nterms, bool f16 = false);
 
 CoNet *co_net_create(int kind, const float *weights, size_t n_floats, size_t max_rows, rt_stream_t s) {
-  if (kind == CO_NET_MLP12X100 && n_floats == (size_t)CO_MLP_NUM_WEIGHTS) return new MlpNet(weights, max_rows, s);
-  if (kind == CO_NET_RESCNN4) return co_rescnn_create(weights, n_floats, max_rows, s);
-  if (kind == CO_NET_RESCNN4_X3) return co_rescnn_split_create(weights, n_floats, max_rows, s, 2);
-  if (kind == CO_NET_RESCNN4_X6) return co_rescnn_split_create(weights, n_floats, max_rows, s, 3);
-  if (kind == CO_NET_MLP12X100_X3) return co_mlp_split_create(weights, n_floats, max_rows, s, 2);
-  if (kind == CO_NET_MLP12X100_X6) return co_mlp_split_create(weights, n_floats, max_rows, s, 3);
-  if (kind == CO_NET_RESCNN4_H3) return co_rescnn_split_create(weights, n_floats, max_rows, s, 2, true);
-  if (kind == CO_NET_MLP12X100_H3) return co_mlp_split_create(weights, n_floats, max_rows, s, 2, true);
-  return nullptr;
+  const CoNetKind *k = co_net_kind(kind);
+  if (!k) return nullptr;
+  if (k->family == CO_FAMILY_RESCNN4)
+    return k->terms ? co_rescnn_split_create(weights, n_floats, max_rows, s, k->terms, k->f16) : co_rescnn_create(weights, n_floats, max_rows, s);
+  if (k->terms) return co_mlp_split_create(weights, n_floats, max_rows, s, k->terms, k->f16);
+  return n_floats == (size_t)CO_MLP_NUM_WEIGHTS ? new MlpNet(weights, max_rows, s) : nullptr;
 }

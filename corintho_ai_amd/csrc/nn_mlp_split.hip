@@ -14,7 +14,7 @@
 // The dense layers of this network are too small for fp32 MFMA to pay: K5 spends as long on them
 // as the whole tree search takes.
 //
-// Mapping (the one of the residual CNN kernel, nn_rescnn.hip).  Transposed evaluation:
+// Mapping (the one of the residual CNN's split kernels, nn_rescnn_split.h).  Transposed evaluation:
 // out^T[feature][row] = W^T[feature][k] act^T[k][row]; a wave owns 32 batch rows = one MFMA
 // column tile and all 128 (padded) output features = four 32-row tiles, 64 accumulator
 // registers.  The accumulator layout (lane = (h, row), register 4g + i of tile T = feature
@@ -47,24 +47,10 @@
 #include "engine_defs.h"
 #include "host.h"
 #include "lds_dma.h"
+#include "nn_split.h"
 
-typedef float m3_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 m3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 m3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 m3_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 m3_f16x2 __attribute__((ext_vector_type(2)));
-typedef float m3_f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t m3_u32x4 __attribute__((ext_vector_type(4)));
-
-#define M3_NLAYERS 13
-#define M3_NCHUNKS (2 * M3_NLAYERS)
-#define M3_STEPS 7      /* hidden layers and heads: K = 112 */
-#define M3_STEPS_L0 5   /* input layer: K = 80 */
-#define M3_STEP_WORDS(NT) (4 * (NT) * 64 * 4) /* 4 output tiles x NT terms x 64 lanes x 4 words */
-#define M3_BIAS_WORDS 1024                     /* 128 biases in a 4 KiB piece: one LDS-DMA per wave */
-#define M3_CHUNK_WORDS(NT) (4 * M3_STEP_WORDS(NT) + M3_BIAS_WORDS) /* NT 2: 36 KB, NT 3: 52 KB */
+/* (the chunks' geometry, M3_NLAYERS .. M3_TOTAL_WORDS: nn_split.h) */
 #define M3_CHUNK_PIECES_PER_WAVE(NT) (M3_CHUNK_WORDS(NT) / 256 / 4)  /* 9 / 13 */
-#define M3_TOTAL_WORDS(NT) (M3_NCHUNKS * M3_CHUNK_WORDS(NT))
 #define M3_LDS_BYTES(NT) (3 * M3_CHUNK_WORDS(NT) * 4)
 #define M3_ROWS_PER_WG 128
 
@@ -79,54 +65,16 @@ __device__ __forceinline__ void m3_stage(const uint32_t *w, uint32_t lds_slot_ad
   }
 }
 
-/* (a, b) -> NT packed 16-bit pairs: the values rounded to bf16 (F16: fp16), then the successive remainders */
-template <int NT, bool F16 = false>
-__device__ __forceinline__ void m3_split(float a, float b, uint32_t (&t)[NT]) {
-  if constexpr (F16 && NT == 2) {
-    /* (as nn_rescnn.hip rcs_split: each second term is one mixed-precision fma, f16(a - float(t0.lo)); the difference is
-     * exact in float32, the one rounding is the conversion's -- the same bits in three instructions instead of five) */
-    const m3_f32x2 v2 = {a, b};
-    const uint32_t t0 = __builtin_bit_cast(uint32_t, __builtin_convertvector(v2, m3_f16x2));
-    uint32_t t1;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(t1)
-        : "v"(t0), "v"(a), "v"(b));
-    t[0] = t0;
-    t[1] = t1;
-    return;
-  }
-  m3_f32x2 v = {a, b};
-#pragma unroll
-  for (int i = 0; i < NT; ++i) {
-    if constexpr (F16) {
-      m3_f16x2 hb = __builtin_convertvector(v, m3_f16x2);
-      t[i] = __builtin_bit_cast(uint32_t, hb);
-      if (i + 1 < NT) {
-        m3_f32x2 hf = __builtin_convertvector(hb, m3_f32x2);
-        v = (m3_f32x2){v.x - hf.x, v.y - hf.y};
-      }
-    } else {
-      m3_bf16x2 hb = __builtin_convertvector(v, m3_bf16x2);
-      t[i] = __builtin_bit_cast(uint32_t, hb);
-      if (i + 1 < NT) {
-        m3_f32x2 hf = __builtin_convertvector(hb, m3_f32x2);
-        v = (m3_f32x2){v.x - hf.x, v.y - hf.y};
-      }
-    }
-  }
-}
-
 /* K steps S0 .. S0 + NS - 1 of a layer from one chunk: acc += W x.  XT = number of terms the B
  * operand has (1 for the input layer).  Products w_i x_j, i + j <= NT - 1, j < XT, largest
  * first.  Weight fragments of step s + 1 are requested from LDS before the MFMAs of step s issue. */
 template <int NT, int S0, int NS, int XT, bool F16 = false>
-__device__ __forceinline__ void m3_steps(m3_f32x16 (&acc)[4], const uint32_t (&b)[NT][8][4], const uint32_t *wl, int lane) {
-  m3_u32x4 a[2][NT][4];
+__device__ __forceinline__ void m3_steps(f32x16 (&acc)[4], const uint32_t (&b)[NT][8][4], const uint32_t *wl, int lane) {
+  u32x4 a[2][NT][4];
 #pragma unroll
   for (int to = 0; to < 4; ++to)
 #pragma unroll
-    for (int t = 0; t < NT; ++t) a[0][t][to] = *reinterpret_cast<const m3_u32x4 *>(wl + (((0 * 4 + to) * NT + t) * 64 + lane) * 4);
+    for (int t = 0; t < NT; ++t) a[0][t][to] = *reinterpret_cast<const u32x4 *>(wl + (((0 * 4 + to) * NT + t) * 64 + lane) * 4);
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     const int cur = s & 1, nxt = cur ^ 1;
@@ -135,9 +83,9 @@ __device__ __forceinline__ void m3_steps(m3_f32x16 (&acc)[4], const uint32_t (&b
       for (int to = 0; to < 4; ++to)
 #pragma unroll
         for (int t = 0; t < NT; ++t)
-          a[nxt][t][to] = *reinterpret_cast<const m3_u32x4 *>(wl + ((((s + 1) * 4 + to) * NT + t) * 64 + lane) * 4);
+          a[nxt][t][to] = *reinterpret_cast<const u32x4 *>(wl + ((((s + 1) * 4 + to) * NT + t) * 64 + lane) * 4);
     }
-    m3_u32x4 B[NT];
+    u32x4 B[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
@@ -150,19 +98,14 @@ __device__ __forceinline__ void m3_steps(m3_f32x16 (&acc)[4], const uint32_t (&b
         if (sum - i < XT) {
 #pragma unroll
           for (int to = 0; to < 4; ++to) {
-            if constexpr (F16)
-              acc[to] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(m3_f16x8, a[cur][i][to]),
-                                                               __builtin_bit_cast(m3_f16x8, B[sum - i]), acc[to], 0, 0, 0);
-            else
-              acc[to] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(m3_bf16x8, a[cur][i][to]),
-                                                                __builtin_bit_cast(m3_bf16x8, B[sum - i]), acc[to], 0, 0, 0);
+            co_mfma_32x32x16<F16>(acc[to], a[cur][i][to], B[sum - i]);
           }
         }
   }
 }
 
 /* accumulators := bias (feature 32T + 8g + 4h + i in register 4g + i of tile T) */
-__device__ __forceinline__ void m3_init_bias(m3_f32x16 (&acc)[4], const float *bias, int h) {
+__device__ __forceinline__ void m3_init_bias(f32x16 (&acc)[4], const float *bias, int h) {
 #pragma unroll
   for (int T = 0; T < 4; ++T)
 #pragma unroll
@@ -220,13 +163,13 @@ __global__ __launch_bounds__(256, 1) void co_k_mlp_forward_split_t(const float *
       const float4 v0 = *reinterpret_cast<const float4 *>(x + 16 * s + 4 * h);
       const float4 v1 = *reinterpret_cast<const float4 *>(x + 16 * s + 8 + 4 * h);
       uint32_t t[NT];
-      m3_split<NT, F16>(v0.x, v0.y, t);
+      co_split_pair<NT, F16>(v0.x, v0.y, t);
       b[0][s][0] = t[0];
-      m3_split<NT, F16>(v0.z, v0.w, t);
+      co_split_pair<NT, F16>(v0.z, v0.w, t);
       b[0][s][1] = t[0];
-      m3_split<NT, F16>(v1.x, v1.y, t);
+      co_split_pair<NT, F16>(v1.x, v1.y, t);
       b[0][s][2] = t[0];
-      m3_split<NT, F16>(v1.z, v1.w, t);
+      co_split_pair<NT, F16>(v1.z, v1.w, t);
       b[0][s][3] = t[0];
     }
   }
@@ -234,9 +177,8 @@ __global__ __launch_bounds__(256, 1) void co_k_mlp_forward_split_t(const float *
    * loads issued behind a transfer would wait for it */
   m3_stage<NT>(wfrag, lds_base, 0, wave, lane);
   m3_stage<NT>(wfrag, lds_base + M3_CHUNK_WORDS(NT) * 4u, 1, wave, lane);
-  m3_f32x16 acc[4];
-  uint32_t amax = 0u; /* F16: the running maximum of the packed first terms (nn.h range_exceeded; nn_rescnn.hip rcs_pk_max_f16: an
-                       * activation beyond fp16's range has the first term +inf; ReLU outputs are never negative) */
+  f32x16 acc[4];
+  uint32_t amax = 0u; /* F16: the running maximum of the packed first terms (nn_split.h co_pk_max_f16) */
   for (int l = 0; l < M3_NLAYERS; ++l) {
     const int c0 = 2 * l;
     {
@@ -265,16 +207,14 @@ __global__ __launch_bounds__(256, 1) void co_k_mlp_forward_split_t(const float *
             v0 = v0 > 0.0f ? v0 : 0.0f;
             v1 = v1 > 0.0f ? v1 : 0.0f;
             uint32_t t[NT];
-            m3_split<NT, F16>(v0, v1, t);
-            if constexpr (F16) asm("v_pk_max_f16 %0, %1, %2" : "=v"(amax) : "v"(amax), "v"(t[0]));
+            co_split_pair<NT, F16>(v0, v1, t);
+            if constexpr (F16) amax = co_pk_max_f16(amax, t[0]);
 #pragma unroll
             for (int i = 0; i < NT; ++i) b[i][2 * T + a][m] = t[i];
           }
     }
   }
-  if constexpr (F16) {
-    if (!((amax & 0x7FFFu) < 0x7C00u && ((amax >> 16) & 0x7FFFu) < 0x7C00u)) atomicOr(range_flag, 1u); /* (never in range: no lane enters) */
-  }
+  if constexpr (F16) co_raise_unless_f16_finite(amax, range_flag);
   /* heads: features 0..95 = policy logits (tiles 0..2), feature 96 = value (tile 3, g 0, h 0, i 0) */
   float mx = -INFINITY;
 #pragma unroll
@@ -307,7 +247,7 @@ __global__ __launch_bounds__(256, 1) void co_k_mlp_forward_split_t(const float *
 }
 #define co_k_mlp_forward_x3 co_k_mlp_forward_split_t<2>
 #define co_k_mlp_forward_x6 co_k_mlp_forward_split_t<3>
-/* "f16x3": two fp16 terms per operand (22 significand bits), three MFMA products -- see nn_rescnn.hip */
+/* "f16x3": two fp16 terms per operand (22 significand bits), three MFMA products -- see nn_rescnn_split.h */
 #define co_k_mlp_forward_h3 co_k_mlp_forward_split_t<2, true>
 
 /* ------------------------------------------------------------------ host */
@@ -318,105 +258,23 @@ struct MlpSplitNet : CoNet {
   int nt;
   bool f16;
   MlpSplitNet(const float *w, size_t max_rows, rt_stream_t s, int nterms, bool fp16 = false) : cap(max_rows), nt(nterms), f16(fp16) {
-    /* float64 copies of the 13 dense layers with BatchNorm l folded into layer l + 1 */
-    std::vector<std::vector<double>> K(M3_NLAYERS), B(M3_NLAYERS);
-    std::vector<int> kin(M3_NLAYERS), kout(M3_NLAYERS);
-    const float *p = w;
-    int in_dim = 70;
-    std::vector<double> a_prev, c_prev;
-    auto fold = [&](int l, const float *kern, const float *bias, int nin, int nout, int out_base) {
-      /* K[l][k * 128 + out_base + o], B[l][out_base + o] */
-      for (int o = 0; o < nout; ++o) {
-        double b = bias[o];
-        for (int k = 0; k < nin; ++k) {
-          double wv = kern[(size_t)k * nout + o];
-          if (!a_prev.empty()) {
-            b += c_prev[k] * wv;
-            wv *= a_prev[k];
-          }
-          K[l][(size_t)k * 128 + out_base + o] = wv;
-        }
-        B[l][out_base + o] = b;
-      }
-    };
-    for (int l = 0; l < 12; ++l) {
-      const float *kern = p, *b = kern + (size_t)in_dim * 100, *ga = b + 100, *be = ga + 100, *mu = be + 100, *va = mu + 100;
-      K[l].assign((size_t)128 * 128, 0.0);
-      B[l].assign(128, 0.0);
-      kin[l] = in_dim;
-      fold(l, kern, b, in_dim, 100, 0);
-      /* the float32 constants K5 applies (BatchNormalization inference, eps 1e-3) */
-      float a[100], c[100];
-      bn_fold(ga, be, mu, va, 100, a, c);
-      a_prev.assign(a, a + 100);
-      c_prev.assign(c, c + 100);
-      p = va + 100;
-      in_dim = 100;
-    }
-    const float *Kv = p, *bv = Kv + 100, *Kp = bv + 1, *bp = Kp + 9600;
-    K[12].assign((size_t)128 * 128, 0.0);
-    B[12].assign(128, 0.0);
-    kin[12] = 100;
-    fold(12, Kp, bp, 100, 96, 0);
-    fold(12, Kv, bv, 100, 1, 96);
-    const size_t step_words = (size_t)4 * nt * 256, chunk_words = 4 * step_words + M3_BIAS_WORDS;
-    std::vector<uint32_t> buf((size_t)M3_NCHUNKS * chunk_words, 0u);
-    for (int l = 0; l < M3_NLAYERS; ++l) {
-      const int ns = l == 0 ? M3_STEPS_L0 : M3_STEPS;
-      for (int st = 0; st < ns; ++st) {
-        /* chunk 2l holds steps 0..3 (and the bias), chunk 2l + 1 steps 4.. */
-        const size_t off = ((size_t)2 * l + (st >> 2)) * chunk_words + (size_t)(st & 3) * step_words;
-        for (int to = 0; to < 4; ++to)
-          for (int h = 0; h < 2; ++h)
-            for (int i = 0; i < 32; ++i)
-              for (int j = 0; j < 8; ++j) {
-                /* step st = 2T + a; k-slot (h, j) <-> input feature 32T + 8(2a + j/4) + 4h + j%4 */
-                int T = st >> 1, a = st & 1;
-                int k = 32 * T + 8 * (2 * a + (j >> 2)) + 4 * h + (j & 3);
-                int o = 32 * to + i;
-                float v = k < kin[l] ? (float)K[l][(size_t)k * 128 + o] : 0.0f;
-                if (f16 && !(fabsf(v) <= CO_F16_MAX))
-                  throw std::invalid_argument("mlp12x100h3: a weight of layer " + std::to_string(l) + " is " + std::to_string(v) +
-                                              " after the BatchNorm fold, beyond the fp16 range of the f16x3 kernels: use mlp12x100x6");
-                size_t lane = 32 * h + i;
-                uint16_t term[3];
-                split_terms(v, nt, f16, term);
-                for (int t = 0; t < nt; ++t)
-                  buf[off + (((size_t)to * nt + t) * 64 + lane) * 4 + j / 2] |= (uint32_t)term[t] << (16 * (j & 1));
-              }
-      }
-      for (int o = 0; o < 128; ++o) {
-        float b = (float)B[l][o];
-        memcpy(&buf[(size_t)2 * l * chunk_words + 4 * step_words + o], &b, 4);
-      }
-    }
+    const std::vector<uint32_t> buf = co_pack_mlp_split(w, nt, f16);
     d_w.upload(buf.data(), buf.size(), s);
     if (f16) range.alloc(s);
     rt_sync(s);
-    if (f16)
-      RT_CHECK(hipFuncSetAttribute((const void *)co_k_mlp_forward_h3, hipFuncAttributeMaxDynamicSharedMemorySize, M3_LDS_BYTES(2)));
-    else if (nt == 2)
-      RT_CHECK(hipFuncSetAttribute((const void *)co_k_mlp_forward_x3, hipFuncAttributeMaxDynamicSharedMemorySize, M3_LDS_BYTES(2)));
-    else
-      RT_CHECK(hipFuncSetAttribute((const void *)co_k_mlp_forward_x6, hipFuncAttributeMaxDynamicSharedMemorySize, M3_LDS_BYTES(3)));
+    rt_max_dynamic_lds(kernel(), M3_LDS_BYTES(nt));
   }
+  /* (the three instances have one signature) */
+  decltype(&co_k_mlp_forward_x3) kernel() const { return f16 ? co_k_mlp_forward_h3 : nt == 2 ? co_k_mlp_forward_x3 : co_k_mlp_forward_x6; }
   bool range_exceeded(rt_stream_t s) override { return range.read(s); }
   size_t max_rows() const override { return cap; }
-  int kind() const override { return f16 ? CO_NET_MLP12X100_H3 : nt == 2 ? CO_NET_MLP12X100_X3 : CO_NET_MLP12X100_X6; }
-  double flop_per_row() const override { return 2.0 * (70 * 100 + 11 * 100 * 100 + 100 + 100 * 96); }
+  int kind() const override { return co_net_kind_of(CO_FAMILY_MLP12X100, nt, f16); }
+  double flop_per_row() const override { return MlpLayout().flop_per_row(); }
   void forward(const float *d_in, int32_t rows_cap, const int32_t *d_rows, float *d_eval, float *d_probs,
                rt_stream_t s, const CoNetIO &io = CoNetIO()) override {
     int grid = (rows_cap + M3_ROWS_PER_WG - 1) / M3_ROWS_PER_WG;
     if (grid < 1) return;
-    if (f16)
-      RT_LAUNCH_LDS(co_k_mlp_forward_h3, grid, 256, M3_LDS_BYTES(2), s, d_in, d_rows, (const uint32_t *)d_w.p, d_eval, d_probs, io,
-                    range.ptr());
-    else if (nt == 2)
-      RT_LAUNCH_LDS(co_k_mlp_forward_x3, grid, 256, M3_LDS_BYTES(2), s, d_in, d_rows, (const uint32_t *)d_w.p, d_eval, d_probs, io,
-                    range.ptr());
-    else
-      RT_LAUNCH_LDS(co_k_mlp_forward_x6, grid, 256, M3_LDS_BYTES(3), s, d_in, d_rows, (const uint32_t *)d_w.p, d_eval, d_probs, io,
-                    range.ptr());
+    RT_LAUNCH_LDS(kernel(), grid, 256, M3_LDS_BYTES(nt), s, d_in, d_rows, (const uint32_t *)d_w.p, d_eval, d_probs, io, range.ptr());
   }
 };
 

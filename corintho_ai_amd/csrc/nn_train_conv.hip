@@ -378,33 +378,8 @@ static void fc_bn_bwd(rt_stream_t s, float *dOut, const float *out, const float 
 }
 
 /* ------------------------------------------------------------------ the network */
-#define FC_NBN 11       /* BatchNorms of rescnn4: nine convolutions, the policy and the value head's 1x1 */
+#define FC_NBN ResCnnLayout::NBN /* BatchNorms of rescnn4: nine convolutions, the policy and the value head's 1x1 */
 #define FC_STAT_LD 128  /* a BatchNorm's slot in stat: the batch mean at 0, the batch variance at 64 (fc_k_bn_final) */
-
-/* rescnn4's flat layout (nets._rescnn4_shapes): convolution l = 0 (stem) .. 8 has its kernel at conv_k[l], the heads'
- * 1x1 convolutions at p_k and v_k; each is followed by its BatchNorm's (j = l, 9 policy, 10 value) bias, gamma, beta,
- * moving mean and moving variance, channels(j) floats each.  Then the heads' dense kernels and biases. */
-struct FcLayout {
-  int conv_k[9], bn_b[FC_NBN];
-  int p_k, p_dk, p_db, v_k, v_d1k, v_d1b, v_d2k, v_d2b, nw;
-  FcLayout() {
-    int p = 0;
-    for (int l = 0; l < 9; ++l) {
-      conv_k[l] = p;
-      p += 9 * (l == 0 ? 10 : FC_C) * FC_C;
-      bn_b[l] = p;
-      p += 5 * FC_C;
-    }
-    p_k = p, bn_b[9] = p_k + FC_C * 4, p_dk = bn_b[9] + 5 * 4, p_db = p_dk + 64 * CA_NUM_MOVES;
-    v_k = p_db + CA_NUM_MOVES, bn_b[10] = v_k + FC_C * 2, v_d1k = bn_b[10] + 5 * 2, v_d1b = v_d1k + 32 * 64;
-    v_d2k = v_d1b + 64, v_d2b = v_d2k + 64, nw = v_d2b + 1;
-  }
-  static int channels(int j) { return j < 9 ? FC_C : j == 9 ? 4 : 2; }
-  int bias(int j) const { return bn_b[j]; }
-  int gamma(int j) const { return bn_b[j] + channels(j); }
-  int mean(int j) const { return bn_b[j] + 3 * channels(j); }
-  int var(int j) const { return bn_b[j] + 4 * channels(j); }
-};
 
 /* hands out consecutive pieces of one allocation; with base null it only adds up their sizes */
 struct FcCarver {
@@ -418,7 +393,7 @@ struct FcCarver {
 };
 
 struct FtResCnn : FtNet {
-  const FcLayout L;
+  static constexpr ResCnnLayout L{}; /* the flat layout (nn_layout.h) */
   const size_t rows; /* max_batch rounded up to whole 16-row tiles */
   DevBuf<float> x0, act, wt, wpart, bnpart;
   /* pieces of act: activations are [rows * 16][C]; the heads' [rows * 16][4] and [rows * 16][2] are [rows][64] and
@@ -484,13 +459,13 @@ struct FtResCnn : FtNet {
     rt_stream_t s = sh.s;
     float *w = sh.w;
     fc_planes(s, sh.states, rws, B, x0.p);
-    fc_conv3(s, x0.p, 10, w + L.conv_k[0], w + L.bias(0), Z[0], B, 0);
+    fc_conv3(s, x0.p, 10, w + L.kernel(0), w + L.bias(0), Z[0], B, 0);
     bn_fwd(sh, 0, Z[0], nullptr, X[0], R, train);
     for (int b = 0; b < 4; ++b) {
       const int l1 = 1 + 2 * b, l2 = 2 + 2 * b;
-      fc_conv3(s, X[b], FC_C, w + L.conv_k[l1], w + L.bias(l1), Z[l1], B, 0);
+      fc_conv3(s, X[b], FC_C, w + L.kernel(l1), w + L.bias(l1), Z[l1], B, 0);
       bn_fwd(sh, l1, Z[l1], nullptr, T[b], R, train);
-      fc_conv3(s, T[b], FC_C, w + L.conv_k[l2], w + L.bias(l2), Z[l2], B, 0);
+      fc_conv3(s, T[b], FC_C, w + L.kernel(l2), w + L.bias(l2), Z[l2], B, 0);
       bn_fwd(sh, l2, Z[l2], X[b], X[b + 1], R, train);
     }
     /* policy: 1x1 convolution to 4 channels, BatchNorm, ReLU, flatten, dense to the 96 logits */
@@ -548,18 +523,18 @@ struct FtResCnn : FtNet {
     /* trunk: G is the gradient at block b's output.  Its ReLU-masked copy (kept in G) is both the second BatchNorm's
      * input gradient and the residual branch's share of the block input's gradient, to which backward-data of the
      * first convolution is added */
-    fc_wtrans(s, w, L.conv_k[1], L.conv_k[2] - L.conv_k[1], 8, wt.p);
+    fc_wtrans(s, w, L.kernel(1), L.kernel(2) - L.kernel(1), 8, wt.p);
     for (int b = 3; b >= 0; --b) {
       const int l1 = 1 + 2 * b, l2 = 2 + 2 * b;
       bn_bwd(sh, l2, G, X[b + 1], Z[l2], DZ, R, true);
-      fc_conv3_wgrad(s, T[b], FC_C, DZ, B, wpart.p, g + L.conv_k[l2]);
+      fc_conv3_wgrad(s, T[b], FC_C, DZ, B, wpart.p, g + L.kernel(l2));
       fc_conv3(s, DZ, FC_C, wt.p + (size_t)(l2 - 1) * FC_WG_FLOATS, nullptr, GB, B, 0);
       bn_bwd(sh, l1, GB, T[b], Z[l1], DZ, R, false);
-      fc_conv3_wgrad(s, X[b], FC_C, DZ, B, wpart.p, g + L.conv_k[l1]);
+      fc_conv3_wgrad(s, X[b], FC_C, DZ, B, wpart.p, g + L.kernel(l1));
       fc_conv3(s, DZ, FC_C, wt.p + (size_t)(l1 - 1) * FC_WG_FLOATS, nullptr, G, B, 1);
     }
     bn_bwd(sh, 0, G, X[0], Z[0], DZ, R, false);
-    fc_conv3_wgrad(s, x0.p, 10, DZ, B, wpart.p, g + L.conv_k[0]);
+    fc_conv3_wgrad(s, x0.p, 10, DZ, B, wpart.p, g + L.kernel(0));
     return {(B + kb - 1) / kb, (R + kr - 1) / kr};
   }
 };

@@ -14,21 +14,8 @@
 
 #define FT_IN_LD 80 /* gathered input row stride: 70 padded to 5 tiles */
 
-/* mlp12x100's flat layout (nn.h): layer l has kernel[in_dim(l)][100], then bias, gamma, beta, moving mean, moving
- * variance, 100 floats each; then the value head's kernel[100][1] and bias, the policy head's kernel[100][96] and bias */
-struct FtMlpLayout {
-  static constexpr int W = CO_MLP_WIDTH;
-  constexpr int in_dim(int l) const { return l == 0 ? CA_GAME_STATE_SIZE : W; }
-  constexpr int kernel(int l) const { return l == 0 ? 0 : (in_dim(0) + 5) * W + (l - 1) * (W + 5) * W; }
-  constexpr int bias(int l) const { return kernel(l) + in_dim(l) * W; }
-  constexpr int gamma(int l) const { return bias(l) + W; }
-  constexpr int beta(int l) const { return bias(l) + 2 * W; }
-  constexpr int mean(int l) const { return bias(l) + 3 * W; }
-  constexpr int var(int l) const { return bias(l) + 4 * W; }
-  int kv = kernel(CO_MLP_LAYERS), bv = kv + W, kp = bv + 1, bp = kp + W * CA_NUM_MOVES, nw = bp + CA_NUM_MOVES;
-};
-static constexpr FtMlpLayout ML;
-static_assert(ML.nw == CO_MLP_NUM_WEIGHTS, "FtMlpLayout is not nn.h's layout");
+static constexpr MlpLayout ML; /* the flat layout (nn_layout.h) */
+static_assert(ML.IN == CA_GAME_STATE_SIZE && ML.MOVES == CA_NUM_MOVES, "MlpLayout is not the engine's state and move count");
 
 /* X0[r][k] = states[rows[r]][k], k < 70 */
 __global__ __launch_bounds__(256) void ft_k_gather(const float *__restrict__ states, const int32_t *__restrict__ rows,

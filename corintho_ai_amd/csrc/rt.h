@@ -123,6 +123,12 @@ inline bool rt_host_register(void *p, size_t n) {
 inline void rt_host_unregister(void *p) {
   if (p) (void)hipHostUnregister(p);
 }
+/* `kernel` may be launched with up to `bytes` of dynamic LDS (the runtime refuses more than 64 KB unasked) */
+template <class K>
+inline void rt_max_dynamic_lds(K *kernel, size_t bytes) {
+  rt_check(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
+           "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+}
 /* a kernel launch with `lds_bytes` of dynamic LDS, checked; grid and block: a count or a dim3 */
 #define RT_LAUNCH_LDS(kernel, grid, block, lds_bytes, stream, ...)                           \
   do {                                                                                        \

@@ -1,9 +1,9 @@
-// Driver of tests/test_host_terms.py: csrc/host.h's split_terms on the float bit patterns read from stdin.
+// Driver of tests/test_host_terms.py: csrc/nn_split.h's split_terms on the float bit patterns read from stdin.
 // usage: split_terms_driver <nt> <f16: 0|1>; one hexadecimal float32 per line in, "t0 t1 [t2]" (hexadecimal) per line out.
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "../../corintho_ai_amd/csrc/host.h"
+#include "../../corintho_ai_amd/csrc/nn_split.h"
 
 int main(int argc, char **argv) {
   if (argc != 3) return 2;

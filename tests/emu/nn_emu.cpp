@@ -15,7 +15,7 @@ struct EmuMlp : CoNet {
   EmuMlp(const float *weights, size_t n, size_t max_rows) : w(weights, weights + n), cap(max_rows) {}
   size_t max_rows() const override { return cap; }
   int kind() const override { return CO_NET_MLP12X100; }
-  double flop_per_row() const override { return 2.0 * (70 * 100 + 11 * 100 * 100 + 100 + 100 * 96); }
+  double flop_per_row() const override { return MlpLayout().flop_per_row(); }
   void forward(const float *in, int32_t rows_cap, const int32_t *d_rows, float *ev, float *pr, rt_stream_t,
                const CoNetIO &io = CoNetIO()) override {
     int n = *d_rows;
@@ -23,12 +23,13 @@ struct EmuMlp : CoNet {
 #pragma omp parallel for
     for (int r = 0; r < n; ++r) {
       float x[100], y[100];
+      constexpr MlpLayout ML;
       const float *p = w.data();
-      int in_dim = 70;
       const size_t irow = io.in_idx ? (size_t)io.in_idx[r] : (size_t)r, orow = io.out_idx ? (size_t)io.out_idx[r] : (size_t)r;
       for (int i = 0; i < 70; ++i) x[i] = in[irow * CO_STATE_STRIDE + i];
       for (int l = 0; l < 12; ++l) {
-        const float *K = p, *b = K + in_dim * 100, *ga = b + 100, *be = ga + 100, *mu = be + 100, *va = mu + 100;
+        const int in_dim = ML.in_dim(l);
+        const float *K = p + ML.kernel(l), *b = p + ML.bias(l), *ga = p + ML.gamma(l), *be = p + ML.beta(l), *mu = p + ML.mean(l), *va = p + ML.var(l);
         for (int o = 0; o < 100; ++o) {
           float s = 0.0f;
           for (int i = 0; i < in_dim; ++i) s = fmaf(x[i], K[i * 100 + o], s);
@@ -39,10 +40,8 @@ struct EmuMlp : CoNet {
           y[o] = a * s + c;
         }
         for (int o = 0; o < 100; ++o) x[o] = y[o];
-        p = va + 100;
-        in_dim = 100;
       }
-      const float *Kv = p, *bv = Kv + 100, *Kp = bv + 1, *bp = Kp + 9600;
+      const float *Kv = p + ML.kv, *bv = p + ML.bv, *Kp = p + ML.kp, *bp = p + ML.bp;
       float v = 0.0f;
       for (int i = 0; i < 100; ++i) v = fmaf(x[i], Kv[i], v);
       ev[orow * (size_t)io.eval_stride] = tanhf(v + bv[0]);

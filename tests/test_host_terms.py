@@ -1,5 +1,5 @@
-"""The 16-bit operand terms the host packs for the split-precision kernels (csrc/host.h split_terms, one copy for the
-MLP and the residual CNN), through a tiny g++-compiled driver (host.h compiles under -DCO_EMU): bf16 terms sum back to
+"""The 16-bit operand terms the host packs for the split-precision kernels (csrc/nn_split.h split_terms, one copy for the
+MLP and the residual CNN), through a tiny g++-compiled driver (its host part compiles under -DCO_EMU): bf16 terms sum back to
 the value within the dropped term and keep a NaN a NaN; fp16 terms are numpy.float16's rounding, bit for bit."""
 import os
 import subprocess

@@ -113,7 +113,7 @@ def test_bf16x6_rows_do_not_depend_on_their_batch(kind, make):
 def test_a_batch_split_between_the_two_f16x3_kernels_is_the_same_rows():
     """A batch that has the GPU to itself (CoNetIO::alone: net_forward, a one-pool trainer) is split on the device: the
     pixel-major kernel takes its whole passes over the chip (32 rows per CU), the small-batch kernel a remainder of up to
-    4096 rows STARTING AT A ROW OFFSET (nn_rescnn.hip rcp_small_begin; its thin path below 2048 rows).  Every row must come
+    4096 rows STARTING AT A ROW OFFSET (nn_rescnn_split.h rcp_small_begin; its thin path below 2048 rows).  Every row must come
     out as it does when its kernel has the batch to itself."""
     pass_rows = 32 * 256  # an MI355X's 256 CUs (on a device with another count the assertions hold all the same, the split falls elsewhere)
     t = make_trainer("hip", (2 * pass_rows + 4096) // 16 + 1, "", 1, 50, 16, 1.0, 0.25, 0, 1, False)
