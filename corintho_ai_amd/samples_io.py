@@ -3,8 +3,12 @@ get_samples): three `np.savez_compressed` files whose single array is stored as 
     <folder>/game_states.npz         [n*8, 70] float32
     <folder>/evaluation_labels.npz   [n*8]     float32
     <folder>/probability_labels.npz  [n*8, 96] float32
-so the reference's Keras training step (main.pyx:221-283) consumes them unchanged."""
+so the reference's Keras training step (main.pyx:221-283) consumes them unchanged.
+
+A training run of this package (run.py) keeps the un-augmented samples instead, `save_packed` / `load_packed`:
+    <folder>/samples.npz             state_policy [n, 166], outcome [n] float32, uncompressed"""
 import os
+import zipfile
 
 import numpy as np
 
@@ -38,6 +42,54 @@ def load_samples(sample_folder):
         with np.load(os.path.join(sample_folder, name + ".npz")) as z:
             out.append(np.reshape(z["arr_0"], shape))
     return tuple(out)
+
+
+PACKED_FILE = "samples.npz"
+SAMPLE_FLOATS = GAME_STATE_SIZE + NUM_MOVES
+
+
+def write_npz(path, arrays):
+    """An uncompressed .npz that np.load reads, written to a temporary file and moved into place.  Unlike np.savez the
+    members carry no time stamp, so equal arrays give equal bytes (a resumed run's files equal an uninterrupted run's)."""
+    tmp = path + ".tmp"
+    with zipfile.ZipFile(tmp, "w", zipfile.ZIP_STORED, allowZip64=True) as z:
+        for name, a in arrays.items():
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asarray(a), allow_pickle=False)
+    os.replace(tmp, path)
+
+
+def _check_packed(state_policy, outcome, where):
+    sp, oc = np.asarray(state_policy), np.asarray(outcome)
+    if sp.ndim != 2 or sp.shape[1] != SAMPLE_FLOATS or oc.shape != (sp.shape[0],):
+        raise ValueError("%s: state_policy must be [n, %d] and outcome [n], got %s and %s"
+                         % (where, SAMPLE_FLOATS, sp.shape, oc.shape))
+    return np.ascontiguousarray(sp, dtype=np.float32), np.ascontiguousarray(oc, dtype=np.float32)
+
+
+def save_packed(sample_folder, state_policy, outcome):
+    """The un-augmented samples of Trainer.export_samples as <folder>/samples.npz (state_policy [n, 166], outcome [n]),
+    uncompressed: an eighth of the bytes of the three expanded files, and no deflate on the host."""
+    sp, oc = _check_packed(state_policy, outcome, "save_packed")
+    os.makedirs(sample_folder, exist_ok=True)
+    write_npz(os.path.join(sample_folder, PACKED_FILE), {"state_policy": sp, "outcome": oc})
+
+
+def load_packed(sample_folder):
+    """(state_policy, outcome) of a sample folder.  A folder that holds only the reference's three files gives their
+    symmetry-0 rows: Trainer::writeSamples puts sample i under symmetry s at row 8 i + s (trainer.cpp:103-113), and
+    symmetry 0 is the position as played."""
+    path = os.path.join(sample_folder, PACKED_FILE)
+    if os.path.exists(path):
+        with np.load(path) as z:
+            return _check_packed(z["state_policy"], z["outcome"], path)
+    gs, ev, pr = load_samples(sample_folder)
+    if gs.shape[0] % NUM_SYMMETRIES or ev.shape[0] != gs.shape[0] or pr.shape[0] != gs.shape[0]:
+        raise ValueError("%s: %d, %d and %d rows are not the 8 symmetries of one sample set"
+                         % (sample_folder, gs.shape[0], ev.shape[0], pr.shape[0]))
+    return _check_packed(np.concatenate([gs[::NUM_SYMMETRIES], pr[::NUM_SYMMETRIES]], axis=1), ev[::NUM_SYMMETRIES],
+                         sample_folder)
 
 
 def samples_for_training(trainer, sample_folder, old_training_samples=(), mix_old=False):
