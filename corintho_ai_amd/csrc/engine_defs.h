@@ -248,7 +248,7 @@ struct EngineParams {
   int32_t *trace;       /* [G][CO_TRACE_CAP] or null */
   /* per-game text logs (Trainer's num_logged, trainer.cpp:243-250): the first num_logged games record what the
    * reference's log prints at every move choice (mcts.h co_log_ply); word 0 of a game's record is its length.  The host
-   * writes the files when the games are over (engine.hip write_logs). */
+   * writes the files when the games are over (game_logs.h GameLogs::write). */
   int32_t *log;         /* [num_logged][CO_LOG_CAP] or null */
   int32_t num_logged;
   const int32_t *log_index; /* tournament: record of match i, or -1 (addMatch's `logging`); null = games 0 .. num_logged - 1 */

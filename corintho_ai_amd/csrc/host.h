@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "../../include/corintho_hip.h"
 #include "nn.h"
@@ -32,6 +33,10 @@ struct DevBuf {
   void upload(const T *h, size_t count, rt_stream_t s) {
     alloc(count, s);
     rt_h2d(p, h, count * sizeof(T), s);
+  }
+  /* room for `count` values, a quarter more when it has to grow (buffers kept between calls); what it held is lost */
+  void grow(size_t count, rt_stream_t s) {
+    if (n < count) alloc(count + count / 4, s);
   }
   void release() {
     if (p) rt_free(p);
@@ -63,6 +68,36 @@ struct Pinned : RtHandle<void *, rt_host_free> { /* page-locked host memory */
     memset(h, 0, count * sizeof(T));
   }
   T &operator[](size_t i) const { return ((T *)h)[i]; }
+};
+
+/* Caller buffers page-locked for direct DMA (ca_trainer_pin_host: the three arrays of main.pyx:132-134 live as long as
+ * the Trainer): copies from / to them are then at PCIe speed instead of staged through the runtime's bounce buffers.  A
+ * buffer must stay allocated until it is unpinned or its owner destroyed. */
+struct HostPins {
+  std::vector<std::pair<void *, size_t>> regs;
+  HostPins() = default;
+  HostPins(const HostPins &) = delete;
+  HostPins &operator=(const HostPins &) = delete;
+  ~HostPins() {
+    for (auto &r : regs) rt_host_unregister(r.first);
+  }
+  bool pin(void *p, size_t bytes) {
+    for (auto &r : regs)
+      if (r.first == p && r.second >= bytes) return true;
+    unpin(p); /* (registered with fewer bytes) */
+    if (!rt_host_register(p, bytes)) return false;
+    regs.emplace_back(p, bytes);
+    return true;
+  }
+  void unpin(void *p) {
+    for (size_t i = 0; i < regs.size(); ++i)
+      if (regs[i].first == p) {
+        rt_host_unregister(p);
+        regs[i] = regs.back();
+        regs.pop_back();
+        return;
+      }
+  }
 };
 
 /* ---- Errors of the C ABI: an exception that carries the CA_ERR_* code its entry point returns */
@@ -106,6 +141,27 @@ int co_guard(H *h, F &&body) {
       throw CaError(CA_ERR_STATE, "called from inside a caller-supplied network function (ca_net_fn) of the same handle");
     rt_set_device(h->dev());
     body();
+  });
+}
+
+/* An entry point without a handle (the *_create calls, the stand-alone probes): the device checked and made current, then
+ * the body under the guard ... */
+template <class F>
+static int on_device(int device, F &&body) {
+  const int rc = ca_device_check(device);
+  if (rc != CA_OK) return rc;
+  return co_guard([&] {
+    rt_set_device(device);
+    body();
+  });
+}
+/* ... with a stream of its own */
+template <class F>
+static int on_device_stream(int device, F &&body) {
+  return on_device(device, [&] {
+    Stream s;
+    s.create();
+    body(s);
   });
 }
 

@@ -1971,7 +1971,7 @@ CO_DEV void co_reset_tree_to_child(CoWave &w, CoTree &t, int choice) {
 }
 
 /* ---- per-game text logs (SelfPlayer::writePreMoveLogs / writeMoveChoice, selfplayer.cpp:185-204).  The device records the
- * numbers, the host prints them (engine.hip write_logs).  One record per move choice:
+ * numbers, the host prints them (game_logs.h GameLogs::write).  One record per move choice:
  *   1, to_play, depth, root visits, root result, root evaluation bits,
  *   nc, nc x {move, visits, evaluation bits, result, probability bits}        the root's children (writeMoves :136-183)
  *   m x {depth, move, visits, result, evaluation bits, probability bits}, -1   the main line (Node::writeMainLine,

@@ -37,6 +37,36 @@ static void check_net_range(CoNet *net, rt_stream_t s, const std::string &who) {
                                        "are not valid -- use the float32-equivalent x6 kind of the same network");
 }
 
+/* Host rows through a network (ca_trainer_net_forward, ca_trainer_net_bench): device buffers kept, and grown on demand,
+ * between calls; the rows travel as the caller holds them (70 floats) and are widened to the kernels' 80 on the device */
+struct HostForward {
+  DevBuf<int32_t> fw_rows;
+  DevBuf<float> fw_in70, fw_in, fw_ev, fw_pr;
+
+  /* states[n][70] -> d80 (null: a buffer of this object's), widened; queued on s */
+  float *stage(const float *states, int32_t n, float *d80, rt_stream_t s) {
+    fw_in70.grow((size_t)n * CO_GAME_STATE_SIZE, s); /* (not the protocols' own row array: they hand that one to the caller) */
+    if (!d80) fw_in.grow((size_t)n * CO_STATE_STRIDE, s), d80 = fw_in.p;
+    rt_h2d(fw_in70.p, states, (size_t)n * CO_GAME_STATE_SIZE * 4, s);
+    expand_rows(fw_in70.p, d80, n, s);
+    return d80;
+  }
+  /* the n staged rows through `net`, the results left in fw_ev / fw_pr */
+  void forward(CoNet *net, const float *states, int32_t n, rt_stream_t s) {
+    fw_ev.grow((size_t)n, s);
+    fw_pr.grow((size_t)n * CO_NUM_MOVES, s);
+    fw_rows.grow(1, s);
+    const float *rows = stage(states, n, nullptr, s);
+    rt_h2d(fw_rows.p, &n, 4, s);
+    net->forward(rows, n, fw_rows.p, fw_ev.p, fw_pr.p, s);
+  }
+  void results(int32_t n, float *evals, float *probs, rt_stream_t s) {
+    rt_d2h(evals, fw_ev.p, (size_t)n * 4, s);
+    rt_d2h(probs, fw_pr.p, (size_t)n * CO_NUM_MOVES * 4, s);
+    rt_sync(s);
+  }
+};
+
 /* ---- A handle whose networks may be the caller's functions (ca_net_fn): `in_callback` is what co_guard (host.h) refuses
  * entry points on while one of them runs; one that returned non-zero ends what the handle was doing for good */
 struct CallbackState {

@@ -3,13 +3,18 @@
 // compiler's sanitizers (tests/emu/sanitize.mk, target host_driver) with nothing loaded into an interpreter.  It walks
 // the paths that build networks, pass the protocol's words between "device" and host, and move samples: a fused
 // generation, the host-driven protocol with the evaluation cache, a caller-supplied network that works and one that
-// fails, a tournament, the three sample exits and a stand-alone network.  Exit status 0: every call returned what it
-// should and the sample exits agree.
+// fails, a tournament with a logged match, the three sample exits, a stand-alone network, the per-game text logs over
+// two generations, an arena, the analysis of given positions, page-locked caller buffers and the read-outs that refuse.
+// Exit status 0: every call returned what it should, the sample exits agree and the logs repeat byte for byte.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
+
+#include <stdlib.h>
+#include <unistd.h>
 
 #include "../../include/corintho_hip.h"
 
@@ -80,6 +85,26 @@ int uniform_net(void *user, int32_t row0, int32_t cap_rows, const int32_t *d_row
     for (int m = 0; m < NM; ++m) n->probs[(size_t)r * NM + m] = 1.0f / NM;
   }
   return 0;
+}
+
+// a fresh directory for the files of one scenario, and what a file in it holds ("" if it cannot be read)
+std::string temp_dir() {
+  char name[] = "/tmp/engine_host_driver_XXXXXX";
+  REQUIRE(mkdtemp(name) != nullptr);
+  return name;
+}
+std::string slurp(const std::string &path) {
+  std::string s;
+  if (FILE *f = fopen(path.c_str(), "rb")) {
+    char buf[4096];
+    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) s.append(buf, n);
+    fclose(f);
+  }
+  return s;
+}
+void remove_dir(const std::string &dir, const std::vector<std::string> &files) {
+  for (const std::string &f : files) remove((dir + "/" + f).c_str());
+  rmdir(dir.c_str());
 }
 
 void fused_generation_and_sample_exits(const std::vector<float> &w) {
@@ -157,7 +182,9 @@ void tournament(const std::vector<float> &w0, const std::vector<float> &w1) {
   OK(ca_tourney_create(0, 0, 0, &t));
   OK(ca_tourney_add_player(t, 0, 0, 16, 4, 1.0f, 0.25f, 0));
   OK(ca_tourney_add_player(t, 1, 1, 12, 4, 1.0f, 0.25f, 0));
-  OK(ca_tourney_add_match(t, 0, 1, 0));
+  const std::string dir = temp_dir();
+  OK(ca_tourney_set_log_folder(t, dir.c_str()));
+  OK(ca_tourney_add_match(t, 0, 1, 1));  // this one writes match_0_1_0.txt
   OK(ca_tourney_add_match(t, 1, 0, 0));
   int32_t done = 0;
   OK(ca_tourney_set_net(t, 0, MLP, w0.data(), w0.size()));
@@ -167,7 +194,10 @@ void tournament(const std::vector<float> &w0, const std::vector<float> &w1) {
   OK(ca_tourney_set_net(t, 1, MLP, w1.data(), w1.size()));
   OK(ca_tourney_run(t, 0, &done));
   REQUIRE(done == 1);
+  OK(ca_tourney_all_done(t, &done));
+  REQUIRE(done == 1 && !slurp(dir + "/match_0_1_0.txt").empty() && slurp(dir + "/match_1_0_1.txt").empty());
   ca_tourney_destroy(t);
+  remove_dir(dir, {"match_0_1_0.txt"});
 }
 
 void stand_alone_network(const std::vector<float> &w) {
@@ -183,6 +213,115 @@ void stand_alone_network(const std::vector<float> &w) {
   REQUIRE(sum > 0.99f && sum < 1.01f);
   ca_net_destroy(n);
 }
+
+// the per-game text logs: the first two of six games on four slots, over two generations of the same seed
+void text_logs(const std::vector<float> &w) {
+  const std::string dir = temp_dir();
+  const std::vector<std::string> files = {"game_0.txt", "game_1.txt"};
+  ca_config c = config(6, 50, 8);
+  c.resident = 4;
+  ca_trainer *t = nullptr;
+  OK(ca_trainer_create(&c, &t));
+  OK(ca_trainer_set_net(t, 0, MLP, w.data(), w.size()));
+  EXPECT(CA_ERR_ARG, ca_trainer_set_logging(t, dir.c_str(), 5));  // a logged game starts in a slot of its own
+  OK(ca_trainer_set_logging(t, dir.c_str(), 2));
+  std::string first[2];
+  for (int generation = 0; generation < 2; ++generation) {
+    int32_t done = 0;
+    OK(ca_trainer_run(t, 0, &done));
+    REQUIRE(done == 1);
+    for (int k = 0; k < 2; ++k) {
+      const std::string text = slurp(dir + "/" + files[k]);
+      REQUIRE(!text.empty());
+      if (generation == 0) first[k] = text;
+      REQUIRE(text == first[k]);
+      remove((dir + "/" + files[k]).c_str());
+    }
+    EXPECT(CA_ERR_STATE, ca_trainer_set_logging(t, dir.c_str(), 2));  // the games have started
+    OK(ca_trainer_reset(t, c.seed));
+  }
+  ca_trainer_destroy(t);
+  remove_dir(dir, files);
+}
+
+void arena(const std::vector<float> &w0, const std::vector<float> &w1) {
+  ca_config c = config(8, 50, 8);
+  c.testing = 1;
+  ca_trainer *t = nullptr;
+  OK(ca_trainer_create(&c, &t));
+  int32_t done = 0;
+  OK(ca_trainer_set_net(t, 0, MLP, w0.data(), w0.size()));
+  EXPECT(CA_ERR_STATE, ca_trainer_run(t, 0, &done));  // arena mode needs both networks
+  OK(ca_trainer_set_net(t, 1, MLP, w1.data(), w1.size()));
+  OK(ca_trainer_run(t, 0, &done));
+  REQUIRE(done == 1);
+  float score = -1.0f;
+  OK(ca_trainer_score(t, &score));
+  REQUIRE(score >= 0.0f && score <= 1.0f);
+  const std::string dir = temp_dir();
+  OK(ca_trainer_write_scores(t, (dir + "/scores.txt").c_str()));
+  const std::string scores = slurp(dir + "/scores.txt");
+  int lines = 0;
+  for (char ch : scores) lines += ch == '\n';
+  REQUIRE(lines == 6);
+  float gs[1], ev[1], pr[1];
+  EXPECT(CA_ERR_STATE, ca_trainer_write_samples(t, gs, ev, pr));  // a testing trainer keeps no samples
+  ca_trainer_destroy(t);
+  remove_dir(dir, {"scores.txt"});
+}
+
+// three positions: the empty board under two seeds, and one met in a random playout (tests/test_analyse.py _positions)
+void analysis(const std::vector<float> &w) {
+  const int n = 3;
+  std::vector<int32_t> boards((size_t)n * 64, 0), to_play = {0, 0, 1}, seeds = {3, 4, 5};
+  std::vector<int32_t> pieces = {4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 3, 3, 3, 3, 4, 3};
+  const uint64_t met = 0x4200090100004000ull;
+  for (int i = 0; i < 64; ++i) boards[(size_t)2 * 64 + i] = (int32_t)(met >> i & 1);
+  ca_config c = config(n, 50, 8);
+  c.analyse = 1;
+  ca_trainer *t = nullptr;
+  OK(ca_trainer_create(&c, &t));
+  OK(ca_trainer_set_net(t, 0, MLP, w.data(), w.size()));
+  int32_t done = 0;
+  std::vector<int32_t> out((size_t)n * 8);
+  EXPECT(CA_ERR_STATE, ca_trainer_run(t, 0, &done));  // no positions yet
+  boards[5] = 2;
+  EXPECT(CA_ERR_ARG, ca_trainer_set_positions(t, boards.data(), to_play.data(), pieces.data(), seeds.data()));
+  boards[5] = 0;
+  OK(ca_trainer_set_positions(t, boards.data(), to_play.data(), pieces.data(), seeds.data()));
+  EXPECT(CA_ERR_STATE, ca_trainer_analysis(t, out.data()));  // nothing searched
+  OK(ca_trainer_run(t, 2, &done));
+  REQUIRE(done == 0);
+  EXPECT(CA_ERR_STATE, ca_trainer_analysis(t, out.data()));  // the searches have not ended
+  OK(ca_trainer_finish(t));
+  OK(ca_trainer_analysis(t, out.data()));
+  for (int i = 0; i < n; ++i) REQUIRE(out[(size_t)i * 8] >= 0 && out[(size_t)i * 8] < NM);
+  ca_trainer_destroy(t);
+  // a trainer of games takes no positions
+  c.analyse = 0;
+  OK(ca_trainer_create(&c, &t));
+  EXPECT(CA_ERR_STATE, ca_trainer_set_positions(t, boards.data(), to_play.data(), pieces.data(), seeds.data()));
+  ca_trainer_destroy(t);
+}
+
+void pins_trace_and_info() {
+  ca_config c = config(8, 24, 8);
+  ca_trainer *t = nullptr;
+  OK(ca_trainer_create(&c, &t));
+  std::vector<float> a(4096), b(64);
+  int32_t pinned = 0, words = 0, info[8];
+  OK(ca_trainer_pin_host(t, a.data(), 1024, &pinned));
+  REQUIRE(pinned == 1);
+  OK(ca_trainer_pin_host(t, a.data(), a.size() * 4, &pinned));  // again, with more bytes
+  REQUIRE(pinned == 1);
+  OK(ca_trainer_unpin_host(t, a.data()));
+  OK(ca_trainer_unpin_host(t, b.data()));  // never pinned
+  OK(ca_trainer_pin_host(t, b.data(), b.size() * 4, &pinned));  // still pinned when the trainer goes
+  EXPECT(CA_ERR_STATE, ca_trainer_trace(t, 0, nullptr, 0, &words));  // created without ca_config.trace
+  EXPECT(CA_ERR_ARG, ca_trainer_game_info(t, c.num_games, info));
+  OK(ca_trainer_game_info(t, c.num_games - 1, info));
+  ca_trainer_destroy(t);
+}
 }  // namespace
 
 int main() {
@@ -192,6 +331,10 @@ int main() {
   caller_supplied_network();
   tournament(w0, w1);
   stand_alone_network(w0);
+  text_logs(w0);
+  arena(w0, w1);
+  analysis(w0);
+  pins_trace_and_info();
   puts("engine_host_driver: ok");
   return 0;
 }

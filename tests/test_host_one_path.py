@@ -1,6 +1,6 @@
 """The host engine's single paths: the three ways samples leave a trainer give the same rows, net_bench widens the
-caller's 70-float rows on the device like net_forward, and a tournament reports a network it cannot build with the
-code a trainer reports (CA_ERR_ARG)."""
+caller's 70-float rows on the device like net_forward, a tournament reports a network it cannot build with the
+code a trainer reports (CA_ERR_ARG), and one trainer gives the same generation through each of its protocols in turn."""
 import numpy as np
 import pytest
 import torch  # before the engine is loaded: the process then holds ONE HIP runtime, torch's (corintho_ai_amd/torch_net.py)
@@ -88,6 +88,55 @@ def test_net_bench_takes_rows_as_the_caller_holds_them(engine):
     t.net_bench(rows, reps=1)
     t.writeRequests(after)
     assert n > 0 and before[:n].any() and before.tobytes() == after.tobytes()
+
+
+@pytest.mark.parametrize("engine", ENGINES)
+def test_one_trainer_through_its_modes(engine, tmp_path):
+    """ONE trainer (10 games on 4 slots, the first two logged), three generations of seed 5: A fused (run), B driven by
+    the host through the evaluation cache with the trainer's own net_forward as the caller's network, C fused again
+    after the cache is switched off.  Each hand-over rebuilds what the launches are given (pools, table, the pending
+    leaves' cache words, the logs' records), so: the samples and both log files of B and of C are A's, byte for byte.
+    (B = A rests on a row's outputs not depending on its batch: tests/test_net_precision.py.)"""
+    G, R, spe = 10, 4, 8
+    t = make_trainer(engine, G, str(tmp_path), 5, 50, spe, 1.0, 0.25, 2, 1, False, stagger=False, resident=R)
+    t.set_net(T.NET_MLP12X100, nets.init_mlp12x100(3, bn_noise=True))
+    logs = [tmp_path / "game_0.txt", tmp_path / "game_1.txt"]
+
+    def harvest():
+        """what the generation left: its samples and log files (taken away, so that the next one has to write them)"""
+        sp, oc = t.export_samples()
+        out = (sp.tobytes(), oc.tobytes()) + tuple(f.read_bytes() for f in logs)
+        for f in logs:
+            f.unlink()
+        return out
+
+    assert t.run()
+    a = harvest()
+    print("generation A: %d sample rows, logs of %d and %d bytes" % (t.num_samples(), len(a[2]), len(a[3])))
+    assert t.num_samples() > 0 and len(a[2]) > 0 and len(a[3]) > 0
+
+    t.reset(5)
+    t.set_host_cache(6)
+    cap = R * spe
+    gs = np.zeros((cap, T.GAME_STATE_SIZE), np.float32)
+    ev, pr = np.zeros(cap, np.float32), np.zeros((cap, T.NUM_MOVES), np.float32)
+    calls = 0
+    while not t.doIteration(ev, pr, -1):
+        calls += 1
+        assert calls < 10 ** 5, "the host-driven generation did not end"
+        n = t.num_requests(-1)
+        assert 0 <= n <= cap
+        if n:
+            t.writeRequests(gs, -1)
+            t.net_forward(gs[:n], out_evals=ev, out_probs=pr)
+    b = harvest()
+
+    t.reset(5)
+    t.set_host_cache(False)
+    assert t.run()
+    c = harvest()
+    assert c == a, "the fused generation after the host-driven one differs from the first"
+    assert b == a, "the host-driven generation differs from the fused ones"
 
 
 def _one_match(engine):
