@@ -68,6 +68,7 @@ class CaStats(C.Structure):
         ("nn_rows_evaluated", C.c_int64),
         ("steps_cut", C.c_int64),
         ("step_budget_last", C.c_int64),
+        ("tourney_path", C.c_int64),
     ]
 
 
@@ -88,8 +89,16 @@ EXPORTS = [
     "ca_fitter_add_trainer_samples", "ca_fitter_drop_samples", "ca_fitter_data_info", "ca_fitter_fetch_rows",
     "ca_trainer_request_rows", "ca_trainer_set_net_fn", "ca_tourney_set_net_fn", "ca_net_create", "ca_net_forward_device",
     "ca_net_destroy",
+    "ca_tourney_set_grouped", "ca_tourney_set_seed", "ca_net_group_create", "ca_net_group_forward", "ca_net_group_info", "ca_net_group_tables",
+    "ca_net_group_bench", "ca_net_group_destroy",
 ]
-NET_FN_EXPORTS = EXPORTS[-6:]  # the caller-supplied network: set_net_fn, ca_net_*
+# the caller-supplied network: an earlier build of the library has none of these
+NET_FN_EXPORTS = ["ca_trainer_request_rows", "ca_trainer_set_net_fn", "ca_tourney_set_net_fn", "ca_net_create", "ca_net_forward_device",
+                  "ca_net_destroy"]
+# grouped multi-model inference and the rating driver's tournament entries: likewise
+GROUP_EXPORTS = ["ca_tourney_set_grouped", "ca_tourney_set_seed", "ca_net_group_create", "ca_net_group_forward", "ca_net_group_info",
+                 "ca_net_group_tables", "ca_net_group_bench", "ca_net_group_destroy"]
+assert set(NET_FN_EXPORTS + GROUP_EXPORTS) <= set(EXPORTS)
 
 
 def declare(L):
@@ -160,6 +169,17 @@ def declare(L):
         L.ca_net_forward_device.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp]
         L.ca_net_destroy.argtypes = [vp]
         L.ca_net_destroy.restype = None
+    group = hasattr(L, "ca_net_group_create")  # (as above: an earlier build has none)
+    if group:
+        L.ca_tourney_set_grouped.argtypes = [vp, C.c_int32]
+        L.ca_tourney_set_seed.argtypes = [vp, C.c_uint32]
+        L.ca_net_group_create.argtypes = [C.c_int, C.c_int, C.POINTER(f32p), C.c_int32, C.c_size_t, C.c_int32, C.POINTER(vp)]
+        L.ca_net_group_forward.argtypes = [vp, f32p, i32p, C.c_int32, f32p, f32p]
+        L.ca_net_group_info.argtypes = [vp, i32p]
+        L.ca_net_group_bench.argtypes = [vp, f32p, i32p, C.c_int32, C.c_int32, f32p]
+        L.ca_net_group_tables.argtypes = [vp, i32p, i32p, i32p, i32p, i32p]
+        L.ca_net_group_destroy.argtypes = [vp]
+        L.ca_net_group_destroy.restype = None
     f64p = C.POINTER(C.c_double)
     fitter = hasattr(L, "ca_fitter_create")  # the emulation build of the engine (tests/emu) has no training kernels
     if fitter:
@@ -169,8 +189,11 @@ def declare(L):
             continue
         if name in NET_FN_EXPORTS and not net_fn:
             continue
+        if name in GROUP_EXPORTS and not group:
+            continue
         fn = getattr(L, name)
-        if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy", "ca_net_destroy"):
+        if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy", "ca_net_destroy",
+                        "ca_net_group_destroy"):
             fn.restype = C.c_int
     return L
 

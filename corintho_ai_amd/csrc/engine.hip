@@ -6,6 +6,7 @@
 //   game_logs.h      GameLogs: the per-game text logs (printed by logfmt.h)
 //   samples_host.h   SampleExits: the three ways samples leave; ca_expand_samples
 //   net_host.h       how a network comes in (NetSpec, HostNet, ExternalNet); HostForward: host rows through a network
+//   nn_group.h       rows of many models in one network launch: the grouping kernels, GroupPlanner, ca_net_group
 //   analysis_host.h  AnalysisPositions: given positions in, their result words out
 //   pools.h          FusedRun: fused training on pools of the games
 //   host.h           owners of runtime resources, HostPins, the guards of the entry points
@@ -33,6 +34,7 @@
 #include "game_store.h"
 #include "game_view.h"
 #include "net_host.h"
+#include "nn_group.h"
 #include "pools.h"
 #include "samples_host.h"
 
@@ -263,6 +265,21 @@ struct ca_trainer {
       net->forward(store.nn_in.p, store.R * spe, store.req_offset.p + store.R, store.nn_eval.p, store.nn_probs.p, stream);
       ++stats.nn_launches;
     }
+    launch_mcts_step(e, store.R, stream);
+    ++stats.mcts_launches;
+    ++iterations;
+  }
+  /* the same for EVERY model of a tournament at once (tourney_host.h, a grouped round): one scan, one compaction, the
+   * rows grouped by the model of the player to move (slot_model: nn_group.h co_k_group_rows), one grouped network
+   * launch, one search launch that steps every match */
+  void queue_grouped_iteration(CoNetGroup *group, GroupPlanner &planner, const int32_t *slot_model, int32_t *row_model) {
+    const EngineParams e = params(CO_TO_PLAY_EVERY_MODEL);
+    scan(e);
+    compact(e);
+    RT_LAUNCH(co_k_group_rows, store.R, CO_WAVE, stream, e, slot_model, row_model);
+    planner.run(row_model, store.req_offset.p + store.R, stream);
+    group->forward(store.nn_in.p, store.R * spe, planner.plan(), store.nn_eval.p, store.nn_probs.p, stream);
+    ++stats.nn_launches;
     launch_mcts_step(e, store.R, stream);
     ++stats.mcts_launches;
     ++iterations;

@@ -186,6 +186,9 @@ struct EvalCache {
   unsigned long long *totals; /* [CO_CACHE_TOTALS] rows evaluated in earlier iterations, - */
 };
 
+/* EngineParams::to_play of a tournament launch that serves the matches of EVERY model at once (a grouped round,
+ * tourney_host.h); apart from the model ids (>= 0) and from the dummy ids of random players (small negative numbers) */
+#define CO_TO_PLAY_EVERY_MODEL INT32_MIN
 struct EngineParams {
   /* configuration */
   int32_t num_games;   /* SLOTS of the pool: games resident at a time (= the trainer's games unless it recycles) */
@@ -196,7 +199,7 @@ struct EngineParams {
   int32_t testing;
   int32_t stagger_div; /* 0 = no staggered start, else max(G / max_searches, 1) (trainer.cpp:184-186) */
   int32_t iteration;   /* Trainer::searches_done_ */
-  int32_t to_play;     /* -1 training, 0/1 arena model to move */
+  int32_t to_play;     /* -1 training, 0/1 arena model to move; a tournament: the model id, or CO_TO_PLAY_EVERY_MODEL */
   int32_t game_base;   /* global index of local game 0 (multi-GPU shard): parity = (base + g) % 2 */
   uint32_t cap_units;  /* arena units per tree */
   int32_t trace_on;

@@ -32,7 +32,7 @@ CO_K3_BOUNDS CO_KERNEL co_k_mcts_step(EngineParams P) {
 /* is game g part of the batch of model `tp` (trainer.cpp:42-46, 84-98)? */
 CO_DEV int co_game_active(const EngineParams &P, int g, const GameCtl &gc, int tp) {
   if (gc.done) return 0;
-  if (P.pcfg) return P.pcfg[2 * g + gc.to_play].model_id == tp; /* tourney.cpp:26, 46, 66 */
+  if (P.pcfg) return tp == CO_TO_PLAY_EVERY_MODEL || P.pcfg[2 * g + gc.to_play].model_id == tp; /* tourney.cpp:26, 46, 66 */
   if (tp == 0 || tp == 1) return gc.to_play == (tp + gc.parity) % 2;
   return 1;
 }

@@ -2497,7 +2497,7 @@ CO_DEV int co_step_gate(const EngineParams &P, int g, const GameCtl &gc) {
   if (gc.done || gc.error) return 0;
   const int tp = P.arena_state ? P.arena_state[CO_AS_MODEL] : P.to_play;
   if (P.pcfg) {
-    if (P.pcfg[2 * g + gc.to_play].model_id != tp) return 0; /* tourney.cpp:66 */
+    if (tp != CO_TO_PLAY_EVERY_MODEL && P.pcfg[2 * g + gc.to_play].model_id != tp) return 0; /* tourney.cpp:66 */
   } else if (tp == 0 || tp == 1) {
     if (gc.to_play != (tp + gc.parity) % 2) return 0;
   } else if (P.stagger_div > 0) {

@@ -114,3 +114,44 @@ struct CoNet {
 #define CO_F16_MAX 65504.0f
 
 CoNet *co_net_create(int kind, const float *weights, size_t n_floats, size_t max_rows, rt_stream_t s);
+
+/* ---- Rows of MANY models of one kind in one launch (a rating round's 95 checkpoints).  A row's result depends on that
+ * row only, so rows of different models may share a launch if every workgroup takes the weights of its own model.  The
+ * grouping kernel (nn_group.h co_k_group) turns "row r belongs to model m" into the three tables below, on the device:
+ *   idx   the batch's rows ordered by model, then by row; model m's segment starts at seg_start[m] -- packed (a grouped
+ *         kernel) or at m * seg_stride (the per-model fallback, whose launches need a start the host knows);
+ *   wg    one entry per workgroup: model, first position in idx, rows (<= the group's tile).  Segments never share a workgroup;
+ *   n_wg  entries of wg; at most rows_cap / tile + models.
+ * Placement is a counting sort in (model, row) order: no atomics, the tables are the same bits from run to run. */
+#define CO_GROUP_MAX_MODELS 256
+#define CO_GROUP_MAX_ROWS 65535 /* the grouping kernel counts in 16-bit LDS words */
+#define CO_GROUP_TILE 128       /* rows per workgroup of the tables unless the group says otherwise (the split MLP kernel's) */
+struct CoGroupWG {
+  int32_t model, first, count, pad;
+};
+struct CoGroupPlan {
+  const int32_t *idx = nullptr;
+  const CoGroupWG *wg = nullptr;
+  const int32_t *n_wg = nullptr;
+  const int32_t *seg_start = nullptr; /* [models] */
+  const int32_t *seg_count = nullptr; /* [models] */
+  int32_t wg_cap = 0;                 /* entries wg has room for: the grid of a grouped launch */
+  int32_t seg_stride = 0;             /* 0: segments packed */
+};
+struct CoNetGroup {
+  virtual ~CoNetGroup() {}
+  virtual int kind() const = 0;
+  virtual int models() const = 0;
+  virtual size_t max_rows() const = 0;
+  /* one kernel for every model (true), or one CoNet::forward per model segment (false): which layout of idx it reads */
+  virtual bool grouped_kernel() const = 0;
+  /* rows per workgroup the tables are cut for: the grouped kernel's */
+  virtual int tile() const { return CO_GROUP_TILE; }
+  /* the rows of d_in named by plan.idx, each through its model; results at the same row of d_eval / d_probs */
+  virtual void forward(const float *d_in, int32_t rows_cap, const CoGroupPlan &plan, float *d_eval, float *d_probs, rt_stream_t s) = 0;
+  /* CoNet::range_exceeded for the launch's models together (the flag is shared) */
+  virtual bool range_exceeded(rt_stream_t) { return false; }
+};
+/* the grouped kernels of `kind`, or null if it has none (the caller then uses the fallback of nn_group.h); throws
+ * std::invalid_argument like co_net_create, naming the model.  Not in the emulation build. */
+CoNetGroup *co_net_group_native(int kind, const float *const *weights, int models, size_t n_floats, size_t max_rows, rt_stream_t s);

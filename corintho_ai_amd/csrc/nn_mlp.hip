@@ -241,3 +241,15 @@ CoNet *co_net_create(int kind, const float *weights, size_t n_floats, size_t max
   if (k->terms) return co_mlp_split_create(weights, n_floats, max_rows, s, k->terms, k->f16);
   return n_floats == (size_t)CO_MLP_NUM_WEIGHTS ? new MlpNet(weights, max_rows, s) : nullptr;
 }
+
+/* the kinds with a grouped kernel (nn.h CoNetGroup): the split-precision MLP, all three widths, and rescnn4 at f16x3; the
+ * others go through the per-model fallback of nn_group.h */
+CoNetGroup *co_mlp_split_group_create(const float *const *weights, int models, size_t n_floats, size_t max_rows, rt_stream_t s, int nterms,
+                                      bool f16);
+CoNetGroup *co_rescnn_h3_group_create(const float *const *weights, int models, size_t n_floats, size_t max_rows, rt_stream_t s);
+CoNetGroup *co_net_group_native(int kind, const float *const *weights, int models, size_t n_floats, size_t max_rows, rt_stream_t s) {
+  const CoNetKind *k = co_net_kind(kind);
+  if (k && k->family == CO_FAMILY_RESCNN4 && k->terms == 2 && k->f16) return co_rescnn_h3_group_create(weights, models, n_floats, max_rows, s);
+  if (!k || k->family != CO_FAMILY_MLP12X100 || !k->terms) return nullptr;
+  return co_mlp_split_group_create(weights, models, n_floats, max_rows, s, k->terms, k->f16);
+}

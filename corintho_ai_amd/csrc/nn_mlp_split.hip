@@ -134,15 +134,12 @@ __device__ __forceinline__ void m3_init_bias(f32x16 (&acc)[4], const float *bias
       m3_stage<NT>(wfrag, lds_base + (uint32_t)(((c) + 2) % 3) * (M3_CHUNK_WORDS(NT) * 4u), (c) + 2, wave, lane); \
   }
 
-template <int NT, bool F16 = false>
-__global__ __launch_bounds__(256, 1) void co_k_mlp_forward_split_t(const float *__restrict__ in, const int32_t *__restrict__ d_rows,
-                                                                   const uint32_t *__restrict__ wfrag, float *__restrict__ eval,
-                                                                   float *__restrict__ probs, CoNetIO io, uint32_t *range_flag) {
+/* rows row0 .. min(row0 + 128, rows) - 1 of the launch, by one workgroup, with the weights at wfrag */
+template <int NT, bool F16>
+__device__ __forceinline__ void m3_forward(const float *__restrict__ in, const int rows, const int row0, const uint32_t *__restrict__ wfrag,
+                                           float *__restrict__ eval, float *__restrict__ probs, const CoNetIO &io, uint32_t *range_flag) {
   static_assert(M3_CHUNK_PIECES_PER_WAVE(2) == 9 && M3_CHUNK_PIECES_PER_WAVE(3) == 13, "vmcnt immediates of M3_CHUNK_HEAD");
   extern __shared__ __attribute__((aligned(16))) uint32_t m3_lds[]; /* ring of three chunk slots */
-  const int rows = *d_rows;
-  const int row0 = blockIdx.x * M3_ROWS_PER_WG;
-  if (row0 >= rows) return;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, h = lane >> 5, n = lane & 31;
   const uint32_t lds_base = co_lds_addr(m3_lds);
 
@@ -245,6 +242,33 @@ __global__ __launch_bounds__(256, 1) void co_k_mlp_forward_split_t(const float *
     if (h == 0) eval[orow * (size_t)io.eval_stride] = tanhf(acc[3][0]);
   }
 }
+
+template <int NT, bool F16 = false>
+__global__ __launch_bounds__(256, 1) void co_k_mlp_forward_split_t(const float *__restrict__ in, const int32_t *__restrict__ d_rows,
+                                                                   const uint32_t *__restrict__ wfrag, float *__restrict__ eval,
+                                                                   float *__restrict__ probs, CoNetIO io, uint32_t *range_flag) {
+  const int rows = *d_rows;
+  const int row0 = blockIdx.x * M3_ROWS_PER_WG;
+  if (row0 >= rows) return;
+  m3_forward<NT, F16>(in, rows, row0, wfrag, eval, probs, io, range_flag);
+}
+
+/* The grouped instance (nn.h CoNetGroup): workgroup b takes entry b of the workgroup table -- a model and up to 128
+ * positions of the index list, all that model's -- reads the weights at wbase + model * M3_TOTAL_WORDS and its rows, and
+ * writes its results, through the index list.  One table read per workgroup; everything behind it is m3_forward. */
+template <int NT, bool F16 = false>
+__global__ __launch_bounds__(256, 1) void co_k_mlp_forward_split_grouped_t(const float *__restrict__ in, const CoGroupWG *__restrict__ wg,
+                                                                           const int32_t *__restrict__ n_wg, const int32_t *__restrict__ idx,
+                                                                           const uint32_t *__restrict__ wbase, float *__restrict__ eval,
+                                                                           float *__restrict__ probs, uint32_t *range_flag) {
+  if ((int)blockIdx.x >= *n_wg) return;
+  const CoGroupWG e = wg[blockIdx.x];
+  const int first = __builtin_amdgcn_readfirstlane(e.first), count = __builtin_amdgcn_readfirstlane(e.count);
+  const int model = __builtin_amdgcn_readfirstlane(e.model);
+  CoNetIO io;
+  io.in_idx = io.out_idx = idx;
+  m3_forward<NT, F16>(in, first + count, first, wbase + (size_t)model * M3_TOTAL_WORDS(NT), eval, probs, io, range_flag);
+}
 #define co_k_mlp_forward_x3 co_k_mlp_forward_split_t<2>
 #define co_k_mlp_forward_x6 co_k_mlp_forward_split_t<3>
 /* "f16x3": two fp16 terms per operand (22 significand bits), three MFMA products -- see nn_rescnn_split.h */
@@ -277,6 +301,55 @@ struct MlpSplitNet : CoNet {
     RT_LAUNCH_LDS(kernel(), grid, 256, M3_LDS_BYTES(nt), s, d_in, d_rows, (const uint32_t *)d_w.p, d_eval, d_probs, io, range.ptr());
   }
 };
+
+/* M weight sets in one buffer at a stride of M3_TOTAL_WORDS, the range flag shared by the launch */
+struct MlpSplitNetGroup : CoNetGroup {
+  DevBuf<uint32_t> d_w;
+  RangeFlag range;
+  size_t cap;
+  int nt, m;
+  bool f16;
+  MlpSplitNetGroup(const float *const *w, int models, size_t max_rows, rt_stream_t s, int nterms, bool fp16)
+      : cap(max_rows), nt(nterms), m(models), f16(fp16) {
+    std::vector<uint32_t> buf;
+    buf.reserve((size_t)models * M3_TOTAL_WORDS(nt));
+    for (int i = 0; i < models; ++i) {
+      try {
+        const std::vector<uint32_t> one = co_pack_mlp_split(w[i], nt, f16);
+        buf.insert(buf.end(), one.begin(), one.end());
+      } catch (const std::invalid_argument &e) {
+        throw std::invalid_argument("model " + std::to_string(i) + " of the group: " + e.what());
+      }
+    }
+    d_w.upload(buf.data(), buf.size(), s);
+    if (f16) range.alloc(s);
+    rt_sync(s);
+    rt_max_dynamic_lds(kernel(), M3_LDS_BYTES(nt));
+  }
+  decltype(&co_k_mlp_forward_split_grouped_t<2>) kernel() const {
+    return f16 ? co_k_mlp_forward_split_grouped_t<2, true> : nt == 2 ? co_k_mlp_forward_split_grouped_t<2> : co_k_mlp_forward_split_grouped_t<3>;
+  }
+  int kind() const override { return co_net_kind_of(CO_FAMILY_MLP12X100, nt, f16); }
+  int models() const override { return m; }
+  size_t max_rows() const override { return cap; }
+  bool grouped_kernel() const override { return true; }
+  bool range_exceeded(rt_stream_t s) override { return range.read(s); }
+  void forward(const float *d_in, int32_t rows_cap, const CoGroupPlan &plan, float *d_eval, float *d_probs, rt_stream_t s) override {
+    static_assert(CO_GROUP_TILE == M3_ROWS_PER_WG, "the workgroup table is cut for this kernel's rows per workgroup");
+    /* the worst case of rows_cap rows: every model ends in a partial workgroup (never more than the table holds) */
+    int grid = rows_cap / M3_ROWS_PER_WG + m;
+    if (grid > plan.wg_cap) grid = plan.wg_cap;
+    if (grid < 1 || plan.seg_stride) return;
+    RT_LAUNCH_LDS(kernel(), grid, 256, M3_LDS_BYTES(nt), s, d_in, plan.wg, plan.n_wg, plan.idx, (const uint32_t *)d_w.p, d_eval, d_probs,
+                  range.ptr());
+  }
+};
+
+CoNetGroup *co_mlp_split_group_create(const float *const *weights, int models, size_t n_floats, size_t max_rows, rt_stream_t s, int nterms,
+                                      bool f16) {
+  if (n_floats != (size_t)CO_MLP_NUM_WEIGHTS || (nterms != 2 && nterms != 3) || (f16 && nterms != 2)) return nullptr;
+  return new MlpSplitNetGroup(weights, models, max_rows, s, nterms, f16);
+}
 
 CoNet *co_mlp_split_create(const float *weights, size_t n_floats, size_t max_rows, rt_stream_t s, int nterms, bool f16) {
   if (n_floats != (size_t)CO_MLP_NUM_WEIGHTS || (nterms != 2 && nterms != 3) || (f16 && nterms != 2)) return nullptr;

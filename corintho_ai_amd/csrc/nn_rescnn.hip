@@ -37,6 +37,8 @@
 #include <vector>
 
 #include "engine_defs.h"
+#include <memory>
+
 #include "host.h"
 #include "lds_dma.h"
 #include "nn_split.h"
@@ -517,6 +519,66 @@ struct ResCnnSplitNet : ResCnnNet {
     }
   }
 };
+
+/* M models of rescnn4 at f16x3 for the grouped small-batch kernel: each model's buffers are made as for the model alone
+ * (ResCnnSplitNet) and copied, device to device, into one buffer at a fixed stride */
+struct ResCnnH3NetGroup : CoNetGroup {
+  DevBuf<uint32_t> d_w;
+  RangeFlag range;
+  size_t cap;
+  int m;
+  uint32_t stride = 0, off_epi = 0, off_head = 0, off_small = 0;
+  ResCnnH3NetGroup(const float *const *w, int models, size_t max_rows, rt_stream_t s) : cap(max_rows), m(models) {
+    for (int i = 0; i < models; ++i) {
+      std::unique_ptr<ResCnnSplitNet> one;
+      try {
+        one.reset(new ResCnnSplitNet(w[i], max_rows, s, 2, true));
+      } catch (const std::invalid_argument &e) {
+        throw std::invalid_argument("model " + std::to_string(i) + " of the group: " + e.what());
+      }
+      if (i == 0) {
+        off_epi = (uint32_t)one->d_trunk3.n;
+        off_head = off_epi + RC3_EPI_WORDS;
+        off_small = off_head + RCS_HEAD_WORDS(2);
+        stride = off_small + RCG_SMALL_WORDS;
+        d_w.alloc((size_t)models * stride, s);
+      }
+      uint32_t *dst = d_w.p + (size_t)i * stride;
+      rt_d2d(dst, one->d_trunk3.p, (size_t)off_epi * 4, s);
+      rt_d2d(dst + off_epi, one->d_epi3.p, (size_t)RC3_EPI_WORDS * 4, s);
+      rt_d2d(dst + off_head, one->d_whead3.p, (size_t)RCS_HEAD_WORDS(2) * 4, s);
+      rt_d2d(dst + off_small, one->P.head_epi, 48 * 4, s);
+      rt_d2d(dst + off_small + 48, one->P.bpol, 96 * 4, s);
+      rt_d2d(dst + off_small + 144, one->P.bv1, 64 * 4, s);
+      rt_d2d(dst + off_small + 208, one->P.bv2, 4, s);
+      rt_sync(s); /* (the model's own buffers go with `one`) */
+    }
+    range.alloc(s);
+    rt_sync(s);
+    rt_max_dynamic_lds(co_k_rescnn_forward_h3_grouped, RCS_LDS_WORDS(2, 1) * 4);
+  }
+  int kind() const override { return co_net_kind_of(CO_FAMILY_RESCNN4, 2, true); }
+  int models() const override { return m; }
+  size_t max_rows() const override { return cap; }
+  bool grouped_kernel() const override { return true; }
+  int tile() const override { return RCG_POS_PER_WG; }
+  bool range_exceeded(rt_stream_t s) override { return range.read(s); }
+  void forward(const float *d_in, int32_t rows_cap, const CoGroupPlan &plan, float *d_eval, float *d_probs, rt_stream_t s) override {
+    int grid = rows_cap / RCG_POS_PER_WG + m; /* the worst case: every model ends in a partial workgroup */
+    if (grid > plan.wg_cap) grid = plan.wg_cap;
+    if (grid < 1 || plan.seg_stride) return;
+    RcGroupParams g;
+    g.in = d_in, g.wg = plan.wg, g.n_wg = plan.n_wg, g.idx = plan.idx, g.wbase = d_w.p;
+    g.stride = stride, g.off_epi = off_epi, g.off_head = off_head, g.off_small = off_small;
+    g.eval = d_eval, g.probs = d_probs, g.range_flag = range.ptr();
+    RT_LAUNCH_LDS(co_k_rescnn_forward_h3_grouped, grid, 512, RCS_LDS_WORDS(2, 1) * 4, s, g);
+  }
+};
+
+CoNetGroup *co_rescnn_h3_group_create(const float *const *weights, int models, size_t n_floats, size_t max_rows, rt_stream_t s) {
+  if (n_floats != (size_t)CO_RESCNN4_NUM_WEIGHTS) return nullptr;
+  return new ResCnnH3NetGroup(weights, models, max_rows, s);
+}
 
 CoNet *co_rescnn_create(const float *weights, size_t n_floats, size_t max_rows, rt_stream_t s) {
   if (n_floats != (size_t)CO_RESCNN4_NUM_WEIGHTS) return nullptr;

@@ -319,17 +319,19 @@ extern "C" int ca_net_trace(unsigned out[160]) {
 #endif
 
 /* NW = waves per workgroup: 8 (two per SIMD), or 4 in the thin-batch kernel of NT = 3 (below) */
-template <int NP, int NT, int NW = 8, bool F16 = false>
-__device__ __forceinline__ void rcs_forward(const Rc3Params &Q, const int rbase = 0) {
+/* GROUPED (the grouped instance below): the workgroup's positions are rbase .. g_end - 1 of the launch, not the ones its
+ * index gives it */
+template <int NP, int NT, int NW = 8, bool F16 = false, bool GROUPED = false>
+__device__ __forceinline__ void rcs_forward(const Rc3Params &Q, const int rbase = 0, const int g_end = 0) {
   const RcParams &P = Q.base;
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[];
   uint32_t *lds_w = lds_dyn;
   /* NT = 3: the features reuse the buffer of the last group (RC3_NUM_GROUPS - 1 = 26 -> buffer 0), free behind
    * the barrier in front of the heads */
   float *lds_feat = reinterpret_cast<float *>(NT == 2 ? lds_dyn + 2 * RCS_GROUP_WORDS(NT) : lds_dyn);
-  const int rows = *P.d_rows; /* this launch works on rows rbase .. rows - 1 */
-  if (NT == 2 && (rows - rbase <= RC3_SMALL_ROWS) != (NP == 1)) return; /* the other kernel takes this batch */
-  const int row0 = rbase + blockIdx.x * (2 * NP * NW);
+  const int rows = GROUPED ? g_end : *P.d_rows; /* this launch works on rows rbase .. rows - 1 */
+  if (!GROUPED && NT == 2 && (rows - rbase <= RC3_SMALL_ROWS) != (NP == 1)) return; /* the other kernel takes this batch */
+  const int row0 = GROUPED ? rbase : rbase + (int)blockIdx.x * (2 * NP * NW);
   if (row0 >= rows) return;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, h = lane >> 5, p2 = (lane >> 4) & 1, c = lane & 15;
@@ -503,4 +505,38 @@ __global__ __launch_bounds__(512, 2) void co_k_rescnn_forward_h3_small(Rc3Params
   } else {
     rcs_forward<1, 2, 8, true>(Q, rbase);
   }
+}
+
+
+/* The grouped instance of the f16x3 small-batch kernel (nn.h CoNetGroup; 16 positions per workgroup at any batch size --
+ * the paths are bit-identical, a throughput choice can come later): workgroup b takes entry b of the workgroup table -- a
+ * model and up to 16 positions of the index list, all that model's -- and finds everything of its model in ONE buffer at a
+ * fixed stride: [trunk fragments | epilogue constants | head weights | head_epi 48, bpol 96, bv1 64, bv2 1 floats]. */
+#define RCG_POS_PER_WG 16
+#define RCG_SMALL_WORDS 256 /* the four small float arrays, padded */
+struct RcGroupParams {
+  const float *in;
+  const CoGroupWG *wg;
+  const int32_t *n_wg, *idx;
+  const uint32_t *wbase;
+  uint32_t stride, off_epi, off_head, off_small; /* words */
+  float *eval, *probs;
+  uint32_t *range_flag;
+};
+__global__ __launch_bounds__(512, 2) void co_k_rescnn_forward_h3_grouped(RcGroupParams G) {
+  if ((int)blockIdx.x >= *G.n_wg) return;
+  const CoGroupWG e = G.wg[blockIdx.x];
+  const int first = __builtin_amdgcn_readfirstlane(e.first), count = __builtin_amdgcn_readfirstlane(e.count);
+  const uint32_t *w = G.wbase + (size_t)__builtin_amdgcn_readfirstlane(e.model) * G.stride;
+  const float *small = reinterpret_cast<const float *>(w + G.off_small);
+  Rc3Params Q;
+  Q.base.in = G.in, Q.base.d_rows = nullptr;
+  Q.base.wtrunk = nullptr, Q.base.epi = nullptr, Q.base.whead = nullptr, Q.base.wpol = nullptr, Q.base.wv1 = nullptr, Q.base.wv2 = nullptr;
+  Q.base.head_epi = small, Q.base.bpol = small + 48, Q.base.bv1 = small + 144, Q.base.bv2 = small + 208;
+  Q.base.eval = G.eval, Q.base.probs = G.probs;
+  Q.base.io = CoNetIO();
+  Q.base.io.in_idx = Q.base.io.out_idx = G.idx;
+  Q.wtrunk = w, Q.epi3 = w + G.off_epi, Q.whead3 = w + G.off_head;
+  Q.range_flag = G.range_flag, Q.pass_rows = 0;
+  rcs_forward<1, 2, 8, true, true>(Q, first, first + count);
 }

@@ -23,6 +23,15 @@ struct ca_tourney {
   std::map<int, std::unique_ptr<CoNet>> nets;
   int dev() const { return device; }
   bool exact_offsets = false;                  /* ca_tourney_set_exact_offsets */
+  /* ca_tourney_set_grouped: a round serves every model at once -- one scan, one compaction, one grouped network launch
+   * (nn_group.h) and one search launch, whatever the number of models.  With exact offsets a match reads its own rows,
+   * so its play depends on nothing but its own evaluations and the order in which matches are stepped does not matter. */
+  bool grouped = false;
+  int path_ran = 0;                            /* ca_stats.tourney_path: the path ca_tourney_run last took */
+  std::unique_ptr<CoNetGroup> group;           /* the models of group_ids, in that order */
+  std::vector<int> group_ids;
+  GroupPlanner planner;
+  DevBuf<int32_t> slot_model, row_model;       /* [2 matches] dense model of a match's side (< 0: random); [request rows] */
 
   /* Tourney::doIteration (tourney.cpp:53-70).  `rows` = rows of the caller's two arrays: the
    * reference reads them at its own offset table (quirk 10), so the whole arrays travel. */
@@ -53,14 +62,37 @@ struct ca_tourney {
         if (std::find(ids.begin(), ids.end(), id) == ids.end()) ids.push_back(id);
       }
     std::sort(ids.begin(), ids.end());
+    /* grouped: every model must be one of the library's kinds (a caller's function evaluates its own launch), and one
+     * kind for all; models of several kinds are served by the per-model path */
+    bool use_group = grouped;
+    if (grouped) {
+      int kind = 0;
+      for (int id : ids) {
+        if (id < 0) continue;
+        auto it = net_specs.find(id);
+        if (it == net_specs.end()) throw CaError(CA_ERR_STATE, "ca_tourney_run: no network for model id " + std::to_string(id));
+        if (it->second.f.fn)
+          throw CaError(CA_ERR_STATE, "ca_tourney_run: a grouped tournament evaluates every model in one launch of the library's kernels; model id " +
+                                          std::to_string(id) + " is a caller-supplied function (ca_tourney_set_net_fn)");
+        if (kind && it->second.kind != kind) use_group = false;
+        kind = it->second.kind;
+      }
+      if (!kind) use_group = false; /* (random players only) */
+      /* more rows or models than the grouping kernel's tables hold: the per-model path, which has no such limit */
+      int n_models = 0;
+      for (int id : ids) n_models += id >= 0;
+      if (p.request_rows() > CO_GROUP_MAX_ROWS || n_models > CO_GROUP_MAX_MODELS) use_group = false;
+    }
     for (int id : ids) {
-      if (id < 0) continue;
+      if (id < 0 || use_group) continue;
       if (!nets.count(id)) {
         auto it = net_specs.find(id);
         if (it == net_specs.end()) throw CaError(CA_ERR_STATE, "ca_tourney_run: no network for model id " + std::to_string(id));
         nets[id] = p.make_net(it->second, &callback, " for model id " + std::to_string(id) + ", this tournament");
       }
     }
+    if (use_group) return run_grouped(p, ids, max_rounds);
+    path_ran = 1;
     int64_t rounds = 0;
     bool done = all_games_done(p.games());
     int failed_id = -1;
@@ -84,6 +116,52 @@ struct ca_tourney {
     }
     p.queued_iterations_done();
     if (done) all_done(); /* (writes the match logs) */
+    return done;
+  }
+
+  /* the rounds of a grouped tournament (ca_tourney_set_grouped) */
+  bool run_grouped(ca_trainer &p, const std::vector<int> &ids, int64_t max_rounds) {
+    std::vector<int> models;
+    for (int id : ids)
+      if (id >= 0) models.push_back(id);
+    if (!group || models != group_ids) {
+      std::vector<const float *> w;
+      size_t n_floats = 0;
+      for (int id : models) {
+        const NetSpec &sp = net_specs.at(id);
+        const size_t n = sp.weights ? sp.n_floats : sp.kept.size();
+        if (n_floats && n != n_floats) throw CaError(CA_ERR_ARG, "ca_tourney_run: model id " + std::to_string(id) + " has another weight count than the models before it");
+        n_floats = n;
+        w.push_back(sp.weights ? sp.weights : sp.kept.data());
+      }
+      const size_t rows = p.request_rows();
+      group = co_net_group_make(net_specs.at(models[0]).kind, w.data(), (int)models.size(), n_floats, rows, p.stream);
+      planner.create((int)models.size(), rows, !group->grouped_kernel(), p.stream, group->tile());
+      std::vector<int32_t> sm;
+      for (auto &m : matches)
+        for (int pid : {m.first, m.second}) {
+          const int id = players.at(pid).model_id;
+          sm.push_back(id < 0 ? -1 : (int32_t)(std::find(models.begin(), models.end(), id) - models.begin()));
+        }
+      slot_model.upload(sm.data(), sm.size(), p.stream);
+      row_model.alloc(rows, p.stream);
+      rt_sync(p.stream); /* (sm leaves scope) */
+      group_ids = models;
+    }
+    path_ran = 2;
+    int64_t rounds = 0;
+    bool done = all_games_done(p.games());
+    while (!done && (max_rounds <= 0 || rounds < max_rounds)) {
+      p.queue_grouped_iteration(group.get(), planner, slot_model.p, row_model.p);
+      ++rounds;
+      /* (the look every eighth round: see run) */
+      if ((rounds & 7) == 0 || (max_rounds > 0 && rounds >= max_rounds)) done = p.poll_all_done(CO_TO_PLAY_EVERY_MODEL);
+    }
+    p.queued_iterations_done();
+    std::string names = "model ids";
+    for (int id : models) names += " " + std::to_string(id);
+    check_group_range(group.get(), p.stream, "ca_tourney_run", names);
+    if (done) all_done();
     return done;
   }
 
@@ -167,6 +245,7 @@ extern "C" int ca_tourney_add_player(ca_tourney *t, int32_t player_id, int32_t m
   return co_guard(t, [&] {
     if (t->pool) throw CaError(CA_ERR_STATE, "addPlayer after the tournament has started");
     if (!random && (max_searches <= 0 || searches_per_eval <= 0)) throw CaError(CA_ERR_ARG, "addPlayer: bad search settings");
+    if (model_id == CO_TO_PLAY_EVERY_MODEL) throw CaError(CA_ERR_ARG, "addPlayer: this model id is reserved");
     PlayerCfg p;
     memset(&p, 0, sizeof p);
     p.player_id = player_id;
@@ -203,6 +282,7 @@ static void tourney_set_net(ca_tourney *t, int32_t model_id, NetSpec spec) {
   if (model_id < 0) throw CaError(CA_ERR_ARG, "negative model ids are the dummy ids of random players");
   t->net_specs[model_id] = std::move(spec);
   t->nets.erase(model_id);
+  t->group.reset(); /* (rebuilt by the next grouped run) */
 }
 extern "C" int ca_tourney_set_net(ca_tourney *t, int32_t model_id, int32_t kind, const float *weights, size_t n_floats) {
   return co_guard(t, [&] {
@@ -219,7 +299,22 @@ extern "C" int ca_tourney_set_net_fn(ca_tourney *t, int32_t model_id, ca_net_fn 
 extern "C" int ca_tourney_set_exact_offsets(ca_tourney *t, int32_t on) {
   return co_guard(t, [&] {
     if (t->pool) throw CaError(CA_ERR_STATE, "set_exact_offsets after the tournament has started");
+    if (t->grouped && !on) throw CaError(CA_ERR_STATE, "set_exact_offsets: a grouped tournament (ca_tourney_set_grouped) needs exact offsets");
     t->exact_offsets = on != 0;
+  });
+}
+/* the generator addMatch draws the matches' seeds from (tourney.h:43: default constructed, seed 5489), seeded anew */
+extern "C" int ca_tourney_set_seed(ca_tourney *t, uint32_t seed) {
+  return co_guard(t, [&] {
+    if (!t->matches.empty()) throw CaError(CA_ERR_STATE, "set_seed after the first addMatch");
+    t->generator.seed(seed);
+  });
+}
+extern "C" int ca_tourney_set_grouped(ca_tourney *t, int32_t on) {
+  return co_guard(t, [&] {
+    if (t->pool) throw CaError(CA_ERR_STATE, "set_grouped after the tournament has started");
+    t->grouped = on != 0;
+    if (on) t->exact_offsets = true;
   });
 }
 extern "C" int ca_tourney_run(ca_tourney *t, int64_t max_rounds, int32_t *all_done) {
@@ -274,5 +369,8 @@ extern "C" int ca_tourney_trace(ca_tourney *t, int32_t match, int32_t *out, int3
   return co_guard(t, [&] { t->built_or_state().read_trace(match, out, cap, n_out); });
 }
 extern "C" int ca_tourney_stats(ca_tourney *t, ca_stats *out) {
-  return co_guard(t, [&] { t->built_or_state().read_stats(out); });
+  return co_guard(t, [&] {
+    t->built_or_state().read_stats(out);
+    out->tourney_path = t->path_ran;
+  });
 }

@@ -89,6 +89,16 @@ class Tourney:
         """diagnostic: matches read their own rows instead of the reference's offset table (tourney.cpp:55-62)"""
         _lib.check(self._L, self._L.ca_tourney_set_exact_offsets(self._t, int(bool(on))))
 
+    def set_seed(self, seed):
+        """the generator the matches' seeds are drawn from (the reference's is default constructed); before the first addMatch"""
+        _lib.check(self._L, self._L.ca_tourney_set_seed(self._t, int(seed) & 0xFFFFFFFF))
+
+    def set_grouped(self, on=True):
+        """a round of run() serves every model at once: one grouped network launch and one search launch, whatever the
+        number of models (turns exact offsets on; before the tournament starts; not with set_net_fn models).
+        stats()["tourney_path"] says which path ran: 1 one iteration per model id, 2 grouped."""
+        _lib.check(self._L, self._L.ca_tourney_set_grouped(self._t, int(bool(on))))
+
     def run(self, max_rounds=0):
         done = C.c_int32()
         _lib.check_callbacks(self._L, self._L.ca_tourney_run(self._t, max_rounds, C.byref(done)), self._net_fns.values())

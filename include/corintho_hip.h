@@ -294,6 +294,7 @@ typedef struct ca_stats {
   int64_t nn_rows_evaluated; /* rows the network kernels worked on; nn_rows - this = rows served by the evaluation cache */
   int64_t steps_cut;         /* ca_config.step_budget: game steps of the generation (since ca_trainer_reset, over every ca_trainer_run) that stopped at their budget and went on in the next iteration */
   int64_t step_budget_last;  /* the budget (microseconds) the first pool's last launch worked under; 0 = none */
+  int64_t tourney_path;      /* ca_tourney_stats: the path the last ca_tourney_run took -- 0 none yet, 1 one iteration per model id, 2 grouped (ca_tourney_set_grouped) */
 } ca_stats;
 int ca_trainer_stats(ca_trainer *t, ca_stats *out);
 /* per-game: {to_play, done, result, n_samples, n_pending, error, mate_turn, plies} */
@@ -352,6 +353,19 @@ int ca_tourney_run(ca_tourney *t, int64_t max_rounds, int32_t *all_done);
  * gave it, instead of through Tourney::doIteration's own offset table (tourney.cpp:55-62, SURVEY 8a quirk 10,
  * which hands most matches the rows of OTHER matches).  Before the first query; default 0 = the reference's table. */
 int ca_tourney_set_exact_offsets(ca_tourney *t, int32_t on);
+/* Not in the reference: 1 = ca_tourney_run serves EVERY model in one round -- one scan, one compaction, one grouped network
+ * launch (every workgroup takes the weights of its own model) and one search launch that steps every match, whatever the
+ * number of models; ca_stats.nn_launches and mcts_launches then grow by 1 per round.  It turns exact offsets on (a match
+ * must read its own rows for its play not to depend on the order of the steps); a later ca_tourney_set_exact_offsets(0)
+ * is CA_ERR_STATE.  Before the first query, else CA_ERR_STATE.  ca_tourney_run then refuses a model that is a caller's
+ * function (CA_ERR_STATE); if the models are not all of one kind, or there are more than 256 of them or more than 65535
+ * request rows (matches x the largest searches_per_eval), it takes the per-model path, and ca_stats.tourney_path says
+ * which one ran. */
+int ca_tourney_set_grouped(ca_tourney *t, int32_t on);
+/* Not in the reference, whose Tourney draws every match's seed from a default-constructed std::mt19937 (tourney.h:43):
+ * that generator seeded with `seed` instead, so that the parts of a rating round play different games.  Before the first
+ * addMatch, else CA_ERR_STATE. */
+int ca_tourney_set_seed(ca_tourney *t, uint32_t seed);
 /* Tourney::writeScores, tourney.cpp:33-41 */
 int ca_tourney_write_scores(ca_tourney *t, const char *filename);
 int ca_tourney_num_matches(ca_tourney *t, int32_t *out);
@@ -373,6 +387,29 @@ int ca_net_create(int device, int kind, const float *weights, size_t n_floats, i
 int ca_net_forward_device(ca_net *n, const float *d_states, int32_t rows_cap, const int32_t *d_rows, float *d_evals,
                           float *d_probs, void *stream);
 void ca_net_destroy(ca_net *n);
+
+/* ---- Many models of one kind on one set of rows, in one launch: `models` (1..256) weight sets of `kind`, n_floats each
+ * (layouts as ca_trainer_set_net).  ca_net_group_forward: states [n][70] on the host, model_of_row[n] in 0 .. models - 1
+ * -> evals [n], probs [n][96]; row r is evaluated by model model_of_row[r], to the same bits as by that model alone.  The
+ * split-precision kinds of mlp12x100 and rescnn4 at f16x3 run ONE kernel whose workgroups each take their own model's
+ * weights; every other kind one launch per model on the same index lists.  An f16x3 weight set beyond fp16's range is refused at creation with the
+ * model's index (CA_ERR_ARG); an activation beyond it is CA_ERR_ENGINE from the forward, naming the launch's models.
+ * n <= max_rows <= 65535. */
+typedef struct ca_net_group ca_net_group;
+int ca_net_group_create(int device, int kind, const float *const *weights, int32_t models, size_t n_floats, int32_t max_rows,
+                        ca_net_group **out);
+int ca_net_group_forward(ca_net_group *g, const float *states, const int32_t *model_of_row, int32_t n, float *evals, float *probs);
+/* out[6] = {models, max_rows, 1 if one grouped kernel serves the group, rows per workgroup of the tables, entries of the
+ * index list, entries of the workgroup table} */
+int ca_net_group_info(ca_net_group *g, int32_t out[6]);
+/* diagnostic: the tables the last forward left on the device -- the index list (rows by model, then by row; model m's
+ * segment at seg_start[m], seg_count[m] rows), the workgroup table [entries][4] = {model, first index, rows, 0} and the
+ * number of its entries in use */
+int ca_net_group_tables(ca_net_group *g, int32_t *idx, int32_t *wg, int32_t *n_wg, int32_t *seg_start, int32_t *seg_count);
+/* diagnostic: kernel-only times (HIP events) of `reps` launches on these rows, milliseconds per call: out_ms[0] the
+ * grouping kernel, out_ms[1] the network launch (or the per-model launches of a kind without a grouped kernel) */
+int ca_net_group_bench(ca_net_group *g, const float *states, const int32_t *model_of_row, int32_t n, int32_t reps, float out_ms[2]);
+void ca_net_group_destroy(ca_net_group *g);
 
 /* rule layer on a batch of positions (one wavefront each): legal-move masks + is_lines */
 int ca_rules_legal_moves(int device, const uint64_t *boards, const uint32_t *metas, int32_t n, uint32_t *masks /* [n][3] */,

@@ -3,6 +3,7 @@
 from this repository alone.  Paths below the output directory mirror the reference's own (corintho_ai/...):
 
     rating/results.txt, rating/tourney/players.txt   the reference's rating tournament (tests/test_reference_results.py)
+    rating/gd_ratings.txt                            the ratings rating_gd.cpp recorded for them (tests/test_rating.py)
     rating/tflite_models/model_{0,51,93}.tflite      three TFLite checkpoints: first, middle, last in name order
                                                      (tests/test_tflite_import.py)
     model/variables.npz                              the Keras SavedModel's variables/: the index file, and the head of the
@@ -75,7 +76,7 @@ def main(ref):
     base = os.path.join(ref, "corintho_ai")
     names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(base, "rating", "tflite_models", "model_*.tflite")))
     assert (names[0], names[len(names) // 2], names[-1]) == TFLITE, names
-    files = ["rating/results.txt", "rating/tourney/players.txt"] + ["rating/tflite_models/" + n for n in TFLITE]
+    files = ["rating/results.txt", "rating/gd_ratings.txt", "rating/tourney/players.txt"] + ["rating/tflite_models/" + n for n in TFLITE]
     for rel in files:
         dst = os.path.join(OUT, rel)
         os.makedirs(os.path.dirname(dst), exist_ok=True)
