@@ -91,6 +91,7 @@ EXPORTS = [
     "ca_net_destroy",
     "ca_tourney_set_grouped", "ca_tourney_set_seed", "ca_net_group_create", "ca_net_group_forward", "ca_net_group_info", "ca_net_group_tables",
     "ca_net_group_bench", "ca_net_group_destroy",
+    "ca_fitter_set_sample_weights", "ca_fitter_get_sample_weights", "ca_fitter_merge_duplicates",
 ]
 # the caller-supplied network: an earlier build of the library has none of these
 NET_FN_EXPORTS = ["ca_trainer_request_rows", "ca_trainer_set_net_fn", "ca_tourney_set_net_fn", "ca_net_create", "ca_net_forward_device",
@@ -98,7 +99,9 @@ NET_FN_EXPORTS = ["ca_trainer_request_rows", "ca_trainer_set_net_fn", "ca_tourne
 # grouped multi-model inference and the rating driver's tournament entries: likewise
 GROUP_EXPORTS = ["ca_tourney_set_grouped", "ca_tourney_set_seed", "ca_net_group_create", "ca_net_group_forward", "ca_net_group_info",
                  "ca_net_group_tables", "ca_net_group_bench", "ca_net_group_destroy"]
-assert set(NET_FN_EXPORTS + GROUP_EXPORTS) <= set(EXPORTS)
+# sample weights and the merging of duplicate positions: likewise
+WEIGHT_EXPORTS = ["ca_fitter_set_sample_weights", "ca_fitter_get_sample_weights", "ca_fitter_merge_duplicates"]
+assert set(NET_FN_EXPORTS + GROUP_EXPORTS + WEIGHT_EXPORTS) <= set(EXPORTS)
 
 
 def declare(L):
@@ -191,6 +194,8 @@ def declare(L):
             continue
         if name in GROUP_EXPORTS and not group:
             continue
+        if name in WEIGHT_EXPORTS and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy", "ca_net_destroy",
                         "ca_net_group_destroy"):
@@ -218,6 +223,10 @@ def _declare_fitter(L, vp, f64p):
     L.ca_fitter_drop_samples.argtypes = [vp, C.c_int32]
     L.ca_fitter_data_info.argtypes = [vp, i32p, i32p]
     L.ca_fitter_fetch_rows.argtypes = [vp, i32p, C.c_int32, f32p, f32p, f32p]
+    if hasattr(L, "ca_fitter_merge_duplicates"):  # (an earlier build has none of these)
+        L.ca_fitter_set_sample_weights.argtypes = [vp, f32p, C.c_int32]
+        L.ca_fitter_get_sample_weights.argtypes = [vp, f32p, C.c_int32]
+        L.ca_fitter_merge_duplicates.argtypes = [vp, C.c_int, i32p, i32p]
 
 
 _lib = None

@@ -13,7 +13,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libcorintho_hip.so")
-SOURCES = ["engine.hip", "nn_mlp.hip", "nn_mlp_split.hip", "nn_rescnn.hip", "nn_train.hip", "nn_train_mlp.hip", "nn_train_conv.hip"]
+SOURCES = ["engine.hip", "nn_mlp.hip", "nn_mlp_split.hip", "nn_rescnn.hip", "nn_train.hip", "nn_train_mlp.hip", "nn_train_conv.hip",
+           "nn_samples.hip"]
 FLAGS = [
     "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-ffp-contract=off",
     "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-Wall", "-Wno-unused-function",
@@ -41,7 +42,9 @@ def build(force=False, verbose=False, extra=(), out=None, csrc=CSRC):
     if out is None and not force and not needs_build():
         return OUT
     out = out or OUT
-    cmd = [hipcc()] + FLAGS + list(extra) + ["-o", out] + [os.path.join(csrc, s) for s in SOURCES]
+    # (an earlier checkout's csrc need not have every source of today's)
+    sources = [s for s in SOURCES if csrc == CSRC or os.path.exists(os.path.join(csrc, s))]
+    cmd = [hipcc()] + FLAGS + list(extra) + ["-o", out] + [os.path.join(csrc, s) for s in sources]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

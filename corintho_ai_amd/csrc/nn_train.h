@@ -100,6 +100,16 @@ struct FtNet {
   /* from hd and what forward kept: the weight gradient of the batch as partials in g (the heads' last biases excepted) */
   virtual FtSplits backward(const FtShared &sh, int B) = 0;
 };
+/* Merging of a packed set's duplicate positions on the device (nn_samples.hip; the definition: ca_fitter_merge_duplicates
+ * in corintho_hip.h).  sp[n][166], oc[n] and wt[n] (null: every weight 1) are read only; the merged samples come back in
+ * buffers of their own with room for `cap` samples, of which `count` are filled.  Everything is queued on s, which is
+ * synchronised on return. */
+struct FtMerged {
+  DevBuf<float> sp, oc, wt;
+  int32_t count = 0, cap = 0;
+};
+FtMerged ft_merge_duplicates(rt_stream_t s, const float *sp, const float *oc, const float *wt, int32_t n, bool normalize);
+
 /* kind: CA_NET_MLP12X100 or CA_NET_RESCNN4; the network's own buffers are sized for max_batch rows and cleared on s */
 FtNet *ft_net_create(int kind, int max_batch, rt_stream_t s);
 FtNet *ft_mlp_create(int max_batch, rt_stream_t s);

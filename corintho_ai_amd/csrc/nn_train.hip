@@ -76,10 +76,14 @@ __global__ __launch_bounds__(256) void ft_k_gemm(FtGemm g) {
 /* Per row of the heads' outputs H[r] (96 logits, value at 96): the loss terms and the gradients of the batch loss
  * value_mse + 0.25 * policy_cce (means over the B rows) with respect to the logits and to v:
  *   Hd[r][0..95] = 0.25 (softmax * sum t - t) / B,  Hd[r][96] = 2 (tanh v - z)(1 - tanh^2 v) / B,
- *   Hd[r][97] = (tanh v - z)^2,  Hd[r][98] = -sum_j t_j log_softmax_j  (from the logits, as Keras does) */
+ *   Hd[r][97] = (tanh v - z)^2,  Hd[r][98] = -sum_j t_j log_softmax_j  (from the logits, as Keras does)
+ * WEIGHTED: every one of these 99 terms times the row's sample weight wts[rows[r]] (Keras's sample_weight under
+ * SUM_OVER_BATCH_SIZE: the divisor stays B); the unweighted instantiation never reads that last operand and has no such
+ * multiply: instruction for instruction the kernel it was before weights existed. */
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void ft_k_loss(const float *__restrict__ H, const int32_t *__restrict__ rows, int B,
                                                 const float *__restrict__ evals, const float *__restrict__ probs,
-                                                float *__restrict__ Hd) {
+                                                float *__restrict__ Hd, const float *__restrict__ wts) {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= B) return;
   const float *h = H + (long)r * FT_PADW;
@@ -96,12 +100,22 @@ __global__ __launch_bounds__(256) void ft_k_loss(const float *__restrict__ H, co
     ce += t[j] * (lse - h[j]);
   }
   const float inv_b = 1.0f / (float)B;
-  for (int j = 0; j < CA_NUM_MOVES; ++j) d[j] = 0.25f * (expf(h[j] - lse) * st - t[j]) * inv_b;
-  const float tv = tanhf(h[96]);
-  const float err = tv - evals[rows[r]];
-  d[96] = 2.0f * err * (1.0f - tv * tv) * inv_b;
-  d[97] = err * err;
-  d[98] = ce;
+  if (!WEIGHTED) {
+    for (int j = 0; j < CA_NUM_MOVES; ++j) d[j] = 0.25f * (expf(h[j] - lse) * st - t[j]) * inv_b;
+    const float tv = tanhf(h[96]);
+    const float err = tv - evals[rows[r]];
+    d[96] = 2.0f * err * (1.0f - tv * tv) * inv_b;
+    d[97] = err * err;
+    d[98] = ce;
+  } else { /* today's terms, each rounded as above, then times w: a weight of 1 changes no bit, one of 2 doubles exactly */
+    const float w = wts[rows[r]];
+    for (int j = 0; j < CA_NUM_MOVES; ++j) d[j] = 0.25f * (expf(h[j] - lse) * st - t[j]) * inv_b * w;
+    const float tv = tanhf(h[96]);
+    const float err = tv - evals[rows[r]];
+    d[96] = 2.0f * err * (1.0f - tv * tv) * inv_b * w;
+    d[97] = err * err * w;
+    d[98] = ce * w;
+  }
 }
 
 /* the engine's symmetry tables (kernels.h CO_SPACE_SYM, CO_MOVE_SYM), from the same initialisers of tables.inc */
@@ -118,10 +132,14 @@ struct FtSource {
  * rows[r].  Of a packed set that is virtual row v = rows[r]: sample v / 8 under symmetry k = v % 8, the gathers of
  * co_k_write_samples (state cell j < 64 from SS[k][j / 4] * 4 + j % 4, cells 64..69 as they are, policy entry m from
  * MS[k][m]).  One thread per float of the batch's 166-float rows, so a wave writes consecutive floats and reads within
- * one or two 664-byte samples. */
+ * one or two 664-byte samples.  WEIGHTED: bw[r] = the row's sample weight as well, next to be[r], from wt (one weight
+ * per packed sample or per expanded row).  The two operands stand last, so that the unweighted instantiation, which
+ * reads neither, is instruction for instruction the kernel it was before weights existed. */
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void ft_k_assemble(FtSource d, const int32_t *__restrict__ rows, int B,
                                                     float *__restrict__ bs, float *__restrict__ be,
-                                                    float *__restrict__ bp) {
+                                                    float *__restrict__ bp, const float *__restrict__ wt,
+                                                    float *__restrict__ bw) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= B * FT_SAMPLE_FLOATS) return;
   const int r = e / FT_SAMPLE_FLOATS, c = e % FT_SAMPLE_FLOATS;
@@ -136,6 +154,7 @@ __global__ __launch_bounds__(256) void ft_k_assemble(FtSource d, const int32_t *
       bp[(long)r * CA_NUM_MOVES + m] = src[CA_GAME_STATE_SIZE + FT_MOVE_SYM[k][m]];
     }
     if (c == 0) be[r] = d.oc[i];
+    if (WEIGHTED && c == 0) bw[r] = wt[i];
   } else {
     if (c < CA_GAME_STATE_SIZE) {
       bs[(long)r * CA_GAME_STATE_SIZE + c] = d.states[(long)v * CA_GAME_STATE_SIZE + c];
@@ -144,6 +163,7 @@ __global__ __launch_bounds__(256) void ft_k_assemble(FtSource d, const int32_t *
       bp[(long)r * CA_NUM_MOVES + m] = d.probs[(long)v * CA_NUM_MOVES + m];
     }
     if (c == 0) be[r] = d.evals[v];
+    if (WEIGHTED && c == 0) bw[r] = wt[v];
   }
 }
 
@@ -247,7 +267,9 @@ struct ca_fitter {
   DevBuf<float> w, m, v, g, gsum, stat, h, hd, loss;
   DevBuf<float> states, evals, probs; /* the expanded set */
   DevBuf<float> sp, oc;               /* the packed set: state_policy[cap][166], outcome[cap] */
-  DevBuf<float> bstates, bevals, bprobs; /* one batch of a packed set as ft_k_assemble wrote it: max_batch rows */
+  DevBuf<float> wt;                   /* sample weights, when `weighted`: [n] of an expanded set, [cap] beside sp and oc */
+  bool weighted = false;              /* ca_fitter_set_sample_weights, ca_fitter_merge_duplicates; until clear_data */
+  DevBuf<float> bstates, bevals, bprobs, bwts; /* one batch of a packed set as ft_k_assemble wrote it: max_batch rows */
   DevBuf<int32_t> sidx, idx, ident, bidx; /* ident[r] = r, the rows of an assembled batch; bidx: ca_fitter_fetch_rows */
   std::vector<float> hloss;
 
@@ -279,22 +301,33 @@ struct ca_fitter {
   struct Batch {
     const int32_t *rows;
     const float *states, *evals, *probs;
+    const float *wts; /* null: an unweighted set */
   };
   FtSource source() const { return FtSource{expanded ? nullptr : sp.p, oc.p, states.p, evals.p, probs.p}; }
   void assemble(const int32_t *rows, int B) {
-    RT_LAUNCH(ft_k_assemble, (B * FT_SAMPLE_FLOATS + 255) / 256, 256, s, source(), rows, B, bstates.p, bevals.p, bprobs.p);
+    const int grid = (B * FT_SAMPLE_FLOATS + 255) / 256;
+    if (weighted)
+      RT_LAUNCH(ft_k_assemble<true>, grid, 256, s, source(), rows, B, bstates.p, bevals.p, bprobs.p, (const float *)wt.p,
+                bwts.p);
+    else
+      RT_LAUNCH(ft_k_assemble<false>, grid, 256, s, source(), rows, B, bstates.p, bevals.p, bprobs.p,
+                (const float *)nullptr, (float *)nullptr);
   }
   /* the batch of rows[0..B) (a device pointer): the expanded set itself, or a packed set's rows assembled */
   Batch batch(const int32_t *rows, int B) {
-    if (expanded) return Batch{rows, states.p, evals.p, probs.p};
+    if (expanded) return Batch{rows, states.p, evals.p, probs.p, weighted ? wt.p : nullptr};
     assemble(rows, B);
-    return Batch{ident.p, bstates.p, bevals.p, bprobs.p};
+    return Batch{ident.p, bstates.p, bevals.p, bprobs.p, weighted ? bwts.p : nullptr};
   }
   FtShared shared(const Batch &b) const { return FtShared{s, w.p, g.p, stat.p, h.p, hd.p, b.states}; }
 
   /* loss terms of the batch (and the logit / value gradients in Hd); loss sums to loss.p[2 * slot] */
   void loss_terms(const Batch &b, int B, bool grads, int slot) {
-    RT_LAUNCH(ft_k_loss, (B + 255) / 256, 256, s, (const float *)h.p, b.rows, B, b.evals, b.probs, hd.p);
+    if (b.wts)
+      RT_LAUNCH(ft_k_loss<true>, (B + 255) / 256, 256, s, (const float *)h.p, b.rows, B, b.evals, b.probs, hd.p, b.wts);
+    else
+      RT_LAUNCH(ft_k_loss<false>, (B + 255) / 256, 256, s, (const float *)h.p, b.rows, B, b.evals, b.probs, hd.p,
+                (const float *)nullptr);
     RT_LAUNCH(ft_k_head_reduce, FT_PADW / 16, 1024, s, (const float *)hd.p, B, grads ? g.p : (float *)nullptr,
               net->policy_bias(), net->value_bias(), loss.p + 2 * slot);
   }
@@ -333,14 +366,15 @@ struct ca_fitter {
     bstates.alloc((size_t)max_batch * CA_GAME_STATE_SIZE, s);
     bevals.alloc((size_t)max_batch, s);
     bprobs.alloc((size_t)max_batch * CA_NUM_MOVES, s);
+    bwts.alloc((size_t)max_batch, s);
     ident.alloc((size_t)max_batch, s);
     rt_h2d(ident.p, id.data(), id.size() * sizeof(int32_t), s);
     rt_sync(s); /* id is a local */
     bidx.alloc((size_t)max_batch, s);
   }
   void clear_data() {
-    n = 0, ns = 0, cap = 0, idx_cap = 0, expanded = false;
-    states.release(), evals.release(), probs.release(), sp.release(), oc.release(), idx.release();
+    n = 0, ns = 0, cap = 0, idx_cap = 0, expanded = false, weighted = false;
+    states.release(), evals.release(), probs.release(), sp.release(), oc.release(), idx.release(), wt.release();
   }
   /* the packed rows [first, first + count) to the front of the buffers they are in (a slide of the window), device to
    * device without a second buffer: in pieces of `first` rows from the front, each of which ends before its source
@@ -355,24 +389,31 @@ struct ca_fitter {
       rt_d2d(sp.p + (size_t)d * FT_SAMPLE_FLOATS, sp.p + ((size_t)d + first) * FT_SAMPLE_FLOATS,
              k * FT_SAMPLE_FLOATS * sizeof(float), s);
       rt_d2d(oc.p + d, oc.p + d + first, k * sizeof(float), s);
+      if (weighted) rt_d2d(wt.p + d, wt.p + d + first, k * sizeof(float), s);
     }
     rt_sync(s);
   }
   /* the packed rows [first, first + count) to the front of new buffers with room for new_cap samples, device to device */
   void move_samples(int32_t first, int32_t count, int32_t new_cap) {
-    DevBuf<float> nsp, noc;
+    DevBuf<float> nsp, noc, nwt;
     nsp.alloc((size_t)new_cap * FT_SAMPLE_FLOATS, s);
     noc.alloc((size_t)new_cap, s);
+    if (weighted) {
+      nwt.alloc((size_t)new_cap, s);
+      rt_d2d(nwt.p, wt.p + first, (size_t)count * sizeof(float), s);
+    }
     rt_d2d(nsp.p, sp.p + (size_t)first * FT_SAMPLE_FLOATS, (size_t)count * FT_SAMPLE_FLOATS * sizeof(float), s);
     rt_d2d(noc.p, oc.p + first, (size_t)count * sizeof(float), s);
     rt_sync(s); /* before the old buffers are freed */
     std::swap(sp, nsp);
     std::swap(oc, noc);
+    if (weighted) std::swap(wt, nwt);
     cap = new_cap;
   }
   /* room for `add` more packed samples behind the ns there are; capacity grows geometrically */
   void reserve(int32_t add) {
     if (expanded) throw CaError(CA_ERR_STATE, "ca_fitter: the data set is expanded (ca_fitter_clear_data first)");
+    if (weighted) throw CaError(CA_ERR_STATE, "ca_fitter: the data set carries sample weights (ca_fitter_clear_data first)");
     if (add < 0) throw CaError(CA_ERR_ARG, "ca_fitter: negative sample count");
     const int64_t need = (int64_t)ns + add, most = INT32_MAX / CA_NUM_SYMMETRIES;
     if (need > most) throw CaError(CA_ERR_ARG, "ca_fitter: more than INT32_MAX virtual rows");
@@ -680,5 +721,65 @@ extern "C" int ca_fitter_fetch_rows(ca_fitter *f, const int32_t *rows, int32_t n
       rt_d2h(probs + (size_t)r0 * CA_NUM_MOVES, f->bprobs.p, (size_t)B * CA_NUM_MOVES * sizeof(float), f->s);
       rt_sync(f->s);
     }
+  });
+}
+
+/* ------------------------------------------------------------------ sample weights, merging of duplicates */
+extern "C" int ca_fitter_set_sample_weights(ca_fitter *f, const float *weights, int32_t n) {
+  return co_guard(f, [&] {
+    f->need_data();
+    if (!weights) { /* back to the unweighted set */
+      rt_sync(f->s);
+      f->weighted = false;
+      f->wt.release();
+      return;
+    }
+    const int32_t units = f->expanded ? f->n : f->ns;
+    if (n != units)
+      throw CaError(CA_ERR_ARG, "ca_fitter_set_sample_weights: " + std::to_string(units) + " weights are needed, got " +
+                                    std::to_string(n));
+    for (int32_t i = 0; i < n; ++i)
+      if (!(weights[i] >= 0.0f) || weights[i] == INFINITY) /* (a NaN fails the first comparison) */
+        throw CaError(CA_ERR_ARG, "ca_fitter_set_sample_weights: every weight must be finite and >= 0");
+    if (!f->weighted) f->wt.alloc((size_t)(f->expanded ? f->n : f->cap), f->s);
+    rt_h2d(f->wt.p, weights, (size_t)n * sizeof(float), f->s);
+    rt_sync(f->s);
+    f->weighted = true;
+  });
+}
+
+extern "C" int ca_fitter_get_sample_weights(ca_fitter *f, float *out, int32_t n) {
+  return co_guard(f, [&] {
+    f->need_data();
+    const int32_t units = f->expanded ? f->n : f->ns;
+    if (!out || n != units)
+      throw CaError(CA_ERR_ARG, "ca_fitter_get_sample_weights: null output, or not the " + std::to_string(units) +
+                                    " weights of the set");
+    if (!f->weighted) { /* an unweighted set counts every row once */
+      for (int32_t i = 0; i < n; ++i) out[i] = 1.0f;
+      return;
+    }
+    rt_d2h(out, f->wt.p, (size_t)n * sizeof(float), f->s);
+    rt_sync(f->s);
+  });
+}
+
+extern "C" int ca_fitter_merge_duplicates(ca_fitter *f, int normalize, int32_t *before, int32_t *after) {
+  return co_guard(f, [&] {
+    if (!before || !after) throw CaError(CA_ERR_ARG, "ca_fitter_merge_duplicates: null output");
+    if (f->expanded) throw CaError(CA_ERR_STATE, "ca_fitter_merge_duplicates: the data set is expanded");
+    if (f->ns <= 0) throw CaError(CA_ERR_STATE, "ca_fitter_merge_duplicates: no samples (ca_fitter_add_samples)");
+    rt_sync(f->s);
+    FtMerged m = ft_merge_duplicates(f->s, f->sp.p, f->oc.p, f->weighted ? f->wt.p : nullptr, f->ns, normalize != 0);
+    /* the merged samples are in buffers of their own: swapped in as move_samples does; nothing waits on the old ones */
+    *before = f->ns;
+    *after = m.count;
+    std::swap(f->sp, m.sp);
+    std::swap(f->oc, m.oc);
+    std::swap(f->wt, m.wt);
+    f->weighted = true;
+    f->cap = m.cap;
+    f->ns = m.count;
+    f->added(0);
   });
 }

@@ -31,6 +31,12 @@ device (DESIGN.md "Network training", "The packed data set"):
 fit_samples(w, sp, oc, seed=s) equals fit(w, *expand_samples(sp, oc), seed=s) to the bit, and fit_trainer(w, t) equals
 fit(w, *samples_io.get_samples(t)): the row order is the same, so the validation split and the permutations are, and a
 step on virtual rows reads the floats the expanded arrays hold.
+
+Samples may carry weights, Keras's model.fit(sample_weight=...): a batch's losses are (1/B) sum_r w_r loss_r, BatchNorm
+statistics stay unweighted (fit(..., sample_weight=w), fit_samples(..., sample_weight=w), Fitter.set_sample_weights).
+Fitter.merge_duplicates merges the duplicate positions of a packed set on the device into one weighted sample each
+(DESIGN.md "Merging duplicate positions"; samples_io.merge_duplicates_host is its definition).  A set without weights
+is fitted by the kernels that know of none.
 """
 import ctypes as C
 import inspect
@@ -182,6 +188,40 @@ class Fitter:
         self._check(self._L.ca_fitter_fetch_rows(self._h, _ptr(r, C.c_int32), r.size, _ptr(s), _ptr(e), _ptr(p)))
         return s, e, p
 
+    # ---- sample weights and merging of duplicates (include/corintho_hip.h, "sample weights") ----
+    def _units(self):
+        """how many weights the set takes: its rows (expanded) or its samples (packed)"""
+        rows, samples = self.data_info()
+        return samples if samples else rows
+
+    def set_sample_weights(self, weights):
+        """Keras's sample_weight: one float32 weight per row of an expanded set, per un-augmented sample of a packed
+        one (virtual row v has the weight of sample v // 8).  Every weight must be finite and >= 0.  None removes the
+        weights: the set is fitted by the unweighted kernels again."""
+        if weights is None:
+            self._check(self._L.ca_fitter_set_sample_weights(self._h, None, 0))
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+        self._check(self._L.ca_fitter_set_sample_weights(self._h, _ptr(w), w.size))
+
+    def get_sample_weights(self):
+        """the weights, one per row or sample; ones for a set that carries none"""
+        w = np.zeros(self._units(), np.float32)
+        self._check(self._L.ca_fitter_get_sample_weights(self._h, _ptr(w), w.size))
+        return w
+
+    def merge_duplicates(self, normalize=True):
+        """Merge the duplicate positions of a packed set on the device: samples whose 70 state floats have the same
+        bits become one sample at the rank of the first of them, with the weighted mean of their policies and outcomes
+        (float64 sums over the members in ascending index, rounded once) and the sum W of their weights as its weight
+        (samples_io.merge_duplicates_host is the definition, and equals this bit for bit).  normalize: the weights are
+        scaled to mean one.  A group whose weights are all 0 has W = 0 and no mean: it is dropped, members and all.
+        The set carries weights afterwards, so add_* is refused until clear_data: merge once, after the last add.
+        Returns (samples before, samples after)."""
+        before, after = C.c_int32(), C.c_int32()
+        self._check(self._L.ca_fitter_merge_duplicates(self._h, 1 if normalize else 0, C.byref(before), C.byref(after)))
+        return before.value, after.value
+
     def train(self, rows, batch_size, learning_rate, batch_losses=False):
         """one epoch over `rows` in that order; returns the three mean losses (and the [batches, 3] per-batch ones)"""
         r = np.ascontiguousarray(rows, dtype=np.int32)
@@ -298,16 +338,40 @@ def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epoch
                    seed)
 
 
-def fit_samples(weights, state_policy, outcome, *, batch_size=2048, device=0, net=NET_MLP12X100, _backend=None, **kw):
+def fit_samples(weights, state_policy, outcome, *, batch_size=2048, device=0, net=NET_MLP12X100, sample_weight=None,
+                merge_duplicates=False, _backend=None, **kw):
     """fit() from un-augmented samples (Trainer.export_samples, dist.SampleGather.rows): a packed data set, 668 bytes
     a sample on the device instead of 5 344.  fit_samples(w, sp, oc, seed=s) equals fit(w, *expand_samples(sp, oc),
     seed=s) to the bit: the 8 n virtual rows are in expand_samples' row order, so the validation split and every
-    epoch's permutation are the same.  Keywords as fit_resident's."""
+    epoch's permutation are the same.  sample_weight: one weight per sample (Keras's sample_weight; the sample's 8
+    virtual rows share it).  merge_duplicates: Fitter.merge_duplicates(normalize=True) on the set, weights and all,
+    before the fit -- the same as fitting samples_io.merge_duplicates_host's three arrays.  Keywords as fit_resident's."""
     name, num_weights = net_info(net)
     if _f32(weights).size != num_weights:
         raise ValueError("fit_samples: %s weights have %d floats, got %d" % (name, num_weights, _f32(weights).size))
     sp, oc = _packed(state_policy, outcome, "fit_samples")
-    return _fit_added(lambda be: be.add_samples(sp, oc), weights, batch_size, device, net, _backend, kw)
+    sw = _sample_weight(sample_weight, sp.shape[0], "fit_samples")
+
+    def add(be):
+        be.add_samples(sp, oc)
+        if sw is not None:
+            be.set_sample_weights(sw)
+        if merge_duplicates:
+            be.merge_duplicates(normalize=True)
+
+    return _fit_added(add, weights, batch_size, device, net, _backend, kw)
+
+
+def _sample_weight(sample_weight, n, who):
+    """the weights of n rows or samples, checked; None stays None"""
+    if sample_weight is None:
+        return None
+    sw = np.ascontiguousarray(sample_weight, dtype=np.float32).ravel()
+    if sw.size != n:
+        raise ValueError("%s: sample_weight must be [n] for n = %d, got %d" % (who, n, sw.size))
+    if not np.all(np.isfinite(sw)) or np.any(sw < 0):
+        raise ValueError("%s: every sample weight must be finite and >= 0" % who)
+    return sw
 
 
 def fit_trainer(weights, trainers, *, batch_size=2048, device=0, net=NET_MLP12X100, _backend=None, **kw):
@@ -349,10 +413,12 @@ def _fit_added(add, weights, batch_size, device, net, backend, kw):
 
 def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, batch_size=2048, epochs=1,
         validation_split=0.3, shuffle=True, anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, device=0,
-        net=NET_MLP12X100, _backend=None):
+        net=NET_MLP12X100, sample_weight=None, _backend=None):
     """main.pyx:249-260 `model.fit(...)` with its callbacks; see the module docstring.  Returns a FitResult.
     optimizer_state: (m, v, iterations) to resume from; None starts Adam from zeros, as a freshly compiled model.
-    net: NET_MLP12X100 or NET_RESCNN4, the network `weights` belong to."""
+    net: NET_MLP12X100 or NET_RESCNN4, the network `weights` belong to.
+    sample_weight: one weight per row, Keras's model.fit(sample_weight=...): a batch's losses are (1/B) sum w_r loss_r,
+    in training and in validation; None fits unweighted."""
     name, num_weights = net_info(net)
     w = _f32(weights).ravel()
     if w.size != num_weights:
@@ -371,6 +437,7 @@ def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, 
         raise ValueError("fit: %d rows leave no training or no validation rows at validation_split=%g"
                          % (n, validation_split))
     batch_size, epochs = int(batch_size), int(epochs)
+    sw = _sample_weight(sample_weight, n, "fit")
 
     own = _backend is None
     be = Fitter(max_batch=batch_size, device=device, net=net) if own else _backend
@@ -382,6 +449,8 @@ def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, 
             m, v, it = optimizer_state
             be.set_optimizer(m, v, it)
         be.set_data(states, evals, probs)
+        if sw is not None:
+            be.set_sample_weights(sw)
         return _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed)
     finally:
         if own:

@@ -19,7 +19,11 @@ What is deliberately not the reference's:
   * the run is not zipped after every generation (wrapper.py:390-400) unless zip_logs is set;
   * metadata files are written through a temporary file and os.replace, current_generation.txt last; on opening a run
     metadata/losses.txt is cut to one line per finished generation (the reference appends the loss before the arena, so
-    an interrupted generation would leave its line behind and count twice in write_learning_rate).
+    an interrupted generation would leave its line behind and count twice in write_learning_rate);
+  * merge_duplicates (off by default): after the last samples of the fit's window are added, positions that occur more
+    than once become one sample each, with the mean of their targets and a weight equal to their share
+    (Fitter.merge_duplicates, normalised to mean one, so that a batch weighs what an unweighted one does; val_loss
+    is lower all the same, because the merged targets are means: profiles/sample_merge.md).  samples.npz stays the un-merged export and fit_time.txt counts the generation's samples, as the reference does.
 """
 import argparse
 import dataclasses
@@ -81,6 +85,7 @@ class RunParams:
     sample_format: str = "packed"
     init_weights: object = None  # flat array or .npz for generation 0
     zip_logs: bool = False
+    merge_duplicates: bool = False  # True: duplicate positions of the fit's window become one weighted sample each
 
     def __post_init__(self):
         for f in dataclasses.fields(self):  # a TOML or command-line value may come as the other number type
@@ -113,6 +118,7 @@ class RunParams:
         if self.seed < 0:
             raise ValueError("seed must not be negative")
         self.mix_old, self.zip_logs = bool(self.mix_old), bool(self.zip_logs)
+        self.merge_duplicates = bool(self.merge_duplicates)
 
     def as_dict(self):
         d = {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
@@ -131,6 +137,7 @@ class GenerationResult:
     num_samples: int
     seeds: dict            # {"selfplay", "arena", "fit"}
     times: dict = field(default_factory=dict)  # seconds of "selfplay", "samples", "fit", "arena"
+    merged: object = None  # merge_duplicates: (samples of the fit's window before, after); None: not asked for
 
     @property
     def val_loss(self):
@@ -317,6 +324,10 @@ def train_generation(params, state, *, _cdll=None, _fitter=None, _hook=None):
         old_sp, old_oc = samples_io.load_packed(folder)
         if p.mix_old:
             _fitter.add_samples(old_sp, old_oc)
+    merged = None
+    if p.merge_duplicates:  # after the last add: a set that carries weights takes no more samples
+        merged = tuple(int(x) for x in _fitter.merge_duplicates(normalize=True))
+        print("generation %d: merged %d samples into %d distinct positions" % (generation, merged[0], merged[1]), flush=True)
     times["samples"] = time.perf_counter() - t0
 
     # fit (main.pyx:221-272): the current generation's model, not the best one's, with its Adam state
@@ -358,7 +369,7 @@ def train_generation(params, state, *, _cdll=None, _fitter=None, _hook=None):
     rating = update_rating(state["new_rating_file"], state["best_gen_rating"], score)
     hook("arena")
     return GenerationResult(generation=generation, improved=bool(score > p.test_threshold), score=score, rating=rating,
-                            fit=res, num_samples=num_samples, seeds=seeds, times=times)
+                            fit=res, num_samples=num_samples, seeds=seeds, times=times, merged=merged)
 
 
 # ---------------------------------------------------------------------------------------------------- the run
@@ -583,6 +594,9 @@ def _parser():
     for f in dataclasses.fields(RunParams):
         if f.name in ("mix_old", "zip_logs"):
             ap.add_argument("--" + f.name, action="store_true", default=False)
+        elif f.name == "merge_duplicates":
+            ap.add_argument("--merge-duplicates", "--merge_duplicates", dest="merge_duplicates", action="store_true",
+                            default=False, help="Merge duplicate positions of the fit's samples into weighted ones")
         elif f.name in ("seed", "init_weights"):
             ap.add_argument("--" + f.name, type=int if f.name == "seed" else str, default=None, help=helps[f.name])
         else:

@@ -92,6 +92,51 @@ def load_packed(sample_folder):
                          sample_folder)
 
 
+def merge_duplicates_host(state_policy, outcome, weights=None, normalize=True):
+    """Merge the duplicate positions of un-augmented samples: -> (state_policy, outcome, weights) float32.  This is the
+    definition that Fitter.merge_duplicates computes on the device, bit for bit.
+
+    Two samples are equal when their 70 state floats have the same bit patterns.  A group of equal samples becomes one
+    sample at the rank of its first member (groups keep the order of their first members).  With w_i the members'
+    weights (`weights`, or 1) and every sum taken in float64 over the members in ascending index:
+        W = sum w_i,   policy[m] = (sum w_i p_i[m]) / W,   outcome = (sum w_i z_i) / W,
+    each rounded once to float32; the new weight is W.  A group with W = 0 has no mean: it is dropped, and its
+    weight-0 members with it.  normalize: every weight is then W * (after / sum W), in float64 with the groups' W summed
+    in order, rounded once, so that the weights have mean one and a weighted fit keeps an unweighted one's loss scale."""
+    sp, oc = _check_packed(state_policy, outcome, "merge_duplicates_host")
+    n = sp.shape[0]
+    if weights is None:
+        w = np.ones(n, np.float64)
+    else:
+        w = np.ascontiguousarray(weights, dtype=np.float32).ravel().astype(np.float64)
+        if w.size != n or not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("merge_duplicates_host: weights must be [n], finite and >= 0")
+    if n == 0:
+        return sp, oc, w.astype(np.float32)
+    # groups by the states' bytes, numbered in the order of their first members
+    keys = np.ascontiguousarray(sp[:, :GAME_STATE_SIZE]).view(np.dtype((np.void, 4 * GAME_STATE_SIZE))).ravel()
+    _, first, inverse = np.unique(keys, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")
+    number = np.empty(order.size, np.int64)
+    number[order] = np.arange(order.size)
+    group = number[np.asarray(inverse).ravel()]
+    first = first[order]
+    # np.add.at applies its terms one by one in index order: the members in ascending index
+    wsum = np.zeros(first.size, np.float64)
+    acc = np.zeros((first.size, NUM_MOVES + 1), np.float64)
+    np.add.at(wsum, group, w)
+    terms = np.concatenate([sp[:, GAME_STATE_SIZE:], oc[:, None]], axis=1).astype(np.float64) * w[:, None]
+    np.add.at(acc, group, terms)
+    keep = wsum > 0
+    first, wsum, acc = first[keep], wsum[keep], acc[keep]
+    mean = (acc / wsum[:, None]).astype(np.float32)
+    out_sp = np.concatenate([sp[first, :GAME_STATE_SIZE], mean[:, :NUM_MOVES]], axis=1)
+    if normalize and wsum.size:
+        total = np.cumsum(wsum)[-1]  # a running sum, in order (np.sum adds pairwise), as the device's summing thread
+        wsum = wsum * (np.float64(wsum.size) / total)
+    return np.ascontiguousarray(out_sp), np.ascontiguousarray(mean[:, NUM_MOVES]), wsum.astype(np.float32)
+
+
 def samples_for_training(trainer, sample_folder, old_training_samples=(), mix_old=False):
     """The whole of get_samples (main.pyx:189-219): fetch this generation's samples, save them, then walk the
     replay window `old_training_samples` (folders of earlier generations, wrapper.py passes the last few).

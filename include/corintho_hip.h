@@ -36,6 +36,7 @@ extern "C" {
 #define CA_ERR_STATE -4    /* call made in the wrong state */
 #define CA_ERR_IO -5
 #define CA_ERR_CALLBACK -6 /* a caller-supplied network function returned non-zero */
+#define CA_ERR_INTERNAL -7 /* a device pass found a state that cannot be (ca_fitter_merge_duplicates) */
 
 typedef struct ca_trainer ca_trainer;
 
@@ -488,6 +489,31 @@ int ca_fitter_data_info(ca_fitter *f, int32_t *rows, int32_t *samples);
  * probs [n_rows][96] -- through the kernel that assembles a packed set's batches (for an expanded set, the same
  * kernel's plain row copy).  n_rows is not bound by max_batch. */
 int ca_fitter_fetch_rows(ca_fitter *f, const int32_t *rows, int32_t n_rows, float *states, float *evals, float *probs);
+
+/* ---- sample weights (Keras's model.fit(sample_weight=...), reduction SUM_OVER_BATCH_SIZE) ----
+ * A data set may carry one float32 weight per row (expanded) or per un-augmented sample (packed: virtual row v has the
+ * weight of sample v / 8).  A batch of B rows then has the value loss (1/B) sum_r w_r (tanh v_r - z_r)^2 and the policy
+ * loss (1/B) sum_r w_r CE_r -- the divisor is B, not sum w -- and ca_fitter_train, _evaluate and _gradients report and
+ * differentiate these.  BatchNorm statistics stay unweighted: a row of weight 0 still counts in them.  A set whose
+ * weights were never set runs the unweighted kernels, bit for bit what it ran before weights existed.  The weights move
+ * with their samples in ca_fitter_drop_samples; ca_fitter_add_* on a set that carries weights: CA_ERR_STATE
+ * (ca_fitter_clear_data first).  ca_fitter_set_data and ca_fitter_clear_data remove them. */
+/* n must be the set's rows (expanded) or samples (packed), every weight finite and >= 0: else CA_ERR_ARG and nothing
+ * changes.  weights == NULL removes the weights (n is not looked at).  No data: CA_ERR_STATE. */
+int ca_fitter_set_sample_weights(ca_fitter *f, const float *weights, int32_t n);
+/* reads them back; an unweighted set gives 1.0 for every row or sample */
+int ca_fitter_get_sample_weights(ca_fitter *f, float *out, int32_t n);
+/* Merges the duplicate positions of a packed set on the device.  Two samples are equal when their 70 state floats have
+ * the same bit patterns.  A group of equal samples is replaced by one sample at the rank of its first member (groups keep
+ * the order of their first members).  With w_i the members' weights (1 on an unweighted set) and the sums taken in
+ * float64 over the members in ascending sample index:
+ *     W = sum w_i,  policy[m] = (sum w_i p_i[m]) / W,  outcome = (sum w_i z_i) / W,  each rounded once to float32,
+ * and the new weight is W.  A group with W = 0 (every member of weight 0) is dropped, members and all.  normalize != 0:
+ * every new weight is then W * (after / sum W), in float64 (the groups' W summed in order), rounded once: the weights
+ * have mean one, so a weighted fit keeps the loss scale of an unweighted one.  *before and *after: the samples before and
+ * after.  The set carries weights from here on.  An expanded or an empty set: CA_ERR_STATE.  CA_ERR_INTERNAL: a device
+ * pass reported an impossible state (its probe loops are bounded); the set is unchanged. */
+int ca_fitter_merge_duplicates(ca_fitter *f, int normalize, int32_t *before, int32_t *after);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,8 @@ def compile_tree(csrc, work, jobs):
     """-> the assembly files of the tree's sources, compiled `jobs` at a time"""
     os.makedirs(work, exist_ok=True)
     flags = [f for f in B.FLAGS if f not in ("-fPIC", "-shared")] + ["--offload-device-only", "-S"]
-    todo = [(os.path.join(csrc, s), os.path.join(work, s + ".s")) for s in B.SOURCES]
+    todo = [(os.path.join(csrc, s), os.path.join(work, s + ".s")) for s in B.SOURCES
+            if os.path.exists(os.path.join(csrc, s))]  # (an earlier tree need not have every source of today's)
     running, done = [], []
     while todo or running:
         while todo and len(running) < jobs:
