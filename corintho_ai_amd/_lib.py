@@ -92,6 +92,7 @@ EXPORTS = [
     "ca_tourney_set_grouped", "ca_tourney_set_seed", "ca_net_group_create", "ca_net_group_forward", "ca_net_group_info", "ca_net_group_tables",
     "ca_net_group_bench", "ca_net_group_destroy",
     "ca_fitter_set_sample_weights", "ca_fitter_get_sample_weights", "ca_fitter_merge_duplicates",
+    "ca_net_forward_device_io",
 ]
 # the caller-supplied network: an earlier build of the library has none of these
 NET_FN_EXPORTS = ["ca_trainer_request_rows", "ca_trainer_set_net_fn", "ca_tourney_set_net_fn", "ca_net_create", "ca_net_forward_device",
@@ -101,7 +102,9 @@ GROUP_EXPORTS = ["ca_tourney_set_grouped", "ca_tourney_set_seed", "ca_net_group_
                  "ca_net_group_tables", "ca_net_group_bench", "ca_net_group_destroy"]
 # sample weights and the merging of duplicate positions: likewise
 WEIGHT_EXPORTS = ["ca_fitter_set_sample_weights", "ca_fitter_get_sample_weights", "ca_fitter_merge_duplicates"]
-assert set(NET_FN_EXPORTS + GROUP_EXPORTS + WEIGHT_EXPORTS) <= set(EXPORTS)
+# a network launch with a fused run's indirection: likewise
+NET_IO_EXPORTS = ["ca_net_forward_device_io"]
+assert set(NET_FN_EXPORTS + GROUP_EXPORTS + WEIGHT_EXPORTS + NET_IO_EXPORTS) <= set(EXPORTS)
 
 
 def declare(L):
@@ -172,6 +175,8 @@ def declare(L):
         L.ca_net_forward_device.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp]
         L.ca_net_destroy.argtypes = [vp]
         L.ca_net_destroy.restype = None
+    if hasattr(L, "ca_net_forward_device_io"):  # (as above)
+        L.ca_net_forward_device_io.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp]
     group = hasattr(L, "ca_net_group_create")  # (as above: an earlier build has none)
     if group:
         L.ca_tourney_set_grouped.argtypes = [vp, C.c_int32]
@@ -194,7 +199,7 @@ def declare(L):
             continue
         if name in GROUP_EXPORTS and not group:
             continue
-        if name in WEIGHT_EXPORTS and not hasattr(L, name):
+        if name in WEIGHT_EXPORTS + NET_IO_EXPORTS and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy", "ca_net_destroy",

@@ -24,16 +24,37 @@ struct ca_net {
     if (!d_states || !d_rows || !d_evals || !d_probs) throw CaError(CA_ERR_ARG, "ca_net_forward_device: null buffer");
     if (rows_cap < 0 || (size_t)rows_cap > net->max_rows()) throw CaError(CA_ERR_ARG, "ca_net_forward_device: more rows than the net's max_rows");
     if (rows_cap == 0) return;
+    launch(d_states, rows_cap, rows_cap, d_rows, d_evals, d_probs, CoNetIO(), stream_arg, "ca_net_forward_device");
+  }
+
+  /* the same launch as a fused run shapes it (pools.h Pools::launch): rows read through io.in_idx from the first state_rows
+   * rows of d_states, outputs through io.out_idx at io's strides, io.alone */
+  void forward_device_io(const float *d_states, int32_t state_rows, int32_t rows_cap, const int32_t *d_rows, float *d_evals,
+                         float *d_probs, const CoNetIO &io, void *stream_arg) {
+    const char *who = "ca_net_forward_device_io";
+    if (!d_states || !d_rows || !d_evals || !d_probs) throw CaError(CA_ERR_ARG, std::string(who) + ": null buffer");
+    if (rows_cap < 0 || (size_t)rows_cap > net->max_rows() || state_rows < 0 || (size_t)state_rows > net->max_rows())
+      throw CaError(CA_ERR_ARG, std::string(who) + ": more rows than the net's max_rows");
+    if (!io.in_idx && state_rows < rows_cap)
+      throw CaError(CA_ERR_ARG, std::string(who) + ": without in_idx the launch reads rows_cap rows, state_rows is fewer");
+    if (io.eval_stride < 1 || io.probs_stride < CO_NET_NUM_MOVES)
+      throw CaError(CA_ERR_ARG, std::string(who) + ": eval_stride < 1 or probs_stride < 96");
+    if (rows_cap == 0) return;
+    launch(d_states, state_rows, rows_cap, d_rows, d_evals, d_probs, io, stream_arg, who);
+  }
+
+  void launch(const float *d_states, int32_t state_rows, int32_t rows_cap, const int32_t *d_rows, float *d_evals, float *d_probs,
+              const CoNetIO &io, void *stream_arg, const char *who) {
     const rt_stream_t s = stream_arg ? (rt_stream_t)(intptr_t)stream_arg : (rt_stream_t)stream;
     if (used_once && used_on != s) rt_stream_wait(s, used);
-    expand_rows(d_states, rows80.p, rows_cap, s);
-    net->forward(rows80.p, rows_cap, d_rows, d_evals, d_probs, s);
+    expand_rows(d_states, rows80.p, state_rows, s);
+    net->forward(rows80.p, rows_cap, d_rows, d_evals, d_probs, s, io);
     rt_event_record(used, s);
     used_on = s;
     used_once = true;
     if (!stream_arg) {
       rt_sync(s);
-      check_net_range(net.get(), s, "ca_net_forward_device");
+      check_net_range(net.get(), s, who);
     }
   }
 };
@@ -55,6 +76,16 @@ extern "C" int ca_net_create(int device, int kind, const float *weights, size_t 
 extern "C" int ca_net_forward_device(ca_net *n, const float *d_states, int32_t rows_cap, const int32_t *d_rows, float *d_evals,
                                      float *d_probs, void *stream) {
   return co_guard(n, [&] { n->forward_device(d_states, rows_cap, d_rows, d_evals, d_probs, stream); });
+}
+/* (the indices themselves cannot be checked here: they live on the device and are read by the kernels, include/corintho_hip.h) */
+extern "C" int ca_net_forward_device_io(ca_net *n, const float *d_states, int32_t state_rows, int32_t rows_cap, const int32_t *d_rows,
+                                        const int32_t *d_in_idx, const int32_t *d_out_idx, float *d_evals, int32_t eval_stride,
+                                        float *d_probs, int32_t probs_stride, int32_t alone, void *stream) {
+  return co_guard(n, [&] {
+    CoNetIO io;
+    io.in_idx = d_in_idx, io.out_idx = d_out_idx, io.eval_stride = eval_stride, io.probs_stride = probs_stride, io.alone = alone != 0;
+    n->forward_device_io(d_states, state_rows, rows_cap, d_rows, d_evals, d_probs, io, stream);
+  });
 }
 extern "C" void ca_net_destroy(ca_net *n) { delete n; }
 

@@ -6,6 +6,11 @@ function (Trainer.set_net_fn) calls to run the library's kernels on the rows it 
 
 All pointers are device addresses as integers: states [rows_cap][70], a device int32 row count, evals [rows_cap],
 probs [rows_cap][96].  stream: a HIP stream handle; 0 = the net's own stream, synchronised before the call returns.
+
+The keyword arguments of forward_device shape the launch as a fused run does (ca_net_forward_device_io): in_idx / out_idx
+are device int32 lists (0: rows in place) -- row r is read from states row in_idx[r], of state_rows rows, and written to
+element out_idx[r] of evals (eval_stride floats per element) and probs (probs_stride); alone=False tells the kernels that
+other streams keep the GPU busy.  The library cannot check the indices.
 """
 import ctypes as C
 
@@ -22,9 +27,16 @@ class Net:
         self.max_rows = int(max_rows)
         _lib.check(self._L, self._L.ca_net_create(device, kind, w.ctypes.data_as(_lib.f32p), w.size, self.max_rows, C.byref(self._n)))
 
-    def forward_device(self, ptr_states, rows_cap, ptr_rows, ptr_evals, ptr_probs, stream=0):
-        _lib.check(self._L, self._L.ca_net_forward_device(self._n, C.c_void_p(ptr_states), int(rows_cap), C.c_void_p(ptr_rows),
-                                                          C.c_void_p(ptr_evals), C.c_void_p(ptr_probs), C.c_void_p(stream or None)))
+    def forward_device(self, ptr_states, rows_cap, ptr_rows, ptr_evals, ptr_probs, stream=0, *, in_idx=0, out_idx=0, eval_stride=1,
+                       probs_stride=96, alone=True, state_rows=None):
+        if not in_idx and not out_idx and (eval_stride, probs_stride) == (1, 96) and alone and state_rows is None:
+            _lib.check(self._L, self._L.ca_net_forward_device(self._n, C.c_void_p(ptr_states), int(rows_cap), C.c_void_p(ptr_rows),
+                                                              C.c_void_p(ptr_evals), C.c_void_p(ptr_probs), C.c_void_p(stream or None)))
+            return
+        _lib.check(self._L, self._L.ca_net_forward_device_io(
+            self._n, C.c_void_p(ptr_states), int(rows_cap if state_rows is None else state_rows), int(rows_cap), C.c_void_p(ptr_rows),
+            C.c_void_p(in_idx or None), C.c_void_p(out_idx or None), C.c_void_p(ptr_evals), int(eval_stride), C.c_void_p(ptr_probs),
+            int(probs_stride), int(bool(alone)), C.c_void_p(stream or None)))
 
     def close(self):
         if getattr(self, "_n", None) and self._n.value:

@@ -387,6 +387,18 @@ typedef struct ca_net ca_net;
 int ca_net_create(int device, int kind, const float *weights, size_t n_floats, int32_t max_rows, ca_net **out);
 int ca_net_forward_device(ca_net *n, const float *d_states, int32_t rows_cap, const int32_t *d_rows, float *d_evals,
                           float *d_probs, void *stream);
+/* The same launch with the indirection a fused run gives it: row r < *d_rows of the launch is read from row d_in_idx[r] of
+ * d_states [state_rows][70] (NULL: row r; state_rows >= rows_cap then) and its outputs go to element d_out_idx[r] (NULL: r)
+ * of d_evals, eval_stride floats per element, and of d_probs, probs_stride floats per element; nothing else is written.
+ * The two output pointers may name one array (the evaluation cache's: strides 100, d_probs = d_evals + 4).  alone: 0 = other
+ * streams keep the GPU busy too, the kernels may choose for throughput (1: what ca_net_forward_device passes).
+ * CA_ERR_ARG: state_rows or rows_cap beyond max_rows, eval_stride < 1, probs_stride < 96, a null d_states, d_rows, d_evals
+ * or d_probs.  THE INDICES ARE NOT CHECKED -- they live on the device and the kernels read them: every entry below *d_rows
+ * must be below state_rows (d_in_idx) or inside the caller's output arrays (d_out_idx), without repeats in d_out_idx;
+ * entries from *d_rows on are never read.  Stream, staging buffer and range flag as ca_net_forward_device. */
+int ca_net_forward_device_io(ca_net *n, const float *d_states, int32_t state_rows, int32_t rows_cap, const int32_t *d_rows,
+                             const int32_t *d_in_idx, const int32_t *d_out_idx, float *d_evals, int32_t eval_stride,
+                             float *d_probs, int32_t probs_stride, int32_t alone, void *stream);
 void ca_net_destroy(ca_net *n);
 
 /* ---- Many models of one kind on one set of rows, in one launch: `models` (1..256) weight sets of `kind`, n_floats each

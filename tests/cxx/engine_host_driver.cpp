@@ -211,6 +211,21 @@ void stand_alone_network(const std::vector<float> &w) {
   float sum = 0;
   for (int m = 0; m < NM; ++m) sum += probs[(size_t)8 * NM + m];
   REQUIRE(sum > 0.99f && sum < 1.01f);
+  // the same rows as a fused run with a cache launches them: read through in_idx, written through out_idx into one array
+  // of 100 floats per element; nothing is written for the entries from the count on
+  const std::vector<int32_t> in_idx = {8, 3, 15, 0, 0, 0}, out_idx = {5, 0, 19, 7, 7, 7};
+  const int32_t three = 3;
+  std::vector<float> val((size_t)20 * 100, -7.0f);
+  OK(ca_net_forward_device_io(n, states.data(), 16, 6, &three, in_idx.data(), out_idx.data(), val.data(), 100, val.data() + 4, 100, 0, nullptr));
+  for (int e = 0; e < 20; ++e)
+    for (int f = 0; f < 100; ++f) {
+      const bool written = (e == 5 || e == 0 || e == 19) && (f == 0 || f >= 4);
+      REQUIRE(written ? val[(size_t)e * 100 + f] == (f == 0 ? evals[8] : probs[(size_t)8 * NM + f - 4]) : val[(size_t)e * 100 + f] == -7.0f);
+    }
+  EXPECT(CA_ERR_ARG, ca_net_forward_device_io(n, states.data(), 17, 6, &three, in_idx.data(), out_idx.data(), val.data(), 100, val.data() + 4, 100, 0, nullptr));
+  EXPECT(CA_ERR_ARG, ca_net_forward_device_io(n, states.data(), 16, 6, &three, in_idx.data(), out_idx.data(), val.data(), 0, val.data() + 4, 100, 0, nullptr));
+  EXPECT(CA_ERR_ARG, ca_net_forward_device_io(n, states.data(), 16, 6, &three, in_idx.data(), out_idx.data(), val.data(), 100, val.data() + 4, 95, 0, nullptr));
+  EXPECT(CA_ERR_ARG, ca_net_forward_device_io(n, states.data(), 5, 6, &three, nullptr, nullptr, val.data(), 100, val.data() + 4, 100, 0, nullptr));
   ca_net_destroy(n);
 }
 

@@ -96,7 +96,7 @@ def test_cpp_tourney_wrapper_compiles_and_links(tmp_path):
 
 
 # one entry point of each family; the emulation build has no fitter
-_FAMILIES = ["ca_trainer_num_requests", "ca_trainer_stats", "ca_tourney_all_done"]
+_FAMILIES = ["ca_trainer_num_requests", "ca_trainer_stats", "ca_tourney_all_done", "ca_net_forward_device_io"]
 _NULL_CASES = [pytest.param("emu", e, id="emu-" + e) for e in _FAMILIES] + [
     pytest.param("hip", e, id="hip-" + e, marks=pytest.mark.gpu) for e in _FAMILIES + ["ca_fitter_data_info"]]
 
@@ -111,6 +111,7 @@ def test_a_null_handle_is_an_argument_error(engine, entry):
         "ca_trainer_num_requests": lambda: L.ca_trainer_num_requests(None, -1, C.byref(i32)),
         "ca_trainer_stats": lambda: L.ca_trainer_stats(None, C.byref(_lib.CaStats())),
         "ca_tourney_all_done": lambda: L.ca_tourney_all_done(None, C.byref(i32)),
+        "ca_net_forward_device_io": lambda: L.ca_net_forward_device_io(None, None, 0, 0, None, None, None, None, 1, None, 96, 1, None),
         "ca_fitter_data_info": lambda: L.ca_fitter_data_info(None, C.byref(i32), C.byref(C.c_int32())),
     }[entry]()
     assert rc == -1  # CA_ERR_ARG

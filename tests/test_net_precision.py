@@ -29,11 +29,12 @@ from tests.engines import make_trainer
 pytestmark = pytest.mark.gpu
 
 
-def _states(n, seed):
+def _states(n, seed, reserves=5):
+    """64 board bits and six piece counts as multiples of 0.25 below `reserves` / 4 (8: everything rules.h can write)"""
     rng = np.random.default_rng(seed)
     s = np.zeros((n, 70), np.float32)
     s[:, :64] = rng.integers(0, 2, (n, 64))
-    s[:, 64:] = rng.integers(0, 5, (n, 6)) * 0.25
+    s[:, 64:] = rng.integers(0, reserves, (n, 6)) * 0.25
     return s
 
 
@@ -87,11 +88,16 @@ def test_mlp12x100_bf16x6_is_float32_equivalent():
 @pytest.mark.parametrize("kind,make", [(NET_RESCNN4_X6, lambda: nets.trained_like_rescnn4(2)),
                                        (NET_MLP12X100_X6, lambda: nets.trained_like_mlp12x100(2)),
                                        (NET_RESCNN4_H3, lambda: nets.trained_like_rescnn4(2)),
-                                       (NET_MLP12X100_H3, lambda: nets.trained_like_mlp12x100(2))],
-                         ids=["rescnn4x6", "mlp12x100x6", "rescnn4h3", "mlp12x100h3"])
+                                       (NET_MLP12X100_H3, lambda: nets.trained_like_mlp12x100(2)),
+                                       (NET_MLP12X100, lambda: nets.trained_like_mlp12x100(2)),
+                                       (NET_RESCNN4, lambda: nets.trained_like_rescnn4(2)),
+                                       (NET_RESCNN4_X3, lambda: nets.trained_like_rescnn4(2)),
+                                       (NET_MLP12X100_X3, lambda: nets.trained_like_mlp12x100(2))],
+                         ids=["rescnn4x6", "mlp12x100x6", "rescnn4h3", "mlp12x100h3", "mlp12x100", "rescnn4", "rescnn4x3", "mlp12x100x3"])
 def test_bf16x6_rows_do_not_depend_on_their_batch(kind, make):
     """SURVEY 8e invariant: a row's outputs are a function of the row only (fixed k order, no
-    batch-dependent tiling), for every batch size around the kernels' tile boundaries"""
+    batch-dependent tiling), for every batch size around the kernels' tile boundaries -- of every kind: the MLP kernels'
+    workgroup of 128 rows, rescnn4 fp32's of 16, and rescnn4 bf16x3's two kernels on both sides of 4096 rows"""
     t = make_trainer("hip", 512, "", 1, 50, 16, 1.0, 0.25, 0, 1, False)
     t.set_net(kind, make())
     states = _states(4096, 9)
@@ -108,6 +114,16 @@ def test_bf16x6_rows_do_not_depend_on_their_batch(kind, make):
                    (0, 2047), (0, 2048), (0, 2049), (1000, 3050), (2040, 4096)):
         e1, p1 = t.net_forward(states[lo:hi])
         assert np.array_equal(e1, ev[lo:hi]) and np.array_equal(p1, pr[lo:hi]), (lo, hi)
+    # rescnn4 fp32's workgroup of 16 rows, the MLP kernels' of 128, and whole small-batch launches of the two-term kinds
+    for lo, hi in ((0, 31), (0, 32), (0, 33), (7, 39), (0, 127), (0, 128), (3, 131), (0, 255), (0, 256), (0, 257), (0, 4095), (0, 4096)):
+        e1, p1 = t.net_forward(states[lo:hi])
+        assert np.array_equal(e1, ev[lo:hi]) and np.array_equal(p1, pr[lo:hi]), (lo, hi)
+    # ... and on both sides of 4096 rows against the 8192-row batch: up to 4096 rows the two-term kinds' small-batch kernel
+    # (16 rows per workgroup; the whole 8192: bf16x3's throughput kernel, f16x3's pixel-major one), above it the other one
+    # on a batch that ends inside a workgroup
+    for lo, hi in ((0, 4095), (0, 4096), (0, 4097), (50, 4146), (50, 4147), (3000, 8192), (4095, 8192)):
+        e1, p1 = t.net_forward(states8[lo:hi])
+        assert np.array_equal(e1, ev8[lo:hi]) and np.array_equal(p1, pr8[lo:hi]), (lo, hi)
 
 
 def test_a_batch_split_between_the_two_f16x3_kernels_is_the_same_rows():
