@@ -1,7 +1,7 @@
 // analysis_host.h -- the positions of an analysis trainer (ca_config.analyse: DockerMC constructor arguments, one per
 // game): their decoding and validation, how a generation's slots start from them, and the eight result words per position
 // at the head of each slot's request area -- written here for a position that is terminal as given, by the search kernel
-// (mcts.h co_analyse_finish) for every other, decoded here for ca_trainer_analysis.
+// (search_move.h co_analyse_finish) for every other, decoded here for ca_trainer_analysis.
 #pragma once
 #include <string>
 #include <vector>

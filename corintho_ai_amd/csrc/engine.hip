@@ -176,7 +176,7 @@ struct ca_trainer {
     n -= cfg.game_base; /* a shard logs the games of the generation's first num_logged that it owns */
     if (n < 0) n = 0;
     if (n > G) n = G;
-    if (n > store.R) /* logged games start in their own slots (mcts.h): fewer slots than logged games would write fewer files than the reference */
+    if (n > store.R) /* logged games start in their own slots (search_step.h co_slot_next_game): fewer slots than logged games would write fewer files than the reference */
       throw CaError(CA_ERR_ARG, "ca_trainer_set_logging: " + std::to_string(n) + " logged games on " + std::to_string(store.R) +
                                         " resident slots -- a logged game must start in its own slot; raise ca_config.resident");
     std::vector<int> first(n);

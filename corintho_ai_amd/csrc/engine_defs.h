@@ -15,19 +15,9 @@
 //   req[G][spe][80] float            leaf states (70 floats, padded to 80)
 //   samples[G][44][166] float        (state, policy) per ply
 //
-// A tree node is a BLOCK of units at offset b of its tree's arena:
-//   unit b+0   {board_lo, board_hi, meta, parent_block}
-//   unit b+1   {self_slot, denominator(f32), 0, 0}
-//   unit b+2+e slot of edge e, e < n_edges, edges in ascending move id:
-//                {child_block | NONE, evaluation(f32),
-//                 move_id:7 | prior:9 | visits:16 (signed), result:8 | all_visited:8}
-//   unit b+2+n (only for a detached root) the root's own stat slot
-// The statistics of a node (Node::evaluation_/visits_/result_/all_visited_,
-// node.h:150-186) live in the SLOT of the edge that leads to it -- in its
-// parent's block -- so that one coalesced 16 B-per-lane load of a block gives
-// the PUCT scan everything it needs (trainmc.cpp:540-600); `self_slot` is the
-// unit offset of that slot.  meta = pieces[6] (3 bits each) | to_play<<18 |
-// depth<<19 (6 bits) | n_edges<<25 (7 bits).
+// A tree node is a BLOCK of units in its tree's arena -- header, {self_slot, denominator}, one stat SLOT per edge; a
+// node's statistics live in the slot of the edge that leads to it.  The layout of block and slot is defined in ONE
+// place, with the macros that decode it: the head of search_tree.h.
 #pragma once
 #include <stdint.h>
 
@@ -121,12 +111,12 @@ struct GameCtl {
   /* the game this slot plays (index within this trainer's games; = the slot index unless the pool recycles
    * slots, see EngineParams::results) */
   int32_t gid;
-  /* the search's hint to itself (mcts.h co_mc_do_iteration): running share, in 1/256, of this game's recent simulations that
+  /* the search's hint to itself (search_iter.h co_mc_do_iteration): running share, in 1/256, of this game's recent simulations that
    * ended in a terminal leaf or a dead end; decides how many simulations are selected together.  Results do not depend on it. */
   int32_t sb_cap;
   /* Fused training, EngineParams::step_budget: the step before this one ran out of its budget of scans and stopped with
    * fewer than searches_per_eval leaves queued -- none of them was submitted, no evaluation is on its way; this step
-   * goes on selecting where that one stopped (mcts.h co_mc_do_iteration).  noise_held = generator outputs owed to the
+   * goes on selecting where that one stopped (search_iter.h co_mc_do_iteration).  noise_held = generator outputs owed to the
    * leaves queued so far (CoWave::noise_words, carried over).  The game's own sequence of operations is unchanged. */
   int32_t held;       /* bit 0: as described; within a step only: bit 1 this step continues one that was cut, bit 2 it has run a simulation */
   int32_t noise_held;
@@ -146,7 +136,7 @@ struct TreeCtl {
   uint32_t peak_units;
 };
 
-/* Evaluation cache of fused training (mcts.h co_cache_resolve), ONE table for all pools of a trainer (round 4; a table
+/* Evaluation cache of fused training (search_step.h co_cache_resolve), ONE table for all pools of a trainer (round 4; a table
  * per pool until then: 2.3 % of a generation's rows are positions the OTHER pool has evaluated): a network's outputs are a function of
  * the request row alone, and a generation asks for the same positions again and again (the two players' trees of a
  * game overlap, thousands of games leave the same opening: 29 % of the rows of a 4096-game generation with
@@ -205,7 +195,7 @@ struct EngineParams {
   int32_t trace_on;
   /* analysis mode (DockerMC, dockermc.cpp / trainmc.cpp:38-45): every slot is ONE position to search --
    * the root is created from gc.pos_* at depth 0, testing = true, and the slot finishes with its
-   * first chooseMove; results in the slot's request area (mcts.h co_analyse_finish) */
+   * first chooseMove; results in the slot's request area (search_move.h co_analyse_finish) */
   int32_t analyse;
   /* analysis mode, ca_trainer_finish: this launch does not search -- every unfinished slot chooses its move on
    * the tree as it stands (DockerMC::chooseMove called after a time limit, choose_move.pyx:110-117 + :199), the
@@ -232,9 +222,9 @@ struct EngineParams {
   int32_t *pend_src;    /* [G][spe] element of the cache's value array that holds the outputs of pending leaf k (resolved at
                          * the end of the step that queued the leaf): K3's receive phase fetches it with the leaf's other words */
   uint32_t *pend_n;     /* [G][spe][4] {(first noise word of the leaf << 8) | legal moves of the leaf, legal-move mask [3]}:
-                         * everything the priors pass (mcts.h co_prior_all) needs to fetch the leaf's priors without walking the tree first */
+                         * everything the priors pass (search_eval.h co_prior_all) needs to fetch the leaf's priors without walking the tree first */
   uint32_t *noise_raw;  /* [G][spe * CO_NUM_MOVES] generator outputs (untempered state words) reserved for the pending
-                         * leaves' Dirichlet noise, in request order: drawn when the leaves are queued (mcts.h
+                         * leaves' Dirichlet noise, in request order: drawn when the leaves are queued (search_eval.h
                          * co_capture_noise), consumed by the priors pass of the step that receives the evaluations */
   uint32_t *rng;        /* [G][624] */
   float *req;           /* [G][spe][CO_STATE_STRIDE] */
@@ -250,7 +240,7 @@ struct EngineParams {
   float *samples;       /* [G][CO_MAX_PLIES][166] */
   int32_t *trace;       /* [G][CO_TRACE_CAP] or null */
   /* per-game text logs (Trainer's num_logged, trainer.cpp:243-250): the first num_logged games record what the
-   * reference's log prints at every move choice (mcts.h co_log_ply); word 0 of a game's record is its length.  The host
+   * reference's log prints at every move choice (search_move.h co_log_ply); word 0 of a game's record is its length.  The host
    * writes the files when the games are over (game_logs.h GameLogs::write). */
   int32_t *log;         /* [num_logged][CO_LOG_CAP] or null */
   int32_t num_logged;
@@ -261,7 +251,7 @@ struct EngineParams {
    * (co_pack_rows, co_pack_running); the other one is cleared for the next iteration.  The network kernels
    * read the low word. */
   int32_t fused_pack;
-  int32_t defer_handover; /* fused mode: end a game's step at the hand-over (see mcts.h co_choose_move_and_continue) */
+  int32_t defer_handover; /* fused mode: end a game's step at the hand-over (see search_step.h co_game_step) */
   /* fused training: a game's step stops selecting after this many PUCT scans and carries on in the next launch, its
    * queued leaves held back until there are searches_per_eval of them (or the searches run out) -- a launch lasts as long
    * as its slowest wavefront, and the slowest are steps of 25-30 simulations ten levels deep (half of them ending in
@@ -272,7 +262,7 @@ struct EngineParams {
    * endgames under a trained network: ~70).  work_counter[CO_WC_WORDS] per pool: [0..2] by iteration mod 3, (steps << 32) |
    * scans of the launch -- this launch adds to [iteration % 3], its first wavefront reads [(iteration - 1) % 3], writes the
    * budget of the NEXT launch to [CO_WC_BUDGET + (iteration & 1)] and clears [(iteration + 1) % 3]; every wavefront reads
-   * its budget from [CO_WC_BUDGET + ((iteration + 1) & 1)], the word the launch before wrote (mcts.h
+   * its budget from [CO_WC_BUDGET + ((iteration + 1) & 1)], the word the launch before wrote (search_step.h
    * co_pool_housekeeping); [CO_WC_MEAN ..]: the mean smoothed over ~8 launches, carried from launch to launch the same way. */
   int32_t step_budget_k16;
   unsigned long long *work_counter;

@@ -226,7 +226,7 @@ struct GameStore {
     return peak;
   }
 
-  /* diagnostic builds (-DCO_PROF): summed in-kernel cycle stamps, see mcts.h */
+  /* diagnostic builds (-DCO_PROF): summed in-kernel cycle stamps, see search_state.h */
   void read_prof(unsigned long long out[2 * CO_NPROF + 24], rt_stream_t s) const {
     /* nothing is written to `out` unless this is a stamped build: a caller of the shipped library with a buffer sized for
      * an earlier round's layout gets the error, not an overflow */

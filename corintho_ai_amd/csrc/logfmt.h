@@ -1,5 +1,5 @@
 // logfmt.h -- host side of the per-game text logs (Trainer's num_logged, trainer.cpp:243-250).
-// The search kernel records the numbers of every move choice (mcts.h co_log_ply, co_game_step); this file prints
+// The search kernel records the numbers of every move choice (search_move.h co_log_ply, co_game_step); this file prints
 // them in the reference's layout:
 //   SelfPlayer::writePreMoveLogs / writeMoves / writeEval / writeMoveChoice   selfplayer.cpp:124-204
 //   (Match's copies of the four, match.cpp:78-159, and Match::endGame :163-190, print the same text)

@@ -242,7 +242,7 @@ struct FusedRun {
     const Pool::Seen &w = q.seen[parity];
     const uint32_t evaluated = q.cache.hdr ? w.evaluated : co_pack_rows(w.pack);
     q.running = (int)co_pack_running(w.pack);
-    /* steps cut in the window: games held their leaves back (mcts.h co_step_tail), which submits no rows for them */
+    /* steps cut in the window: games held their leaves back (search_step.h co_step_tail), which submits no rows for them */
     const bool holding = w.cuts != q.cuts_seen;
     q.cuts_seen = w.cuts;
     if (q.timed[parity]) {
@@ -302,7 +302,7 @@ struct FusedRun {
     Pool &q = pools[p];
     if (q.finished) return;
     EngineParams pp = run_params;
-    /* Deferring the new mover's first searches to the next step (mcts.h co_game_step) balances
+    /* Deferring the new mover's first searches to the next step (search_step.h co_game_step) balances
      * the waves of a full launch but costs the game one more iteration per ply; once the pool
      * has thinned out, an iteration is as long as its slowest wave anyway and the number of
      * iterations of the longest game is what the generation waits for.  Per-game results do

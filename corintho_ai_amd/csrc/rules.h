@@ -225,7 +225,7 @@ CO_DEV void co_do_move(uint64_t *board, uint32_t *meta, int id, const CoLanes &K
   *meta = m ^ (1u << 18);
 }
 
-/* ---- the rule layer for FOUR positions at a time, one per row of 16 lanes (round 5; mcts.h co_search_rows): position,
+/* ---- the rule layer for FOUR positions at a time, one per row of 16 lanes (round 5; search_group.h co_search_rows): position,
  * legal-move mask and everything in between are row-uniform values in vector registers; a lane's column is a cell.
  * Same rules, same citations as above; checked against co_legal_moves on the rules corpus and by every parity test. */
 

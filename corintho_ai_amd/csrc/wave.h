@@ -27,7 +27,7 @@
 
 #define CO_WAVE 64
 
-/* Simulations of a step selected together by the search kernel (mcts.h co_search_rows): one per row of the wavefront
+/* Simulations of a step selected together by the search kernel (search_group.h co_search_rows): one per row of the wavefront
  * (rounds 1-4: one after another, what co_search still does for a simulation that ends its group). */
 #define CO_SB 4
 

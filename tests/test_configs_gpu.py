@@ -214,7 +214,7 @@ def test_cfg5_arena_1024_two_model_games(kind):
 @pytest.mark.parametrize("pools,bits,seed", [(2, 14, 1), (3, 14, 2), (3, 17, 3)], ids=["2_pools_2^14", "3_pools_2^14", "3_pools_2^17"])
 def test_shared_cache_table_under_real_concurrency(pools, bits, seed):
     """The pools share one evaluation-cache table through relaxed atomics, per-pool progress words and an emptying protocol
-    (DESIGN section 4; mcts.h co_cache_resolve, EvalCache::guard_from).  The emulation build runs the pools of an iteration
+    (DESIGN section 4; search_step.h co_cache_resolve, EvalCache::guard_from).  The emulation build runs the pools of an iteration
     one after the other and cannot see a race; here the streams really run side by side, with tables so small that they
     are emptied hundreds of times per generation -- and every game must still replay on the oracle bit for bit.
     (tools/exp/cache_stress.py as a test)"""

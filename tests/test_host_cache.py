@@ -85,7 +85,7 @@ def assert_first_batch_is_the_start_position(batch, ref, G):
     each other: ONE row is what the first batch is expected to be, and what it is whenever the games' wavefronts reach
     the table one after another (the emulation build on one thread: always).  Exactly one cannot be asserted: a
     wavefront that finds a slot claimed an instant ago, its key words not yet visible, takes the next slot for the same
-    position (mcts.h co_cache_resolve: "correctness does not depend on who wins a race") -- seen on the emulation build
+    position (search_step.h co_cache_resolve: "correctness does not depend on who wins a race") -- seen on the emulation build
     with OpenMP threads as 2 or 3 copies of one position in a batch, in 1 run of 4.  What holds in every schedule: the
     batch holds nothing but the start position, at least once and at most once per game."""
     assert 1 <= batch.shape[0] <= G

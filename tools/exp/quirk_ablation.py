@@ -23,13 +23,13 @@ Q1_CODE = """      has_draw = 0; /* ablation: the evident intent -- a drawn CHIL
         FOR_LANES {
           int e = base + lane;
           L(dr) = 0;
-          if (e < n) L(dr) = co_res_drawn(co_slot_result(A[pb + 2 + e]));
+          if (e < n) L(dr) = co_res_drawn(co_slot_result(A[CO_NODE_EDGE(pb, e)]));
         }
         if (WAVE_BALLOT(dr)) has_draw = 1;
       }
 """
-Q6_ANCHOR = "          uc = searchable ? uc : CO_NEG_INF;\n"
-Q6_CODE = "          uc = drawn ? (float)b : uv; /* ablation: the drawn child's term divided like the others */\n"
+Q6_ANCHOR = "  uc = searchable ? uc : CO_NEG_INF;\n"
+Q6_CODE = "  uc = drawn ? (float)b : uv; /* ablation: the drawn child's term divided like the others */\n"
 
 
 def build_ablated(which):
@@ -41,10 +41,10 @@ def build_ablated(which):
     src = os.path.join(ROOT, "build_ab", "ablate_q%d" % which)
     shutil.rmtree(src, ignore_errors=True)
     shutil.copytree(build.CSRC, src)
-    path = os.path.join(src, "mcts.h")
+    path = os.path.join(src, "search_eval.h" if which == 1 else "search_puct.h")
     text = open(path).read()
     anchor, code = (Q1_ANCHOR, Q1_CODE) if which == 1 else (Q6_ANCHOR, Q6_CODE)
-    assert text.count(anchor) == 1, "mcts.h no longer holds the expression this experiment rewrites"
+    assert text.count(anchor) == 1, "%s no longer holds the expression this experiment rewrites" % os.path.basename(path)
     open(path, "w").write(text.replace(anchor, code + anchor))
     out = os.path.join(ROOT, "build_ab", "libcorintho_hip_q%d.so" % which)
     subprocess.check_call([build.hipcc()] + build.FLAGS + ["-I", os.path.join(ROOT, "include"), "-o", out] +

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device code of two csrc trees, kernel by kernel, without a GPU.
 
-    python tools/kernel_diff.py PARENT_CSRC NEW_CSRC [--work DIR] [--jobs N]
+    python tools/kernel_diff.py PARENT_CSRC NEW_CSRC [--flag FLAG]... [--work DIR] [--jobs N]
 
 Every source of build.py's SOURCES in both directories is compiled to gfx950 assembly with build.py's FLAGS (without
 -fPIC -shared, plus --offload-device-only -S).  Kernels are the entries of the code objects' metadata, matched by mangled
@@ -9,7 +9,15 @@ name.  Two kernels are identical when their instruction streams are, after comme
 renumbered in order of appearance, and their VGPR / AGPR / SGPR counts, static LDS, scratch and workgroup size agree.
 The streams are compared as text: no instruction is looked for by name.  A kernel that differs is listed with the
 opcodes whose counts differ.  Prints a markdown table (the figures are the second tree's); exit status 1 if any kernel
-differs or exists in one tree only.  --work keeps the assembly there (default: a temporary directory)."""
+differs or exists in one tree only.  --work keeps the assembly there (default: a temporary directory).
+
+--flag (repeatable) appends a compiler flag for both trees, so the search kernel's diagnostic builds can be compared as
+well: --flag=-DCO_PROF, --flag=-DCO_COLD_NOINLINE, --flag=-DCO_SB=1 ...
+
+The parent's tree: csrc/host.h includes ../../include/corintho_hip.h, so an export of the parent commit has to keep
+include/ beside corintho_ai_amd/ --
+    mkdir /tmp/parent && git archive HEAD~1 corintho_ai_amd include | tar -x -C /tmp/parent
+    python tools/kernel_diff.py /tmp/parent/corintho_ai_amd/csrc corintho_ai_amd/csrc"""
 import argparse
 import collections
 import os
@@ -27,10 +35,10 @@ META = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "p
 LOCAL = re.compile(r"\.L[A-Za-z_]*\d+(?:_\d+)?")
 
 
-def compile_tree(csrc, work, jobs):
+def compile_tree(csrc, work, jobs, extra=()):
     """-> the assembly files of the tree's sources, compiled `jobs` at a time"""
     os.makedirs(work, exist_ok=True)
-    flags = [f for f in B.FLAGS if f not in ("-fPIC", "-shared")] + ["--offload-device-only", "-S"]
+    flags = [f for f in B.FLAGS if f not in ("-fPIC", "-shared")] + ["--offload-device-only", "-S"] + list(extra)
     todo = [(os.path.join(csrc, s), os.path.join(work, s + ".s")) for s in B.SOURCES
             if os.path.exists(os.path.join(csrc, s))]  # (an earlier tree need not have every source of today's)
     running, done = [], []
@@ -93,6 +101,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("parent")
     ap.add_argument("new")
+    ap.add_argument("--flag", action="append", default=[], help="extra compiler flag for both trees (repeatable)")
     ap.add_argument("--work")
     ap.add_argument("--jobs", type=int, default=8)
     a = ap.parse_args()
@@ -101,7 +110,7 @@ def main():
     trees = []
     for label, csrc in (("parent", a.parent), ("new", a.new)):
         k = {}
-        for s in compile_tree(csrc, os.path.join(work, label), a.jobs):
+        for s in compile_tree(csrc, os.path.join(work, label), a.jobs, a.flag):
             parse(s, k)
         trees.append(k)
     old, new = trees

@@ -1,4 +1,4 @@
-"""Counters of the grouped search (mcts.h co_search_batch) on the emulation build: how many simulations of a step end
+"""Counters of the grouped search (search_group.h co_search_rows) on the emulation build: how many simulations of a step end
 the ORDINARY way (and are committed in groups), what ends a group early, how often two simulations of a group meet in
 one node below the root.  CPU only:
 
