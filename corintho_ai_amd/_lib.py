@@ -72,6 +72,35 @@ class CaStats(C.Structure):
     ]
 
 
+class CaFitOptions(C.Structure):
+    """ca_fit_options (include/corintho_hip.h, "fit options"); struct_size is filled in by whoever passes it"""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("regularize", C.c_int32),
+        ("l1", C.c_float),
+        ("l2", C.c_float),
+        ("weight_decay", C.c_float),
+        ("clipvalue", C.c_float),
+        ("clipnorm", C.c_float),
+        ("global_clipnorm", C.c_float),
+    ]
+
+
+class CaFitStats(C.Structure):
+    """ca_fit_stats"""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("steps", C.c_int64),
+        ("clipped_steps", C.c_int64),
+        ("regularization", C.c_double),
+        ("grad_norm", C.c_double),
+        ("grad_norm_max", C.c_double),
+    ]
+
+
 # every symbol include/corintho_hip.h declares
 EXPORTS = [
     "ca_last_error", "ca_device_check", "ca_trainer_create", "ca_trainer_destroy", "ca_trainer_num_requests",
@@ -93,6 +122,7 @@ EXPORTS = [
     "ca_net_group_bench", "ca_net_group_destroy",
     "ca_fitter_set_sample_weights", "ca_fitter_get_sample_weights", "ca_fitter_merge_duplicates",
     "ca_net_forward_device_io",
+    "ca_fitter_set_options", "ca_fitter_get_options", "ca_fitter_train_stats", "ca_fitter_tensor_table",
 ]
 # the caller-supplied network: an earlier build of the library has none of these
 NET_FN_EXPORTS = ["ca_trainer_request_rows", "ca_trainer_set_net_fn", "ca_tourney_set_net_fn", "ca_net_create", "ca_net_forward_device",
@@ -104,7 +134,9 @@ GROUP_EXPORTS = ["ca_tourney_set_grouped", "ca_tourney_set_seed", "ca_net_group_
 WEIGHT_EXPORTS = ["ca_fitter_set_sample_weights", "ca_fitter_get_sample_weights", "ca_fitter_merge_duplicates"]
 # a network launch with a fused run's indirection: likewise
 NET_IO_EXPORTS = ["ca_net_forward_device_io"]
-assert set(NET_FN_EXPORTS + GROUP_EXPORTS + WEIGHT_EXPORTS + NET_IO_EXPORTS) <= set(EXPORTS)
+# the fit options (regulariser, weight decay, clipping): likewise
+OPTION_EXPORTS = ["ca_fitter_set_options", "ca_fitter_get_options", "ca_fitter_train_stats", "ca_fitter_tensor_table"]
+assert set(NET_FN_EXPORTS + GROUP_EXPORTS + WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS) <= set(EXPORTS)
 
 
 def declare(L):
@@ -199,7 +231,7 @@ def declare(L):
             continue
         if name in GROUP_EXPORTS and not group:
             continue
-        if name in WEIGHT_EXPORTS + NET_IO_EXPORTS and not hasattr(L, name):
+        if name in WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy", "ca_net_destroy",
@@ -232,6 +264,11 @@ def _declare_fitter(L, vp, f64p):
         L.ca_fitter_set_sample_weights.argtypes = [vp, f32p, C.c_int32]
         L.ca_fitter_get_sample_weights.argtypes = [vp, f32p, C.c_int32]
         L.ca_fitter_merge_duplicates.argtypes = [vp, C.c_int, i32p, i32p]
+    if hasattr(L, "ca_fitter_set_options"):  # (likewise)
+        L.ca_fitter_set_options.argtypes = [vp, C.POINTER(CaFitOptions)]
+        L.ca_fitter_get_options.argtypes = [vp, C.POINTER(CaFitOptions)]
+        L.ca_fitter_train_stats.argtypes = [vp, C.POINTER(CaFitStats)]
+        L.ca_fitter_tensor_table.argtypes = [vp, i32p, C.c_int32, i32p]
 
 
 _lib = None

@@ -84,6 +84,11 @@ struct FtSplits {
   int rows, pixels;
 };
 
+/* a contiguous range of the flat weight vector and its class (CA_TENSOR_* of corintho_hip.h, "fit options") */
+struct FtTensor {
+  int32_t off, count, cls;
+};
+
 struct FtNet {
   virtual ~FtNet() {}
   virtual const char *name() const = 0;
@@ -94,6 +99,8 @@ struct FtNet {
   virtual int value_bias() const = 0;
   /* ft_k_update's code of every weight: sidx has num_weights entries */
   virtual void update_table(std::vector<int32_t> &sidx) const = 0;
+  /* the network's tensors in the order of the weight vector: together they cover it without a gap */
+  virtual void tensor_table(std::vector<FtTensor> &tensors) const = 0;
   /* forward of rows[0..B) (a device pointer) of the data set; train = batch statistics (left in stat), else the moving
    * ones.  Leaves h. */
   virtual void forward(const FtShared &sh, const int32_t *rows, int B, bool train) = 0;
@@ -109,6 +116,41 @@ struct FtMerged {
   int32_t count = 0, cap = 0;
 };
 FtMerged ft_merge_duplicates(rt_stream_t s, const float *sp, const float *oc, const float *wt, int32_t n, bool normalize);
+
+/* The step with fit options (nn_train_opt.hip; the definition: corintho_hip.h, "fit options").  The weight vector is cut
+ * into PIECES of at most 256 floats of one tensor; a workgroup owns a piece.  A step is three launches on the summed
+ * gradient ft_k_update(apply = 0) left in gsum: the regulariser gradient added and per-piece float64 partials of
+ * sum g'^2, R and the count of |g'| > clipvalue (ft_k_opt_partials); the partials combined by a tree of fixed shape
+ * into the tensors' scales, the step's R and the call's statistics (ft_k_opt_combine); the clamp or scale, the decay,
+ * Adam and the moving statistics (ft_k_opt_update). */
+struct FtOptStats { /* accumulated on the device over the steps of one ca_fitter_train */
+  double reg_sum, norm_sum, norm_max, clipped;
+};
+struct FtOpt {
+  ca_fit_options o = {};
+  int nt = 0, npieces = 0;
+  DevBuf<int32_t> pieces, tfirst; /* [npieces][4] = {offset, floats, tensor, class}; [nt + 1]: a tensor's first piece */
+  DevBuf<double> part;            /* [npieces][3] */
+  DevBuf<float> scale;            /* [nt] */
+  DevBuf<double> out;             /* the statistics (4 doubles), then R of every batch of the call */
+  size_t slots = 0;
+  std::vector<double> hout;
+
+  bool regularized() const { return o.l1 > 0.0f || o.l2 > 0.0f; }
+  bool on() const { return regularized() || o.weight_decay > 0.0f || o.clipvalue > 0.0f || o.clipnorm > 0.0f || o.global_clipnorm > 0.0f; }
+  /* the piece table of a network's tensors; once */
+  void plan(const std::vector<FtTensor> &tensors, int nw, rt_stream_t s);
+  /* room for the R of `n` batches; clears the statistics */
+  void begin(int n, rt_stream_t s);
+  /* R(w) to slot `slot`; nothing else is read or written */
+  void regularization(rt_stream_t s, const float *w, int slot);
+  /* steps 1 to 4 on gsum; R to slot, the statistics accumulated */
+  void step(rt_stream_t s, float *w, float *m, float *v, float *gsum, const int32_t *sidx, const float *stat, float lr,
+            float lr_t, int slot);
+  /* queues the copy of the statistics and the first n R to hout; valid after the stream is synchronised */
+  void fetch(int n, rt_stream_t s);
+  double R(int slot) const { return hout[4 + slot]; }
+};
 
 /* kind: CA_NET_MLP12X100 or CA_NET_RESCNN4; the network's own buffers are sized for max_batch rows and cleared on s */
 FtNet *ft_net_create(int kind, int max_batch, rt_stream_t s);

@@ -272,6 +272,8 @@ struct ca_fitter {
   DevBuf<float> bstates, bevals, bprobs, bwts; /* one batch of a packed set as ft_k_assemble wrote it: max_batch rows */
   DevBuf<int32_t> sidx, idx, ident, bidx; /* ident[r] = r, the rows of an assembled batch; bidx: ca_fitter_fetch_rows */
   std::vector<float> hloss;
+  FtOpt opt;                                       /* the fit options (nn_train_opt.hip); all 0: never touched by a step */
+  ca_fit_stats last = {sizeof(ca_fit_stats), 0, 0, 0, 0.0, 0.0, 0.0}; /* of the last ca_fitter_train */
 
   void init(int dev, int kind, int mb) {
     device = dev;
@@ -346,6 +348,26 @@ struct ca_fitter {
   void update(FtSplits ns, float lr_t, bool apply) {
     RT_LAUNCH(ft_k_update, (nw + 255) / 256, 256, s, w.p, m.p, v.p, (const float *)g.p, nw, ns.rows, ns.pixels,
               (const int32_t *)sidx.p, (const float *)stat.p, lr_t, apply ? 1 : 0, gsum.p);
+  }
+
+  /* the end of a step with options on: the summed gradient to gsum as ca_fitter_gradients has it, then steps 1 to 4 */
+  void update_with_options(FtSplits ns, float lr, float lr_t, int slot) {
+    update(ns, 0.0f, false);
+    opt.step(s, w.p, m.p, v.p, gsum.p, sidx.p, stat.p, lr, lr_t, slot);
+  }
+  /* the piece table of the options' kernels, made when options are first switched on.  Those kernels take a weight for
+   * a moving statistic by its tensor's class and ft_k_update by its code: the two tables must agree. */
+  void plan_options() {
+    if (opt.pieces.p) return;
+    std::vector<FtTensor> tt;
+    std::vector<int32_t> si;
+    net->tensor_table(tt);
+    net->update_table(si);
+    for (const FtTensor &t : tt)
+      for (int32_t i = t.off; i < t.off + t.count && i >= 0 && i < nw; ++i)
+        if ((si[i] >= 0) != (t.cls == CA_TENSOR_MOVING))
+          throw CaError(CA_ERR_INTERNAL, "ca_fitter: tensor_table and update_table disagree about the moving statistics");
+    opt.plan(tt, nw, s);
   }
 
   void need_data() {
@@ -449,25 +471,31 @@ struct ca_fitter {
     }
   }
   /* per-batch sums -> out[3] = {value + 0.25 policy, value, policy}, means weighted by batch size; per[3 * b] */
-  void losses(int nb, int32_t nr, int32_t batch, double *out, float *per) {
+  void losses(int nb, int32_t nr, int32_t batch, double *out, float *per) { losses(nb, nr, batch, out, per, 0); }
+  /* reg: with the regulariser's R added to the totals, 1: R of every batch (ca_fitter_train), 2: one R for all
+   * (ca_fitter_evaluate); the options' buffer comes back in the same synchronisation */
+  void losses(int nb, int32_t nr, int32_t batch, double *out, float *per, int reg) {
     rt_d2h(hloss.data(), loss.p, (size_t)2 * nb * sizeof(float), s);
+    if (reg) opt.fetch(reg == 1 ? nb : 1, s);
     rt_sync(s);
-    double sv = 0.0, sp = 0.0;
+    double sv = 0.0, sp = 0.0, sr = 0.0;
     for (int b = 0; b < nb; ++b) {
       const int rb = b * batch + batch <= nr ? batch : nr - b * batch;
       const float lv = hloss[2 * b] / (float)rb, lp = hloss[2 * b + 1] / (float)rb;
       if (per) {
-        per[3 * b] = lv + 0.25f * lp;
+        per[3 * b] = reg ? lv + 0.25f * lp + (float)opt.R(reg == 1 ? b : 0) : lv + 0.25f * lp;
         per[3 * b + 1] = lv;
         per[3 * b + 2] = lp;
       }
       sv += (double)lv * rb;
       sp += (double)lp * rb;
+      if (reg) sr += opt.R(reg == 1 ? b : 0) * rb;
     }
     if (out) {
       out[1] = nr ? sv / nr : 0.0;
       out[2] = nr ? sp / nr : 0.0;
       out[0] = out[1] + 0.25 * out[2];
+      if (reg) out[0] += nr ? sr / nr : 0.0;
     }
   }
 };
@@ -574,16 +602,30 @@ extern "C" int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows
     const int nb = (n_rows + batch - 1) / batch;
     f->ensure_loss(nb);
     rt_h2d(f->idx.p, rows, (size_t)n_rows * sizeof(int32_t), f->s);
+    const bool options = f->opt.on();
+    if (options) f->opt.begin(nb, f->s);
+    f->last = ca_fit_stats{sizeof(ca_fit_stats), 0, 0, 0, 0.0, 0.0, 0.0};
     for (int b = 0; b < nb; ++b) {
       const int B = b * batch + batch <= n_rows ? batch : n_rows - b * batch;
       const FtSplits ns = f->gradient(f->idx.p + (size_t)b * batch, B, b);
       /* Keras Adam: local_step = iterations + 1, lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), in float32 */
       const float t = (float)(f->iterations + 1);
       const float lr_t = learning_rate * (sqrtf(1.0f - powf(0.999f, t)) / (1.0f - powf(0.9f, t)));
-      f->update(ns, lr_t, true);
+      if (options)
+        f->update_with_options(ns, learning_rate, lr_t, b);
+      else
+        f->update(ns, lr_t, true);
       f->iterations += 1;
     }
-    f->losses(nb, n_rows, batch, out_losses, batch_losses);
+    f->losses(nb, n_rows, batch, out_losses, batch_losses, options ? 1 : 0);
+    if (options) { /* the statistics came back with the losses */
+      const double *st = f->opt.hout.data();
+      f->last.steps = nb;
+      f->last.clipped_steps = (int64_t)st[3];
+      f->last.regularization = st[0] / nb;
+      f->last.grad_norm = st[1] / nb;
+      f->last.grad_norm_max = st[2];
+    }
   });
 }
 
@@ -599,13 +641,18 @@ extern "C" int ca_fitter_evaluate(ca_fitter *f, int32_t row0, int32_t n_rows, in
     const int nb = (n_rows + batch - 1) / batch;
     f->ensure_loss(nb);
     rt_h2d(f->idx.p, rows.data(), (size_t)n_rows * sizeof(int32_t), f->s);
+    const bool reg = f->opt.on() && f->opt.regularized(); /* the weights do not move: one R for the call */
+    if (reg) {
+      f->opt.begin(1, f->s);
+      f->opt.regularization(f->s, f->w.p, 0);
+    }
     for (int b = 0; b < nb; ++b) {
       const int B = b * batch + batch <= n_rows ? batch : n_rows - b * batch;
       const ca_fitter::Batch bt = f->batch(f->idx.p + (size_t)b * batch, B);
       f->net->forward(f->shared(bt), bt.rows, B, false);
       f->loss_terms(bt, B, false, b);
     }
-    f->losses(nb, n_rows, batch, out_losses, nullptr);
+    f->losses(nb, n_rows, batch, out_losses, nullptr, reg ? 2 : 0);
   });
 }
 
@@ -781,5 +828,55 @@ extern "C" int ca_fitter_merge_duplicates(ca_fitter *f, int normalize, int32_t *
     f->cap = m.cap;
     f->ns = m.count;
     f->added(0);
+  });
+}
+
+/* ------------------------------------------------------------------ fit options */
+extern "C" int ca_fitter_set_options(ca_fitter *f, const ca_fit_options *options) {
+  return co_guard(f, [&] {
+    if (!options || options->struct_size < sizeof(uint32_t)) throw CaError(CA_ERR_ARG, "ca_fitter_set_options: null, or a struct_size below 4");
+    ca_fit_options o = {}; /* the defaults: everything off */
+    const size_t n = options->struct_size < sizeof(o) ? options->struct_size : sizeof(o);
+    memcpy(&o, options, n);
+    o.struct_size = sizeof(o);
+    const float vals[6] = {o.l1, o.l2, o.weight_decay, o.clipvalue, o.clipnorm, o.global_clipnorm};
+    for (float x : vals)
+      if (!(x >= 0.0f) || x == INFINITY) /* (a NaN fails the first comparison) */
+        throw CaError(CA_ERR_ARG, "ca_fitter_set_options: every value must be finite and >= 0");
+    if (o.regularize < 0 || o.regularize > 1) throw CaError(CA_ERR_ARG, "ca_fitter_set_options: regularize must be 0 or 1");
+    if ((o.clipvalue > 0.0f) + (o.clipnorm > 0.0f) + (o.global_clipnorm > 0.0f) > 1)
+      throw CaError(CA_ERR_ARG, "ca_fitter_set_options: at most one of clipvalue, clipnorm and global_clipnorm");
+    FtOpt probe;
+    probe.o = o;
+    if (probe.on()) f->plan_options();
+    f->opt.o = o;
+  });
+}
+
+extern "C" int ca_fitter_get_options(ca_fitter *f, ca_fit_options *out) {
+  return co_guard(f, [&] {
+    if (!out || out->struct_size < sizeof(uint32_t)) throw CaError(CA_ERR_ARG, "ca_fitter_get_options: null, or a struct_size below 4");
+    ca_fit_options o = f->opt.o;
+    o.struct_size = (uint32_t)(out->struct_size < sizeof(o) ? out->struct_size : sizeof(o));
+    memcpy(out, &o, o.struct_size);
+  });
+}
+
+extern "C" int ca_fitter_train_stats(ca_fitter *f, ca_fit_stats *out) {
+  return co_guard(f, [&] {
+    if (!out || out->struct_size < sizeof(uint32_t)) throw CaError(CA_ERR_ARG, "ca_fitter_train_stats: null, or a struct_size below 4");
+    ca_fit_stats st = f->last;
+    st.struct_size = (uint32_t)(out->struct_size < sizeof(st) ? out->struct_size : sizeof(st));
+    memcpy(out, &st, st.struct_size);
+  });
+}
+
+extern "C" int ca_fitter_tensor_table(ca_fitter *f, int32_t *out, int32_t cap, int32_t *count) {
+  return co_guard(f, [&] {
+    if (!count || cap < 0 || (cap > 0 && !out)) throw CaError(CA_ERR_ARG, "ca_fitter_tensor_table: null output or negative cap");
+    std::vector<FtTensor> tt;
+    f->net->tensor_table(tt);
+    *count = (int32_t)tt.size();
+    for (int32_t k = 0; k < cap && k < *count; ++k) out[3 * k] = tt[k].off, out[3 * k + 1] = tt[k].count, out[3 * k + 2] = tt[k].cls;
   });
 }

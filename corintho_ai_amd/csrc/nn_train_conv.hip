@@ -445,6 +445,32 @@ struct FtResCnn : FtNet {
         sidx[L.var(j) + c] = j * FC_STAT_LD + 64 + c;
       }
   }
+  void tensor_table(std::vector<FtTensor> &t) const override {
+    t.clear();
+    /* BatchNorm j's five arrays behind its convolution's kernel */
+    auto bn = [&](int j) {
+      const int c = L.channels(j);
+      t.push_back({L.bias(j), c, CA_TENSOR_BIAS});
+      t.push_back({L.gamma(j), c, CA_TENSOR_GAMMA});
+      t.push_back({L.beta(j), c, CA_TENSOR_BETA});
+      t.push_back({L.mean(j), c, CA_TENSOR_MOVING});
+      t.push_back({L.var(j), c, CA_TENSOR_MOVING});
+    };
+    for (int l = 0; l < L.CONVS; ++l) {
+      t.push_back({L.kernel(l), 9 * L.cin(l) * FC_C, CA_TENSOR_TRUNK_KERNEL});
+      bn(l);
+    }
+    t.push_back({L.p_k, FC_C * 4, CA_TENSOR_HEAD_KERNEL});
+    bn(9);
+    t.push_back({L.p_dk, 64 * CA_NUM_MOVES, CA_TENSOR_HEAD_KERNEL});
+    t.push_back({L.p_db, CA_NUM_MOVES, CA_TENSOR_BIAS});
+    t.push_back({L.v_k, FC_C * 2, CA_TENSOR_HEAD_KERNEL});
+    bn(10);
+    t.push_back({L.v_d1k, 32 * 64, CA_TENSOR_HEAD_KERNEL});
+    t.push_back({L.v_d1b, 64, CA_TENSOR_BIAS});
+    t.push_back({L.v_d2k, 64, CA_TENSOR_HEAD_KERNEL});
+    t.push_back({L.v_d2b, 1, CA_TENSOR_BIAS});
+  }
 
   void bn_fwd(const FtShared &sh, int j, const float *Zj, const float *res, float *out, int R, bool train) {
     fc_bn_fwd(sh.s, Zj, res, out, R, L.channels(j), sh.w + L.gamma(j), train ? 1 : 0, bnpart.p, sh.stat + j * FC_STAT_LD);

@@ -129,6 +129,21 @@ struct FtMlp : FtNet {
         sidx[ML.var(l) + f] = l * FT_STAT_LD + FT_PADW + f;
       }
   }
+  void tensor_table(std::vector<FtTensor> &t) const override {
+    t.clear();
+    for (int l = 0; l < CO_MLP_LAYERS; ++l) {
+      t.push_back({ML.kernel(l), ML.in_dim(l) * CO_MLP_WIDTH, CA_TENSOR_TRUNK_KERNEL});
+      t.push_back({ML.bias(l), CO_MLP_WIDTH, CA_TENSOR_BIAS});
+      t.push_back({ML.gamma(l), CO_MLP_WIDTH, CA_TENSOR_GAMMA});
+      t.push_back({ML.beta(l), CO_MLP_WIDTH, CA_TENSOR_BETA});
+      t.push_back({ML.mean(l), CO_MLP_WIDTH, CA_TENSOR_MOVING});
+      t.push_back({ML.var(l), CO_MLP_WIDTH, CA_TENSOR_MOVING});
+    }
+    t.push_back({ML.kv, CO_MLP_WIDTH, CA_TENSOR_HEAD_KERNEL});
+    t.push_back({ML.bv, 1, CA_TENSOR_BIAS});
+    t.push_back({ML.kp, CO_MLP_WIDTH * CA_NUM_MOVES, CA_TENSOR_HEAD_KERNEL});
+    t.push_back({ML.bp, CA_NUM_MOVES, CA_TENSOR_BIAS});
+  }
 
   float *A(int l) { return act.p + l * rows_ld; } /* layer l after its ReLU */
   float *Y(int l) { return y.p + l * rows_ld; }   /* and after its BatchNorm */

@@ -37,6 +37,16 @@ statistics stay unweighted (fit(..., sample_weight=w), fit_samples(..., sample_w
 Fitter.merge_duplicates merges the duplicate positions of a packed set on the device into one weighted sample each
 (DESIGN.md "Merging duplicate positions"; samples_io.merge_duplicates_host is its definition).  A set without weights
 is fitted by the kernels that know of none.
+
+Fit options (FitOptions; include/corintho_hip.h "fit options" is the definition): what the reference's model declares and
+leaves at zero -- kernel_regularizer=L1L2() on its hidden Dense layers -- and what its Adam's constructor takes:
+    res = fit_resident(fitter, weights, options=FitOptions(l2=1e-4, weight_decay=1e-4, global_clipnorm=1.0))
+l1, l2: the regulariser, on the trunk kernels (regularize=0) or on all kernels (1); its R(w) is part of "loss" and
+"val_loss", as Keras adds layer losses.  weight_decay: decoupled, on the kernels, times the learning rate.  clipvalue,
+clipnorm (per tensor), global_clipnorm: at most one.  Everything runs in the device's step (csrc/nn_train_opt.hip); with
+every option 0 a step is what it is without them, kernel for kernel and bit for bit.  fit_resident puts the fitter into
+the state its call asks for: options=None switches a Fitter's options off.  With an option on, `history` gains
+"regularization_loss", "grad_norm" (both means over the epoch's steps) and "clipped_steps", one entry per epoch.
 """
 import ctypes as C
 import inspect
@@ -80,6 +90,74 @@ def _packed(state_policy, outcome, who):
     if oc.size != sp.shape[0]:
         raise ValueError("%s: outcome must be [n] for n = %d, got %d" % (who, sp.shape[0], oc.size))
     return sp, oc
+
+
+OPTION_NAMES = ("l1", "l2", "weight_decay", "clipvalue", "clipnorm", "global_clipnorm")
+OPTION_HISTORY_KEYS = ("regularization_loss", "grad_norm", "clipped_steps")
+
+
+@dataclass(frozen=True)
+class FitOptions:
+    """ca_fit_options: every value 0 is off.  The device takes the values in float32."""
+    l1: float = 0.0
+    l2: float = 0.0
+    regularize: int = 0          # 0: l1 and l2 on the trunk kernels, 1: on all kernels
+    weight_decay: float = 0.0
+    clipvalue: float = 0.0
+    clipnorm: float = 0.0
+    global_clipnorm: float = 0.0
+
+    def check(self):
+        """ValueError unless the options are ones the device takes; returns self"""
+        for k in OPTION_NAMES:
+            x = getattr(self, k)
+            if not isinstance(x, (int, float, np.floating, np.integer)) or not np.isfinite(x) or x < 0:
+                raise ValueError("fit options: %s must be finite and >= 0, got %r" % (k, x))
+            with np.errstate(over="ignore"):
+                narrow = np.float32(x)
+            if not np.isfinite(narrow):
+                raise ValueError("fit options: %s = %r is not finite in float32" % (k, x))
+        if self.regularize not in (0, 1):
+            raise ValueError("fit options: regularize must be 0 (trunk kernels) or 1 (all kernels), got %r" % (self.regularize,))
+        if sum(1 for k in ("clipvalue", "clipnorm", "global_clipnorm") if np.float32(getattr(self, k)) > 0) > 1:
+            raise ValueError("fit options: at most one of clipvalue, clipnorm and global_clipnorm may be set")
+        return self
+
+    def any(self):
+        """is any option on (in float32, as the device sees them)"""
+        return any(np.float32(getattr(self, k)) > 0 for k in OPTION_NAMES)
+
+    def as_dict(self):
+        d = {k: float(getattr(self, k)) for k in OPTION_NAMES}
+        d["regularize"] = int(self.regularize)
+        return d
+
+
+def _options(options):
+    """None or a FitOptions (or a mapping of its fields), checked; None stays None"""
+    if options is None:
+        return None
+    if isinstance(options, dict):
+        unknown = sorted(set(options) - set(OPTION_NAMES + ("regularize",)))
+        if unknown:
+            raise ValueError("fit options: unknown %s" % ", ".join(unknown))
+        options = FitOptions(**options)
+    if not isinstance(options, FitOptions):
+        raise ValueError("fit: options must be a FitOptions, a dict of its fields or None, got %r" % (options,))
+    return options.check()
+
+
+def _apply_options(be, opts):
+    """put the backend into the state the call asks for: a backend that has options gets them (None: all off); one that
+    has none serves only a call that asks for none"""
+    def has(name):  # (without asking a backend's __getattr__)
+        return inspect.getattr_static(be, name, None) is not None
+
+    if has("set_options"):
+        be.set_options(opts if opts is not None else FitOptions())
+    elif opts is not None and opts.any():
+        raise ValueError("fit: the backend %s has no set_options" % type(be).__name__)
+    return opts is not None and opts.any() and has("train_stats")
 
 
 class Fitter:
@@ -222,6 +300,39 @@ class Fitter:
         self._check(self._L.ca_fitter_merge_duplicates(self._h, 1 if normalize else 0, C.byref(before), C.byref(after)))
         return before.value, after.value
 
+    # ---- fit options (include/corintho_hip.h, "fit options") ----
+    def set_options(self, options=None):
+        """the regulariser, weight decay and clipping of every later step (FitOptions, or a dict of its fields); None:
+        all off.  They stay until set again."""
+        o = _options(options) or FitOptions()
+        c = _lib.CaFitOptions(struct_size=C.sizeof(_lib.CaFitOptions), regularize=int(o.regularize),
+                              **{k: float(np.float32(getattr(o, k))) for k in OPTION_NAMES})
+        self._check(self._L.ca_fitter_set_options(self._h, C.byref(c)))
+
+    def get_options(self):
+        c = _lib.CaFitOptions(struct_size=C.sizeof(_lib.CaFitOptions))
+        self._check(self._L.ca_fitter_get_options(self._h, C.byref(c)))
+        return FitOptions(regularize=int(c.regularize), **{k: float(getattr(c, k)) for k in OPTION_NAMES})
+
+    def train_stats(self):
+        """of the last train(): {"steps", "clipped_steps", "regularization_loss", "grad_norm", "grad_norm_max"} -- the
+        means over the steps of R(w) and of the norm of the regularised gradient before clipping, and that norm's
+        maximum; zeros when no option is set"""
+        c = _lib.CaFitStats(struct_size=C.sizeof(_lib.CaFitStats))
+        self._check(self._L.ca_fitter_train_stats(self._h, C.byref(c)))
+        return {"steps": int(c.steps), "clipped_steps": int(c.clipped_steps), "regularization_loss": float(c.regularization),
+                "grad_norm": float(c.grad_norm), "grad_norm_max": float(c.grad_norm_max)}
+
+    def tensor_table(self):
+        """the device's table of the network's tensors: [(offset, floats, class)], class a name of nets.TENSOR_CLASSES;
+        nets.tensor_table(name) is the same with the tensors' names"""
+        from .nets import TENSOR_CLASSES
+        n = C.c_int32()
+        self._check(self._L.ca_fitter_tensor_table(self._h, None, 0, C.byref(n)))
+        t = np.zeros((n.value, 3), np.int32)
+        self._check(self._L.ca_fitter_tensor_table(self._h, _ptr(t, C.c_int32), n.value, C.byref(n)))
+        return [(int(o), int(k), TENSOR_CLASSES[c]) for o, k, c in t]
+
     def train(self, rows, batch_size, learning_rate, batch_losses=False):
         """one epoch over `rows` in that order; returns the three mean losses (and the [batches, 3] per-batch ones)"""
         r = np.ascontiguousarray(rows, dtype=np.int32)
@@ -270,16 +381,21 @@ def epoch_order(rng, n_train, shuffle):
     return rng.permutation(n_train).astype(np.int32) if shuffle else np.arange(n_train, dtype=np.int32)
 
 
-def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed):
-    """the epochs of model.fit on the n rows the backend holds, rows [0, split_at) training; the callbacks' logic"""
+def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed, stats=False):
+    """the epochs of model.fit on the n rows the backend holds, rows [0, split_at) training; the callbacks' logic.
+    stats: an option is on, the backend's train_stats() of every epoch go to the history"""
     rng = np.random.default_rng(seed)
     lr = np.float32(learning_rate)
-    history = {k: [] for k in HISTORY_KEYS}
+    history = {k: [] for k in HISTORY_KEYS + (OPTION_HISTORY_KEYS if stats else ())}
     ckpt_best, plateau_best, wait = np.inf, np.inf, 0
     best = None
     for epoch in range(epochs):
         order = epoch_order(rng, split_at, shuffle)
         loss = be.train(order, batch_size, lr)
+        if stats:
+            st = be.train_stats()
+            for k in OPTION_HISTORY_KEYS:
+                history[k].append(st[k])
         val = be.evaluate(split_at, n - split_at, batch_size)
         for k, x in zip(HISTORY_KEYS, tuple(loss) + tuple(val) + (lr,)):
             history[k].append(float(x))
@@ -312,12 +428,14 @@ def _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_
 
 
 def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epochs=1, validation_split=0.3, shuffle=True,
-                 anneal_factor=0.5, patience=3, seed=0, optimizer_state=None):
+                 anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, options=None):
     """fit() on whatever data set `fitter` holds -- packed (add_samples, add_device_samples, add_trainer_samples) or
     expanded (set_data) -- without touching it: the rows are data_info()'s, the split, the permutations, the checkpoint
     and the plateau logic are fit()'s, and so is the FitResult.  On a packed set of n samples the rows are the 8 n
     virtual rows, so the result equals fit() on expand_samples of the same samples to the bit.  batch_size may not
-    exceed the fitter's max_batch."""
+    exceed the fitter's max_batch.  options: a FitOptions; None: no option, and a fitter that has options is set to all
+    off -- the call decides, not what the fitter was left with."""
+    opts = _options(options)
     w = _f32(weights).ravel()
     num_weights = getattr(fitter, "num_weights", w.size)
     if w.size != num_weights:
@@ -334,8 +452,9 @@ def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epoch
     else:
         m, v, it = optimizer_state
         fitter.set_optimizer(m, v, it)
+    stats = _apply_options(fitter, opts)
     return _epochs(fitter, n, split_at, learning_rate, int(batch_size), int(epochs), shuffle, anneal_factor, patience,
-                   seed)
+                   seed, stats)
 
 
 def fit_samples(weights, state_policy, outcome, *, batch_size=2048, device=0, net=NET_MLP12X100, sample_weight=None,
@@ -400,6 +519,7 @@ def _fit_added(add, weights, batch_size, device, net, backend, kw):
     a = args.arguments
     _check_fit_args(a["learning_rate"], a["batch_size"], a["epochs"], a["validation_split"], a["anneal_factor"],
                     a["patience"])
+    _options(a["options"])
     own = backend is None
     be = Fitter(max_batch=int(batch_size), device=device, net=net) if own else backend
     try:
@@ -413,12 +533,14 @@ def _fit_added(add, weights, batch_size, device, net, backend, kw):
 
 def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, batch_size=2048, epochs=1,
         validation_split=0.3, shuffle=True, anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, device=0,
-        net=NET_MLP12X100, sample_weight=None, _backend=None):
+        net=NET_MLP12X100, sample_weight=None, options=None, _backend=None):
     """main.pyx:249-260 `model.fit(...)` with its callbacks; see the module docstring.  Returns a FitResult.
     optimizer_state: (m, v, iterations) to resume from; None starts Adam from zeros, as a freshly compiled model.
     net: NET_MLP12X100 or NET_RESCNN4, the network `weights` belong to.
     sample_weight: one weight per row, Keras's model.fit(sample_weight=...): a batch's losses are (1/B) sum w_r loss_r,
-    in training and in validation; None fits unweighted."""
+    in training and in validation; None fits unweighted.
+    options: a FitOptions (the module docstring); None: none."""
+    opts = _options(options)
     name, num_weights = net_info(net)
     w = _f32(weights).ravel()
     if w.size != num_weights:
@@ -451,7 +573,8 @@ def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, 
         be.set_data(states, evals, probs)
         if sw is not None:
             be.set_sample_weights(sw)
-        return _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed)
+        stats = _apply_options(be, opts)
+        return _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed, stats)
     finally:
         if own:
             be.close()

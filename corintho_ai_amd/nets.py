@@ -188,3 +188,51 @@ def trained_like_rescnn4(seed=0):
             w[ga:ga + n] = (rng.uniform(0.5, 1.5, n) * np.sqrt(w[p:p + n]) / 4.0).astype(np.float32)
         p += n
     return w
+
+
+# --------------------------------------------------------------------------- tensors
+# The flat weight vector as a sequence of tensors, each with a class (include/corintho_hip.h, "fit options"): what the
+# fit's regulariser, weight decay and per-tensor clipping go by.  The device's own table is Fitter.tensor_table().
+TENSOR_CLASSES = ("trunk_kernel", "head_kernel", "bias", "gamma", "beta", "moving")
+_RESCNN4_HEAD_KERNELS = ("p_k", "p_dk", "v_k", "v_d1k", "v_d2k")
+
+
+def tensor_table(net):
+    """[(name, offset, floats, class)] of `net` ("mlp12x100" or "rescnn4") in the order of the weight vector; class is
+    one of TENSOR_CLASSES.  mlp12x100: the trunk kernels are the 12 hidden Dense kernels k0..k11, the head kernels kv and
+    kp.  rescnn4: the names of _rescnn4_shapes(); the trunk kernels are stem_k and b{0..3}_c{1,2}_k, the head kernels
+    p_k, p_dk, v_k, v_d1k and v_d2k."""
+    out, p = [], 0
+
+    def add(name, n, cls):
+        nonlocal p
+        out.append((name, p, int(n), cls))
+        p += int(n)
+
+    if net == "mlp12x100":
+        fan_in = GAME_STATE_SIZE
+        for l in range(12):
+            add("k%d" % l, fan_in * 100, "trunk_kernel")
+            for name, cls in (("b", "bias"), ("gamma", "gamma"), ("beta", "beta"), ("mean", "moving"), ("var", "moving")):
+                add("%s%d" % (name, l), 100, cls)
+            fan_in = 100
+        add("kv", 100, "head_kernel")
+        add("bv", 1, "bias")
+        add("kp", 100 * NUM_MOVES, "head_kernel")
+        add("bp", NUM_MOVES, "bias")
+        assert p == MLP_NUM_WEIGHTS
+    elif net == "rescnn4":
+        for name, shape in _rescnn4_shapes():
+            if "_bn" in name:
+                cls = ("gamma", "beta", "moving", "moving")[int(name[-1])]
+            elif name in _RESCNN4_HEAD_KERNELS:
+                cls = "head_kernel"
+            elif name.endswith("_k"):
+                cls = "trunk_kernel"
+            else:
+                cls = "bias"
+            add(name, np.prod(shape), cls)
+        assert p == RESCNN4_NUM_WEIGHTS
+    else:
+        raise ValueError("tensor_table: net must be \"mlp12x100\" or \"rescnn4\", not %r" % (net,))
+    return out

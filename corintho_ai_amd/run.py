@@ -24,6 +24,11 @@ What is deliberately not the reference's:
     than once become one sample each, with the mean of their targets and a weight equal to their share
     (Fitter.merge_duplicates, normalised to mean one, so that a batch weighs what an unweighted one does; val_loss
     is lower all the same, because the merged targets are means: profiles/sample_merge.md).  samples.npz stays the un-merged export and fit_time.txt counts the generation's samples, as the reference does.
+  * l1, l2, regularize, weight_decay, clipvalue, clipnorm, global_clipnorm (all off by default): the fit options of
+    fit.FitOptions -- the regulariser the reference declares on its hidden layers and leaves at zero, and the arguments
+    its Adam's constructor takes.  A generation that fits with any of them writes training_logs/fit_options.json: the
+    options, and per epoch the regularisation loss, the mean gradient norm and the clipped steps.  val_loss, and with
+    it metadata/losses.txt, then includes the regulariser's R(w), as Keras's does.  model.npz is what it was.
 """
 import argparse
 import dataclasses
@@ -39,7 +44,7 @@ import numpy as np
 
 from . import _lib, nets, samples_io
 from . import trainer as _trainer
-from .fit import Fitter, fit_resident, net_info
+from .fit import OPTION_HISTORY_KEYS, FitOptions, Fitter, fit_resident, net_info
 
 NETS = {"mlp12x100": (_trainer.NET_MLP12X100, nets.init_mlp12x100), "rescnn4": (_trainer.NET_RESCNN4, nets.init_rescnn4)}
 # the network kind self-play and arena evaluate with: (net, arith) -> Trainer.set_net's kind
@@ -86,6 +91,14 @@ class RunParams:
     init_weights: object = None  # flat array or .npz for generation 0
     zip_logs: bool = False
     merge_duplicates: bool = False  # True: duplicate positions of the fit's window become one weighted sample each
+    # the fit options (fit.FitOptions; include/corintho_hip.h "fit options"): 0 is off
+    l1: float = 0.0
+    l2: float = 0.0
+    regularize: int = 0          # 0: l1 and l2 on the trunk kernels, 1: on all kernels
+    weight_decay: float = 0.0
+    clipvalue: float = 0.0
+    clipnorm: float = 0.0
+    global_clipnorm: float = 0.0
 
     def __post_init__(self):
         for f in dataclasses.fields(self):  # a TOML or command-line value may come as the other number type
@@ -119,6 +132,12 @@ class RunParams:
             raise ValueError("seed must not be negative")
         self.mix_old, self.zip_logs = bool(self.mix_old), bool(self.zip_logs)
         self.merge_duplicates = bool(self.merge_duplicates)
+        self.fit_options()  # ValueError: a negative value, two clip modes
+
+    def fit_options(self):
+        """the fit options of the run as a fit.FitOptions, checked"""
+        return FitOptions(l1=self.l1, l2=self.l2, regularize=self.regularize, weight_decay=self.weight_decay,
+                          clipvalue=self.clipvalue, clipnorm=self.clipnorm, global_clipnorm=self.global_clipnorm).check()
 
     def as_dict(self):
         d = {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
@@ -333,9 +352,11 @@ def train_generation(params, state, *, _cdll=None, _fitter=None, _hook=None):
     # fit (main.pyx:221-272): the current generation's model, not the best one's, with its Adam state
     t0 = time.perf_counter()
     cur_weights, cur_optimizer = load_model(state["cur_gen_location"], p.net)
+    options = p.fit_options()
     res = fit_resident(_fitter, cur_weights, learning_rate=state["learning_rate"], batch_size=p.batch_size,
                             epochs=p.epochs, validation_split=VALIDATION_SPLIT, anneal_factor=p.anneal_factor,
-                            patience=p.patience, seed=seeds["fit"], optimizer_state=cur_optimizer)
+                            patience=p.patience, seed=seeds["fit"], optimizer_state=cur_optimizer,
+                            options=options if options.any() else None)
     save_model(state["new_model_location"], res.best_weights, res.best_optimizer, p.net)  # ModelCheckpoint
     times["fit"] = time.perf_counter() - t0
     log = state["train_log_folder"]
@@ -343,6 +364,9 @@ def train_generation(params, state, *, _cdll=None, _fitter=None, _hook=None):
     for e in range(len(res.history["val_loss"])):
         rows.append("\t".join([str(e)] + [repr(res.history[k][e]) for k in LOSS_COLUMNS]))
     _write_text(os.path.join(log, "train_loss.csv"), "\n".join(rows) + "\n")
+    if options.any():  # nothing in it is a time or a path: a generation played again writes the same bytes
+        described = {"options": options.as_dict(), "epochs": {k: res.history[k] for k in OPTION_HISTORY_KEYS}}
+        _write_text(os.path.join(log, "fit_options.json"), json.dumps(described, indent=4, sort_keys=True) + "\n")
     n = max(1, num_samples)
     _write_text(os.path.join(log, "fit_time.txt"),  # main.pyx:261-270
                 "Neural network fitting completed in %s\n%d samples\n%d batch size\n%d epochs\n%s per epoch\n%s per batch\n"
@@ -590,6 +614,12 @@ def _parser():
         "device": "HIP device ordinal", "seed": "Seed of the run; default: from the clock",
         "sample_format": "packed, or reference to write the three expanded files as well",
         "init_weights": ".npz with the weights of generation 0",
+        "l1": "L1 factor of the fit's regulariser", "l2": "L2 factor of the fit's regulariser",
+        "regularize": "What l1 and l2 act on: 0 the trunk kernels, 1 all kernels",
+        "weight_decay": "Decoupled weight decay of the fit's Adam, on the kernels",
+        "clipvalue": "Clip every gradient entry of the fit to [-c, c]",
+        "clipnorm": "Clip every tensor's gradient of the fit to this norm",
+        "global_clipnorm": "Clip the fit's whole gradient to this norm",
     }
     for f in dataclasses.fields(RunParams):
         if f.name in ("mix_old", "zip_logs"):

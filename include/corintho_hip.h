@@ -527,6 +527,74 @@ int ca_fitter_get_sample_weights(ca_fitter *f, float *out, int32_t n);
  * pass reported an impossible state (its probe loops are bounded); the set is unchanged. */
 int ca_fitter_merge_duplicates(ca_fitter *f, int normalize, int32_t *before, int32_t *after);
 
+/* ---- fit options: the L1L2 regulariser, decoupled weight decay and gradient clipping, on the device ----
+ * What the reference's model declares and leaves at zero (kernel_regularizer=regularizers.L1L2() on its twelve hidden
+ * Dense layers, wrapper.py:263) and what its optimizer's constructor takes (Adam(weight_decay=, clipnorm=,
+ * global_clipnorm=, clipvalue=), wrapper.py:273).  This comment is the definition.
+ *
+ * A network's flat weight vector is a sequence of TENSORS, contiguous ranges (ca_fitter_tensor_table; in Python
+ * nets.tensor_table): the pieces of the MLP's layers, the entries of nets._rescnn4_shapes().  A tensor has a class:
+ *   CA_TENSOR_TRUNK_KERNEL  mlp12x100: the 12 hidden Dense kernels;  rescnn4: stem_k and b{0..3}_c{1,2}_k
+ *   CA_TENSOR_HEAD_KERNEL   mlp12x100: Kv and Kp;                    rescnn4: p_k, p_dk, v_k, v_d1k, v_d2k
+ *   CA_TENSOR_BIAS, CA_TENSOR_GAMMA, CA_TENSOR_BETA, CA_TENSOR_MOVING (a moving mean or variance: not trainable)
+ *
+ * One step at learning rate lr.  w: the weights before the step; g: the summed data gradient, the very floats
+ * ca_fitter_gradients returns (which keeps its meaning whatever the options: the gradient of the data loss).
+ *   1. regulariser   on the regularised tensors (regularize = 0: the trunk kernels, where the reference puts its
+ *                    regulariser; 1: all kernels) r_i = l1 sgn(w_i) + (2 l2) w_i, sgn(+-0) = 0; elsewhere r_i = 0.
+ *                    g' = g + r, evaluated in float64 and rounded once to float32 (so nothing is lost where g and r
+ *                    cancel); l1 and l2 themselves are float32 values.
+ *   2. clipping      of g' on the trainable tensors, by at most one of
+ *                      clipvalue c        g'' = min(max(g', -c), c)
+ *                      clipnorm c         per tensor T: n_T = sqrt(sum g'_i^2), g'' = g' s_T, s_T = float32(c / max(n_T, c))
+ *                      global_clipnorm c  the same with one norm over all trainable tensors
+ *                    An unclipped tensor has s = 1.0f exactly: its bits do not change.  A norm that is not finite is
+ *                    not treated specially.
+ *   3. decay         decoupled (Keras Adam(weight_decay=), biases, gamma and beta excluded): on every kernel, trunk and
+ *                    head, w' = w - (lr weight_decay) w -- the multiplier is lr, not Adam's lr_t; elsewhere w' = w.
+ *   4. Adam          as without options, on g'' from w'; the moving statistics move as without options.
+ *   5. loss          total = value + 0.25 policy + R(w), R = l1 sum |w_i| + l2 sum w_i^2 over the regularised tensors:
+ *                    in ca_fitter_train (out_losses[0]; batch_losses[][0] with the w from before that batch's step) and in
+ *                    ca_fitter_evaluate, as Keras adds layer losses to loss and val_loss.  out_losses[1] and [2] do
+ *                    not change.
+ * The sums of R and of the norms are accumulated in float64 in a fixed order (a tree of fixed shape over fixed pieces
+ * of the weight vector) without float atomics: two identical fits stay bitwise identical.  With every option 0 a step
+ * launches the kernels it launches without this section and produces the same bytes. */
+#define CA_TENSOR_TRUNK_KERNEL 0
+#define CA_TENSOR_HEAD_KERNEL 1
+#define CA_TENSOR_BIAS 2
+#define CA_TENSOR_GAMMA 3
+#define CA_TENSOR_BETA 4
+#define CA_TENSOR_MOVING 5
+typedef struct ca_fit_options {
+  uint32_t struct_size; /* sizeof(ca_fit_options) of the caller: the library reads and writes min(struct_size, its own
+                           sizeof) bytes and takes the defaults for what the caller's struct does not have */
+  int32_t regularize;   /* 0: l1 and l2 on the trunk kernels, 1: on all kernels */
+  float l1, l2;
+  float weight_decay;
+  float clipvalue, clipnorm, global_clipnorm; /* at most one of the three */
+} ca_fit_options; /* every option 0: off */
+/* what the steps of the last ca_fitter_train did; all 0 when no option is set */
+typedef struct ca_fit_stats {
+  uint32_t struct_size; /* as above */
+  uint32_t reserved;
+  int64_t steps;         /* steps of the call */
+  int64_t clipped_steps; /* ... in which clipping changed anything */
+  double regularization; /* mean over the steps of R(w), w from before each step */
+  double grad_norm;      /* mean and ... */
+  double grad_norm_max;  /* ... maximum over the steps of the norm of g' over all trainable tensors, before clipping */
+} ca_fit_stats;
+/* CA_ERR_ARG and nothing changes: a negative or non-finite value, regularize outside 0..1, more than one clip mode, a
+ * struct_size below 4.  The options stay, across ca_fitter_set_weights, _set_optimizer and every change of the data,
+ * until they are set again. */
+int ca_fitter_set_options(ca_fitter *f, const ca_fit_options *options);
+/* out->struct_size must be set by the caller; on return it is the number of bytes written */
+int ca_fitter_get_options(ca_fitter *f, ca_fit_options *out);
+int ca_fitter_train_stats(ca_fitter *f, ca_fit_stats *out);
+/* the network's tensors in the order of the weight vector: out[k] = {offset, floats, class} of the first
+ * min(cap, *count) of them; *count = how many there are (out may be null with cap 0) */
+int ca_fitter_tensor_table(ca_fitter *f, int32_t *out /* [cap][3] */, int32_t cap, int32_t *count);
+
 #ifdef __cplusplus
 }
 #endif

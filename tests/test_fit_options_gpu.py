@@ -1,0 +1,519 @@
+"""The fit options on the MI355X (csrc/nn_train_opt.hip; include/corintho_hip.h, "fit options"): with everything off a
+step is what it was, and with an option on the new arithmetic is what the definition says -- judged from the device's
+own gradients() pushed through steps 1 to 3 in numpy float64 (tests/fit_ref_options.py), so that no ReLU kink of the
+network's backward pass is in the comparison.  Shapes: 40 un-augmented samples (320 virtual rows), max_batch 129,
+batches of 1, 17 and 129 rows, both networks.
+
+The bounds of a step from a zero optimizer state, m = c1 g'' and v = c2 g''^2 with c1 = float32(1) - float32(0.9) and
+c2 = float32(1) - float32(0.999): m may differ by 8 float32 roundings of its largest term, 2^-21 c1 (|g| + l1 + 2 l2 |w|);
+v by 2^-20 of itself (and never by less than float32's smallest normal number, below which v has no 24 bits)."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+from corintho_ai_amd import NET_MLP12X100, NET_RESCNN4, FitOptions, Run, nets, samples_io
+from corintho_ai_amd import _lib
+from corintho_ai_amd import run as R
+from corintho_ai_amd.fit import Fitter, fit_resident, fit_samples
+from tests import fit_ref
+from tests import fit_ref_options as O
+
+pytestmark = pytest.mark.gpu
+
+KINDS = {"mlp12x100": (NET_MLP12X100, nets.init_mlp12x100), "rescnn4": (NET_RESCNN4, nets.init_rescnn4)}
+NETS = pytest.mark.parametrize("net", list(KINDS))
+BATCHES = pytest.mark.parametrize("B", [1, 17, 129])
+LR = 1e-3
+C1 = np.float32(1) - np.float32(0.9)
+C2 = np.float32(1) - np.float32(0.999)
+F32_MIN = float(np.finfo(np.float32).tiny)
+
+
+def packed():
+    s, z, p = fit_ref.synthetic_samples(40, 23)
+    return np.concatenate([s, p], axis=1).astype(np.float32), z
+
+
+class Ctx:
+    """one fitter of `net` on the packed set, reused by the tests of this file: every use sets everything it relies on"""
+
+    def __init__(self, net):
+        self.net = net
+        self.kind, init = KINDS[net]
+        self.w = init(5, bn_noise=True)
+        self.f = Fitter(max_batch=129, net=self.kind)
+        self.f.add_samples(*packed())
+        self.tensors = O.tensors(net)
+        self.cache = {}
+
+    def rows(self, B):
+        return np.random.default_rng(100 + B).permutation(320)[:B].astype(np.int32)
+
+    def gradient(self, B, w=None):
+        """the device's data gradient of the batch, as float64"""
+        self.f.set_weights(self.w if w is None else w)
+        return self.f.gradients(self.rows(B))[0].astype(np.float64)
+
+    def step(self, B, options, w=None):
+        """one step of the batch from a zero optimizer state -> dict(w, m, v, per, losses, stats)"""
+        w = self.w if w is None else w
+        f = self.f
+        f.set_options(options)
+        f.set_weights(w)
+        f.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
+        losses, per = f.train(self.rows(B), B, LR, batch_losses=True)
+        m, v, it = f.get_optimizer()
+        assert it == 1
+        return dict(w=f.get_weights(), m=m, v=v, per=per, losses=losses, stats=f.train_stats())
+
+    def plain(self, B):
+        """the step without options on the context's weights, computed once"""
+        if B not in self.cache:
+            self.cache[B] = (self.step(B, None), self.gradient(B))
+        return self.cache[B]
+
+
+_CTX = {}
+
+
+@pytest.fixture(scope="module")
+def ctxs():
+    yield _CTX
+    for c in _CTX.values():
+        c.f.close()
+    _CTX.clear()
+
+
+@pytest.fixture
+def ctx(ctxs, net):
+    if net not in ctxs:
+        ctxs[net] = Ctx(net)
+    return ctxs[net]
+
+
+def same(a, b, sl=slice(None)):
+    return a[sl].tobytes() == b[sl].tobytes()
+
+
+def check_m_v(ctx, got, g2, g, w, o, where=slice(None), what=""):
+    """m and v of a first step against c1 g'' and c2 g''^2 within the bounds of the module docstring"""
+    l1, l2 = float(np.float32(o.l1)), float(np.float32(o.l2))
+    m_ref, v_ref = float(C1) * g2[where], float(C2) * g2[where] ** 2
+    m_tol = 2.0 ** -21 * float(C1) * (np.abs(g[where]) + l1 + 2 * l2 * np.abs(w[where].astype(np.float64)))
+    em = np.abs(got["m"][where].astype(np.float64) - m_ref)
+    ev = np.abs(got["v"][where].astype(np.float64) - v_ref)
+    v_tol = np.maximum(2.0 ** -20 * v_ref, F32_MIN)
+    print("%s %s: m error / bound %.3f, v error / bound %.3f" % (ctx.net, what, float(np.max(em / np.maximum(m_tol, 1e-300))),
+                                                                float(np.max(ev / v_tol))))
+    assert np.all(em <= m_tol), (what, "m", float(np.max(em - m_tol)))
+    assert np.all(ev <= v_tol), (what, "v", float(np.max(ev - v_tol)))
+
+
+def expect(ctx, g, w, o):
+    """steps 1 and 2 in float64 on the device's gradient: (g'', info of the clip)"""
+    return O.clip(ctx.net, g + O.reg_grad(ctx.net, w, o), o)
+
+
+# ---------------------------------------------------------------------------------------------------- off is off
+@NETS
+def test_off_is_off(net):
+    """a fitter that never saw options, one set to all-zero options and one set and then reset: two epochs at batch 17
+    and a validation pass give identical bytes"""
+    kind, init = KINDS[net]
+    w = init(5, bn_noise=True)
+    outs = []
+    for how in ("never", "zero", "reset"):
+        with Fitter(max_batch=129, net=kind) as f:
+            f.add_samples(*packed())
+            if how == "zero":
+                f.set_options(FitOptions())
+            if how == "reset":
+                f.set_options(FitOptions(l1=1e-3, l2=1e-3, regularize=1, weight_decay=0.1, clipnorm=1e-3))
+                f.set_weights(w)
+                f.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
+                f.train(np.arange(40, dtype=np.int32), 17, LR)
+                f.evaluate(0, 40, 17)
+                f.set_options(None)
+            f.set_weights(w)
+            f.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
+            parts = []
+            for epoch in range(2):
+                rows = np.random.default_rng(epoch).permutation(224).astype(np.int32)
+                parts.append(f.train(rows, 17, LR, batch_losses=True)[1])
+            parts.append(np.asarray(f.evaluate(224, 96, 17)))
+            m, v, it = f.get_optimizer()
+            assert it == 2 * 14
+            st = f.train_stats()
+            assert st == dict(steps=0, clipped_steps=0, regularization_loss=0.0, grad_norm=0.0, grad_norm_max=0.0)
+            outs.append([a.tobytes() for a in [f.get_weights(), m, v] + parts])
+    for name, a, b, c in zip(("weights", "m", "v", "epoch 0", "epoch 1", "validation"), *outs):
+        assert a == b == c, name
+    assert outs[0][0] != w.tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------- one step, one option
+@NETS
+@BATCHES
+def test_global_clipnorm(ctx, B):
+    plain, g = ctx.plain(B)
+    norm = float(np.sqrt((g[O.trainable_mask(ctx.net)] ** 2).sum()))
+    # half the norm: the step clips, by the scale of the definition
+    o = FitOptions(global_clipnorm=norm / 2)
+    got = ctx.step(B, o)
+    g2, info = expect(ctx, g, ctx.w, o)
+    assert info["clipped"] and got["stats"]["clipped_steps"] == 1 and got["stats"]["steps"] == 1
+    check_m_v(ctx, got, g2, g, ctx.w, o, what="global clip B=%d" % B)
+    tr = O.trainable_mask(ctx.net)
+    s_ref = float(next(iter(info["scales"].values())))
+    s_dev = float((got["m"][tr].astype(np.float64) * g[tr]).sum() / (float(C1) * (g[tr] ** 2).sum()))
+    print("scale: device %.9g, float64 %.9g" % (s_dev, s_ref))
+    assert abs(s_dev - s_ref) <= 2.0 ** -22 * s_ref
+    assert abs(got["stats"]["grad_norm"] - norm) <= 1e-6 * norm and got["stats"]["grad_norm_max"] == got["stats"]["grad_norm"]
+    assert same(got["w"], plain["w"], O.class_mask(ctx.net, ("moving",)))
+    # twice the norm: s = 1.0f, the bytes of the plain step
+    got = ctx.step(B, FitOptions(global_clipnorm=2 * norm))
+    assert got["stats"]["clipped_steps"] == 0 and got["stats"]["steps"] == 1
+    assert abs(got["stats"]["grad_norm"] - norm) <= 1e-6 * norm
+    for k in ("w", "m", "v", "per"):
+        assert same(got[k], plain[k]), k
+
+
+@NETS
+@BATCHES
+def test_clipnorm(ctx, B):
+    """the threshold at the geometric mean of the two adjacent (non-zero) tensor norms that lie furthest apart"""
+    plain, g = ctx.plain(B)
+    norms = {name: float(np.sqrt((g[sl] ** 2).sum())) for name, sl, cls in ctx.tensors if cls != "moving"}
+    pos = sorted(x for x in norms.values() if x > 0)
+    assert len(pos) >= 2
+    k = int(np.argmax([pos[i + 1] / pos[i] for i in range(len(pos) - 1)]))
+    c = float(np.sqrt(pos[k] * pos[k + 1]))
+    assert all(abs(x - c) > 1e-3 * c for x in norms.values()), "a tensor norm at the threshold"
+    o = FitOptions(clipnorm=c)
+    c = float(np.float32(c))
+    got = ctx.step(B, o)
+    g2, info = expect(ctx, g, ctx.w, o)
+    above = [name for name in norms if norms[name] > c]
+    assert above and len(above) < len(norms) and got["stats"]["clipped_steps"] == 1
+    for name, sl, cls in ctx.tensors:
+        if cls == "moving" or norms[name] < c:
+            for q in ("w", "m", "v"):
+                assert same(got[q], plain[q], sl), (name, q)
+        else:
+            assert info["scales"][name] < 1 and not same(got["m"], plain["m"], sl), name
+            check_m_v(ctx, got, g2, g, ctx.w, o, sl, "clipnorm %s B=%d" % (name, B))
+
+
+@NETS
+@BATCHES
+def test_clipvalue(ctx, B):
+    """at the median of |g| (of its non-zero entries where more than half of them are zero: a batch of one row)"""
+    plain, g = ctx.plain(B)
+    tr = O.trainable_mask(ctx.net)
+    c = float(np.median(np.abs(g[tr])))
+    if c == 0.0:
+        c = float(np.median(np.abs(g[tr])[g[tr] != 0]))
+    o = FitOptions(clipvalue=c)
+    c = float(np.float32(c))
+    got = ctx.step(B, o)
+    g2, info = expect(ctx, g, ctx.w, o)
+    assert info["clipped"] and got["stats"]["clipped_steps"] == 1
+    check_m_v(ctx, got, g2, g, ctx.w, o, what="clipvalue B=%d" % B)
+    inside = tr & (np.abs(g) <= c)
+    assert inside.any() and (tr & ~inside).any()
+    assert same(got["m"], plain["m"], inside) and same(got["v"], plain["v"], inside) and same(got["w"], plain["w"], inside)
+    assert np.all(np.abs(got["m"][tr].astype(np.float64)) <= float(C1) * c * (1 + 2.0 ** -22))
+    # a value above every entry clips nothing
+    got = ctx.step(B, FitOptions(clipvalue=2 * float(np.abs(g).max())))
+    assert got["stats"]["clipped_steps"] == 0
+    for k in ("w", "m", "v"):
+        assert same(got[k], plain[k]), k
+
+
+@NETS
+@BATCHES
+def test_l1_with_planted_zeros(ctx, B):
+    trunk = [sl for _, sl, cls in ctx.tensors if cls == "trunk_kernel"][3]
+    w = ctx.w.copy()
+    planted = np.zeros(w.size, bool)
+    planted[trunk.start:trunk.stop:5] = True
+    w[planted] = 0.0
+    w[trunk.start + 5] = -0.0
+    g = ctx.gradient(B, w)
+    plain = ctx.step(B, None, w)
+    for regularize in (0, 1):
+        o = FitOptions(l1=1e-3, regularize=regularize)
+        got = ctx.step(B, o, w)
+        g2, _ = expect(ctx, g, w, o)
+        scope = O.regularized_mask(ctx.net, o)
+        assert same(got["m"], plain["m"], planted) and same(got["v"], plain["v"], planted)
+        for q in ("w", "m", "v"):
+            assert same(got[q], plain[q], ~scope), (regularize, q)
+        moved = scope & ~planted
+        assert np.all(got["m"][moved] != plain["m"][moved])
+        check_m_v(ctx, got, g2, g, w, o, what="l1 regularize=%d B=%d" % (regularize, B))
+        heads = O.class_mask(ctx.net, ("head_kernel",))
+        assert same(got["m"], plain["m"], heads) == (regularize == 0)
+        R = O.reg_loss(ctx.net, w, o)
+        assert abs(got["stats"]["regularization_loss"] - R) <= 1e-6 * R
+        assert got["stats"]["clipped_steps"] == 0
+
+
+@NETS
+@BATCHES
+def test_l2(ctx, B):
+    plain, g = ctx.plain(B)
+    o = FitOptions(l2=1e-2, regularize=1)
+    got = ctx.step(B, o)
+    g2, _ = expect(ctx, g, ctx.w, o)
+    check_m_v(ctx, got, g2, g, ctx.w, o, what="l2 B=%d" % B)
+    scope = O.regularized_mask(ctx.net, o)
+    for q in ("w", "m", "v"):
+        assert same(got[q], plain[q], ~scope), q
+    assert not same(got["m"], plain["m"], scope)
+    norm = float(np.sqrt((g2[O.trainable_mask(ctx.net)] ** 2).sum()))  # no clip: g'' is g'
+    assert abs(got["stats"]["grad_norm"] - norm) <= 1e-6 * norm
+
+
+@NETS
+@BATCHES
+def test_weight_decay(ctx, B):
+    plain, g = ctx.plain(B)
+    o = FitOptions(weight_decay=0.5)
+    got = ctx.step(B, o)
+    assert same(got["m"], plain["m"]) and same(got["v"], plain["v"]) and same(got["per"], plain["per"])
+    kernels = O.class_mask(ctx.net, O.KERNELS)
+    assert same(got["w"], plain["w"], ~kernels)
+    # the restatement: the decayed weight minus Adam's update from the (byte-checked) m and v, lr_t in float32 as the device has it
+    w1 = O.decay(ctx.net, ctx.w, LR, o)
+    f = np.float32
+    lr_t = float(f(LR) * (np.sqrt(f(1) - f(0.999)) / (f(1) - f(0.9))))
+    m, v = got["m"].astype(np.float64), got["v"].astype(np.float64)
+    want = w1 - lr_t * m / (np.sqrt(v) + float(f(1e-7)))
+    err = np.abs(got["w"].astype(np.float64) - want)[kernels]
+    tol = 2.0 ** -21 * (np.abs(ctx.w.astype(np.float64)) + LR)[kernels]
+    print("%s weight decay B=%d: error / bound %.3f" % (ctx.net, B, float(np.max(err / tol))))
+    assert np.all(err <= tol)
+    moved = np.abs(got["w"].astype(np.float64) - plain["w"])[kernels]
+    assert np.max(moved) > 100 * np.max(tol)
+    assert got["stats"] == dict(steps=1, clipped_steps=0, regularization_loss=0.0, grad_norm=got["stats"]["grad_norm"],
+                                grad_norm_max=got["stats"]["grad_norm"])
+
+
+# ---------------------------------------------------------------------------------------------------- reported quantities
+@NETS
+def test_reported_regularisation(ctx):
+    """R per batch in train (the weights from before each step) and in evaluate, float64 numpy of the weights to 1e-6"""
+    o = FitOptions(l1=1e-4, l2=1e-3, regularize=1)
+    f = ctx.f
+    f.set_options(o)
+    f.set_weights(ctx.w)
+    f.set_optimizer(np.zeros_like(ctx.w), np.zeros_like(ctx.w), 0)
+    Rs = []
+    for k, B in enumerate((17, 129, 1)):
+        w = f.get_weights()
+        R_ref = O.reg_loss(ctx.net, w, o)
+        Rs.append(R_ref)
+        g2, _ = expect(ctx, ctx.gradient(B, w), w, o)  # (sets the weights it was given: those the fitter has)
+        norm = float(np.sqrt((g2[O.trainable_mask(ctx.net)] ** 2).sum()))
+        losses, per = f.train(ctx.rows(B), B, LR, batch_losses=True)
+        st = f.train_stats()
+        assert abs(st["regularization_loss"] - R_ref) <= 1e-6 * R_ref
+        want = np.float32(np.float32(per[0][1] + np.float32(0.25) * per[0][2]) + np.float32(R_ref))
+        assert abs(float(per[0][0]) - float(want)) <= 2.0 ** -22 * float(want)
+        assert abs((losses[0] - (losses[1] + 0.25 * losses[2])) - R_ref) <= 1e-6 * R_ref
+        assert abs(st["grad_norm"] - norm) <= 1e-6 * norm
+    assert Rs[0] > 0.01 and len(set(Rs)) == 3
+    w = f.get_weights()
+    R_ref = O.reg_loss(ctx.net, w, o)
+    val = f.evaluate(224, 96, 17)
+    assert abs((val[0] - (val[1] + 0.25 * val[2])) - R_ref) <= 1e-6 * R_ref
+    # the same weights without the regulariser: the two parts are what they were, the total is their sum
+    f.set_options(FitOptions(weight_decay=0.1))
+    off = f.evaluate(224, 96, 17)
+    assert off[1:] == val[1:] and off[0] == off[1] + 0.25 * off[2]
+
+
+@NETS
+def test_batches_of_one_call_are_the_steps_of_single_calls(ctx):
+    """two epochs' worth of slots: 34 rows at batch 17 in one call, and as two calls"""
+    o = FitOptions(l2=1e-3, weight_decay=0.01, global_clipnorm=0.05)
+    rows = ctx.rows(129)[:34]
+    outs = []
+    for pieces in ([rows], [rows[:17], rows[17:]]):
+        f = ctx.f
+        f.set_options(o)
+        f.set_weights(ctx.w)
+        f.set_optimizer(np.zeros_like(ctx.w), np.zeros_like(ctx.w), 0)
+        per, stats = [], []
+        for r in pieces:
+            per.append(f.train(r, 17, LR, batch_losses=True)[1])
+            stats.append(f.train_stats())
+        outs.append((f.get_weights().tobytes(), np.concatenate(per).tobytes(), stats))
+    assert outs[0][0] == outs[1][0] and outs[0][1] == outs[1][1]
+    one, (a, b) = outs[0][2][0], outs[1][2]
+    assert one["steps"] == 2 and one["clipped_steps"] == a["clipped_steps"] + b["clipped_steps"]
+    assert abs(one["regularization_loss"] - (a["regularization_loss"] + b["regularization_loss"]) / 2) <= 1e-12
+    assert one["grad_norm_max"] == max(a["grad_norm_max"], b["grad_norm_max"])
+
+
+# ---------------------------------------------------------------------------------------------------- twenty steps
+def _within(dev, f32, f64, floor):
+    e_dev = float(np.max(np.abs(np.asarray(dev, np.float64) - f64)))
+    e_32 = float(np.max(np.abs(np.asarray(f32, np.float64) - f64)))
+    return e_dev <= 4.0 * e_32 + floor, e_dev, e_32
+
+
+@NETS
+def test_twenty_steps_with_options(net):
+    """l2, weight_decay and global_clipnorm together, 20 steps of 256 rows, by the rule and floors of
+    test_fit_gpu.test_twenty_adam_steps: the device's error against float64 at most 4 x the float32 restatement's + 1e-6"""
+    kind, init = KINDS[net]
+    ref = O.BASE[net]
+    o = FitOptions(l2=1e-3, weight_decay=1e-2, global_clipnorm=0.5)
+    s, z, p = ref.synthetic_samples(5120 + 512, 12)
+    w = init(5, bn_noise=True)
+    rows = np.random.default_rng(4).permutation(5120).astype(np.int32)
+    zeros = np.zeros_like(w)
+    with Fitter(max_batch=256, net=kind) as f:
+        f.set_data(s, z, p)
+        f.set_weights(w)
+        f.set_optimizer(zeros, zeros, 0)
+        f.set_options(o)
+        _, per = f.train(rows, 256, 1e-3, batch_losses=True)
+        wd = f.get_weights()
+        st = f.train_stats()
+        assert f.get_optimizer()[2] == 20 and st["steps"] == 20
+    refs = {}
+    for dt in (ref.torch.float64, ref.torch.float32):
+        be = O.RefBackend(net, dt)
+        be.set_weights(w)
+        be.set_optimizer(zeros, zeros, 0)
+        be.set_data(s, z, p)
+        be.set_options(o)
+        _, pr = be.train(rows, 256, 1e-3, batch_losses=True)
+        refs[dt] = (pr, be.w.astype(np.float64), np.asarray(be.step_norms))
+    (p64, w64, n64), (p32, w32, _) = refs[ref.torch.float64], refs[ref.torch.float32]
+    # the clipped steps: those of the float64 restatement, but for a step whose norm lies within 1e-3 of the threshold
+    c = float(np.float32(o.global_clipnorm))
+    print("norms %s, device clipped %d" % (np.round(n64, 4), st["clipped_steps"]))
+    assert 0 < (n64 > c).sum() and (n64 > c * (1 + 1e-3)).sum() <= st["clipped_steps"] <= (n64 > c * (1 - 1e-3)).sum()
+    ok, ed, e3 = _within(per, p32, p64, 1e-6)
+    print("batch losses dev %.3e f32 %.3e" % (ed, e3))
+    assert ok, ("batch losses", ed, e3)
+    mask = ref.stat_mask()
+    ok, ed, e3 = _within(wd[mask], w32[mask], w64[mask], 1e-6)
+    print("moving statistics dev %.3e f32 %.3e" % (ed, e3))
+    assert ok, ("moving statistics", ed, e3)
+    held = slice(5120, 5632)
+    out64 = ref.evaluate(w64, s[held], z[held], p[held])[1]
+    out32 = ref.evaluate(w32, s[held], z[held], p[held])[1]
+    outd = ref.evaluate(wd.astype(np.float64), s[held], z[held], p[held])[1]
+    for k, name in enumerate(("value", "policy")):
+        ok, ed, e3 = _within(outd[k], out32[k], out64[k], 1e-6)
+        print("%s dev %.3e f32 %.3e" % (name, ed, e3))
+        assert ok, (name, ed, e3)
+
+
+# ---------------------------------------------------------------------------------------------------- other checks
+@NETS
+def test_two_fits_with_options_are_bitwise_identical(net):
+    kind, init = KINDS[net]
+    sp, oc = packed()
+    w = init(6, bn_noise=True)
+    o = FitOptions(l1=1e-5, l2=1e-3, regularize=1, weight_decay=1e-2, clipnorm=0.02)
+    a = fit_samples(w, sp, oc, batch_size=17, epochs=2, seed=3, net=kind, options=o)
+    b = fit_samples(w, sp, oc, batch_size=17, epochs=2, seed=3, net=kind, options=o)
+    assert a.weights.tobytes() == b.weights.tobytes() and a.best_weights.tobytes() == b.best_weights.tobytes()
+    for x, y in zip(a.optimizer[:2] + a.best_optimizer[:2], b.optimizer[:2] + b.best_optimizer[:2]):
+        assert x.tobytes() == y.tobytes()
+    assert a.history == b.history and len(a.history["clipped_steps"]) == 2 and sum(a.history["clipped_steps"]) > 0
+    off = fit_samples(w, sp, oc, batch_size=17, epochs=2, seed=3, net=kind)
+    assert off.weights.tobytes() != a.weights.tobytes() and "clipped_steps" not in off.history
+
+
+@NETS
+def test_options_persist(ctx):
+    """across clear_data, add_samples, set_weights and set_optimizer, until they are set again"""
+    o = FitOptions(l2=1e-3, weight_decay=1e-2, global_clipnorm=0.05)
+    seen = FitOptions(**{k: (float(np.float32(v)) if k != "regularize" else v) for k, v in o.as_dict().items()})
+    first = ctx.step(17, o)
+    f = ctx.f
+    f.clear_data()
+    assert f.get_options() == seen
+    f.add_samples(*packed())
+    f.set_weights(ctx.w)
+    f.set_optimizer(np.zeros_like(ctx.w), np.zeros_like(ctx.w), 0)
+    assert f.get_options() == seen
+    f.train(ctx.rows(17), 17, LR)
+    assert same(f.get_weights(), first["w"]) and f.train_stats() == first["stats"]
+    assert not same(first["w"], ctx.plain(17)[0]["w"])
+    f.set_options(None)
+    assert f.get_options() == FitOptions()
+
+
+def test_abi_errors_change_nothing():
+    L = _lib.load()
+    size = C.sizeof(_lib.CaFitOptions)
+    with Fitter(max_batch=16) as f:
+        good = FitOptions(l2=0.5, clipnorm=2.0)
+        f.set_options(good)
+        bad = [dict(l2=-1.0), dict(l1=float("nan")), dict(weight_decay=float("inf")), dict(regularize=2), dict(regularize=-1),
+               dict(clipvalue=1.0, clipnorm=1.0), dict(clipnorm=1.0, global_clipnorm=1.0), dict(clipvalue=1.0, global_clipnorm=1.0),
+               dict(struct_size=3)]
+        for kw in bad:
+            c = _lib.CaFitOptions(**dict(dict(struct_size=size), **kw))
+            assert L.ca_fitter_set_options(f._h, C.byref(c)) == -1 and L.ca_last_error(), kw
+            assert f.get_options() == good
+        assert L.ca_fitter_set_options(f._h, None) == -1
+        assert L.ca_fitter_set_options(None, C.byref(_lib.CaFitOptions(struct_size=size))) == -1
+        assert L.ca_fitter_get_options(None, C.byref(_lib.CaFitOptions(struct_size=size))) == -1
+        assert L.ca_fitter_train_stats(None, C.byref(_lib.CaFitStats(struct_size=C.sizeof(_lib.CaFitStats)))) == -1
+        assert f.get_options() == good
+        # a shorter struct of an earlier caller: what it does not have is taken as off
+        c = _lib.CaFitOptions(struct_size=16, l1=0.25, l2=0.125, weight_decay=-1.0, clipvalue=float("nan"))
+        assert L.ca_fitter_set_options(f._h, C.byref(c)) == 0
+        assert f.get_options() == FitOptions(l1=0.25, l2=0.125)
+        # and only as many bytes are written back as the caller has
+        c = _lib.CaFitOptions(struct_size=12, l2=7.0)
+        assert L.ca_fitter_get_options(f._h, C.byref(c)) == 0
+        assert (c.struct_size, c.l1, c.l2) == (12, 0.25, 7.0)
+
+
+@NETS
+def test_device_tensor_table(ctx):
+    assert ctx.f.tensor_table() == [(off, n, cls) for _, off, n, cls in nets.tensor_table(ctx.net)]
+
+
+@NETS
+def test_generation_with_options_equals_the_pieces(net, tmp_path):
+    """64 games x 50 searches through Run with l2 and global_clipnorm in the TOML, and the same fit by hand"""
+    toml = tmp_path / "o.toml"
+    toml.write_text("[hyperparameters]\nname = \"run\"\ncwd = \"%s\"\nnet = \"%s\"\nnum_games = 64\nmax_searches = 50\n"
+                    "searches_per_eval = 16\nnum_test_games = 32\nepochs = 2\nbatch_size = 256\nlearning_rate = 0.001\n"
+                    "patience = 2\nc_puct = 3.0\nseed = 11\nl2 = 1e-3\nglobal_clipnorm = 0.25\n" % (tmp_path, net))
+    p, _ = R.parse_args(["--config", str(toml)])
+    o = FitOptions(l2=1e-3, global_clipnorm=0.25)
+    assert p.fit_options() == o
+    with Run.open(p) as run:
+        res = run.generation()
+    gen = os.path.join(run.root, "generations")
+    assert set(res.fit.history) >= {"regularization_loss", "grad_norm", "clipped_steps"}
+    assert os.path.exists(os.path.join(gen, "gen_1", "training_logs", "fit_options.json"))
+    w0, opt0 = R.load_model(os.path.join(gen, "gen_0", "model.npz"))
+    sp, oc = samples_io.load_packed(os.path.join(run.root, "samples", "gen_1"))
+    with Fitter(max_batch=256, net=KINDS[net][0]) as f:
+        f.add_samples(sp, oc)
+        hand = fit_resident(f, w0, learning_rate=0.001, batch_size=256, epochs=2, validation_split=R.VALIDATION_SPLIT,
+                            anneal_factor=p.anneal_factor, patience=p.patience, seed=res.seeds["fit"], optimizer_state=opt0,
+                            options=o)
+        plain = fit_resident(f, w0, learning_rate=0.001, batch_size=256, epochs=2, validation_split=R.VALIDATION_SPLIT,
+                             anneal_factor=p.anneal_factor, patience=p.patience, seed=res.seeds["fit"], optimizer_state=opt0)
+    w1, (m1, v1, it1) = R.load_model(os.path.join(gen, "gen_1", "model.npz"))
+    assert hand.history == res.fit.history
+    assert hand.best_weights.tobytes() == w1.tobytes() == res.fit.best_weights.tobytes()
+    assert hand.best_optimizer[0].tobytes() == m1.tobytes() and hand.best_optimizer[1].tobytes() == v1.tobytes()
+    assert hand.best_optimizer[2] == it1
+    assert plain.best_weights.tobytes() != w1.tobytes() and "clipped_steps" not in plain.history

@@ -20,6 +20,10 @@ process: what the batch-assembly launch costs.
 turn, --reps times: samples_io.get_samples + Fitter.set_data (expand on the device, 8x rows to the host and back), and
 Fitter.add_trainer_samples (packed device to device) into an emptied fitter and into one that has the capacity.
 
+--l1, --l2, --regularize, --weight_decay, --clipvalue, --clipnorm, --global_clipnorm: the fit options
+(include/corintho_hip.h, "fit options") of the HIP step and of the packed one; the result then carries the options and
+the last call's train_stats.  All 0 (the default): the step without them, and no option entry point is called.
+
     python tools/fit_bench.py --torch [--net rescnn4] [--rows 1000000 --batch 2048 --steps 200 --reps 3] [--out file.json]
     python tools/fit_bench.py --packed [--net rescnn4]
     python tools/fit_bench.py --handoff [--games 4096 --sims 400]
@@ -37,7 +41,7 @@ sys.path.insert(0, ROOT)
 
 from corintho_ai_amd import nets  # noqa: E402
 from corintho_ai_amd import NET_MLP12X100, NET_RESCNN4  # noqa: E402
-from corintho_ai_amd.fit import Fitter  # noqa: E402
+from corintho_ai_amd.fit import OPTION_NAMES, FitOptions, Fitter  # noqa: E402
 
 FLOP_PER_ROW_STEP = {"mlp12x100": 3 * 2.0 * (70 * 100 + 11 * 100 * 100 + 100 * 97),
                      "rescnn4": 3 * nets.rescnn4_flop_per_row()}
@@ -237,7 +241,11 @@ def main():
     ap.add_argument("--sims", type=int, default=400, help="--handoff: searches per move")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default="")
+    for name in OPTION_NAMES:  # the fit options (fit.FitOptions); all 0: the step without them
+        ap.add_argument("--" + name, type=float, default=0.0)
+    ap.add_argument("--regularize", type=int, choices=(0, 1), default=0)
     a = ap.parse_args()
+    options = FitOptions(regularize=a.regularize, **{k: getattr(a, k) for k in OPTION_NAMES}).check()
     if a.handoff:
         emit(handoff(a), a.out)
         return
@@ -262,6 +270,8 @@ def main():
     f.set_data(*data)
     f.set_weights(w)
     f.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
+    if options.any():  # (asked only then: an earlier build of the library has no options)
+        f.set_options(options)
     f.train(order[:a.warmup * a.batch], a.batch, 1e-3)
     if ts:
         for i in range(a.warmup):
@@ -274,6 +284,8 @@ def main():
         fp.add_samples(np.concatenate([data[0][:k], data[2][:k]], axis=1), data[1][:k])
         fp.set_weights(w)
         fp.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
+        if options.any():
+            fp.set_options(options)
         fp.train(order[:a.warmup * a.batch], a.batch, 1e-3)
     hip, tor, pak = [], [], []
     timed = order[a.warmup * a.batch:]
@@ -292,6 +304,7 @@ def main():
                 ts.step(torder[(a.warmup + i) * a.batch:(a.warmup + i + 1) * a.batch])
             torch.cuda.synchronize(ts.dev)
             tor.append((time.perf_counter() - t0) * 1e3 / a.steps)
+    stats = f.train_stats() if options.any() else None
     f.close()
     if fp:
         fp.close()
@@ -305,6 +318,9 @@ def main():
 
     out = {"net": a.net, "batch": a.batch, "rows": a.rows, "steps": a.steps, "flop_per_row_step": flop_per_row_step,
            "hip": rec(hip)}
+    if stats:
+        out["options"] = options.as_dict()
+        out["train_stats"] = stats
     if tor:
         out["torch"] = rec(tor)
         out["hip_speedup_over_torch"] = min(tor) / min(hip)
