@@ -87,6 +87,20 @@ class CaFitOptions(C.Structure):
     ]
 
 
+class CaFitAdam(C.Structure):
+    """ca_fit_adam (include/corintho_hip.h, "Adam's arguments"); the defaults are not zeros: fit.AdamOptions has them"""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("beta_1", C.c_float),
+        ("beta_2", C.c_float),
+        ("epsilon", C.c_float),
+        ("amsgrad", C.c_int32),
+        ("ema_momentum", C.c_float),
+        ("ema_overwrite_frequency", C.c_int32),
+    ]
+
+
 class CaFitStats(C.Structure):
     """ca_fit_stats"""
 
@@ -123,6 +137,8 @@ EXPORTS = [
     "ca_fitter_set_sample_weights", "ca_fitter_get_sample_weights", "ca_fitter_merge_duplicates",
     "ca_net_forward_device_io",
     "ca_fitter_set_options", "ca_fitter_get_options", "ca_fitter_train_stats", "ca_fitter_tensor_table",
+    "ca_fitter_set_adam", "ca_fitter_get_adam", "ca_fitter_set_slot", "ca_fitter_get_slot", "ca_fitter_swap_average",
+    "ca_fitter_apply_average",
 ]
 # the caller-supplied network: an earlier build of the library has none of these
 NET_FN_EXPORTS = ["ca_trainer_request_rows", "ca_trainer_set_net_fn", "ca_tourney_set_net_fn", "ca_net_create", "ca_net_forward_device",
@@ -136,7 +152,10 @@ WEIGHT_EXPORTS = ["ca_fitter_set_sample_weights", "ca_fitter_get_sample_weights"
 NET_IO_EXPORTS = ["ca_net_forward_device_io"]
 # the fit options (regulariser, weight decay, clipping): likewise
 OPTION_EXPORTS = ["ca_fitter_set_options", "ca_fitter_get_options", "ca_fitter_train_stats", "ca_fitter_tensor_table"]
-assert set(NET_FN_EXPORTS + GROUP_EXPORTS + WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS) <= set(EXPORTS)
+# Adam's arguments, the third slot and the averaged weights: likewise
+ADAM_EXPORTS = ["ca_fitter_set_adam", "ca_fitter_get_adam", "ca_fitter_set_slot", "ca_fitter_get_slot", "ca_fitter_swap_average",
+                "ca_fitter_apply_average"]
+assert set(NET_FN_EXPORTS + GROUP_EXPORTS + WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS + ADAM_EXPORTS) <= set(EXPORTS)
 
 
 def declare(L):
@@ -231,7 +250,7 @@ def declare(L):
             continue
         if name in GROUP_EXPORTS and not group:
             continue
-        if name in WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS and not hasattr(L, name):
+        if name in WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS + ADAM_EXPORTS and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy", "ca_net_destroy",
@@ -269,6 +288,13 @@ def _declare_fitter(L, vp, f64p):
         L.ca_fitter_get_options.argtypes = [vp, C.POINTER(CaFitOptions)]
         L.ca_fitter_train_stats.argtypes = [vp, C.POINTER(CaFitStats)]
         L.ca_fitter_tensor_table.argtypes = [vp, i32p, C.c_int32, i32p]
+    if hasattr(L, "ca_fitter_set_adam"):  # (likewise)
+        L.ca_fitter_set_adam.argtypes = [vp, C.POINTER(CaFitAdam)]
+        L.ca_fitter_get_adam.argtypes = [vp, C.POINTER(CaFitAdam)]
+        L.ca_fitter_set_slot.argtypes = [vp, C.c_int32, f32p, C.c_size_t]
+        L.ca_fitter_get_slot.argtypes = [vp, C.c_int32, f32p, C.c_size_t]
+        L.ca_fitter_swap_average.argtypes = [vp]
+        L.ca_fitter_apply_average.argtypes = [vp]
 
 
 _lib = None

@@ -107,6 +107,41 @@ struct FtNet {
   /* from hd and what forward kept: the weight gradient of the batch as partials in g (the heads' last biases excepted) */
   virtual FtSplits backward(const FtShared &sh, int B) = 0;
 };
+/* Adam's arguments as the update kernels take them (the definition: corintho_hip.h, "Adam's arguments") */
+struct FtAdamArgs {
+  float beta_1, beta_2, epsilon, ema_momentum;
+  float *h;      /* the third slot ("vhat"); null: amsgrad is off */
+  float *a;      /* the average; null: ema_momentum is 0 */
+  int overwrite; /* this step brings the step count to a multiple of ema_overwrite_frequency: w := a' */
+};
+
+/* Adam on trainable weight i: gradient s (g''), wv the weight the step starts from (w').  Both update kernels, with and
+ * without fit options, end in this one expression.  PARAM = false: the Adam defaults as literals and neither the third
+ * slot nor the average; A is not looked at, and the code is what the kernels held before Adam had arguments. */
+template <bool PARAM>
+__device__ __forceinline__ void ft_adam(float *__restrict__ w, float *__restrict__ m, float *__restrict__ v, int i,
+                                        float wv, float s, float lr_t, const FtAdamArgs &A) {
+  const float b1 = PARAM ? A.beta_1 : 0.9f, b2 = PARAM ? A.beta_2 : 0.999f, eps = PARAM ? A.epsilon : 1e-7f;
+  const float mt = m[i] + (s - m[i]) * (1.0f - b1);
+  const float vt = v[i] + (s * s - v[i]) * (1.0f - b2);
+  m[i] = mt;
+  v[i] = vt;
+  float d = vt;
+  if (PARAM && A.h) {
+    const float hv = A.h[i];
+    d = hv > vt ? hv : vt;
+    A.h[i] = d;
+  }
+  float wn = wv - lr_t * mt / (sqrtf(d) + eps);
+  if (PARAM && A.a) {
+    const float av = A.a[i];
+    const float an = av + (wn - av) * (1.0f - A.ema_momentum);
+    A.a[i] = an;
+    if (A.overwrite) wn = an;
+  }
+  w[i] = wn;
+}
+
 /* Merging of a packed set's duplicate positions on the device (nn_samples.hip; the definition: ca_fitter_merge_duplicates
  * in corintho_hip.h).  sp[n][166], oc[n] and wt[n] (null: every weight 1) are read only; the merged samples come back in
  * buffers of their own with room for `cap` samples, of which `count` are filled.  Everything is queued on s, which is
@@ -122,7 +157,7 @@ FtMerged ft_merge_duplicates(rt_stream_t s, const float *sp, const float *oc, co
  * gradient ft_k_update(apply = 0) left in gsum: the regulariser gradient added and per-piece float64 partials of
  * sum g'^2, R and the count of |g'| > clipvalue (ft_k_opt_partials); the partials combined by a tree of fixed shape
  * into the tensors' scales, the step's R and the call's statistics (ft_k_opt_combine); the clamp or scale, the decay,
- * Adam and the moving statistics (ft_k_opt_update). */
+ * Adam and the moving statistics (ft_k_opt_update; with Adam's arguments off their defaults ft_k_opt_update_adam). */
 struct FtOptStats { /* accumulated on the device over the steps of one ca_fitter_train */
   double reg_sum, norm_sum, norm_max, clipped;
 };
@@ -144,9 +179,10 @@ struct FtOpt {
   void begin(int n, rt_stream_t s);
   /* R(w) to slot `slot`; nothing else is read or written */
   void regularization(rt_stream_t s, const float *w, int slot);
-  /* steps 1 to 4 on gsum; R to slot, the statistics accumulated */
+  /* steps 1 to 4 on gsum; R to slot, the statistics accumulated.  adam: null, the Adam defaults (ft_k_opt_update), or
+   * the arguments of ft_k_opt_update_adam */
   void step(rt_stream_t s, float *w, float *m, float *v, float *gsum, const int32_t *sidx, const float *stat, float lr,
-            float lr_t, int slot);
+            float lr_t, int slot, const FtAdamArgs *adam);
   /* queues the copy of the statistics and the first n R to hout; valid after the stream is synchronised */
   void fetch(int n, rt_stream_t s);
   double R(int slot) const { return hout[4 + slot]; }

@@ -207,12 +207,14 @@ __global__ __launch_bounds__(1024) void ft_k_relu_bwd(float *__restrict__ dA, co
 
 /* The end of a step, one thread per weight of the nw: its gradient is the sum of its partials in order.  sidx[i] < 0:
  * a trainable weight with ns0 (FT_SPLIT0), ns1 (FT_SPLIT1) or one (FT_WHOLE) partial, Adam (TF ResourceApplyAdam,
- * epsilon outside the root); sidx[i] >= 0: a moving statistic, moved toward the batch statistic stat[sidx[i]] with
- * momentum 0.99.  apply = 0: write the summed gradient to gout only. */
-__global__ __launch_bounds__(256) void ft_k_update(float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
-                                                  const float *__restrict__ g, int nw, int ns0, int ns1,
-                                                  const int32_t *__restrict__ sidx, const float *__restrict__ stat,
-                                                  float lr_t, int apply, float *__restrict__ gout) {
+ * epsilon outside the root; ft_adam, nn_train.h); sidx[i] >= 0: a moving statistic, moved toward the batch statistic
+ * stat[sidx[i]] with momentum 0.99.  apply = 0: write the summed gradient to gout only.  PARAM: with Adam's arguments A,
+ * and a moving statistic's new value goes to the average as well. */
+template <bool PARAM>
+__device__ __forceinline__ void ft_update_weight(float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
+                                                 const float *__restrict__ g, int nw, int ns0, int ns1,
+                                                 const int32_t *__restrict__ sidx, const float *__restrict__ stat,
+                                                 float lr_t, int apply, float *__restrict__ gout, const FtAdamArgs &A) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= nw) return;
   const int si = sidx[i];
@@ -226,16 +228,46 @@ __global__ __launch_bounds__(256) void ft_k_update(float *__restrict__ w, float 
   }
   if (si >= 0) {
     const float mv = w[i];
-    w[i] = mv - (mv - stat[si]) * 0.01f;
+    const float nv = mv - (mv - stat[si]) * 0.01f;
+    w[i] = nv;
+    if (PARAM && A.a) A.a[i] = nv;
     return;
   }
   float s = 0.0f;
   for (int k = 0; k < nsplit; ++k) s += g[(long)k * nw + i];
-  const float mt = m[i] + (s - m[i]) * (1.0f - 0.9f);
-  const float vt = v[i] + (s * s - v[i]) * (1.0f - 0.999f);
-  m[i] = mt;
-  v[i] = vt;
-  w[i] = w[i] - lr_t * mt / (sqrtf(vt) + 1e-7f);
+  ft_adam<PARAM>(w, m, v, i, w[i], s, lr_t, A);
+}
+
+/* the Adam defaults: the kernel of a step before Adam had arguments, instruction for instruction */
+__global__ __launch_bounds__(256) void ft_k_update(float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
+                                                  const float *__restrict__ g, int nw, int ns0, int ns1,
+                                                  const int32_t *__restrict__ sidx, const float *__restrict__ stat,
+                                                  float lr_t, int apply, float *__restrict__ gout) {
+  ft_update_weight<false>(w, m, v, g, nw, ns0, ns1, sidx, stat, lr_t, apply, gout, FtAdamArgs{});
+}
+
+__global__ __launch_bounds__(256) void ft_k_update_adam(float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
+                                                       const float *__restrict__ g, int nw, int ns0, int ns1,
+                                                       const int32_t *__restrict__ sidx, const float *__restrict__ stat,
+                                                       float lr_t, FtAdamArgs A) {
+  ft_update_weight<true>(w, m, v, g, nw, ns0, ns1, sidx, stat, lr_t, 1, (float *)nullptr, A);
+}
+
+/* w <-> a, every entry of the weight vector (ca_fitter_swap_average) */
+__global__ __launch_bounds__(256) void ft_k_average_swap(float *__restrict__ w, float *__restrict__ a, int nw) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nw) return;
+  const float t = w[i];
+  w[i] = a[i];
+  a[i] = t;
+}
+
+/* w := a on the trainable weights (ca_fitter_apply_average) */
+__global__ __launch_bounds__(256) void ft_k_average_apply(float *__restrict__ w, const float *__restrict__ a,
+                                                         const int32_t *__restrict__ sidx, int nw) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nw) return;
+  if (sidx[i] < 0) w[i] = a[i];
 }
 
 /* ------------------------------------------------------------------ host */
@@ -274,6 +306,9 @@ struct ca_fitter {
   std::vector<float> hloss;
   FtOpt opt;                                       /* the fit options (nn_train_opt.hip); all 0: never touched by a step */
   ca_fit_stats last = {sizeof(ca_fit_stats), 0, 0, 0, 0.0, 0.0, 0.0}; /* of the last ca_fitter_train */
+  ca_fit_adam adam = CA_FIT_ADAM_INIT; /* Adam's arguments; at their defaults a step never looks at what follows */
+  DevBuf<float> vhat, avg;             /* the third slot and the average: no memory before their first use */
+  bool avg_valid = false;              /* until ca_fitter_set_weights */
 
   void init(int dev, int kind, int mb) {
     device = dev;
@@ -351,9 +386,39 @@ struct ca_fitter {
   }
 
   /* the end of a step with options on: the summed gradient to gsum as ca_fitter_gradients has it, then steps 1 to 4 */
-  void update_with_options(FtSplits ns, float lr, float lr_t, int slot) {
+  void update_with_options(FtSplits ns, float lr, float lr_t, int slot, const FtAdamArgs *A) {
     update(ns, 0.0f, false);
-    opt.step(s, w.p, m.p, v.p, gsum.p, sidx.p, stat.p, lr, lr_t, slot);
+    opt.step(s, w.p, m.p, v.p, gsum.p, sidx.p, stat.p, lr, lr_t, slot, A);
+  }
+  /* the end of a step with Adam's arguments off their defaults: ft_k_update's work, parametrised */
+  void update_adam(FtSplits ns, float lr_t, const FtAdamArgs &A) {
+    RT_LAUNCH(ft_k_update_adam, (nw + 255) / 256, 256, s, w.p, m.p, v.p, (const float *)g.p, nw, ns.rows, ns.pixels,
+              (const int32_t *)sidx.p, (const float *)stat.p, lr_t, A);
+  }
+  /* is every one of Adam's arguments at its default?  Then a step runs the kernels that know of none. */
+  bool adam_default() const {
+    return adam.beta_1 == 0.9f && adam.beta_2 == 0.999f && adam.epsilon == 1e-7f && !adam.amsgrad &&
+           !(adam.ema_momentum > 0.0f);
+  }
+  /* Adam's arguments of the step that brings the step count to `step`.  The third slot and the average get their memory
+   * at their first use (zeroed, on the stream); an invalid average starts as the weights before the step. */
+  FtAdamArgs adam_args(int64_t step) {
+    FtAdamArgs A = {adam.beta_1, adam.beta_2, adam.epsilon, adam.ema_momentum, nullptr, nullptr, 0};
+    if (adam.amsgrad) {
+      if (!vhat.p) vhat.alloc(nw, s);
+      A.h = vhat.p;
+    }
+    if (adam.ema_momentum > 0.0f) {
+      if (!avg.p) avg.alloc(nw, s);
+      if (!avg_valid) rt_d2d(avg.p, w.p, (size_t)nw * sizeof(float), s);
+      avg_valid = true;
+      A.a = avg.p;
+      A.overwrite = adam.ema_overwrite_frequency > 0 && step % adam.ema_overwrite_frequency == 0;
+    }
+    return A;
+  }
+  void need_average(const char *who) {
+    if (!avg_valid) throw CaError(CA_ERR_STATE, std::string(who) + ": the fitter has no average (no step with ema_momentum > 0, no ca_fitter_set_slot)");
   }
   /* the piece table of the options' kernels, made when options are first switched on.  Those kernels take a weight for
    * a moving statistic by its tensor's class and ft_k_update by its code: the two tables must agree. */
@@ -539,6 +604,7 @@ extern "C" int ca_fitter_set_weights(ca_fitter *f, const float *weights, size_t 
     if (!weights) throw CaError(CA_ERR_ARG, "null weights");
     rt_h2d(f->w.p, weights, f->nw * sizeof(float), f->s);
     rt_sync(f->s);
+    f->avg_valid = false;
   });
 }
 
@@ -557,6 +623,7 @@ extern "C" int ca_fitter_set_optimizer(ca_fitter *f, const float *m, const float
     if (!m || !v || iterations < 0) throw CaError(CA_ERR_ARG, "null slots or negative iterations");
     rt_h2d(f->m.p, m, f->nw * sizeof(float), f->s);
     rt_h2d(f->v.p, v, f->nw * sizeof(float), f->s);
+    if (f->vhat.p) rt_memset(f->vhat.p, 0, f->nw * sizeof(float), f->s);
     rt_sync(f->s);
     f->iterations = iterations;
   });
@@ -602,7 +669,7 @@ extern "C" int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows
     const int nb = (n_rows + batch - 1) / batch;
     f->ensure_loss(nb);
     rt_h2d(f->idx.p, rows, (size_t)n_rows * sizeof(int32_t), f->s);
-    const bool options = f->opt.on();
+    const bool options = f->opt.on(), adam_on = !f->adam_default();
     if (options) f->opt.begin(nb, f->s);
     f->last = ca_fit_stats{sizeof(ca_fit_stats), 0, 0, 0, 0.0, 0.0, 0.0};
     for (int b = 0; b < nb; ++b) {
@@ -610,9 +677,15 @@ extern "C" int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows
       const FtSplits ns = f->gradient(f->idx.p + (size_t)b * batch, B, b);
       /* Keras Adam: local_step = iterations + 1, lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), in float32 */
       const float t = (float)(f->iterations + 1);
-      const float lr_t = learning_rate * (sqrtf(1.0f - powf(0.999f, t)) / (1.0f - powf(0.9f, t)));
-      if (options)
-        f->update_with_options(ns, learning_rate, lr_t, b);
+      const float lr_t = learning_rate * (sqrtf(1.0f - powf(f->adam.beta_2, t)) / (1.0f - powf(f->adam.beta_1, t)));
+      if (adam_on) {
+        const FtAdamArgs A = f->adam_args(f->iterations + 1);
+        if (options)
+          f->update_with_options(ns, learning_rate, lr_t, b, &A);
+        else
+          f->update_adam(ns, lr_t, A);
+      } else if (options)
+        f->update_with_options(ns, learning_rate, lr_t, b, nullptr);
       else
         f->update(ns, lr_t, true);
       f->iterations += 1;
@@ -868,6 +941,81 @@ extern "C" int ca_fitter_train_stats(ca_fitter *f, ca_fit_stats *out) {
     ca_fit_stats st = f->last;
     st.struct_size = (uint32_t)(out->struct_size < sizeof(st) ? out->struct_size : sizeof(st));
     memcpy(out, &st, st.struct_size);
+  });
+}
+
+/* ------------------------------------------------------------------ Adam's arguments, the third slot, the average */
+extern "C" int ca_fitter_set_adam(ca_fitter *f, const ca_fit_adam *adam) {
+  return co_guard(f, [&] {
+    if (!adam || adam->struct_size < sizeof(uint32_t)) throw CaError(CA_ERR_ARG, "ca_fitter_set_adam: null, or a struct_size below 4");
+    ca_fit_adam a = CA_FIT_ADAM_INIT; /* the defaults for what the caller's struct does not have */
+    const size_t n = adam->struct_size < sizeof(a) ? adam->struct_size : sizeof(a);
+    memcpy(&a, adam, n);
+    a.struct_size = sizeof(a);
+    /* (a NaN fails every comparison) */
+    if (!(a.beta_1 >= 0.0f && a.beta_1 < 1.0f) || !(a.beta_2 >= 0.0f && a.beta_2 < 1.0f))
+      throw CaError(CA_ERR_ARG, "ca_fitter_set_adam: beta_1 and beta_2 must lie in [0, 1)");
+    if (!(a.epsilon > 0.0f) || a.epsilon == INFINITY) throw CaError(CA_ERR_ARG, "ca_fitter_set_adam: epsilon must be finite and > 0");
+    if (!(a.ema_momentum >= 0.0f && a.ema_momentum < 1.0f)) throw CaError(CA_ERR_ARG, "ca_fitter_set_adam: ema_momentum must lie in [0, 1)");
+    if (a.ema_overwrite_frequency < 0 || (a.ema_overwrite_frequency > 0 && !(a.ema_momentum > 0.0f)))
+      throw CaError(CA_ERR_ARG, "ca_fitter_set_adam: ema_overwrite_frequency must be >= 0, and > 0 only with ema_momentum > 0");
+    a.amsgrad = a.amsgrad != 0;
+    f->adam = a;
+  });
+}
+
+extern "C" int ca_fitter_get_adam(ca_fitter *f, ca_fit_adam *out) {
+  return co_guard(f, [&] {
+    if (!out || out->struct_size < sizeof(uint32_t)) throw CaError(CA_ERR_ARG, "ca_fitter_get_adam: null, or a struct_size below 4");
+    ca_fit_adam a = f->adam;
+    a.struct_size = (uint32_t)(out->struct_size < sizeof(a) ? out->struct_size : sizeof(a));
+    memcpy(out, &a, a.struct_size);
+  });
+}
+
+static void ft_check_slot(ca_fitter *f, int32_t which, const void *values, size_t n_floats) {
+  if (which != CA_SLOT_VHAT && which != CA_SLOT_AVERAGE) throw CaError(CA_ERR_ARG, "ca_fitter: the slot must be CA_SLOT_VHAT or CA_SLOT_AVERAGE");
+  if (!values) throw CaError(CA_ERR_ARG, "ca_fitter: null slot values");
+  f->check_n(n_floats);
+}
+
+extern "C" int ca_fitter_set_slot(ca_fitter *f, int32_t which, const float *values, size_t n_floats) {
+  return co_guard(f, [&] {
+    ft_check_slot(f, which, values, n_floats);
+    DevBuf<float> &b = which == CA_SLOT_VHAT ? f->vhat : f->avg;
+    if (!b.p) b.alloc(f->nw, f->s);
+    rt_h2d(b.p, values, f->nw * sizeof(float), f->s);
+    rt_sync(f->s);
+    if (which == CA_SLOT_AVERAGE) f->avg_valid = true;
+  });
+}
+
+extern "C" int ca_fitter_get_slot(ca_fitter *f, int32_t which, float *values, size_t n_floats) {
+  return co_guard(f, [&] {
+    ft_check_slot(f, which, values, n_floats);
+    if (which == CA_SLOT_AVERAGE) f->need_average("ca_fitter_get_slot");
+    const DevBuf<float> &b = which == CA_SLOT_VHAT ? f->vhat : f->avg;
+    if (!b.p) { /* a third slot that no step has used yet */
+      for (int i = 0; i < f->nw; ++i) values[i] = 0.0f;
+      return;
+    }
+    rt_d2h(values, b.p, f->nw * sizeof(float), f->s);
+    rt_sync(f->s);
+  });
+}
+
+extern "C" int ca_fitter_swap_average(ca_fitter *f) {
+  return co_guard(f, [&] {
+    f->need_average("ca_fitter_swap_average");
+    RT_LAUNCH(ft_k_average_swap, (f->nw + 255) / 256, 256, f->s, f->w.p, f->avg.p, f->nw);
+  });
+}
+
+extern "C" int ca_fitter_apply_average(ca_fitter *f) {
+  return co_guard(f, [&] {
+    f->need_average("ca_fitter_apply_average");
+    RT_LAUNCH(ft_k_average_apply, (f->nw + 255) / 256, 256, f->s, f->w.p, (const float *)f->avg.p, (const int32_t *)f->sidx.p,
+              f->nw);
   });
 }
 

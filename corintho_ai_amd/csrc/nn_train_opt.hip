@@ -124,18 +124,22 @@ __global__ __launch_bounds__(1024) void ft_k_opt_combine(const double *__restric
 }
 
 /* Steps 2 to 4 of piece blockIdx.x on g' in gsum: the clamp or the tensor's scale, the decay of the kernels
- * (decay = lr * weight_decay), Adam as ft_k_update has it, expression for expression; a moving statistic moves as there */
-__global__ __launch_bounds__(FT_PIECE) void ft_k_opt_update(const int4 *__restrict__ pieces, float *__restrict__ w,
-                                                           float *__restrict__ m, float *__restrict__ v,
-                                                           const float *__restrict__ gsum, const int32_t *__restrict__ sidx,
-                                                           const float *__restrict__ stat, const float *__restrict__ scale,
-                                                           float clipvalue, float decay, float lr_t) {
+ * (decay = lr * weight_decay), Adam as ft_k_update has it (ft_adam, nn_train.h); a moving statistic moves as there.
+ * PARAM: with Adam's arguments A, and a moving statistic's new value goes to the average as well. */
+template <bool PARAM>
+__device__ __forceinline__ void ft_opt_update_piece(const int4 *__restrict__ pieces, float *__restrict__ w,
+                                                    float *__restrict__ m, float *__restrict__ v,
+                                                    const float *__restrict__ gsum, const int32_t *__restrict__ sidx,
+                                                    const float *__restrict__ stat, const float *__restrict__ scale,
+                                                    float clipvalue, float decay, float lr_t, const FtAdamArgs &A) {
   const int4 pc = pieces[blockIdx.x];
   if ((int)threadIdx.x >= pc.y) return;
   const int i = pc.x + threadIdx.x;
   if (pc.w == CA_TENSOR_MOVING) {
     const float mv = w[i];
-    w[i] = mv - (mv - stat[sidx[i]]) * 0.01f;
+    const float nv = mv - (mv - stat[sidx[i]]) * 0.01f;
+    w[i] = nv;
+    if (PARAM && A.a) A.a[i] = nv;
     return;
   }
   float s = gsum[i];
@@ -145,11 +149,26 @@ __global__ __launch_bounds__(FT_PIECE) void ft_k_opt_update(const int4 *__restri
     s = s * scale[pc.z];
   float wv = w[i];
   if (decay > 0.0f && pc.w <= CA_TENSOR_HEAD_KERNEL) wv = wv - decay * wv;
-  const float mt = m[i] + (s - m[i]) * (1.0f - 0.9f);
-  const float vt = v[i] + (s * s - v[i]) * (1.0f - 0.999f);
-  m[i] = mt;
-  v[i] = vt;
-  w[i] = wv - lr_t * mt / (sqrtf(vt) + 1e-7f);
+  ft_adam<PARAM>(w, m, v, i, wv, s, lr_t, A);
+}
+
+/* the Adam defaults: the kernel of a step with fit options before Adam had arguments, instruction for instruction */
+__global__ __launch_bounds__(FT_PIECE) void ft_k_opt_update(const int4 *__restrict__ pieces, float *__restrict__ w,
+                                                           float *__restrict__ m, float *__restrict__ v,
+                                                           const float *__restrict__ gsum, const int32_t *__restrict__ sidx,
+                                                           const float *__restrict__ stat, const float *__restrict__ scale,
+                                                           float clipvalue, float decay, float lr_t) {
+  ft_opt_update_piece<false>(pieces, w, m, v, gsum, sidx, stat, scale, clipvalue, decay, lr_t, FtAdamArgs{});
+}
+
+__global__ __launch_bounds__(FT_PIECE) void ft_k_opt_update_adam(const int4 *__restrict__ pieces, float *__restrict__ w,
+                                                                float *__restrict__ m, float *__restrict__ v,
+                                                                const float *__restrict__ gsum,
+                                                                const int32_t *__restrict__ sidx,
+                                                                const float *__restrict__ stat,
+                                                                const float *__restrict__ scale, float clipvalue,
+                                                                float decay, float lr_t, FtAdamArgs A) {
+  ft_opt_update_piece<true>(pieces, w, m, v, gsum, sidx, stat, scale, clipvalue, decay, lr_t, A);
 }
 
 /* ------------------------------------------------------------------ host */
@@ -204,7 +223,7 @@ void FtOpt::regularization(rt_stream_t s, const float *w, int slot) {
 }
 
 void FtOpt::step(rt_stream_t s, float *w, float *m, float *v, float *gsum, const int32_t *sidx, const float *stat, float lr,
-                 float lr_t, int slot) {
+                 float lr_t, int slot, const FtAdamArgs *adam) {
   const int mode = o.clipvalue > 0.0f ? FT_OPT_MODE_VALUE : o.clipnorm > 0.0f ? FT_OPT_MODE_NORM
                  : o.global_clipnorm > 0.0f ? FT_OPT_MODE_GLOBAL : FT_OPT_MODE_NONE;
   const float clip = mode == FT_OPT_MODE_VALUE ? o.clipvalue : mode == FT_OPT_MODE_NORM ? o.clipnorm : o.global_clipnorm;
@@ -212,8 +231,12 @@ void FtOpt::step(rt_stream_t s, float *w, float *m, float *v, float *gsum, const
             2.0f * o.l2, ft_opt_reg_mask(o), o.clipvalue, 0, part.p);
   RT_LAUNCH(ft_k_opt_combine, 1, 1024, s, (const double *)part.p, (const int32_t *)tfirst.p, nt, mode, clip, scale.p,
             out.p + 4 + slot, (FtOptStats *)out.p);
-  RT_LAUNCH(ft_k_opt_update, npieces, FT_PIECE, s, (const int4 *)pieces.p, w, m, v, (const float *)gsum, sidx, stat,
-            (const float *)scale.p, o.clipvalue, lr * o.weight_decay, lr_t);
+  if (adam)
+    RT_LAUNCH(ft_k_opt_update_adam, npieces, FT_PIECE, s, (const int4 *)pieces.p, w, m, v, (const float *)gsum, sidx, stat,
+              (const float *)scale.p, o.clipvalue, lr * o.weight_decay, lr_t, *adam);
+  else
+    RT_LAUNCH(ft_k_opt_update, npieces, FT_PIECE, s, (const int4 *)pieces.p, w, m, v, (const float *)gsum, sidx, stat,
+              (const float *)scale.p, o.clipvalue, lr * o.weight_decay, lr_t);
 }
 
 void FtOpt::fetch(int n, rt_stream_t s) { rt_d2h(hout.data(), out.p, (4 + (size_t)n) * sizeof(double), s); }

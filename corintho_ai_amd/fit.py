@@ -47,6 +47,15 @@ clipnorm (per tensor), global_clipnorm: at most one.  Everything runs in the dev
 every option 0 a step is what it is without them, kernel for kernel and bit for bit.  fit_resident puts the fitter into
 the state its call asks for: options=None switches a Fitter's options off.  With an option on, `history` gains
 "regularization_loss", "grad_norm" (both means over the epoch's steps) and "clipped_steps", one entry per epoch.
+
+Adam's arguments (AdamOptions; include/corintho_hip.h "Adam's arguments" is the definition): beta_1, beta_2, epsilon,
+amsgrad (a third slot, "vhat") and averaged weights (Keras's use_ema, ema_momentum, ema_overwrite_frequency):
+    res = fit_resident(fitter, weights, adam=AdamOptions(beta_2=0.99, amsgrad=True, ema_momentum=0.99))
+adam=None means the defaults, and a fitter left with other values is set back.  With ema_momentum > 0 a fit is Keras 3's
+SwapEMAWeights(swap_on_epoch=True) plus the finalisation its fit() does: every epoch is judged by the averaged weights
+(swap, evaluate, swap back), so "val_loss", the best-epoch checkpoint and the plateau rule see those numbers and
+best_weights are the averaged weights of the best epoch; at the end the average is applied, so `weights` and the fitter
+hold it.  With every argument at its default a step is what it is without them, kernel for kernel and bit for bit.
 """
 import ctypes as C
 import inspect
@@ -131,6 +140,82 @@ class FitOptions:
         d = {k: float(getattr(self, k)) for k in OPTION_NAMES}
         d["regularize"] = int(self.regularize)
         return d
+
+
+ADAM_NAMES = ("beta_1", "beta_2", "epsilon", "amsgrad", "ema_momentum", "ema_overwrite_frequency")
+SLOTS = {"vhat": 0, "average": 1}  # CA_SLOT_VHAT, CA_SLOT_AVERAGE
+
+
+@dataclass(frozen=True)
+class AdamOptions:
+    """ca_fit_adam: the defaults are Keras Adam's.  The device takes the floats in float32."""
+    beta_1: float = 0.9
+    beta_2: float = 0.999
+    epsilon: float = 1e-7
+    amsgrad: bool = False
+    ema_momentum: float = 0.0    # 0: no averaged weights
+    ema_overwrite_frequency: int = 0
+
+    def check(self):
+        """ValueError unless the arguments are ones the device takes (judged in float32, as it does); returns self"""
+        for k in ("beta_1", "beta_2", "epsilon", "ema_momentum"):
+            x = getattr(self, k)
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.floating, np.integer)) or not np.isfinite(x):
+                raise ValueError("adam: %s must be a finite number, got %r" % (k, x))
+        with np.errstate(over="ignore", under="ignore"):
+            b1, b2, eps, mom = (np.float32(getattr(self, k)) for k in ("beta_1", "beta_2", "epsilon", "ema_momentum"))
+        for k, x in (("beta_1", b1), ("beta_2", b2), ("ema_momentum", mom)):
+            if not 0 <= x < 1:
+                raise ValueError("adam: %s must lie in [0, 1) in float32, got %r" % (k, getattr(self, k)))
+        if not (np.isfinite(eps) and eps > 0):
+            raise ValueError("adam: epsilon must be finite and > 0 in float32, got %r" % (self.epsilon,))
+        if not isinstance(self.amsgrad, (bool, np.bool_)) and self.amsgrad not in (0, 1):
+            raise ValueError("adam: amsgrad must be a bool, got %r" % (self.amsgrad,))
+        k = self.ema_overwrite_frequency
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 0 or k >= 2 ** 31:
+            raise ValueError("adam: ema_overwrite_frequency must be an integer >= 0, got %r" % (k,))
+        if k > 0 and not mom > 0:
+            raise ValueError("adam: ema_overwrite_frequency needs ema_momentum > 0")
+        return self
+
+    def is_default(self):
+        """is every argument at its default (in float32, as the device sees them)"""
+        d = AdamOptions()
+        return (all(np.float32(getattr(self, k)) == np.float32(getattr(d, k)) for k in ("beta_1", "beta_2", "epsilon"))
+                and not self.amsgrad and not self.averaged())
+
+    def averaged(self):
+        return bool(np.float32(self.ema_momentum) > 0)
+
+    def as_dict(self):
+        return {"beta_1": float(self.beta_1), "beta_2": float(self.beta_2), "epsilon": float(self.epsilon),
+                "amsgrad": bool(self.amsgrad), "ema_momentum": float(self.ema_momentum),
+                "ema_overwrite_frequency": int(self.ema_overwrite_frequency)}
+
+
+def _adam(adam):
+    """None or an AdamOptions (or a mapping of its fields), checked; None stays None"""
+    if adam is None:
+        return None
+    if isinstance(adam, dict):
+        unknown = sorted(set(adam) - set(ADAM_NAMES))
+        if unknown:
+            raise ValueError("adam: unknown %s" % ", ".join(unknown))
+        adam = AdamOptions(**adam)
+    if not isinstance(adam, AdamOptions):
+        raise ValueError("fit: adam must be an AdamOptions, a dict of its fields or None, got %r" % (adam,))
+    return adam.check()
+
+
+def _apply_adam(be, adam):
+    """as _apply_options: a backend that has set_adam gets the call's arguments (None: the defaults); one that has none
+    serves only a call that asks for the defaults.  Returns the AdamOptions if any is off its default, else None"""
+    on = adam is not None and not adam.is_default()
+    if inspect.getattr_static(be, "set_adam", None) is not None:
+        be.set_adam(adam if adam is not None else AdamOptions())
+    elif on:
+        raise ValueError("fit: the backend %s has no set_adam" % type(be).__name__)
+    return adam if on else None
 
 
 def _options(options):
@@ -323,6 +408,48 @@ class Fitter:
         return {"steps": int(c.steps), "clipped_steps": int(c.clipped_steps), "regularization_loss": float(c.regularization),
                 "grad_norm": float(c.grad_norm), "grad_norm_max": float(c.grad_norm_max)}
 
+    # ---- Adam's arguments, the third slot and the averaged weights (include/corintho_hip.h, "Adam's arguments") ----
+    def set_adam(self, adam=None):
+        """Adam's arguments of every later step (AdamOptions, or a dict of its fields); None: the defaults.  They stay
+        until set again."""
+        a = _adam(adam) or AdamOptions()
+        c = _lib.CaFitAdam(struct_size=C.sizeof(_lib.CaFitAdam), beta_1=float(np.float32(a.beta_1)),
+                           beta_2=float(np.float32(a.beta_2)), epsilon=float(np.float32(a.epsilon)),
+                           amsgrad=int(bool(a.amsgrad)), ema_momentum=float(np.float32(a.ema_momentum)),
+                           ema_overwrite_frequency=int(a.ema_overwrite_frequency))
+        self._check(self._L.ca_fitter_set_adam(self._h, C.byref(c)))
+
+    def get_adam(self):
+        c = _lib.CaFitAdam(struct_size=C.sizeof(_lib.CaFitAdam))
+        self._check(self._L.ca_fitter_get_adam(self._h, C.byref(c)))
+        return AdamOptions(beta_1=float(c.beta_1), beta_2=float(c.beta_2), epsilon=float(c.epsilon), amsgrad=bool(c.amsgrad),
+                           ema_momentum=float(c.ema_momentum), ema_overwrite_frequency=int(c.ema_overwrite_frequency))
+
+    @staticmethod
+    def _slot(which):
+        if which not in SLOTS:
+            raise ValueError('the slot must be "vhat" or "average", got %r' % (which,))
+        return SLOTS[which]
+
+    def set_slot(self, which, values):
+        """install AMSGrad's third slot ("vhat") or the averaged weights ("average", which makes the average valid)"""
+        a = _f32(values).ravel()
+        self._check(self._L.ca_fitter_set_slot(self._h, self._slot(which), _ptr(a), a.size))
+
+    def get_slot(self, which):
+        """"vhat": zeros if no step has used it; "average": an EngineError (CA_ERR_STATE) while there is none"""
+        a = np.zeros(self.num_weights, np.float32)
+        self._check(self._L.ca_fitter_get_slot(self._h, self._slot(which), _ptr(a), a.size))
+        return a
+
+    def swap_average(self):
+        """exchange the weights and the average (Keras's SwapEMAWeights)"""
+        self._check(self._L.ca_fitter_swap_average(self._h))
+
+    def apply_average(self):
+        """the trainable weights become the average (Keras's finalize_variable_values)"""
+        self._check(self._L.ca_fitter_apply_average(self._h))
+
     def tensor_table(self):
         """the device's table of the network's tensors: [(offset, floats, class)], class a name of nets.TENSOR_CLASSES;
         nets.tensor_table(name) is the same with the tensors' names"""
@@ -367,6 +494,10 @@ class FitResult:
     optimizer: tuple
     learning_rate: float          # after the last epoch's ReduceLROnPlateau
     history: dict = field(default_factory=dict)  # one entry per epoch in each list
+    # the extra slots in use, by name ("vhat" with amsgrad, "average" with ema_momentum > 0): of the best epoch and after
+    # the last one.  None when Adam's arguments ask for neither.
+    best_slots: dict = None
+    slots: dict = None
 
 
 HISTORY_KEYS = ("loss", "value_loss", "policy_loss", "val_loss", "val_value_loss", "val_policy_loss", "lr")
@@ -381,9 +512,19 @@ def epoch_order(rng, n_train, shuffle):
     return rng.permutation(n_train).astype(np.int32) if shuffle else np.arange(n_train, dtype=np.int32)
 
 
-def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed, stats=False):
+def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed, stats=False,
+            adam=None):
     """the epochs of model.fit on the n rows the backend holds, rows [0, split_at) training; the callbacks' logic.
-    stats: an option is on, the backend's train_stats() of every epoch go to the history"""
+    stats: an option is on, the backend's train_stats() of every epoch go to the history.
+    adam: the call's AdamOptions if any is off its default.  With ema_momentum > 0 this is Keras 3's
+    SwapEMAWeights(swap_on_epoch=True) plus the finalisation fit() does: an epoch is judged by the averaged weights (swap,
+    evaluate, swap back), the checkpoint holds them, and at the end the average is applied to the weights."""
+    averaged = adam is not None and adam.averaged()
+    names = (("vhat",) if adam is not None and adam.amsgrad else ()) + (("average",) if averaged else ())
+
+    def slots():
+        return {k: be.get_slot(k) for k in names} if names else None
+
     rng = np.random.default_rng(seed)
     lr = np.float32(learning_rate)
     history = {k: [] for k in HISTORY_KEYS + (OPTION_HISTORY_KEYS if stats else ())}
@@ -396,13 +537,18 @@ def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_
             st = be.train_stats()
             for k in OPTION_HISTORY_KEYS:
                 history[k].append(st[k])
+        if averaged:
+            be.swap_average()
         val = be.evaluate(split_at, n - split_at, batch_size)
+        judged = be.get_weights() if averaged and val[0] < ckpt_best else None
+        if averaged:
+            be.swap_average()
         for k, x in zip(HISTORY_KEYS, tuple(loss) + tuple(val) + (lr,)):
             history[k].append(float(x))
         val_loss = val[0]
         if val_loss < ckpt_best:  # ModelCheckpoint(save_best_only=True): np.less
             ckpt_best = val_loss
-            best = (be.get_weights(), be.get_optimizer(), epoch)
+            best = (judged if averaged else be.get_weights(), be.get_optimizer(), epoch, slots())
         if val_loss < plateau_best - MIN_DELTA:  # ReduceLROnPlateau, mode "min"
             plateau_best, wait = val_loss, 0
         else:
@@ -412,8 +558,11 @@ def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_
                 wait = 0
     if best is None:  # every val_loss NaN: Keras saves nothing either; report the starting point
         raise FloatingPointError("fit: no epoch produced a finite val_loss")
+    if averaged:
+        be.apply_average()
     return FitResult(best_weights=best[0], best_optimizer=best[1], best_epoch=best[2], weights=be.get_weights(),
-                     optimizer=be.get_optimizer(), learning_rate=float(lr), history=history)
+                     optimizer=be.get_optimizer(), learning_rate=float(lr), history=history, best_slots=best[3],
+                     slots=slots())
 
 
 def _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_factor, patience):
@@ -428,14 +577,16 @@ def _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_
 
 
 def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epochs=1, validation_split=0.3, shuffle=True,
-                 anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, options=None):
+                 anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, options=None, adam=None, slots=None):
     """fit() on whatever data set `fitter` holds -- packed (add_samples, add_device_samples, add_trainer_samples) or
     expanded (set_data) -- without touching it: the rows are data_info()'s, the split, the permutations, the checkpoint
     and the plateau logic are fit()'s, and so is the FitResult.  On a packed set of n samples the rows are the 8 n
     virtual rows, so the result equals fit() on expand_samples of the same samples to the bit.  batch_size may not
     exceed the fitter's max_batch.  options: a FitOptions; None: no option, and a fitter that has options is set to all
-    off -- the call decides, not what the fitter was left with."""
-    opts = _options(options)
+    off -- the call decides, not what the fitter was left with.  adam: an AdamOptions; None: the defaults, decided by the
+    call in the same way.  slots: {"vhat": ..., "average": ...} to resume from (a FitResult's slots), installed after the
+    optimizer state; None starts vhat from zeros and the average from `weights`."""
+    opts, adam = _options(options), _adam(adam)
     w = _f32(weights).ravel()
     num_weights = getattr(fitter, "num_weights", w.size)
     if w.size != num_weights:
@@ -452,9 +603,11 @@ def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epoch
     else:
         m, v, it = optimizer_state
         fitter.set_optimizer(m, v, it)
+    for k in sorted(slots or {}):
+        fitter.set_slot(k, slots[k])
     stats = _apply_options(fitter, opts)
     return _epochs(fitter, n, split_at, learning_rate, int(batch_size), int(epochs), shuffle, anneal_factor, patience,
-                   seed, stats)
+                   seed, stats, _apply_adam(fitter, adam))
 
 
 def fit_samples(weights, state_policy, outcome, *, batch_size=2048, device=0, net=NET_MLP12X100, sample_weight=None,
@@ -520,6 +673,7 @@ def _fit_added(add, weights, batch_size, device, net, backend, kw):
     _check_fit_args(a["learning_rate"], a["batch_size"], a["epochs"], a["validation_split"], a["anneal_factor"],
                     a["patience"])
     _options(a["options"])
+    _adam(a["adam"])
     own = backend is None
     be = Fitter(max_batch=int(batch_size), device=device, net=net) if own else backend
     try:
@@ -533,14 +687,15 @@ def _fit_added(add, weights, batch_size, device, net, backend, kw):
 
 def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, batch_size=2048, epochs=1,
         validation_split=0.3, shuffle=True, anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, device=0,
-        net=NET_MLP12X100, sample_weight=None, options=None, _backend=None):
+        net=NET_MLP12X100, sample_weight=None, options=None, adam=None, _backend=None):
     """main.pyx:249-260 `model.fit(...)` with its callbacks; see the module docstring.  Returns a FitResult.
     optimizer_state: (m, v, iterations) to resume from; None starts Adam from zeros, as a freshly compiled model.
     net: NET_MLP12X100 or NET_RESCNN4, the network `weights` belong to.
     sample_weight: one weight per row, Keras's model.fit(sample_weight=...): a batch's losses are (1/B) sum w_r loss_r,
     in training and in validation; None fits unweighted.
-    options: a FitOptions (the module docstring); None: none."""
-    opts = _options(options)
+    options: a FitOptions (the module docstring); None: none.
+    adam: an AdamOptions (the module docstring); None: Adam's defaults."""
+    opts, adam = _options(options), _adam(adam)
     name, num_weights = net_info(net)
     w = _f32(weights).ravel()
     if w.size != num_weights:
@@ -574,7 +729,8 @@ def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, 
         if sw is not None:
             be.set_sample_weights(sw)
         stats = _apply_options(be, opts)
-        return _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed, stats)
+        return _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed, stats,
+                       _apply_adam(be, adam))
     finally:
         if own:
             be.close()

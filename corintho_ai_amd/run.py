@@ -44,7 +44,7 @@ import numpy as np
 
 from . import _lib, nets, samples_io
 from . import trainer as _trainer
-from .fit import OPTION_HISTORY_KEYS, FitOptions, Fitter, fit_resident, net_info
+from .fit import OPTION_HISTORY_KEYS, AdamOptions, FitOptions, Fitter, fit_resident, net_info
 
 NETS = {"mlp12x100": (_trainer.NET_MLP12X100, nets.init_mlp12x100), "rescnn4": (_trainer.NET_RESCNN4, nets.init_rescnn4)}
 # the network kind self-play and arena evaluate with: (net, arith) -> Trainer.set_net's kind
@@ -99,6 +99,13 @@ class RunParams:
     clipvalue: float = 0.0
     clipnorm: float = 0.0
     global_clipnorm: float = 0.0
+    # Adam's arguments (fit.AdamOptions; include/corintho_hip.h "Adam's arguments"); `epsilon` is the search's noise weight
+    beta_1: float = 0.9
+    beta_2: float = 0.999
+    adam_epsilon: float = 1e-7
+    amsgrad: bool = False
+    ema_momentum: float = 0.0    # > 0: the fit judges and hands on averaged weights
+    ema_overwrite_frequency: int = 0
 
     def __post_init__(self):
         for f in dataclasses.fields(self):  # a TOML or command-line value may come as the other number type
@@ -132,12 +139,19 @@ class RunParams:
             raise ValueError("seed must not be negative")
         self.mix_old, self.zip_logs = bool(self.mix_old), bool(self.zip_logs)
         self.merge_duplicates = bool(self.merge_duplicates)
+        self.amsgrad = bool(self.amsgrad)
         self.fit_options()  # ValueError: a negative value, two clip modes
+        self.adam_options()  # ValueError: a beta outside [0, 1), ...
 
     def fit_options(self):
         """the fit options of the run as a fit.FitOptions, checked"""
         return FitOptions(l1=self.l1, l2=self.l2, regularize=self.regularize, weight_decay=self.weight_decay,
                           clipvalue=self.clipvalue, clipnorm=self.clipnorm, global_clipnorm=self.global_clipnorm).check()
+
+    def adam_options(self):
+        """Adam's arguments of the run as a fit.AdamOptions, checked"""
+        return AdamOptions(beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.adam_epsilon, amsgrad=self.amsgrad,
+                           ema_momentum=self.ema_momentum, ema_overwrite_frequency=self.ema_overwrite_frequency).check()
 
     def as_dict(self):
         d = {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
@@ -177,11 +191,15 @@ def _read_text(path):
         return f.read().strip()
 
 
-def save_model(path, weights, optimizer, net):
+def save_model(path, weights, optimizer, net, slots=None):
+    """slots: {"vhat": ..., "average": ...} (a FitResult's best_slots), written as adam_vhat and adam_average; None or
+    empty: the file is what it is without them"""
     m, v, it = optimizer
-    samples_io.write_npz(path, {"weights": np.asarray(weights, np.float32), "adam_m": np.asarray(m, np.float32),
-                                "adam_v": np.asarray(v, np.float32), "adam_iterations": np.asarray(it, np.int64),
-                                "net": np.asarray(net)})
+    arrays = {"weights": np.asarray(weights, np.float32), "adam_m": np.asarray(m, np.float32),
+              "adam_v": np.asarray(v, np.float32), "adam_iterations": np.asarray(it, np.int64), "net": np.asarray(net)}
+    for k in sorted(slots or {}):
+        arrays["adam_" + k] = np.asarray(slots[k], np.float32)
+    samples_io.write_npz(path, arrays)
 
 
 def load_model(path, net=None):
@@ -190,6 +208,12 @@ def load_model(path, net=None):
         if net is not None and str(z["net"]) != net:
             raise ValueError("%s holds a %s, the run is asked for a %s" % (path, z["net"], net))
         return z["weights"], (z["adam_m"], z["adam_v"], int(z["adam_iterations"]))
+
+
+def load_model_slots(path):
+    """the extra slots of a generation's model.npz: {"vhat": ..., "average": ...} with the ones it holds, {} if none"""
+    with np.load(path) as z:
+        return {k: z["adam_" + k] for k in ("vhat", "average") if "adam_" + k in z.files}
 
 
 def format_time(t):
@@ -352,20 +376,28 @@ def train_generation(params, state, *, _cdll=None, _fitter=None, _hook=None):
     # fit (main.pyx:221-272): the current generation's model, not the best one's, with its Adam state
     t0 = time.perf_counter()
     cur_weights, cur_optimizer = load_model(state["cur_gen_location"], p.net)
-    options = p.fit_options()
+    options, adam = p.fit_options(), p.adam_options()
+    # the slots the model was saved with, as far as this generation's Adam uses them
+    slots = {k: a for k, a in load_model_slots(state["cur_gen_location"]).items()
+             if (k == "vhat" and adam.amsgrad) or (k == "average" and adam.averaged())}
     res = fit_resident(_fitter, cur_weights, learning_rate=state["learning_rate"], batch_size=p.batch_size,
                             epochs=p.epochs, validation_split=VALIDATION_SPLIT, anneal_factor=p.anneal_factor,
                             patience=p.patience, seed=seeds["fit"], optimizer_state=cur_optimizer,
-                            options=options if options.any() else None)
-    save_model(state["new_model_location"], res.best_weights, res.best_optimizer, p.net)  # ModelCheckpoint
+                            options=options if options.any() else None, adam=None if adam.is_default() else adam,
+                            slots=slots or None)
+    save_model(state["new_model_location"], res.best_weights, res.best_optimizer, p.net, res.best_slots)  # ModelCheckpoint
     times["fit"] = time.perf_counter() - t0
     log = state["train_log_folder"]
     rows = ["\t".join(("epoch",) + LOSS_COLUMNS)]
     for e in range(len(res.history["val_loss"])):
         rows.append("\t".join([str(e)] + [repr(res.history[k][e]) for k in LOSS_COLUMNS]))
     _write_text(os.path.join(log, "train_loss.csv"), "\n".join(rows) + "\n")
-    if options.any():  # nothing in it is a time or a path: a generation played again writes the same bytes
-        described = {"options": options.as_dict(), "epochs": {k: res.history[k] for k in OPTION_HISTORY_KEYS}}
+    if options.any() or not adam.is_default():  # nothing in it is a time or a path: a generation played again writes the same bytes
+        described = {"options": options.as_dict()}
+        if options.any():
+            described["epochs"] = {k: res.history[k] for k in OPTION_HISTORY_KEYS}
+        if not adam.is_default():
+            described["adam"] = adam.as_dict()
         _write_text(os.path.join(log, "fit_options.json"), json.dumps(described, indent=4, sort_keys=True) + "\n")
     n = max(1, num_samples)
     _write_text(os.path.join(log, "fit_time.txt"),  # main.pyx:261-270
@@ -620,6 +652,10 @@ def _parser():
         "clipvalue": "Clip every gradient entry of the fit to [-c, c]",
         "clipnorm": "Clip every tensor's gradient of the fit to this norm",
         "global_clipnorm": "Clip the fit's whole gradient to this norm",
+        "beta_1": "beta_1 of the fit's Adam", "beta_2": "beta_2 of the fit's Adam",
+        "adam_epsilon": "epsilon of the fit's Adam",
+        "ema_momentum": "Momentum of the fit's averaged weights (Keras use_ema); 0: none",
+        "ema_overwrite_frequency": "Every this many steps the weights become the average; 0: never",
     }
     for f in dataclasses.fields(RunParams):
         if f.name in ("mix_old", "zip_logs"):
@@ -627,6 +663,8 @@ def _parser():
         elif f.name == "merge_duplicates":
             ap.add_argument("--merge-duplicates", "--merge_duplicates", dest="merge_duplicates", action="store_true",
                             default=False, help="Merge duplicate positions of the fit's samples into weighted ones")
+        elif f.name == "amsgrad":
+            ap.add_argument("--amsgrad", action="store_true", default=False, help="AMSGrad variant of the fit's Adam")
         elif f.name in ("seed", "init_weights"):
             ap.add_argument("--" + f.name, type=int if f.name == "seed" else str, default=None, help=helps[f.name])
         else:

@@ -552,7 +552,8 @@ int ca_fitter_merge_duplicates(ca_fitter *f, int normalize, int32_t *before, int
  *                    not treated specially.
  *   3. decay         decoupled (Keras Adam(weight_decay=), biases, gamma and beta excluded): on every kernel, trunk and
  *                    head, w' = w - (lr weight_decay) w -- the multiplier is lr, not Adam's lr_t; elsewhere w' = w.
- *   4. Adam          as without options, on g'' from w'; the moving statistics move as without options.
+ *   4. Adam          as defined under "Adam's arguments" below, on g'' from w'; the moving statistics move as without
+ *                    options.
  *   5. loss          total = value + 0.25 policy + R(w), R = l1 sum |w_i| + l2 sum w_i^2 over the regularised tensors:
  *                    in ca_fitter_train (out_losses[0]; batch_losses[][0] with the w from before that batch's step) and in
  *                    ca_fitter_evaluate, as Keras adds layer losses to loss and val_loss.  out_losses[1] and [2] do
@@ -594,6 +595,57 @@ int ca_fitter_train_stats(ca_fitter *f, ca_fit_stats *out);
 /* the network's tensors in the order of the weight vector: out[k] = {offset, floats, class} of the first
  * min(cap, *count) of them; *count = how many there are (out may be null with cap 0) */
 int ca_fitter_tensor_table(ca_fitter *f, int32_t *out /* [cap][3] */, int32_t cap, int32_t *count);
+
+/* ---- Adam's arguments: beta_1, beta_2, epsilon, AMSGrad and averaged weights, on the device ----
+ * What Keras's Adam(beta_1=, beta_2=, epsilon=, amsgrad=, use_ema=, ema_momentum=, ema_overwrite_frequency=) takes.
+ * This comment is the definition.
+ *
+ * One step at learning rate lr for trainable weight i.  g'' and w' are what the fit options' steps 1 to 3 leave; without
+ * options they are the summed gradient g of ca_fitter_gradients and w.  Everything is float32, in this operation order,
+ * without contraction:
+ *     t     = float(iterations + 1)
+ *     lr_t  = lr * (sqrtf(1 - powf(beta_2, t)) / (1 - powf(beta_1, t)))      on the host
+ *     m'    = m + (g'' - m) * (1.0f - beta_1)
+ *     v'    = v + (g''*g'' - v) * (1.0f - beta_2)
+ *     d     = amsgrad ? (h' = max(h, v')) : v'                               h: the third slot, "vhat"
+ *     w''   = w' - lr_t * m' / (sqrtf(d) + epsilon)
+ *     a'    = a + (w'' - a) * (1.0f - ema_momentum)                          only with ema_momentum > 0; a: the average
+ *     w'''  = a'   if ema_overwrite_frequency = k > 0 and (iterations + 1) % k == 0, else w''
+ * A moving statistic moves as without these arguments, and its entry of a is rewritten with its new value at every step
+ * that averages, so the average is always a complete, usable weight vector.  m, v and h are 0 at moving statistics.
+ * Step 4 of the fit options ("Adam as without options") is this Adam.
+ *
+ * State.  h is 0 on a new fitter and after every ca_fitter_set_optimizer.  The average is INVALID on a new fitter and
+ * after every ca_fitter_set_weights; the first step with ema_momentum > 0 that finds it invalid first copies the
+ * pre-step weights into it; installing one with ca_fitter_set_slot makes it valid.  Neither slot occupies device memory
+ * before its first use.  With every argument at its default a step launches the kernels it launches without this
+ * section and produces the same bytes. */
+typedef struct ca_fit_adam {
+  uint32_t struct_size; /* as ca_fit_options': min(struct_size, the library's sizeof) bytes are read and written */
+  float beta_1, beta_2; /* in [0, 1); 0 is a legal value, so the defaults are NOT zeros: use CA_FIT_ADAM_INIT */
+  float epsilon;        /* finite and > 0 */
+  int32_t amsgrad;      /* 0 or not 0 */
+  float ema_momentum;   /* in [0, 1); 0: no averaging */
+  int32_t ema_overwrite_frequency; /* k >= 0; k > 0 needs ema_momentum > 0 */
+} ca_fit_adam;
+/* the Adam defaults: what a new fitter has, and what a caller's shorter struct leaves to the library */
+#define CA_FIT_ADAM_INIT {sizeof(ca_fit_adam), 0.9f, 0.999f, 1e-7f, 0, 0.0f, 0}
+#define CA_SLOT_VHAT 0
+#define CA_SLOT_AVERAGE 1
+/* CA_ERR_ARG and nothing changes unless, judged in float32: 0 <= beta_1 < 1, 0 <= beta_2 < 1, epsilon finite and > 0,
+ * 0 <= ema_momentum < 1, ema_overwrite_frequency >= 0 and > 0 only with ema_momentum > 0 (and struct_size >= 4).  The
+ * values stay, as the options do, until they are set again. */
+int ca_fitter_set_adam(ca_fitter *f, const ca_fit_adam *adam);
+/* out->struct_size must be set by the caller; on return it is the number of bytes written */
+int ca_fitter_get_adam(ca_fitter *f, ca_fit_adam *out);
+/* which: CA_SLOT_VHAT or CA_SLOT_AVERAGE, n_floats the fitter's weight count: else CA_ERR_ARG and nothing changes.  A
+ * vhat that was never used reads as zeros; an invalid average gives CA_ERR_STATE. */
+int ca_fitter_set_slot(ca_fitter *f, int32_t which, const float *values, size_t n_floats);
+int ca_fitter_get_slot(ca_fitter *f, int32_t which, float *values, size_t n_floats);
+/* exchanges w and a, every entry.  CA_ERR_STATE and nothing changes if the average is invalid. */
+int ca_fitter_swap_average(ca_fitter *f);
+/* w := a on the trainable weights (Keras's finalize_variable_values); CA_ERR_STATE if the average is invalid */
+int ca_fitter_apply_average(ca_fitter *f);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,11 @@ Fitter.add_trainer_samples (packed device to device) into an emptied fitter and 
 (include/corintho_hip.h, "fit options") of the HIP step and of the packed one; the result then carries the options and
 the last call's train_stats.  All 0 (the default): the step without them, and no option entry point is called.
 
+--adam default | on: Adam's arguments (include/corintho_hip.h, "Adam's arguments") of the HIP step and of the packed one.
+`default` sets the fitter to the Adam defaults through set_adam, which must cost nothing: the step runs the kernels that
+know of no arguments.  `on` switches AMSGrad and averaged weights (ema_momentum 0.99) on: the parametrised update kernel
+with its third slot and the average.  Not given: no Adam entry point is called (an earlier build has none).
+
     python tools/fit_bench.py --torch [--net rescnn4] [--rows 1000000 --batch 2048 --steps 200 --reps 3] [--out file.json]
     python tools/fit_bench.py --packed [--net rescnn4]
     python tools/fit_bench.py --handoff [--games 4096 --sims 400]
@@ -41,7 +46,7 @@ sys.path.insert(0, ROOT)
 
 from corintho_ai_amd import nets  # noqa: E402
 from corintho_ai_amd import NET_MLP12X100, NET_RESCNN4  # noqa: E402
-from corintho_ai_amd.fit import OPTION_NAMES, FitOptions, Fitter  # noqa: E402
+from corintho_ai_amd.fit import OPTION_NAMES, AdamOptions, FitOptions, Fitter  # noqa: E402
 
 FLOP_PER_ROW_STEP = {"mlp12x100": 3 * 2.0 * (70 * 100 + 11 * 100 * 100 + 100 * 97),
                      "rescnn4": 3 * nets.rescnn4_flop_per_row()}
@@ -244,7 +249,10 @@ def main():
     for name in OPTION_NAMES:  # the fit options (fit.FitOptions); all 0: the step without them
         ap.add_argument("--" + name, type=float, default=0.0)
     ap.add_argument("--regularize", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--adam", choices=("default", "on"), default=None,
+                    help="set Adam's arguments: the defaults, or AMSGrad and averaged weights on")
     a = ap.parse_args()
+    adam = {None: None, "default": AdamOptions(), "on": AdamOptions(amsgrad=True, ema_momentum=0.99)}[a.adam]
     options = FitOptions(regularize=a.regularize, **{k: getattr(a, k) for k in OPTION_NAMES}).check()
     if a.handoff:
         emit(handoff(a), a.out)
@@ -272,6 +280,8 @@ def main():
     f.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
     if options.any():  # (asked only then: an earlier build of the library has no options)
         f.set_options(options)
+    if adam is not None:  # (likewise)
+        f.set_adam(adam)
     f.train(order[:a.warmup * a.batch], a.batch, 1e-3)
     if ts:
         for i in range(a.warmup):
@@ -286,6 +296,8 @@ def main():
         fp.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
         if options.any():
             fp.set_options(options)
+        if adam is not None:
+            fp.set_adam(adam)
         fp.train(order[:a.warmup * a.batch], a.batch, 1e-3)
     hip, tor, pak = [], [], []
     timed = order[a.warmup * a.batch:]
@@ -321,6 +333,8 @@ def main():
     if stats:
         out["options"] = options.as_dict()
         out["train_stats"] = stats
+    if adam is not None:
+        out["adam"] = adam.as_dict()
     if tor:
         out["torch"] = rec(tor)
         out["hip_speedup_over_torch"] = min(tor) / min(hip)
