@@ -4,7 +4,8 @@ from .trainer import (NET_MLP12X100, NET_MLP12X100_H3, NET_MLP12X100_X3, NET_MLP
                       NET_RESCNN4_H3, NET_RESCNN4_X3, NET_RESCNN4_X6, Trainer, expand_samples)
 from .tourney import Tourney  # noqa: F401
 from .net import Net, NetGroup  # noqa: F401
-from .fit import AdamOptions, FitOptions, FitResult, Fitter, fit, fit_resident, fit_samples, fit_trainer  # noqa: F401,E402
+from .fit import (AdamOptions, FitOptions, FitResult, Fitter, LossOptions, fit, fit_resident, fit_samples,  # noqa: F401,E402
+                  fit_trainer)
 
 
 def __getattr__(name):

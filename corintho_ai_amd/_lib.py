@@ -101,6 +101,35 @@ class CaFitAdam(C.Structure):
     ]
 
 
+class CaFitLoss(C.Structure):
+    """ca_fit_loss (include/corintho_hip.h, "loss and metrics"); the defaults are not zeros: fit.LossOptions has them"""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("value_weight", C.c_float),
+        ("policy_weight", C.c_float),
+        ("label_smoothing", C.c_float),
+        ("value_loss", C.c_int32),
+        ("huber_delta", C.c_float),
+    ]
+
+
+class CaFitMetrics(C.Structure):
+    """ca_fit_metrics"""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("top_k", C.c_int32),
+        ("rows", C.c_int64),
+        ("weight_sum", C.c_double),
+        ("categorical_accuracy", C.c_double),
+        ("top_k_categorical_accuracy", C.c_double),
+        ("mean_absolute_error", C.c_double),
+        ("policy_entropy", C.c_double),
+        ("target_entropy", C.c_double),
+    ]
+
+
 class CaFitStats(C.Structure):
     """ca_fit_stats"""
 
@@ -139,6 +168,7 @@ EXPORTS = [
     "ca_fitter_set_options", "ca_fitter_get_options", "ca_fitter_train_stats", "ca_fitter_tensor_table",
     "ca_fitter_set_adam", "ca_fitter_get_adam", "ca_fitter_set_slot", "ca_fitter_get_slot", "ca_fitter_swap_average",
     "ca_fitter_apply_average",
+    "ca_fitter_set_loss", "ca_fitter_get_loss", "ca_fitter_set_metrics", "ca_fitter_metrics", "ca_fitter_predict",
 ]
 # the caller-supplied network: an earlier build of the library has none of these
 NET_FN_EXPORTS = ["ca_trainer_request_rows", "ca_trainer_set_net_fn", "ca_tourney_set_net_fn", "ca_net_create", "ca_net_forward_device",
@@ -155,7 +185,10 @@ OPTION_EXPORTS = ["ca_fitter_set_options", "ca_fitter_get_options", "ca_fitter_t
 # Adam's arguments, the third slot and the averaged weights: likewise
 ADAM_EXPORTS = ["ca_fitter_set_adam", "ca_fitter_get_adam", "ca_fitter_set_slot", "ca_fitter_get_slot", "ca_fitter_swap_average",
                 "ca_fitter_apply_average"]
-assert set(NET_FN_EXPORTS + GROUP_EXPORTS + WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS + ADAM_EXPORTS) <= set(EXPORTS)
+# the loss options, the metrics and predict: likewise
+LOSS_EXPORTS = ["ca_fitter_set_loss", "ca_fitter_get_loss", "ca_fitter_set_metrics", "ca_fitter_metrics", "ca_fitter_predict"]
+assert set(NET_FN_EXPORTS + GROUP_EXPORTS + WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS + ADAM_EXPORTS
+           + LOSS_EXPORTS) <= set(EXPORTS)
 
 
 def declare(L):
@@ -250,7 +283,7 @@ def declare(L):
             continue
         if name in GROUP_EXPORTS and not group:
             continue
-        if name in WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS + ADAM_EXPORTS and not hasattr(L, name):
+        if name in WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS + ADAM_EXPORTS + LOSS_EXPORTS and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy", "ca_net_destroy",
@@ -295,6 +328,12 @@ def _declare_fitter(L, vp, f64p):
         L.ca_fitter_get_slot.argtypes = [vp, C.c_int32, f32p, C.c_size_t]
         L.ca_fitter_swap_average.argtypes = [vp]
         L.ca_fitter_apply_average.argtypes = [vp]
+    if hasattr(L, "ca_fitter_set_loss"):  # (likewise)
+        L.ca_fitter_set_loss.argtypes = [vp, C.POINTER(CaFitLoss)]
+        L.ca_fitter_get_loss.argtypes = [vp, C.POINTER(CaFitLoss)]
+        L.ca_fitter_set_metrics.argtypes = [vp, C.c_int32, C.c_int32]
+        L.ca_fitter_metrics.argtypes = [vp, C.POINTER(CaFitMetrics)]
+        L.ca_fitter_predict.argtypes = [vp, i32p, C.c_int32, C.c_int32, f32p, f32p]
 
 
 _lib = None

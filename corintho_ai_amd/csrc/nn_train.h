@@ -188,6 +188,20 @@ struct FtOpt {
   double R(int slot) const { return hout[4 + slot]; }
 };
 
+/* The loss off its defaults and the metrics (nn_train_loss.hip; the definition: corintho_hip.h, "loss and metrics").
+ * Both read a batch as ft_k_loss does: H[B][FT_PADW], the labels through rows[r], wts null on an unweighted set. */
+struct FtLossArgs {
+  float value_weight, policy_weight, label_smoothing, huber_delta;
+  int huber;
+};
+#define FT_METRIC_W 8 /* floats of a row's and of a batch's metric terms: the five sums of w x, the sum of w, two spare */
+/* ft_k_loss's work with the arguments L: Hd[B][FT_PADW], for ft_k_head_reduce as ft_k_loss leaves it */
+void ft_loss_opt(rt_stream_t s, const float *H, const int32_t *rows, int B, const float *evals, const float *probs,
+                 float *Hd, const float *wts, const FtLossArgs &L);
+/* the rows' metric terms to mrow[B][FT_METRIC_W], and their column sums in a fixed order to out[FT_METRIC_W] */
+void ft_metrics(rt_stream_t s, const float *H, const int32_t *rows, int B, const float *evals, const float *probs,
+                const float *wts, int top_k, float *mrow, float *out);
+
 /* kind: CA_NET_MLP12X100 or CA_NET_RESCNN4; the network's own buffers are sized for max_batch rows and cleared on s */
 FtNet *ft_net_create(int kind, int max_batch, rt_stream_t s);
 FtNet *ft_mlp_create(int max_batch, rt_stream_t s);

@@ -8,6 +8,8 @@
 //   forward     FtNet::forward: the batch's rows -> the heads' outputs H (96 logits and the value per row)
 //   loss        per row: (tanh v - z)^2, -sum t log_softmax, and their gradients (ft_k_loss);
 //               column sums of the head gradients and of the loss terms (ft_k_head_reduce)     2 launches
+//               (off the default loss ft_k_loss_opt in ft_k_loss's place; with metrics on two launches more, which
+//               read H and touch nothing a step uses: nn_train_loss.hip)
 //   backward    FtNet::backward: the weight gradient as partials, and how many of them a weight has
 //   update      sum of the split partials in a fixed order, Adam (TF ResourceApplyAdam) on kernels, biases,
 //               gamma and beta, moving statistics from the batch statistics (ft_k_update)      1 launch
@@ -309,6 +311,12 @@ struct ca_fitter {
   ca_fit_adam adam = CA_FIT_ADAM_INIT; /* Adam's arguments; at their defaults a step never looks at what follows */
   DevBuf<float> vhat, avg;             /* the third slot and the average: no memory before their first use */
   bool avg_valid = false;              /* until ca_fitter_set_weights */
+  ca_fit_loss lossopt = CA_FIT_LOSS_INIT; /* the loss; at its defaults a step launches ft_k_loss and no other loss kernel */
+  bool metrics_on = false;                /* ca_fitter_set_metrics; off: nothing below has memory */
+  int32_t top_k = 5;
+  DevBuf<float> mrow, metric; /* the metric terms of a batch's rows [max_batch][8]; the batches' sums [slots][8] */
+  std::vector<float> hmetric;
+  ca_fit_metrics lastm = {sizeof(ca_fit_metrics), 5, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; /* of the last train or evaluate */
 
   void init(int dev, int kind, int mb) {
     device = dev;
@@ -358,9 +366,22 @@ struct ca_fitter {
   }
   FtShared shared(const Batch &b) const { return FtShared{s, w.p, g.p, stat.p, h.p, hd.p, b.states}; }
 
+  /* is the loss the reference's value_mse + 0.25 policy_cce?  Then a step runs the kernels that know of no other. */
+  bool loss_default() const {
+    return lossopt.value_weight == 1.0f && lossopt.policy_weight == 0.25f && lossopt.label_smoothing == 0.0f &&
+           lossopt.value_loss == CA_VALUE_LOSS_MSE;
+  }
+  /* the batch's metric sums to metric.p[FT_METRIC_W * slot], from the H the loss kernel reads */
+  void metric_terms(const Batch &b, int B, int slot) {
+    ft_metrics(s, h.p, b.rows, B, b.evals, b.probs, b.wts, top_k, mrow.p, metric.p + (size_t)FT_METRIC_W * slot);
+  }
   /* loss terms of the batch (and the logit / value gradients in Hd); loss sums to loss.p[2 * slot] */
   void loss_terms(const Batch &b, int B, bool grads, int slot) {
-    if (b.wts)
+    if (!loss_default())
+      ft_loss_opt(s, h.p, b.rows, B, b.evals, b.probs, hd.p, b.wts,
+                  FtLossArgs{lossopt.value_weight, lossopt.policy_weight, lossopt.label_smoothing, lossopt.huber_delta,
+                             lossopt.value_loss == CA_VALUE_LOSS_HUBER});
+    else if (b.wts)
       RT_LAUNCH(ft_k_loss<true>, (B + 255) / 256, 256, s, (const float *)h.p, b.rows, B, b.evals, b.probs, hd.p, b.wts);
     else
       RT_LAUNCH(ft_k_loss<false>, (B + 255) / 256, 256, s, (const float *)h.p, b.rows, B, b.evals, b.probs, hd.p,
@@ -369,12 +390,14 @@ struct ca_fitter {
               net->policy_bias(), net->value_bias(), loss.p + 2 * slot);
   }
 
-  /* forward, loss (sums to slot) and backward of one batch: leaves the gradient partials and returns their counts */
-  FtSplits gradient(const int32_t *rows, int B, int slot) {
+  /* forward, loss (sums to slot) and backward of one batch: leaves the gradient partials and returns their counts.
+   * metrics: the batch's metric sums to slot as well */
+  FtSplits gradient(const int32_t *rows, int B, int slot, bool metrics = false) {
     const Batch b = batch(rows, B);
     const FtShared sh = shared(b);
     net->forward(sh, b.rows, B, true);
     loss_terms(b, B, true, slot);
+    if (metrics) metric_terms(b, B, slot);
     return net->backward(sh, B);
   }
 
@@ -535,20 +558,42 @@ struct ca_fitter {
       hloss.assign((size_t)2 * slots, 0.0f);
     }
   }
-  /* per-batch sums -> out[3] = {value + 0.25 policy, value, policy}, means weighted by batch size; per[3 * b] */
-  void losses(int nb, int32_t nr, int32_t batch, double *out, float *per) { losses(nb, nr, batch, out, per, 0); }
+  /* the metrics' buffers, for a call of `slots` batches */
+  void ensure_metrics(int slots) {
+    if (!mrow.p) mrow.alloc((size_t)max_batch * FT_METRIC_W, s);
+    if (hmetric.size() < (size_t)FT_METRIC_W * slots) {
+      metric.alloc((size_t)FT_METRIC_W * slots, s);
+      hmetric.assign((size_t)FT_METRIC_W * slots, 0.0f);
+    }
+  }
+  /* the call's metrics from its nb batches' sums, which losses() fetched: the batches added in float64 */
+  void metrics_of(int nb, int32_t nr) {
+    double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = 0; b < nb; ++b)
+      for (int k = 0; k < 6; ++k) sum[k] += (double)hmetric[(size_t)FT_METRIC_W * b + k];
+    const double ws = sum[5];
+    auto mean = [&](int k) { return ws > 0.0 ? sum[k] / ws : 0.0; };
+    lastm = ca_fit_metrics{sizeof(ca_fit_metrics), top_k, nr, ws, mean(0), mean(1), mean(2), mean(3), mean(4)};
+  }
+  /* per-batch sums -> out[3] = {value_weight value + policy_weight policy, value, policy}, means weighted by batch size;
+   * per[3 * b] */
+  void losses(int nb, int32_t nr, int32_t batch, double *out, float *per) { losses(nb, nr, batch, out, per, 0, false); }
   /* reg: with the regulariser's R added to the totals, 1: R of every batch (ca_fitter_train), 2: one R for all
-   * (ca_fitter_evaluate); the options' buffer comes back in the same synchronisation */
-  void losses(int nb, int32_t nr, int32_t batch, double *out, float *per, int reg) {
+   * (ca_fitter_evaluate); the options' buffer, and with `metrics` the batches' metric sums, come back in the same
+   * synchronisation */
+  void losses(int nb, int32_t nr, int32_t batch, double *out, float *per, int reg, bool metrics) {
     rt_d2h(hloss.data(), loss.p, (size_t)2 * nb * sizeof(float), s);
     if (reg) opt.fetch(reg == 1 ? nb : 1, s);
+    if (metrics) rt_d2h(hmetric.data(), metric.p, (size_t)FT_METRIC_W * nb * sizeof(float), s);
     rt_sync(s);
+    if (metrics) metrics_of(nb, nr);
+    const float vw = lossopt.value_weight, pw = lossopt.policy_weight; /* 1.0f * lv has the bits of lv */
     double sv = 0.0, sp = 0.0, sr = 0.0;
     for (int b = 0; b < nb; ++b) {
       const int rb = b * batch + batch <= nr ? batch : nr - b * batch;
       const float lv = hloss[2 * b] / (float)rb, lp = hloss[2 * b + 1] / (float)rb;
       if (per) {
-        per[3 * b] = reg ? lv + 0.25f * lp + (float)opt.R(reg == 1 ? b : 0) : lv + 0.25f * lp;
+        per[3 * b] = reg ? vw * lv + pw * lp + (float)opt.R(reg == 1 ? b : 0) : vw * lv + pw * lp;
         per[3 * b + 1] = lv;
         per[3 * b + 2] = lp;
       }
@@ -559,7 +604,7 @@ struct ca_fitter {
     if (out) {
       out[1] = nr ? sv / nr : 0.0;
       out[2] = nr ? sp / nr : 0.0;
-      out[0] = out[1] + 0.25 * out[2];
+      out[0] = (double)vw * out[1] + (double)pw * out[2];
       if (reg) out[0] += nr ? sr / nr : 0.0;
     }
   }
@@ -668,13 +713,14 @@ extern "C" int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows
     f->need_idx(n_rows);
     const int nb = (n_rows + batch - 1) / batch;
     f->ensure_loss(nb);
+    if (f->metrics_on) f->ensure_metrics(nb);
     rt_h2d(f->idx.p, rows, (size_t)n_rows * sizeof(int32_t), f->s);
     const bool options = f->opt.on(), adam_on = !f->adam_default();
     if (options) f->opt.begin(nb, f->s);
     f->last = ca_fit_stats{sizeof(ca_fit_stats), 0, 0, 0, 0.0, 0.0, 0.0};
     for (int b = 0; b < nb; ++b) {
       const int B = b * batch + batch <= n_rows ? batch : n_rows - b * batch;
-      const FtSplits ns = f->gradient(f->idx.p + (size_t)b * batch, B, b);
+      const FtSplits ns = f->gradient(f->idx.p + (size_t)b * batch, B, b, f->metrics_on);
       /* Keras Adam: local_step = iterations + 1, lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), in float32 */
       const float t = (float)(f->iterations + 1);
       const float lr_t = learning_rate * (sqrtf(1.0f - powf(f->adam.beta_2, t)) / (1.0f - powf(f->adam.beta_1, t)));
@@ -690,7 +736,7 @@ extern "C" int ca_fitter_train(ca_fitter *f, const int32_t *rows, int32_t n_rows
         f->update(ns, lr_t, true);
       f->iterations += 1;
     }
-    f->losses(nb, n_rows, batch, out_losses, batch_losses, options ? 1 : 0);
+    f->losses(nb, n_rows, batch, out_losses, batch_losses, options ? 1 : 0, f->metrics_on);
     if (options) { /* the statistics came back with the losses */
       const double *st = f->opt.hout.data();
       f->last.steps = nb;
@@ -713,6 +759,7 @@ extern "C" int ca_fitter_evaluate(ca_fitter *f, int32_t row0, int32_t n_rows, in
     for (int32_t i = 0; i < n_rows; ++i) rows[i] = row0 + i;
     const int nb = (n_rows + batch - 1) / batch;
     f->ensure_loss(nb);
+    if (f->metrics_on) f->ensure_metrics(nb);
     rt_h2d(f->idx.p, rows.data(), (size_t)n_rows * sizeof(int32_t), f->s);
     const bool reg = f->opt.on() && f->opt.regularized(); /* the weights do not move: one R for the call */
     if (reg) {
@@ -724,8 +771,9 @@ extern "C" int ca_fitter_evaluate(ca_fitter *f, int32_t row0, int32_t n_rows, in
       const ca_fitter::Batch bt = f->batch(f->idx.p + (size_t)b * batch, B);
       f->net->forward(f->shared(bt), bt.rows, B, false);
       f->loss_terms(bt, B, false, b);
+      if (f->metrics_on) f->metric_terms(bt, B, b);
     }
-    f->losses(nb, n_rows, batch, out_losses, nullptr, reg ? 2 : 0);
+    f->losses(nb, n_rows, batch, out_losses, nullptr, reg ? 2 : 0, f->metrics_on);
   });
 }
 
@@ -1016,6 +1064,78 @@ extern "C" int ca_fitter_apply_average(ca_fitter *f) {
     f->need_average("ca_fitter_apply_average");
     RT_LAUNCH(ft_k_average_apply, (f->nw + 255) / 256, 256, f->s, f->w.p, (const float *)f->avg.p, (const int32_t *)f->sidx.p,
               f->nw);
+  });
+}
+
+/* ------------------------------------------------------------------ loss, metrics, predict */
+extern "C" int ca_fitter_set_loss(ca_fitter *f, const ca_fit_loss *loss) {
+  return co_guard(f, [&] {
+    if (!loss || loss->struct_size < sizeof(uint32_t)) throw CaError(CA_ERR_ARG, "ca_fitter_set_loss: null, or a struct_size below 4");
+    ca_fit_loss l = CA_FIT_LOSS_INIT; /* the defaults for what the caller's struct does not have */
+    const size_t n = loss->struct_size < sizeof(l) ? loss->struct_size : sizeof(l);
+    memcpy(&l, loss, n);
+    l.struct_size = sizeof(l);
+    /* (a NaN fails every comparison) */
+    if (!(l.value_weight >= 0.0f) || l.value_weight == INFINITY || !(l.policy_weight >= 0.0f) || l.policy_weight == INFINITY)
+      throw CaError(CA_ERR_ARG, "ca_fitter_set_loss: value_weight and policy_weight must be finite and >= 0");
+    if (l.value_weight == 0.0f && l.policy_weight == 0.0f)
+      throw CaError(CA_ERR_ARG, "ca_fitter_set_loss: value_weight and policy_weight may not both be 0");
+    if (!(l.label_smoothing >= 0.0f && l.label_smoothing < 1.0f))
+      throw CaError(CA_ERR_ARG, "ca_fitter_set_loss: label_smoothing must lie in [0, 1)");
+    if (l.value_loss != CA_VALUE_LOSS_MSE && l.value_loss != CA_VALUE_LOSS_HUBER)
+      throw CaError(CA_ERR_ARG, "ca_fitter_set_loss: value_loss must be CA_VALUE_LOSS_MSE or CA_VALUE_LOSS_HUBER");
+    if (!(l.huber_delta > 0.0f) || l.huber_delta == INFINITY)
+      throw CaError(CA_ERR_ARG, "ca_fitter_set_loss: huber_delta must be finite and > 0");
+    f->lossopt = l;
+  });
+}
+
+extern "C" int ca_fitter_get_loss(ca_fitter *f, ca_fit_loss *out) {
+  return co_guard(f, [&] {
+    if (!out || out->struct_size < sizeof(uint32_t)) throw CaError(CA_ERR_ARG, "ca_fitter_get_loss: null, or a struct_size below 4");
+    ca_fit_loss l = f->lossopt;
+    l.struct_size = (uint32_t)(out->struct_size < sizeof(l) ? out->struct_size : sizeof(l));
+    memcpy(out, &l, l.struct_size);
+  });
+}
+
+extern "C" int ca_fitter_set_metrics(ca_fitter *f, int32_t on, int32_t top_k) {
+  return co_guard(f, [&] {
+    if (on && (top_k < 1 || top_k > CA_NUM_MOVES)) throw CaError(CA_ERR_ARG, "ca_fitter_set_metrics: top_k must be in 1..96");
+    if (on) f->top_k = top_k;
+    f->metrics_on = on != 0;
+    f->lastm = ca_fit_metrics{sizeof(ca_fit_metrics), f->top_k, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  });
+}
+
+extern "C" int ca_fitter_metrics(ca_fitter *f, ca_fit_metrics *out) {
+  return co_guard(f, [&] {
+    if (!out || out->struct_size < sizeof(uint32_t)) throw CaError(CA_ERR_ARG, "ca_fitter_metrics: null, or a struct_size below 4");
+    if (!f->metrics_on) throw CaError(CA_ERR_STATE, "ca_fitter_metrics: metrics are off (ca_fitter_set_metrics)");
+    ca_fit_metrics m = f->lastm;
+    m.struct_size = (uint32_t)(out->struct_size < sizeof(m) ? out->struct_size : sizeof(m));
+    memcpy(out, &m, m.struct_size);
+  });
+}
+
+extern "C" int ca_fitter_predict(ca_fitter *f, const int32_t *rows, int32_t n_rows, int32_t train, float *logits,
+                                 float *values) {
+  return co_guard(f, [&] {
+    f->need_data();
+    if (!rows || !logits || !values) throw CaError(CA_ERR_ARG, "ca_fitter_predict: null argument");
+    f->check_batch(n_rows);
+    f->check_rows(rows, n_rows);
+    f->need_idx(n_rows);
+    rt_h2d(f->idx.p, rows, (size_t)n_rows * sizeof(int32_t), f->s);
+    const ca_fitter::Batch bt = f->batch(f->idx.p, n_rows);
+    f->net->forward(f->shared(bt), bt.rows, n_rows, train != 0);
+    std::vector<float> hh((size_t)n_rows * FT_PADW);
+    rt_d2h(hh.data(), f->h.p, hh.size() * sizeof(float), f->s);
+    rt_sync(f->s);
+    for (int32_t r = 0; r < n_rows; ++r) {
+      memcpy(logits + (size_t)r * CA_NUM_MOVES, hh.data() + (size_t)r * FT_PADW, CA_NUM_MOVES * sizeof(float));
+      values[r] = hh[(size_t)r * FT_PADW + CA_NUM_MOVES];
+    }
   });
 }
 

@@ -56,6 +56,20 @@ SwapEMAWeights(swap_on_epoch=True) plus the finalisation its fit() does: every e
 (swap, evaluate, swap back), so "val_loss", the best-epoch checkpoint and the plateau rule see those numbers and
 best_weights are the averaged weights of the best epoch; at the end the average is applied, so `weights` and the fitter
 hold it.  With every argument at its default a step is what it is without them, kernel for kernel and bit for bit.
+
+The loss and the metrics (LossOptions; include/corintho_hip.h "loss and metrics" is the definition): the other half of
+the reference's model.compile() -- loss_weights, CategoricalCrossentropy(label_smoothing=), Huber(delta) on the value head
+and metrics=:
+    res = fit_resident(fitter, weights, loss=LossOptions(value_weight=0.7, policy_weight=1.3, label_smoothing=0.1,
+                                                         value_loss="huber", huber_delta=0.5), metrics={"top_k": 3})
+"loss" and "val_loss" are value_weight x value + policy_weight x policy (+ R), and the checkpoint and the plateau rule see
+them; "value_loss" and "policy_loss" stay the means of the two terms.  loss=None means the reference's loss, decided by
+the call.  With metrics the history gains METRIC_HISTORY_KEYS, one entry per epoch: how often the network's best move is
+the target's (and within its top k), the value head's mean absolute error, and the entropies of the policy and of its
+target -- during the epoch from each step's own forward, as Keras logs them, and "val_" + each from the validation pass
+(the averaged weights' with ema_momentum > 0).  They come from two launches on the head outputs a step already has;
+with metrics off nothing is launched, and on or off the losses and the weights of a fit are the same bytes.
+Fitter.predict(rows) reads the heads themselves.
 """
 import ctypes as C
 import inspect
@@ -218,6 +232,110 @@ def _apply_adam(be, adam):
     return adam if on else None
 
 
+LOSS_NAMES = ("value_weight", "policy_weight", "label_smoothing", "value_loss", "huber_delta")
+VALUE_LOSSES = {"mse": 0, "huber": 1}  # CA_VALUE_LOSS_MSE, CA_VALUE_LOSS_HUBER
+METRIC_NAMES = ("categorical_accuracy", "top_k_categorical_accuracy", "mean_absolute_error", "policy_entropy",
+                "target_entropy")  # ca_fit_metrics' fields, and the keys of Fitter.metrics()
+# what a fit's history calls them (Keras's names for a model whose outputs are "policy" and "value"), then their val_ forms
+METRIC_KEYS = ("policy_categorical_accuracy", "policy_top_k_categorical_accuracy", "value_mean_absolute_error",
+               "policy_entropy", "target_entropy")
+METRIC_HISTORY_KEYS = METRIC_KEYS + tuple("val_" + k for k in METRIC_KEYS)
+DEFAULT_TOP_K = 5
+
+
+@dataclass(frozen=True)
+class LossOptions:
+    """ca_fit_loss: the defaults are the reference's compile(): MSE + 0.25 x cross-entropy.  The device takes the floats
+    in float32."""
+    value_weight: float = 1.0
+    policy_weight: float = 0.25
+    label_smoothing: float = 0.0
+    value_loss: str = "mse"      # or "huber"
+    huber_delta: float = 1.0     # read only with "huber"
+
+    def check(self):
+        """ValueError unless the values are ones the device takes (judged in float32, as it does); returns self"""
+        for k in ("value_weight", "policy_weight", "label_smoothing", "huber_delta"):
+            x = getattr(self, k)
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.floating, np.integer)) or not np.isfinite(x):
+                raise ValueError("loss: %s must be a finite number, got %r" % (k, x))
+        with np.errstate(over="ignore", under="ignore"):
+            vw, pw, ls, delta = (np.float32(getattr(self, k)) for k in ("value_weight", "policy_weight", "label_smoothing",
+                                                                        "huber_delta"))
+        for k, x in (("value_weight", vw), ("policy_weight", pw)):
+            if not (np.isfinite(x) and x >= 0):
+                raise ValueError("loss: %s must be finite and >= 0 in float32, got %r" % (k, getattr(self, k)))
+        if vw == 0 and pw == 0:
+            raise ValueError("loss: value_weight and policy_weight may not both be 0 (in float32)")
+        if not 0 <= ls < 1:
+            raise ValueError("loss: label_smoothing must lie in [0, 1) in float32, got %r" % (self.label_smoothing,))
+        if not isinstance(self.value_loss, str) or self.value_loss not in VALUE_LOSSES:
+            raise ValueError('loss: value_loss must be "mse" or "huber", got %r' % (self.value_loss,))
+        if not (np.isfinite(delta) and delta > 0):
+            raise ValueError("loss: huber_delta must be finite and > 0 in float32, got %r" % (self.huber_delta,))
+        return self
+
+    def is_default(self):
+        """is the loss the reference's (in float32, as the device sees it; huber_delta is not read with "mse")"""
+        d = LossOptions()
+        return (all(np.float32(getattr(self, k)) == np.float32(getattr(d, k)) for k in ("value_weight", "policy_weight",
+                                                                                       "label_smoothing"))
+                and self.value_loss == "mse")
+
+    def as_dict(self):
+        return {"value_weight": float(self.value_weight), "policy_weight": float(self.policy_weight),
+                "label_smoothing": float(self.label_smoothing), "value_loss": str(self.value_loss),
+                "huber_delta": float(self.huber_delta)}
+
+
+def _loss(loss):
+    """None or a LossOptions (or a mapping of its fields), checked; None stays None"""
+    if loss is None:
+        return None
+    if isinstance(loss, dict):
+        unknown = sorted(set(loss) - set(LOSS_NAMES))
+        if unknown:
+            raise ValueError("loss: unknown %s" % ", ".join(unknown))
+        loss = LossOptions(**loss)
+    if not isinstance(loss, LossOptions):
+        raise ValueError("fit: loss must be a LossOptions, a dict of its fields or None, got %r" % (loss,))
+    return loss.check()
+
+
+def _top_k(metrics):
+    """the metrics argument of a fit -- False or None, True, or {"top_k": k} -- as None (off) or k"""
+    if metrics is None or metrics is False:
+        return None
+    if metrics is True:
+        return DEFAULT_TOP_K
+    if isinstance(metrics, dict):
+        unknown = sorted(set(metrics) - {"top_k"})
+        if unknown:
+            raise ValueError("metrics: unknown %s" % ", ".join(unknown))
+        k = metrics.get("top_k", DEFAULT_TOP_K)
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= NUM_MOVES:
+            raise ValueError("metrics: top_k must be an integer in 1..%d, got %r" % (NUM_MOVES, k))
+        return int(k)
+    raise ValueError('fit: metrics must be False, True or {"top_k": k}, got %r' % (metrics,))
+
+
+def _apply_loss(be, loss, top_k):
+    """as _apply_options: a backend that has set_loss / set_metrics gets what the call asks for (None: the default loss,
+    metrics off); one that has neither serves only a call that asks for the defaults.  Returns whether metrics are on"""
+    def has(name):
+        return inspect.getattr_static(be, name, None) is not None
+
+    if has("set_loss"):
+        be.set_loss(loss if loss is not None else LossOptions())
+    elif loss is not None and not loss.is_default():
+        raise ValueError("fit: the backend %s has no set_loss" % type(be).__name__)
+    if has("set_metrics"):
+        be.set_metrics(top_k is not None, top_k if top_k is not None else DEFAULT_TOP_K)
+    elif top_k is not None:
+        raise ValueError("fit: the backend %s has no set_metrics" % type(be).__name__)
+    return top_k is not None
+
+
 def _options(options):
     """None or a FitOptions (or a mapping of its fields), checked; None stays None"""
     if options is None:
@@ -247,7 +365,7 @@ def _apply_options(be, opts):
 
 class Fitter:
     """One device's fitter of mlp12x100 or rescnn4 (include/corintho_hip.h, "network training").  Losses come back as
-    (value + 0.25 policy, value, policy)."""
+    (value_weight value + policy_weight policy, value, policy): value + 0.25 policy unless set_loss says otherwise."""
 
     def __init__(self, max_batch=2048, device=0, net=NET_MLP12X100):
         self.net = net
@@ -450,6 +568,47 @@ class Fitter:
         """the trainable weights become the average (Keras's finalize_variable_values)"""
         self._check(self._L.ca_fitter_apply_average(self._h))
 
+    # ---- the loss, the metrics and predict (include/corintho_hip.h, "loss and metrics") ----
+    def set_loss(self, loss=None):
+        """the loss of every later step, evaluation and gradients() (LossOptions, or a dict of its fields); None: the
+        reference's value MSE + 0.25 policy cross-entropy.  It stays until set again."""
+        o = _loss(loss) or LossOptions()
+        c = _lib.CaFitLoss(struct_size=C.sizeof(_lib.CaFitLoss), value_weight=float(np.float32(o.value_weight)),
+                           policy_weight=float(np.float32(o.policy_weight)),
+                           label_smoothing=float(np.float32(o.label_smoothing)), value_loss=VALUE_LOSSES[o.value_loss],
+                           huber_delta=float(np.float32(o.huber_delta)))
+        self._check(self._L.ca_fitter_set_loss(self._h, C.byref(c)))
+
+    def get_loss(self):
+        c = _lib.CaFitLoss(struct_size=C.sizeof(_lib.CaFitLoss))
+        self._check(self._L.ca_fitter_get_loss(self._h, C.byref(c)))
+        name = {v: k for k, v in VALUE_LOSSES.items()}[int(c.value_loss)]
+        return LossOptions(value_weight=float(c.value_weight), policy_weight=float(c.policy_weight),
+                           label_smoothing=float(c.label_smoothing), value_loss=name, huber_delta=float(c.huber_delta))
+
+    def set_metrics(self, on=True, top_k=DEFAULT_TOP_K):
+        """switch the metrics of train() and evaluate() on or off; top_k in 1..96"""
+        self._check(self._L.ca_fitter_set_metrics(self._h, 1 if on else 0, int(top_k)))
+
+    def metrics(self):
+        """of the last train() or evaluate(): METRIC_NAMES' means weighted by the sample weights, and "rows",
+        "weight_sum" and "top_k"; an EngineError (CA_ERR_STATE) while metrics are off"""
+        c = _lib.CaFitMetrics(struct_size=C.sizeof(_lib.CaFitMetrics))
+        self._check(self._L.ca_fitter_metrics(self._h, C.byref(c)))
+        out = {k: float(getattr(c, k)) for k in METRIC_NAMES}
+        out.update(rows=int(c.rows), weight_sum=float(c.weight_sum), top_k=int(c.top_k))
+        return out
+
+    def predict(self, rows, train=False):
+        """Keras's predict: (logits [n, 96], values [n], pre-tanh) of at most max_batch rows.  train: the rows as one
+        training batch, with batch statistics.  Nothing of the fitter changes."""
+        r = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+        logits = np.zeros((r.size, NUM_MOVES), np.float32)
+        values = np.zeros(r.size, np.float32)
+        self._check(self._L.ca_fitter_predict(self._h, _ptr(r, C.c_int32), r.size, 1 if train else 0, _ptr(logits),
+                                              _ptr(values)))
+        return logits, values
+
     def tensor_table(self):
         """the device's table of the network's tensors: [(offset, floats, class)], class a name of nets.TENSOR_CLASSES;
         nets.tensor_table(name) is the same with the tensors' names"""
@@ -513,12 +672,13 @@ def epoch_order(rng, n_train, shuffle):
 
 
 def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed, stats=False,
-            adam=None):
+            adam=None, metrics=False):
     """the epochs of model.fit on the n rows the backend holds, rows [0, split_at) training; the callbacks' logic.
     stats: an option is on, the backend's train_stats() of every epoch go to the history.
     adam: the call's AdamOptions if any is off its default.  With ema_momentum > 0 this is Keras 3's
     SwapEMAWeights(swap_on_epoch=True) plus the finalisation fit() does: an epoch is judged by the averaged weights (swap,
-    evaluate, swap back), the checkpoint holds them, and at the end the average is applied to the weights."""
+    evaluate, swap back), the checkpoint holds them, and at the end the average is applied to the weights.
+    metrics: the backend's metrics() of every epoch's train() and evaluate() go to the history (METRIC_HISTORY_KEYS)."""
     averaged = adam is not None and adam.averaged()
     names = (("vhat",) if adam is not None and adam.amsgrad else ()) + (("average",) if averaged else ())
 
@@ -527,12 +687,16 @@ def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_
 
     rng = np.random.default_rng(seed)
     lr = np.float32(learning_rate)
-    history = {k: [] for k in HISTORY_KEYS + (OPTION_HISTORY_KEYS if stats else ())}
+    history = {k: [] for k in HISTORY_KEYS + (OPTION_HISTORY_KEYS if stats else ()) + (METRIC_HISTORY_KEYS if metrics else ())}
     ckpt_best, plateau_best, wait = np.inf, np.inf, 0
     best = None
     for epoch in range(epochs):
         order = epoch_order(rng, split_at, shuffle)
         loss = be.train(order, batch_size, lr)
+        if metrics:
+            mt = be.metrics()
+            for k, name in zip(METRIC_KEYS, METRIC_NAMES):
+                history[k].append(float(mt[name]))
         if stats:
             st = be.train_stats()
             for k in OPTION_HISTORY_KEYS:
@@ -540,6 +704,10 @@ def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_
         if averaged:
             be.swap_average()
         val = be.evaluate(split_at, n - split_at, batch_size)
+        if metrics:
+            mt = be.metrics()
+            for k, name in zip(METRIC_KEYS, METRIC_NAMES):
+                history["val_" + k].append(float(mt[name]))
         judged = be.get_weights() if averaged and val[0] < ckpt_best else None
         if averaged:
             be.swap_average()
@@ -577,7 +745,8 @@ def _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_
 
 
 def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epochs=1, validation_split=0.3, shuffle=True,
-                 anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, options=None, adam=None, slots=None):
+                 anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, options=None, adam=None, slots=None,
+                 loss=None, metrics=False):
     """fit() on whatever data set `fitter` holds -- packed (add_samples, add_device_samples, add_trainer_samples) or
     expanded (set_data) -- without touching it: the rows are data_info()'s, the split, the permutations, the checkpoint
     and the plateau logic are fit()'s, and so is the FitResult.  On a packed set of n samples the rows are the 8 n
@@ -585,8 +754,10 @@ def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epoch
     exceed the fitter's max_batch.  options: a FitOptions; None: no option, and a fitter that has options is set to all
     off -- the call decides, not what the fitter was left with.  adam: an AdamOptions; None: the defaults, decided by the
     call in the same way.  slots: {"vhat": ..., "average": ...} to resume from (a FitResult's slots), installed after the
-    optimizer state; None starts vhat from zeros and the average from `weights`."""
-    opts, adam = _options(options), _adam(adam)
+    optimizer state; None starts vhat from zeros and the average from `weights`.  loss: a LossOptions; None: the
+    reference's loss.  metrics: True or {"top_k": k}: the history gains METRIC_HISTORY_KEYS; False: off.  Both are decided
+    by the call in the same way."""
+    opts, adam, loss, top_k = _options(options), _adam(adam), _loss(loss), _top_k(metrics)
     w = _f32(weights).ravel()
     num_weights = getattr(fitter, "num_weights", w.size)
     if w.size != num_weights:
@@ -607,7 +778,7 @@ def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epoch
         fitter.set_slot(k, slots[k])
     stats = _apply_options(fitter, opts)
     return _epochs(fitter, n, split_at, learning_rate, int(batch_size), int(epochs), shuffle, anneal_factor, patience,
-                   seed, stats, _apply_adam(fitter, adam))
+                   seed, stats, _apply_adam(fitter, adam), _apply_loss(fitter, loss, top_k))
 
 
 def fit_samples(weights, state_policy, outcome, *, batch_size=2048, device=0, net=NET_MLP12X100, sample_weight=None,
@@ -674,6 +845,8 @@ def _fit_added(add, weights, batch_size, device, net, backend, kw):
                     a["patience"])
     _options(a["options"])
     _adam(a["adam"])
+    _loss(a["loss"])
+    _top_k(a["metrics"])
     own = backend is None
     be = Fitter(max_batch=int(batch_size), device=device, net=net) if own else backend
     try:
@@ -687,15 +860,16 @@ def _fit_added(add, weights, batch_size, device, net, backend, kw):
 
 def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, batch_size=2048, epochs=1,
         validation_split=0.3, shuffle=True, anneal_factor=0.5, patience=3, seed=0, optimizer_state=None, device=0,
-        net=NET_MLP12X100, sample_weight=None, options=None, adam=None, _backend=None):
+        net=NET_MLP12X100, sample_weight=None, options=None, adam=None, loss=None, metrics=False, _backend=None):
     """main.pyx:249-260 `model.fit(...)` with its callbacks; see the module docstring.  Returns a FitResult.
     optimizer_state: (m, v, iterations) to resume from; None starts Adam from zeros, as a freshly compiled model.
     net: NET_MLP12X100 or NET_RESCNN4, the network `weights` belong to.
     sample_weight: one weight per row, Keras's model.fit(sample_weight=...): a batch's losses are (1/B) sum w_r loss_r,
     in training and in validation; None fits unweighted.
     options: a FitOptions (the module docstring); None: none.
-    adam: an AdamOptions (the module docstring); None: Adam's defaults."""
-    opts, adam = _options(options), _adam(adam)
+    adam: an AdamOptions (the module docstring); None: Adam's defaults.
+    loss: a LossOptions (the module docstring); None: the reference's loss.  metrics: True or {"top_k": k}; False: off."""
+    opts, adam, loss, top_k = _options(options), _adam(adam), _loss(loss), _top_k(metrics)
     name, num_weights = net_info(net)
     w = _f32(weights).ravel()
     if w.size != num_weights:
@@ -730,7 +904,7 @@ def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, 
             be.set_sample_weights(sw)
         stats = _apply_options(be, opts)
         return _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed, stats,
-                       _apply_adam(be, adam))
+                       _apply_adam(be, adam), _apply_loss(be, loss, top_k))
     finally:
         if own:
             be.close()

@@ -29,6 +29,10 @@ What is deliberately not the reference's:
     its Adam's constructor takes.  A generation that fits with any of them writes training_logs/fit_options.json: the
     options, and per epoch the regularisation loss, the mean gradient norm and the clipped steps.  val_loss, and with
     it metadata/losses.txt, then includes the regulariser's R(w), as Keras's does.  model.npz is what it was.
+  * value_weight, policy_weight, label_smoothing, value_loss, huber_delta (the reference's loss by default): the loss of
+    fit.LossOptions; off the defaults fit_options.json holds them under "loss", and val_loss is the weighted one.
+    metrics, top_k (off by default): train_loss.csv carries fit.METRIC_HISTORY_KEYS' columns after the ones it has;
+    write_loss takes val_loss by its column's name.
 """
 import argparse
 import dataclasses
@@ -44,7 +48,8 @@ import numpy as np
 
 from . import _lib, nets, samples_io
 from . import trainer as _trainer
-from .fit import OPTION_HISTORY_KEYS, AdamOptions, FitOptions, Fitter, fit_resident, net_info
+from .fit import (METRIC_HISTORY_KEYS, OPTION_HISTORY_KEYS, AdamOptions, FitOptions, Fitter, LossOptions, fit_resident,
+                  net_info)
 
 NETS = {"mlp12x100": (_trainer.NET_MLP12X100, nets.init_mlp12x100), "rescnn4": (_trainer.NET_RESCNN4, nets.init_rescnn4)}
 # the network kind self-play and arena evaluate with: (net, arith) -> Trainer.set_net's kind
@@ -106,6 +111,14 @@ class RunParams:
     amsgrad: bool = False
     ema_momentum: float = 0.0    # > 0: the fit judges and hands on averaged weights
     ema_overwrite_frequency: int = 0
+    # the loss and the metrics (fit.LossOptions; include/corintho_hip.h "loss and metrics")
+    value_weight: float = 1.0
+    policy_weight: float = 0.25
+    label_smoothing: float = 0.0
+    value_loss: str = "mse"      # or "huber"
+    huber_delta: float = 1.0
+    metrics: bool = False        # True: train_loss.csv gains the metrics' columns
+    top_k: int = 5
 
     def __post_init__(self):
         for f in dataclasses.fields(self):  # a TOML or command-line value may come as the other number type
@@ -142,6 +155,10 @@ class RunParams:
         self.amsgrad = bool(self.amsgrad)
         self.fit_options()  # ValueError: a negative value, two clip modes
         self.adam_options()  # ValueError: a beta outside [0, 1), ...
+        self.loss_options()  # ValueError: a negative weight, both 0, an unknown value_loss, ...
+        self.metrics = bool(self.metrics)
+        if not 1 <= self.top_k <= nets.NUM_MOVES:
+            raise ValueError("top_k must be in 1..%d, not %r" % (nets.NUM_MOVES, self.top_k))
 
     def fit_options(self):
         """the fit options of the run as a fit.FitOptions, checked"""
@@ -152,6 +169,12 @@ class RunParams:
         """Adam's arguments of the run as a fit.AdamOptions, checked"""
         return AdamOptions(beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.adam_epsilon, amsgrad=self.amsgrad,
                            ema_momentum=self.ema_momentum, ema_overwrite_frequency=self.ema_overwrite_frequency).check()
+
+    def loss_options(self):
+        """the loss of the run as a fit.LossOptions, checked"""
+        return LossOptions(value_weight=self.value_weight, policy_weight=self.policy_weight,
+                           label_smoothing=self.label_smoothing, value_loss=self.value_loss,
+                           huber_delta=self.huber_delta).check()
 
     def as_dict(self):
         d = {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}
@@ -228,11 +251,15 @@ def format_time(t):
 
 
 def write_loss(loss_csv, loss_file):
-    """main.pyx:56-68: the smallest last column of the csv, appended to the run's loss file"""
+    """main.pyx:56-68: the smallest val_loss of the csv -- its last column, unless the metrics' columns follow it --
+    appended to the run's loss file"""
     best_loss = 999
     with open(loss_csv, encoding="utf-8") as f:
-        for line in list(f)[1:]:
-            best_loss = min(best_loss, float(line.split("\t")[-1]))
+        lines = list(f)
+    header = lines[0].rstrip("\n").split("\t") if lines else []
+    col = header.index("val_loss") if "val_loss" in header else -1
+    for line in lines[1:]:
+        best_loss = min(best_loss, float(line.split("\t")[col]))
     with open(loss_file, "a+", encoding="utf-8") as f:
         f.write("%s\n" % best_loss)
 
@@ -376,7 +403,7 @@ def train_generation(params, state, *, _cdll=None, _fitter=None, _hook=None):
     # fit (main.pyx:221-272): the current generation's model, not the best one's, with its Adam state
     t0 = time.perf_counter()
     cur_weights, cur_optimizer = load_model(state["cur_gen_location"], p.net)
-    options, adam = p.fit_options(), p.adam_options()
+    options, adam, loss = p.fit_options(), p.adam_options(), p.loss_options()
     # the slots the model was saved with, as far as this generation's Adam uses them
     slots = {k: a for k, a in load_model_slots(state["cur_gen_location"]).items()
              if (k == "vhat" and adam.amsgrad) or (k == "average" and adam.averaged())}
@@ -384,20 +411,24 @@ def train_generation(params, state, *, _cdll=None, _fitter=None, _hook=None):
                             epochs=p.epochs, validation_split=VALIDATION_SPLIT, anneal_factor=p.anneal_factor,
                             patience=p.patience, seed=seeds["fit"], optimizer_state=cur_optimizer,
                             options=options if options.any() else None, adam=None if adam.is_default() else adam,
-                            slots=slots or None)
+                            slots=slots or None, loss=None if loss.is_default() else loss,
+                            metrics={"top_k": p.top_k} if p.metrics else False)
     save_model(state["new_model_location"], res.best_weights, res.best_optimizer, p.net, res.best_slots)  # ModelCheckpoint
     times["fit"] = time.perf_counter() - t0
     log = state["train_log_folder"]
-    rows = ["\t".join(("epoch",) + LOSS_COLUMNS)]
+    columns = LOSS_COLUMNS + (METRIC_HISTORY_KEYS if p.metrics else ())
+    rows = ["\t".join(("epoch",) + columns)]
     for e in range(len(res.history["val_loss"])):
-        rows.append("\t".join([str(e)] + [repr(res.history[k][e]) for k in LOSS_COLUMNS]))
+        rows.append("\t".join([str(e)] + [repr(res.history[k][e]) for k in columns]))
     _write_text(os.path.join(log, "train_loss.csv"), "\n".join(rows) + "\n")
-    if options.any() or not adam.is_default():  # nothing in it is a time or a path: a generation played again writes the same bytes
+    if options.any() or not adam.is_default() or not loss.is_default():  # nothing in it is a time or a path: a generation played again writes the same bytes
         described = {"options": options.as_dict()}
         if options.any():
             described["epochs"] = {k: res.history[k] for k in OPTION_HISTORY_KEYS}
         if not adam.is_default():
             described["adam"] = adam.as_dict()
+        if not loss.is_default():
+            described["loss"] = loss.as_dict()
         _write_text(os.path.join(log, "fit_options.json"), json.dumps(described, indent=4, sort_keys=True) + "\n")
     n = max(1, num_samples)
     _write_text(os.path.join(log, "fit_time.txt"),  # main.pyx:261-270
@@ -656,6 +687,10 @@ def _parser():
         "adam_epsilon": "epsilon of the fit's Adam",
         "ema_momentum": "Momentum of the fit's averaged weights (Keras use_ema); 0: none",
         "ema_overwrite_frequency": "Every this many steps the weights become the average; 0: never",
+        "value_weight": "Weight of the value loss in the fit's loss", "policy_weight": "Weight of the policy loss in the fit's loss",
+        "label_smoothing": "Label smoothing of the policy cross-entropy, in [0, 1)",
+        "value_loss": "Value loss of the fit: mse or huber", "huber_delta": "delta of the Huber value loss",
+        "top_k": "k of the top-k accuracy metric, 1..96",
     }
     for f in dataclasses.fields(RunParams):
         if f.name in ("mix_old", "zip_logs"):
@@ -665,6 +700,9 @@ def _parser():
                             default=False, help="Merge duplicate positions of the fit's samples into weighted ones")
         elif f.name == "amsgrad":
             ap.add_argument("--amsgrad", action="store_true", default=False, help="AMSGrad variant of the fit's Adam")
+        elif f.name == "metrics":
+            ap.add_argument("--metrics", action="store_true", default=False,
+                            help="Log accuracy, top-k accuracy, value error and entropies per epoch in train_loss.csv")
         elif f.name in ("seed", "init_weights"):
             ap.add_argument("--" + f.name, type=int if f.name == "seed" else str, default=None, help=helps[f.name])
         else:

@@ -647,6 +647,74 @@ int ca_fitter_swap_average(ca_fitter *f);
 /* w := a on the trainable weights (Keras's finalize_variable_values); CA_ERR_STATE if the average is invalid */
 int ca_fitter_apply_average(ca_fitter *f);
 
+/* ---- loss and metrics: loss weights, Huber value loss, label smoothing, Keras's metrics, and the heads read back ----
+ * The other half of the reference's model.compile(...) (wrapper.py:272): loss=, loss_weights= and metrics=.  This comment
+ * is the definition.
+ *
+ * Per row with logits h[0..96), pre-tanh value v, policy target t[0..96) and outcome z, ls = label_smoothing:
+ *     t'_j         = t_j (1 - ls) + ls / 96                   Keras CategoricalCrossentropy(label_smoothing=); ls = 0: t' = t
+ *     policy term  = -sum_j t'_j log_softmax_j(h)
+ *     e            = tanh v - z
+ *     value term   = e^2                                      CA_VALUE_LOSS_MSE
+ *                  = 0.5 e^2 if |e| <= delta, else delta (|e| - 0.5 delta)     CA_VALUE_LOSS_HUBER (Keras Huber(delta))
+ * The batch loss is value_weight * mean(value term) + policy_weight * mean(policy term) over the B rows, and its
+ * gradients with respect to the heads' outputs, in float32 and the operation order of the default loss kernel:
+ *     Hd[j]  = policy_weight * (softmax_j * sum_j t'_j - t'_j) / B
+ *     Hd[96] = value_weight * 2 e (1 - tanh^2 v) / B                           MSE
+ *            = value_weight * clamp(e, -delta, delta) (1 - tanh^2 v) / B       Huber
+ * The sample weight multiplies last, as without this section.  out_losses[1] and [2] are the means of the two terms
+ * (not times their weights) and out_losses[0] = value_weight * [1] + policy_weight * [2] (+ R of the fit options), in
+ * ca_fitter_train, its batch_losses, ca_fitter_evaluate and ca_fitter_gradients, whose gradient is that of this
+ * weighted data loss.  The values stay until they are set again.  At the defaults a step launches the kernels it launches
+ * without this section and writes the same bytes.
+ *
+ * Metrics, per row from the same head outputs the loss reads (Keras's metric names in brackets), c = argmax_j t_j:
+ *     categorical_accuracy        argmax_j h_j == c, the FIRST maximum on both sides, the unsmoothed t
+ *     top_k_categorical_accuracy  #{j : h_j > h_c} < top_k      (TensorFlow's in_top_k: ties at the boundary are in)
+ *     mean_absolute_error         |tanh v - z|
+ *     policy_entropy              -sum_j p_j log p_j, p = softmax(h)
+ *     target_entropy              -sum_j t_j log t_j, 0 log 0 = 0
+ * A call's metric is sum_r w_r x_r / sum_r w_r (Keras's Mean with sample_weight; w_r = 1 on an unweighted set; 0 if the
+ * weights sum to 0).  A batch's six sums (of w x for the five, of w) are float32 in a fixed order without atomics; the
+ * batches are added in float64 on the host.  ca_fitter_train reports the step's own forward (batch statistics, the
+ * weights from before the step: what Keras logs during an epoch), ca_fitter_evaluate the inference-mode one.  Metrics off:
+ * nothing is launched or allocated.  On: the losses, gradients and weights of a fit do not change by a bit. */
+#define CA_VALUE_LOSS_MSE 0
+#define CA_VALUE_LOSS_HUBER 1
+typedef struct ca_fit_loss {
+  uint32_t struct_size;  /* as ca_fit_options': min(struct_size, the library's sizeof) bytes are read and written */
+  float value_weight;    /* finite, >= 0; default 1 */
+  float policy_weight;   /* finite, >= 0; default 0.25; not both 0 */
+  float label_smoothing; /* in [0, 1); default 0 */
+  int32_t value_loss;    /* CA_VALUE_LOSS_MSE (default) or CA_VALUE_LOSS_HUBER */
+  float huber_delta;     /* finite, > 0; default 1; read only with HUBER */
+} ca_fit_loss;
+/* the defaults: what a new fitter has, and what a caller's shorter struct leaves to the library */
+#define CA_FIT_LOSS_INIT {sizeof(ca_fit_loss), 1.0f, 0.25f, 0.0f, 0, 1.0f}
+/* CA_ERR_ARG and nothing changes on a value outside what the struct's comments allow, judged in float32 (or a
+ * struct_size below 4) */
+int ca_fitter_set_loss(ca_fitter *f, const ca_fit_loss *loss);
+/* out->struct_size must be set by the caller; on return it is the number of bytes written */
+int ca_fitter_get_loss(ca_fitter *f, ca_fit_loss *out);
+typedef struct ca_fit_metrics {
+  uint32_t struct_size; /* as above */
+  int32_t top_k;        /* as set */
+  int64_t rows;         /* rows of the call */
+  double weight_sum;    /* sum of their sample weights (= rows when unweighted) */
+  double categorical_accuracy, top_k_categorical_accuracy, mean_absolute_error, policy_entropy, target_entropy;
+} ca_fit_metrics;
+/* on != 0: every later ca_fitter_train and ca_fitter_evaluate computes the metrics; top_k in 1..96 (else CA_ERR_ARG and
+ * nothing changes; looked at only when switching on).  Off on a new fitter, where top_k is 5. */
+int ca_fitter_set_metrics(ca_fitter *f, int32_t on, int32_t top_k);
+/* of the last ca_fitter_train or ca_fitter_evaluate since metrics were switched on (rows = 0 before the first);
+ * CA_ERR_STATE if metrics are off */
+int ca_fitter_metrics(ca_fitter *f, ca_fit_metrics *out);
+/* Keras's predict: the heads' outputs of rows[0..n_rows), 1 <= n_rows <= max_batch, of a packed or an expanded set.
+ * train = 0: inference mode; train != 0: the rows as one training batch, with batch statistics.  Nothing of the
+ * fitter's weights, slots or step count changes.  values are pre-tanh. */
+int ca_fitter_predict(ca_fitter *f, const int32_t *rows, int32_t n_rows, int32_t train, float *logits /* [n_rows][96] */,
+                      float *values /* [n_rows] */);
+
 #ifdef __cplusplus
 }
 #endif

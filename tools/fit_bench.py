@@ -29,6 +29,11 @@ the last call's train_stats.  All 0 (the default): the step without them, and no
 know of no arguments.  `on` switches AMSGrad and averaged weights (ema_momentum 0.99) on: the parametrised update kernel
 with its third slot and the average.  Not given: no Adam entry point is called (an earlier build has none).
 
+--loss default | on: the loss (include/corintho_hip.h, "loss and metrics") likewise.  `default` sets the reference's loss
+through set_loss, which must cost nothing; `on` is loss weights (0.7, 1.3), label smoothing 0.1 and Huber(0.5): the
+parametrised loss kernel in ft_k_loss's place.  --metrics switches the metrics on (top 5): two launches more per step.
+--lib FILE times another build of the library (the parent commit's, built with `python -m corintho_ai_amd.build --out`).
+
     python tools/fit_bench.py --torch [--net rescnn4] [--rows 1000000 --batch 2048 --steps 200 --reps 3] [--out file.json]
     python tools/fit_bench.py --packed [--net rescnn4]
     python tools/fit_bench.py --handoff [--games 4096 --sims 400]
@@ -46,7 +51,8 @@ sys.path.insert(0, ROOT)
 
 from corintho_ai_amd import nets  # noqa: E402
 from corintho_ai_amd import NET_MLP12X100, NET_RESCNN4  # noqa: E402
-from corintho_ai_amd.fit import OPTION_NAMES, AdamOptions, FitOptions, Fitter  # noqa: E402
+from corintho_ai_amd import _lib  # noqa: E402
+from corintho_ai_amd.fit import OPTION_NAMES, AdamOptions, FitOptions, Fitter, LossOptions  # noqa: E402
 
 FLOP_PER_ROW_STEP = {"mlp12x100": 3 * 2.0 * (70 * 100 + 11 * 100 * 100 + 100 * 97),
                      "rescnn4": 3 * nets.rescnn4_flop_per_row()}
@@ -251,7 +257,15 @@ def main():
     ap.add_argument("--regularize", type=int, choices=(0, 1), default=0)
     ap.add_argument("--adam", choices=("default", "on"), default=None,
                     help="set Adam's arguments: the defaults, or AMSGrad and averaged weights on")
+    ap.add_argument("--loss", choices=("default", "on"), default=None,
+                    help="set the loss: the reference's, or loss weights, label smoothing and Huber on")
+    ap.add_argument("--metrics", action="store_true", help="switch the metrics on")
+    ap.add_argument("--lib", default="", help="another build of libcorintho_hip.so to time")
     a = ap.parse_args()
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
+    loss = {None: None, "default": LossOptions(),
+            "on": LossOptions(value_weight=0.7, policy_weight=1.3, label_smoothing=0.1, value_loss="huber", huber_delta=0.5)}[a.loss]
     adam = {None: None, "default": AdamOptions(), "on": AdamOptions(amsgrad=True, ema_momentum=0.99)}[a.adam]
     options = FitOptions(regularize=a.regularize, **{k: getattr(a, k) for k in OPTION_NAMES}).check()
     if a.handoff:
@@ -282,6 +296,10 @@ def main():
         f.set_options(options)
     if adam is not None:  # (likewise)
         f.set_adam(adam)
+    if loss is not None:  # (likewise)
+        f.set_loss(loss)
+    if a.metrics:
+        f.set_metrics(True)
     f.train(order[:a.warmup * a.batch], a.batch, 1e-3)
     if ts:
         for i in range(a.warmup):
@@ -298,6 +316,10 @@ def main():
             fp.set_options(options)
         if adam is not None:
             fp.set_adam(adam)
+        if loss is not None:
+            fp.set_loss(loss)
+        if a.metrics:
+            fp.set_metrics(True)
         fp.train(order[:a.warmup * a.batch], a.batch, 1e-3)
     hip, tor, pak = [], [], []
     timed = order[a.warmup * a.batch:]
@@ -317,6 +339,7 @@ def main():
             torch.cuda.synchronize(ts.dev)
             tor.append((time.perf_counter() - t0) * 1e3 / a.steps)
     stats = f.train_stats() if options.any() else None
+    metrics = f.metrics() if a.metrics else None
     f.close()
     if fp:
         fp.close()
@@ -335,6 +358,10 @@ def main():
         out["train_stats"] = stats
     if adam is not None:
         out["adam"] = adam.as_dict()
+    if loss is not None:
+        out["loss"] = loss.as_dict()
+    if metrics:
+        out["metrics"] = metrics
     if tor:
         out["torch"] = rec(tor)
         out["hip_speedup_over_torch"] = min(tor) / min(hip)
