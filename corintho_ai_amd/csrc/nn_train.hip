@@ -79,9 +79,13 @@ __global__ __launch_bounds__(256) void ft_k_gemm(FtGemm g) {
  * value_mse + 0.25 * policy_cce (means over the B rows) with respect to the logits and to v:
  *   Hd[r][0..95] = 0.25 (softmax * sum t - t) / B,  Hd[r][96] = 2 (tanh v - z)(1 - tanh^2 v) / B,
  *   Hd[r][97] = (tanh v - z)^2,  Hd[r][98] = -sum_j t_j log_softmax_j  (from the logits, as Keras does)
+ * 1 - tanh^2 v is one fused multiply-add, rounded once.  As 1 - (t * t) it is biased where tanh saturates: with t = 1 - a
+ * the product 1 - 2a + a^2 rounds to 1 - 2a whenever a^2 is under half an ulp of one (a < 1.7e-4, |v| > 4.7), so every
+ * such row's factor 2a - a^2 comes out a / 2 of itself too large, all rows the same way (measured 1e-5 to 3e-5 of the
+ * value head's whole gradient on a saturated head).
  * WEIGHTED: every one of these 99 terms times the row's sample weight wts[rows[r]] (Keras's sample_weight under
  * SUM_OVER_BATCH_SIZE: the divisor stays B); the unweighted instantiation never reads that last operand and has no such
- * multiply: instruction for instruction the kernel it was before weights existed. */
+ * multiply. */
 template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void ft_k_loss(const float *__restrict__ H, const int32_t *__restrict__ rows, int B,
                                                 const float *__restrict__ evals, const float *__restrict__ probs,
@@ -106,7 +110,7 @@ __global__ __launch_bounds__(256) void ft_k_loss(const float *__restrict__ H, co
     for (int j = 0; j < CA_NUM_MOVES; ++j) d[j] = 0.25f * (expf(h[j] - lse) * st - t[j]) * inv_b;
     const float tv = tanhf(h[96]);
     const float err = tv - evals[rows[r]];
-    d[96] = 2.0f * err * (1.0f - tv * tv) * inv_b;
+    d[96] = 2.0f * err * fmaf(-tv, tv, 1.0f) * inv_b;
     d[97] = err * err;
     d[98] = ce;
   } else { /* today's terms, each rounded as above, then times w: a weight of 1 changes no bit, one of 2 doubles exactly */
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(256) void ft_k_loss(const float *__restrict__ H, co
     for (int j = 0; j < CA_NUM_MOVES; ++j) d[j] = 0.25f * (expf(h[j] - lse) * st - t[j]) * inv_b * w;
     const float tv = tanhf(h[96]);
     const float err = tv - evals[rows[r]];
-    d[96] = 2.0f * err * (1.0f - tv * tv) * inv_b * w;
+    d[96] = 2.0f * err * fmaf(-tv, tv, 1.0f) * inv_b * w;
     d[97] = err * err * w;
     d[98] = ce * w;
   }

@@ -203,21 +203,32 @@ __global__ __launch_bounds__(256) void fc_k_bn_part(const float *__restrict__ Z,
   }
 }
 
-/* the chunks combined in order: mean = sum n_j mean_j / R, variance = sum (M2_j + n_j (mean_j - mean)^2) / R (biased) */
+/* the chunks combined in order: mean = sum n_j mean_j / R, variance = sum (M2_j + n_j (mean_j - mean)^2) / R (biased).
+ * The sums over the chunks are float64, each statistic rounded once: a float32 running sum of up to 256 terms n_j mean_j
+ * leaves the mean some 3e-7 of itself off, the same for every row, and xhat = (z - mean) rstd carries that times
+ * |mean| / sigma into every row alike -- an error that does not average out over the batch (it reached the policy head's
+ * gradient and the policy loss where a channel's mean is tens of its sigma; the backward sums are float64 for the same
+ * reason, below).  Every chunk but the last has rpc rows, so the sums run over the chunks' means, their M2 and their
+ * squared distances from the mean as they are, and the row counts come in once at the end. */
 __global__ __launch_bounds__(64) void fc_k_bn_final(const float *__restrict__ part, int nch, int R, int rpc, int C,
                                                     float *__restrict__ stat) {
   const int c = threadIdx.x;
   if (c >= C) return;
-  float sm = 0.0f;
-  for (int j = 0; j < nch; ++j) sm += part[(j * 2) * 64 + c] * (float)(min(R, (j + 1) * rpc) - j * rpc);
-  const float mu = sm / (float)R;
-  float m2 = 0.0f;
-  for (int j = 0; j < nch; ++j) {
-    const float d = part[(j * 2) * 64 + c] - mu;
-    m2 += part[(j * 2 + 1) * 64 + c] + (float)(min(R, (j + 1) * rpc) - j * rpc) * (d * d);
+  const int full = nch - 1, nlast = R - full * rpc; /* chunks of rpc rows, and the rows of the last one */
+  const double mlast = (double)part[(full * 2) * 64 + c], slast = (double)part[(full * 2 + 1) * 64 + c];
+  double sm = 0.0;
+  for (int j = 0; j < full; ++j) sm += (double)part[(j * 2) * 64 + c];
+  const double mu = (sm * (double)rpc + mlast * (double)nlast) / (double)R;
+  double s2 = 0.0, q = 0.0;
+  for (int j = 0; j < full; ++j) {
+    const double d = (double)part[(j * 2) * 64 + c] - mu;
+    s2 += (double)part[(j * 2 + 1) * 64 + c];
+    q += d * d;
   }
-  stat[c] = mu;
-  stat[64 + c] = m2 / (float)R;
+  const double dl = mlast - mu;
+  const double m2 = s2 + slast + (double)rpc * q + (double)nlast * (dl * dl);
+  stat[c] = (float)mu;
+  stat[64 + c] = (float)(m2 / (double)R);
 }
 
 /* out = relu(gamma (z - mu) rsqrt(var + eps) + beta (+ res)); 4096 elements per block */

@@ -45,10 +45,10 @@ __global__ __launch_bounds__(256) void ft_k_loss_opt(const float *__restrict__ H
   if (L.huber) {
     const float dl = L.huber_delta, a = fabsf(err);
     const float c = err > dl ? dl : err < -dl ? -dl : err;
-    gv = L.value_weight * c * (1.0f - tv * tv) * inv_b;
+    gv = L.value_weight * c * fmaf(-tv, tv, 1.0f) * inv_b;
     lv = a <= dl ? 0.5f * err * err : dl * (a - 0.5f * dl);
   } else {
-    gv = L.value_weight * 2.0f * err * (1.0f - tv * tv) * inv_b;
+    gv = L.value_weight * 2.0f * err * fmaf(-tv, tv, 1.0f) * inv_b;
     lv = err * err;
   }
   d[96] = WEIGHTED ? gv * w : gv;
