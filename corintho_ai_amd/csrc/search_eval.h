@@ -232,6 +232,7 @@ CO_DEV void co_prior_all(CoWave &w, CoTree &t, int c0, int nc, const float *prob
     CO_PRIOR_FETCH(c0, on, leaf, l0, l1, l2, pq, rw)
     for (int k0 = c0; k0 < c0 + nc; k0 += CO_SB_ROWS) {
       const int more = k0 + CO_SB_ROWS < c0 + nc;
+      CO_SBS(28 + (more ? CO_SB_ROWS : c0 + nc - k0) - 1, 1);
       CO_PPH(16);
       LV(float, gq[6]);
       FOR_LANES_HOT {
@@ -419,6 +420,7 @@ CO_DEV void co_receive_eval(CoWave &w, CoTree &t, const float *eval, const float
      * of leaf c0 + k in lane k (one trip for the step instead of two dependent scalar loads per leaf behind the priors'
      * stores) */
     if (c0 > 0 || w.pre_n != nc) co_pending_records(w, c0, nc); /* (else: requested when the step began) */
+    CO_SBS(25, c0 > 0);
     w.pre_n = 0;
     LV(uint32_t, evl);
     {
@@ -435,6 +437,8 @@ CO_DEV void co_receive_eval(CoWave &w, CoTree &t, const float *eval, const float
     CO_PH_MEM(13);
     for (int k0 = c0; k0 < c0 + nc; k0 += CO_RB) {
       const int nb = c0 + nc - k0 < CO_RB ? c0 + nc - k0 : CO_RB;
+      CO_SBS(26, 1);
+      CO_SBS(27, k0 > c0);
       /* (requested in front of the priors' passes instead -- 8 or 16 registers across them: +-0 with the first batch's,
        * 4 % slower with both, the product build's allocation gives way; round 5) */
       co_backup_paths(w, k0, nb, pa);

@@ -47,19 +47,7 @@
 #define CO_SB_AT(j, lv) ((j) * CO_SB_DEPTH + (lv))
 #define CO_SB_SLOT_AT(j, lv) ((j) * (CO_SB_DEPTH + 1) + (lv))
 
-#if defined(CO_SB_STATS) && defined(CO_EMU)
-/* emulation-build counters of the grouped search (tools/sb_stats.py): 0 groups, 1 simulations asked for, 2 committed,
- * 3 nothing searchable, 4 terminal child, 5 wide node, 6 too deep, 7 terminal leaf / full arena, 8 sequential simulations,
- * 9 levels of the groups, 10 scans, 11 patches applied (same node, same level), 12 + k: groups that committed k,
- * 20 shared levels below the root, 21 / 22 levels scanned wave-wide for one / two rows, 23 levels in row form, 24 turns taken there */
-extern unsigned long long co_sb_stats[32];
-extern unsigned long long co_sb_ply[8][8]; /* by game progress (plies / 4): groups, asked, committed, terminal leaves, nothing searchable, levels, sequential, - */
-#define CO_SBS(i, v) __atomic_fetch_add(&co_sb_stats[i], (unsigned long long)(v), __ATOMIC_RELAXED)
-#define CO_SBP(w, i, v) __atomic_fetch_add(&co_sb_ply[(w).gc.plies / 4 > 7 ? 7 : (w).gc.plies / 4][i], (unsigned long long)(v), __ATOMIC_RELAXED)
-#else
-#define CO_SBS(i, v) ((void)0)
-#define CO_SBP(w, i, v) ((void)0)
-#endif
+/* (the emulation build's counters CO_SBS / CO_SBP: search_state.h) */
 
 /* m = simulations that are certainly due (1 < m <= CO_SB = 4: each adds one pending leaf and one search).  Returns how
  * many were committed; fewer than m: the next one takes co_search.

@@ -14,6 +14,24 @@ CO_CONST uint32_t CO_GAMMA_BITS[CO_NUM_GAMMA] = CO_GAMMA_BITS_INIT;
 
 #define CO_NEG_INF (-__builtin_huge_valf())
 
+#if defined(CO_SB_STATS) && defined(CO_EMU)
+/* emulation-build counters of the grouped search (tools/sb_stats.py, tests/test_search_census_cpu.py): 0 groups,
+ * 1 simulations asked for, 2 committed, 3 nothing searchable, 4 terminal child, 5 wide node, 6 too deep, 7 terminal leaf /
+ * full arena, 8 sequential simulations, 9 levels of the groups, 10 scans, 11 patches applied (same node, same level),
+ * 12 + k: groups that committed k, 20 shared levels below the root, 21 / 22 levels scanned wave-wide for one / two rows,
+ * 23 levels in row form, 24 turns taken there;
+ * and of co_receive_eval (search_eval.h): 25 rounds of pending-leaf records after a step's first (more than CO_PRE leaves),
+ * 26 backup batches, 27 of them after a round's first (more than CO_RB leaves), 28 + k: passes of co_prior_all that set the
+ * priors of k + 1 leaves (k < CO_SB_ROWS) */
+extern unsigned long long co_sb_stats[32];
+extern unsigned long long co_sb_ply[8][8]; /* by game progress (plies / 4): groups, asked, committed, terminal leaves, nothing searchable, levels, sequential, - */
+#define CO_SBS(i, v) __atomic_fetch_add(&co_sb_stats[i], (unsigned long long)(v), __ATOMIC_RELAXED)
+#define CO_SBP(w, i, v) __atomic_fetch_add(&co_sb_ply[(w).gc.plies / 4 > 7 ? 7 : (w).gc.plies / 4][i], (unsigned long long)(v), __ATOMIC_RELAXED)
+#else
+#define CO_SBS(i, v) ((void)0)
+#define CO_SBP(w, i, v) ((void)0)
+#endif
+
 /* In-kernel phase stamps (diagnostic build only: hipcc -DCO_PROF, tools/prof_phases.py).  A wavefront keeps ONE running
  * clock (w.tph): CO_PH(slot) charges the cycles since the previous stamp to `slot`, so the slots add up to the wave's
  * whole step; the sums live in registers and are written once, at the end of the step (a stamp is an s_memtime and a

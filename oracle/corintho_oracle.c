@@ -407,6 +407,22 @@ typedef struct {
   int64_t searches, leaf_evals, nodes_created, plies;
 } counters_t;
 
+/* ------------------------------------------------------------------ census
+ * One counter per deciding branch of the TrainMC restatement below (indices: corintho_oracle.h CO_CENSUS_*), process
+ * wide and counted atomically (games run under OpenMP).  Nothing reads them but co_census(): no result depends on them. */
+static int64_t g_census[CO_CENSUS_N];
+#define CENSUS(i) ((void)__atomic_fetch_add(&g_census[i], (int64_t)1, __ATOMIC_RELAXED))
+static void census_max(int i, int64_t v) {
+  int64_t old = __atomic_load_n(&g_census[i], __ATOMIC_RELAXED);
+  while (v > old && !__atomic_compare_exchange_n(&g_census[i], &old, v, 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+}
+void co_census(int64_t out[CO_CENSUS_N]) {
+  for (int i = 0; i < CO_CENSUS_N; ++i) out[i] = __atomic_load_n(&g_census[i], __ATOMIC_RELAXED);
+}
+void co_census_reset(void) {
+  for (int i = 0; i < CO_CENSUS_N; ++i) __atomic_store_n(&g_census[i], (int64_t)0, __ATOMIC_RELAXED);
+}
+
 static inline int e_move(uint16_t e) { return e & 127; }
 static inline int e_prob(uint16_t e) { return e >> 7; }
 
@@ -711,10 +727,12 @@ static int choose_move_opening(trainmc_t *mc, float *prob_sample) {
     }
   }
   if (visits == 0) {
+    CENSUS(CO_CENSUS_MOVE_OPENING_RESET);
     prob_sample[choice] = 1.0f;
     reset_tree_to_child(mc, choice);
     return choice;
   }
+  CENSUS(CO_CENSUS_MOVE_OPENING);
   int32_t target = (int32_t)(mt_next(mc->generator) % (uint32_t)visits);
   int32_t total = 0;
   cur = mc->root->first_child;
@@ -743,8 +761,12 @@ static int choose_move_normal(trainmc_t *mc, float *prob_sample) {
   while (cur != NULL) {
     if (!n_won(cur)) {
       float eval = cur->evaluation;
-      if (cur->result == kResultDraw || cur->result == kDeducedDraw) eval = 0.0f;
+      if (cur->result == kResultDraw || cur->result == kDeducedDraw) {
+        CENSUS(CO_CENSUS_MOVE_DRAWN_CHILD);
+        eval = 0.0f;
+      }
       if (cur->visits > max_visits || (cur->visits == max_visits && eval > max_eval)) {
+        if (cur->visits <= max_visits) CENSUS(CO_CENSUS_MOVE_TIE_BY_EVAL);
         choice = cur->child_id;
         best_prev = prev;
         max_visits = cur->visits;
@@ -756,9 +778,11 @@ static int choose_move_normal(trainmc_t *mc, float *prob_sample) {
   }
   if (prob_sample != NULL) prob_sample[choice] = 1.0f;
   if (max_visits == 0) {
+    CENSUS(CO_CENSUS_MOVE_NORMAL_RESET);
     reset_tree_to_child(mc, choice);
     return choice;
   }
+  CENSUS(CO_CENSUS_MOVE_NORMAL);
   move_down(mc, best_prev);
   return choice;
 }
@@ -769,8 +793,14 @@ static int mc_choose_move(trainmc_t *mc, float *game_state, float *prob_sample) 
     write_game_state(&mc->root->game, game_state);
     memset(prob_sample, 0, CO_NUM_MOVES * sizeof(float));
   }
-  if (n_won(mc->root)) return choose_move_won(mc, prob_sample);
-  if (n_lost(mc->root) || n_drawn(mc->root)) return choose_move_lost_drawn(mc, prob_sample);
+  if (n_won(mc->root)) {
+    CENSUS(CO_CENSUS_MOVE_WON);
+    return choose_move_won(mc, prob_sample);
+  }
+  if (n_lost(mc->root) || n_drawn(mc->root)) {
+    CENSUS(n_lost(mc->root) ? CO_CENSUS_MOVE_LOST : CO_CENSUS_MOVE_DRAWN_ROOT);
+    return choose_move_lost_drawn(mc, prob_sample);
+  }
   if (mc->root->depth < 6 && !mc->testing) return choose_move_opening(mc, prob_sample);
   return choose_move_normal(mc, prob_sample);
 }
@@ -782,6 +812,7 @@ static void propagate_terminal(trainmc_t *mc) {
     if (n_lost(cur)) {
       cur = cur->parent;
       cur->result = kDeducedWin;
+      CENSUS(CO_CENSUS_DEDUCED_WIN);
     } else {
       cur = cur->parent;
       node_t *cur_child = cur->first_child;
@@ -795,6 +826,7 @@ static void propagate_terminal(trainmc_t *mc) {
       }
       if (edge_index < cur->num_legal_moves) return;
       cur->result = has_draw ? kDeducedDraw : kDeducedLoss;
+      CENSUS(has_draw ? CO_CENSUS_DEDUCED_DRAW : CO_CENSUS_DEDUCED_LOSS);
     }
   }
 }
@@ -820,17 +852,22 @@ static choose_next_t choose_next(trainmc_t *mc) {
     if (cur_child != NULL && cur_child->child_id == n_move_id(cur, edge_index)) {
       if ((!n_known(cur_child) || n_drawn(cur_child)) && !cur_child->all_visited) {
         if (n_drawn(cur_child)) {
+          CENSUS(CO_CENSUS_SCORE_DRAWN_CHILD);
           u = n_probability(cur, edge_index) * v_sqrt;
         } else {
+          CENSUS(CO_CENSUS_SCORE_VISITED_CHILD);
           float pv = n_probability(cur, edge_index) * v_sqrt;
           double a = -1.0 * (double)cur_child->evaluation / (double)(float)cur_child->visits;
           double b = (double)pv / ((double)(float)cur_child->visits + 1.0);
           u = (float)(a + b);
         }
+      } else {
+        CENSUS(CO_CENSUS_SCORE_CLOSED_CHILD);
       }
       prev = cur_child;
       cur_child = cur_child->next_sibling;
     } else {
+      CENSUS(CO_CENSUS_SCORE_UNVISITED_EDGE);
       u = n_probability(cur, edge_index) * v_sqrt;
     }
     if (u > max_eval) {
@@ -858,11 +895,13 @@ static void mc_search(trainmc_t *mc) {
   mc->cur = mc->root;
   ++mc->searches_done;
   if (mc->ctr) mc->ctr->searches++;
+  int levels = 0; /* edges from the root to the leaf (census only) */
   while (!n_terminal(mc->cur)) {
     choose_next_t res = choose_next(mc);
     ++mc->cur->visits;
     mc->cur->evaluation += 1.0f;
     if (res.type == 2) {
+      CENSUS(mc->cur->parent != NULL ? CO_CENSUS_SEARCH_RETREAT_BELOW : CO_CENSUS_SEARCH_RETREAT_ROOT);
       mc->cur->all_visited = 1;
       while (mc->cur->parent != NULL) {
         --mc->cur->visits;
@@ -875,13 +914,16 @@ static void mc_search(trainmc_t *mc) {
       if (mc->ctr) mc->ctr->searches--;
       return;
     }
+    ++levels;
     if (res.type == 1 && res.node == NULL) {
+      CENSUS(CO_CENSUS_SEARCH_NEW_FIRST_CHILD);
       mc->cur->first_child =
           node_new_child(&mc->cur->game, mc->cur, mc->cur->first_child, res.choice, mc->cur->depth + 1, mc->ctr);
       mc->cur = mc->cur->first_child;
       break;
     }
     if (res.type == 1) {
+      CENSUS(CO_CENSUS_SEARCH_NEW_BEHIND_SIBLING);
       res.node->next_sibling =
           node_new_child(&mc->cur->game, mc->cur, res.node->next_sibling, res.choice, mc->cur->depth + 1, mc->ctr);
       mc->cur = res.node->next_sibling;
@@ -889,7 +931,9 @@ static void mc_search(trainmc_t *mc) {
     }
     mc->cur = res.node;
   }
+  census_max(CO_CENSUS_MAX_PATH, levels);
   if (n_terminal(mc->cur)) {
+    CENSUS(n_drawn(mc->cur) ? CO_CENSUS_SEARCH_LEAF_DRAWN : CO_CENSUS_SEARCH_LEAF_LOST);
     propagate_terminal(mc);
     float cur_eval = -1.0f;
     if (n_drawn(mc->cur)) cur_eval = 0.0f;
@@ -916,6 +960,7 @@ static int mc_do_iteration(trainmc_t *mc, const float *eval, const float *probs)
     return 0;
   }
   if (mc->searches_done == 0 && mc->root->visits == 1 && mc->root->all_visited) {
+    CENSUS(CO_CENSUS_ITER_REREQUEST);
     mc->searches_done = 1;
     mc_request(mc, mc->cur);
     return 0;
@@ -933,12 +978,14 @@ static int mc_receive_opponent_move(trainmc_t *mc, int move_choice, const game_t
   node_t *cur = mc->root->first_child, *prev = NULL;
   while (cur != NULL) {
     if (cur->child_id == move_choice) {
+      CENSUS(CO_CENSUS_OPP_MOVE_FOUND);
       move_down(mc, prev);
       return 0;
     }
     prev = cur;
     cur = cur->next_sibling;
   }
+  CENSUS(CO_CENSUS_OPP_MOVE_NEW_ROOT);
   node_delete(mc->root);
   mc->root = NULL;
   mc_create_root(mc, game, depth);
@@ -1194,6 +1241,8 @@ static void sp_end_game(selfplayer_t *sp) {
   if (sp->players[sp->to_play].root->result == kResultDraw) sp->result = kResultDraw;
   else if (sp->to_play == 1) sp->result = kResultLoss;
   else sp->result = kResultWin;
+  CENSUS(sp->result == kResultDraw ? CO_CENSUS_GAME_DRAWN : CO_CENSUS_GAME_DECISIVE);
+  census_max(CO_CENSUS_MAX_PLIES, sp->ctr.plies);
   if (sp->log) {
     if (sp->result == kResultDraw) fputs("GAME IS DRAWN.\n", sp->log);
     else fprintf(sp->log, "PLAYER %d WON!\n", sp->to_play + 1);
@@ -1699,6 +1748,8 @@ static void match_end_game(match_t *m) {
   if (m->root->result == kResultDraw) m->result = kResultDraw;
   else if (m->to_play == 1) m->result = kResultLoss;
   else m->result = kResultWin;
+  CENSUS(m->result == kResultDraw ? CO_CENSUS_MATCH_DRAWN : CO_CENSUS_MATCH_DECISIVE);
+  census_max(CO_CENSUS_MAX_PLIES, m->ctr.plies);
   if (m->log) { /* match.cpp:173-179, 190 */
     if (m->result == kResultDraw) fputs("GAME IS DRAWN.\n", m->log);
     else fprintf(m->log, "PLAYER %d WON!\n", m->to_play + 1);

@@ -104,6 +104,45 @@ int co_trainer_trace(const co_trainer *t, int game, int32_t *out, int cap);
 /* counters summed over games: [searches, leaf_evals, nodes_created, plies] */
 void co_trainer_counters(const co_trainer *t, int64_t out[4]);
 
+/* ---- census: how often each deciding branch of the TrainMC restatement was taken, process wide since the last reset
+ * (atomic counts; the last two entries are maxima).  tests/test_search_census_cpu.py holds the classing of each. */
+enum {
+  CO_CENSUS_DEDUCED_WIN,              /* propagate_terminal: a lost child makes its parent won */
+  CO_CENSUS_DEDUCED_DRAW,             /* ... every child known, one of them "drawn" */
+  CO_CENSUS_DEDUCED_LOSS,             /* ... every child known, none drawn */
+  CO_CENSUS_SCORE_DRAWN_CHILD,        /* choose_next: an open drawn child, scored by its prior alone */
+  CO_CENSUS_SCORE_VISITED_CHILD,      /* ... an open child, the PUCT score */
+  CO_CENSUS_SCORE_CLOSED_CHILD,       /* ... a decided or all-visited child, never chosen */
+  CO_CENSUS_SCORE_UNVISITED_EDGE,     /* ... an edge without a child */
+  CO_CENSUS_SEARCH_RETREAT_BELOW,     /* mc_search: nothing searchable below a node under the root */
+  CO_CENSUS_SEARCH_RETREAT_ROOT,      /* ... at the root */
+  CO_CENSUS_SEARCH_LEAF_DRAWN,        /* ... a terminal new leaf, drawn */
+  CO_CENSUS_SEARCH_LEAF_LOST,         /* ... lost */
+  CO_CENSUS_SEARCH_NEW_FIRST_CHILD,   /* ... the new child becomes its parent's first child */
+  CO_CENSUS_SEARCH_NEW_BEHIND_SIBLING,/* ... is linked in behind a sibling */
+  CO_CENSUS_ITER_REREQUEST,           /* mc_do_iteration: an all-visited root with one visit is requested again */
+  CO_CENSUS_MOVE_WON,                 /* mc_choose_move: root deduced won */
+  CO_CENSUS_MOVE_LOST,                /* ... lost */
+  CO_CENSUS_MOVE_DRAWN_ROOT,          /* ... drawn */
+  CO_CENSUS_MOVE_OPENING_RESET,       /* ... opening rule, no visits to sample from: fresh tree */
+  CO_CENSUS_MOVE_OPENING,             /* ... opening rule, sampled by visits */
+  CO_CENSUS_MOVE_NORMAL_RESET,        /* ... most visits, none had any: fresh tree */
+  CO_CENSUS_MOVE_NORMAL,              /* ... most visits */
+  CO_CENSUS_MOVE_TIE_BY_EVAL,         /* ... a tie on visits decided by the evaluation */
+  CO_CENSUS_MOVE_DRAWN_CHILD,         /* ... a drawn child considered (evaluation read as 0) */
+  CO_CENSUS_OPP_MOVE_FOUND,           /* mc_receive_opponent_move: the move's child becomes the root */
+  CO_CENSUS_OPP_MOVE_NEW_ROOT,        /* ... no such child: new root, requested */
+  CO_CENSUS_GAME_DRAWN,               /* sp_end_game */
+  CO_CENSUS_GAME_DECISIVE,
+  CO_CENSUS_MATCH_DRAWN,              /* match_end_game */
+  CO_CENSUS_MATCH_DECISIVE,
+  CO_CENSUS_MAX_PLIES,                /* the longest finished game or match, in plies */
+  CO_CENSUS_MAX_PATH,                 /* the deepest leaf, in edges below its root */
+  CO_CENSUS_N
+};
+void co_census(int64_t out[CO_CENSUS_N]);
+void co_census_reset(void);
+
 /* ---- DockerMC (dockermc.h:13-51): single-position search from an arbitrary position ---- */
 typedef struct co_dockermc co_dockermc;
 co_dockermc *co_dockermc_create(int seed, int max_searches, int searches_per_eval, float c_puct, float epsilon,

@@ -136,6 +136,9 @@ def lib():
     L.co_tourney_counters.argtypes = [vp, C.POINTER(C.c_int64)]
     L.co_uniform_below.argtypes = [vp, C.c_uint32]
     L.co_uniform_below.restype = C.c_uint32
+    L.co_census.argtypes = [C.POINTER(C.c_int64)]
+    L.co_census.restype = None
+    L.co_census_reset.restype = None
     _lib = L
     return L
 
@@ -456,3 +459,31 @@ class Tourney:
 def uniform_below(gen, n):
     """std::uniform_int_distribution<int32_t>(0, n - 1)(gen) as restated in the oracle"""
     return int(lib().co_uniform_below(gen._g, n))
+
+
+# ------------------------------------------------------------------ census
+# corintho_oracle.h CO_CENSUS_*, in order.  The last two are maxima, the rest counts.
+CENSUS_NAMES = (
+    "deduced_win", "deduced_draw", "deduced_loss",
+    "score_drawn_child", "score_visited_child", "score_closed_child", "score_unvisited_edge",
+    "search_retreat_below", "search_retreat_root", "search_leaf_drawn", "search_leaf_lost",
+    "search_new_first_child", "search_new_behind_sibling",
+    "iter_rerequest",
+    "move_won", "move_lost", "move_drawn_root", "move_opening_reset", "move_opening", "move_normal_reset", "move_normal",
+    "move_tie_by_eval", "move_drawn_child",
+    "opp_move_found", "opp_move_new_root",
+    "game_drawn", "game_decisive", "match_drawn", "match_decisive",
+    "max_plies", "max_path",
+)
+CENSUS_MAXIMA = ("max_plies", "max_path")
+
+
+def census():
+    """{branch: times taken since census_reset()} over everything this process ran on the oracle"""
+    out = (C.c_int64 * len(CENSUS_NAMES))()
+    lib().co_census(out)
+    return {k: int(out[i]) for i, k in enumerate(CENSUS_NAMES)}
+
+
+def census_reset():
+    lib().co_census_reset()

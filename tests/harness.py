@@ -43,6 +43,26 @@ def hash_net(states, salt=0):
     return ev, pr
 
 
+def peaked_net(power=32.0, value_scale=None, value_const=None, salt=0):
+    """hash_net sharpened: priors raised to `power` and renormalised over the 96 moves, the value scaled by
+    `value_scale` or replaced by `value_const`.  A function of the 70-float row alone, computed in float64 and
+    rounded once to float32.  Nearly all of a node's prior sits on one move, so a few simulations run down long
+    forced lines -- which hash_net and uniform_net, spreading them over the root's children, cannot."""
+    assert (value_scale is None) != (value_const is None)
+
+    def net(states):
+        ev, pr = hash_net(states, salt)
+        p = pr.astype(np.float64) ** float(power)
+        p = np.maximum(p / p.sum(axis=1, keepdims=True), 1e-30)  # no prior rounds to 0: a node's legal ones never sum to 0
+        if value_const is not None:
+            v = np.full(states.shape[0], float(value_const), np.float64)
+        else:
+            v = ev.astype(np.float64) * float(value_scale)
+        return v.astype(np.float32), p.astype(np.float32)
+
+    return net
+
+
 def random_net_factory(seed=12345):
     """eval ~ U(-1,1), probs ~ U(0,1) normalised -- the kind of stand-in the
     reference tests use (selfplayer_test.cpp:31-55).  NOT state-determined."""
