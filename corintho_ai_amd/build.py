@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libcorintho_hip.so")
 SOURCES = ["engine.hip", "nn_mlp.hip", "nn_mlp_split.hip", "nn_rescnn.hip", "nn_train.hip", "nn_train_mlp.hip", "nn_train_conv.hip",
-           "nn_train_opt.hip", "nn_train_loss.hip", "nn_samples.hip"]
+           "nn_train_opt.hip", "nn_train_loss.hip", "nn_train_data.hip", "nn_samples.hip"]
 FLAGS = [
     "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-ffp-contract=off",
     "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-Wall", "-Wno-unused-function",

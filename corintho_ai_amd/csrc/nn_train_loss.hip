@@ -1,11 +1,63 @@
-// nn_train_loss.hip -- the loss off its defaults and the metrics of a fit (the definition: corintho_hip.h, "loss and
-// metrics").  ft_k_loss_opt is ft_k_loss's row loop (nn_train.hip) with the loss weights, label smoothing and the Huber
-// value loss as arguments; a fit at the defaults never launches it.  ft_k_metrics reads the same head outputs H, one
-// wavefront per row, and ft_k_metrics_reduce sums the rows' terms in the fixed order of ft_colsum: no atomics, so a
-// call's metrics are bitwise reproducible.
+// nn_train_loss.hip -- every loss kernel of a fit, the metrics, and what a call reports (FtLoss, nn_train.h; the
+// definition: corintho_hip.h, "loss and metrics").  ft_k_loss is the reference's value_mse + 0.25 policy_cce;
+// ft_k_loss_opt is its row loop with the loss weights, label smoothing and the Huber value loss as arguments, and a fit
+// at the defaults never launches it; ft_k_head_reduce sums either one's rows.  FtLoss::terms is the one function that
+// chooses among them.  ft_k_metrics reads the same head outputs H, one wavefront per row, and ft_k_metrics_reduce sums
+// the rows' terms in the fixed order of ft_colsum: no atomics, so a call's metrics are bitwise reproducible.  The host
+// part owns the loss arguments, the per-batch loss and metric sums on the device and the host, and turns them into
+// the losses and the ca_fit_metrics a call returns.
 #include <math.h>
 
 #include "nn_train.h"
+
+/* Per row of the heads' outputs H[r] (96 logits, value at 96): the loss terms and the gradients of the batch loss
+ * value_mse + 0.25 * policy_cce (means over the B rows) with respect to the logits and to v:
+ *   Hd[r][0..95] = 0.25 (softmax * sum t - t) / B,  Hd[r][96] = 2 (tanh v - z)(1 - tanh^2 v) / B,
+ *   Hd[r][97] = (tanh v - z)^2,  Hd[r][98] = -sum_j t_j log_softmax_j  (from the logits, as Keras does)
+ * 1 - tanh^2 v is one fused multiply-add, rounded once.  As 1 - (t * t) it is biased where tanh saturates: with t = 1 - a
+ * the product 1 - 2a + a^2 rounds to 1 - 2a whenever a^2 is under half an ulp of one (a < 1.7e-4, |v| > 4.7), so every
+ * such row's factor 2a - a^2 comes out a / 2 of itself too large, all rows the same way (measured 1e-5 to 3e-5 of the
+ * value head's whole gradient on a saturated head).
+ * WEIGHTED: every one of these 99 terms times the row's sample weight wts[rows[r]] (Keras's sample_weight under
+ * SUM_OVER_BATCH_SIZE: the divisor stays B); the unweighted instantiation never reads that last operand and has no such
+ * multiply. */
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void ft_k_loss(const float *__restrict__ H, const int32_t *__restrict__ rows, int B,
+                                                const float *__restrict__ evals, const float *__restrict__ probs,
+                                                float *__restrict__ Hd, const float *__restrict__ wts) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= B) return;
+  const float *h = H + (long)r * FT_PADW;
+  const float *t = probs + (long)rows[r] * CA_NUM_MOVES;
+  float *d = Hd + (long)r * FT_PADW;
+  float m = -INFINITY;
+  for (int j = 0; j < CA_NUM_MOVES; ++j) m = h[j] > m ? h[j] : m;
+  float se = 0.0f;
+  for (int j = 0; j < CA_NUM_MOVES; ++j) se += expf(h[j] - m);
+  const float lse = m + logf(se);
+  float st = 0.0f, ce = 0.0f;
+  for (int j = 0; j < CA_NUM_MOVES; ++j) {
+    st += t[j];
+    ce += t[j] * (lse - h[j]);
+  }
+  const float inv_b = 1.0f / (float)B;
+  if (!WEIGHTED) {
+    for (int j = 0; j < CA_NUM_MOVES; ++j) d[j] = 0.25f * (expf(h[j] - lse) * st - t[j]) * inv_b;
+    const float tv = tanhf(h[96]);
+    const float err = tv - evals[rows[r]];
+    d[96] = 2.0f * err * fmaf(-tv, tv, 1.0f) * inv_b;
+    d[97] = err * err;
+    d[98] = ce;
+  } else { /* today's terms, each rounded as above, then times w: a weight of 1 changes no bit, one of 2 doubles exactly */
+    const float w = wts[rows[r]];
+    for (int j = 0; j < CA_NUM_MOVES; ++j) d[j] = 0.25f * (expf(h[j] - lse) * st - t[j]) * inv_b * w;
+    const float tv = tanhf(h[96]);
+    const float err = tv - evals[rows[r]];
+    d[96] = 2.0f * err * fmaf(-tv, tv, 1.0f) * inv_b * w;
+    d[97] = err * err * w;
+    d[98] = ce * w;
+  }
+}
 
 /* ft_k_loss with L: the smoothed target t' = t (1 - ls) + ls / 96 in place of t, the policy gradient times
  * policy_weight where ft_k_loss has 0.25f, the value gradient times value_weight, and with L.huber Keras's Huber(delta)
@@ -54,6 +106,26 @@ __global__ __launch_bounds__(256) void ft_k_loss_opt(const float *__restrict__ H
   d[96] = WEIGHTED ? gv * w : gv;
   d[97] = WEIGHTED ? lv * w : lv;
   d[98] = WEIGHTED ? ce * w : ce;
+}
+
+/* Column sums of Hd over the B rows (fixed order): the head biases' gradients (when g is given; the policy bias at
+ * off_bp, the value bias at off_bv) and the batch's value and policy loss sums (loss[0], loss[1]). */
+__global__ __launch_bounds__(1024) void ft_k_head_reduce(const float *__restrict__ Hd, int B, float *__restrict__ g,
+                                                        int off_bp, int off_bv, float *__restrict__ loss) {
+  __shared__ float red[(FT_BN_RG + 1) * 16];
+  const int f = blockIdx.x * 16 + (threadIdx.x & 15), rg = threadIdx.x >> 4;
+  float s = 0.0f;
+  if (f < 99)
+    for (int r = rg; r < B; r += FT_BN_RG) s += Hd[(long)r * FT_PADW + f];
+  s = ft_colsum(red, s);
+  if (rg != 0 || f >= 99) return;
+  if (f < 96) {
+    if (g) g[off_bp + f] = s;
+  } else if (f == 96) {
+    if (g) g[off_bv] = s;
+  } else {
+    loss[f - 97] = s;
+  }
 }
 
 /* the sum of v over the 64 lanes, to every lane: a butterfly of fixed shape (both lanes of a pair add the same two
@@ -132,19 +204,96 @@ __global__ __launch_bounds__(1024) void ft_k_metrics_reduce(const float *__restr
 }
 
 /* ------------------------------------------------------------------ host */
-void ft_loss_opt(rt_stream_t s, const float *H, const int32_t *rows, int B, const float *evals, const float *probs,
-                 float *Hd, const float *wts, const FtLossArgs &L) {
-  if (wts)
-    RT_LAUNCH(ft_k_loss_opt<true>, (B + 255) / 256, 256, s, H, rows, B, evals, probs, Hd, wts, L);
-  else
-    RT_LAUNCH(ft_k_loss_opt<false>, (B + 255) / 256, 256, s, H, rows, B, evals, probs, Hd, (const float *)nullptr, L);
+/* is the loss the reference's value_mse + 0.25 policy_cce?  Then a step runs the kernels that know of no other. */
+bool FtLoss::is_default() const {
+  return args.value_weight == 1.0f && args.policy_weight == 0.25f && args.label_smoothing == 0.0f &&
+         args.value_loss == CA_VALUE_LOSS_MSE;
 }
 
-void ft_metrics(rt_stream_t s, const float *H, const int32_t *rows, int B, const float *evals, const float *probs,
-                const float *wts, int top_k, float *mrow, float *out) {
-  if (wts)
-    RT_LAUNCH(ft_k_metrics<true>, (B + 3) / 4, 256, s, H, rows, B, evals, probs, wts, top_k, mrow);
+void FtLoss::terms(const FtShared &sh, const FtNet &net, const FtBatch &b, int B, bool grads, int slot) {
+  const float *H = sh.h;
+  const int grid = (B + 255) / 256;
+  if (!is_default()) {
+    const FtLossArgs L = {args.value_weight, args.policy_weight, args.label_smoothing, args.huber_delta,
+                          args.value_loss == CA_VALUE_LOSS_HUBER};
+    if (b.wts)
+      RT_LAUNCH(ft_k_loss_opt<true>, grid, 256, sh.s, H, b.rows, B, b.evals, b.probs, sh.hd, b.wts, L);
+    else
+      RT_LAUNCH(ft_k_loss_opt<false>, grid, 256, sh.s, H, b.rows, B, b.evals, b.probs, sh.hd, (const float *)nullptr, L);
+  } else if (b.wts)
+    RT_LAUNCH(ft_k_loss<true>, grid, 256, sh.s, H, b.rows, B, b.evals, b.probs, sh.hd, b.wts);
   else
-    RT_LAUNCH(ft_k_metrics<false>, (B + 3) / 4, 256, s, H, rows, B, evals, probs, (const float *)nullptr, top_k, mrow);
-  RT_LAUNCH(ft_k_metrics_reduce, 1, 1024, s, (const float *)mrow, B, out);
+    RT_LAUNCH(ft_k_loss<false>, grid, 256, sh.s, H, b.rows, B, b.evals, b.probs, sh.hd, (const float *)nullptr);
+  RT_LAUNCH(ft_k_head_reduce, FT_PADW / 16, 1024, sh.s, (const float *)sh.hd, B, grads ? sh.g : (float *)nullptr,
+            net.policy_bias(), net.value_bias(), loss.p + 2 * slot);
+}
+
+void FtLoss::metric_terms(const FtShared &sh, const FtBatch &b, int B, int slot) {
+  const float *H = sh.h;
+  if (b.wts)
+    RT_LAUNCH(ft_k_metrics<true>, (B + 3) / 4, 256, sh.s, H, b.rows, B, b.evals, b.probs, b.wts, top_k, mrow.p);
+  else
+    RT_LAUNCH(ft_k_metrics<false>, (B + 3) / 4, 256, sh.s, H, b.rows, B, b.evals, b.probs, (const float *)nullptr, top_k,
+              mrow.p);
+  RT_LAUNCH(ft_k_metrics_reduce, 1, 1024, sh.s, (const float *)mrow.p, B, metric.p + (size_t)FT_METRIC_W * slot);
+}
+
+void FtLoss::set_metrics(bool on, int32_t k) {
+  if (on) top_k = k;
+  metrics_on = on;
+  lastm = ca_fit_metrics{sizeof(ca_fit_metrics), top_k, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+}
+
+void FtLoss::ensure(int slots, bool metrics, int32_t max_batch, rt_stream_t s) {
+  if ((int)hloss.size() < 2 * slots) {
+    loss.alloc((size_t)2 * slots, s);
+    hloss.assign((size_t)2 * slots, 0.0f);
+  }
+  if (!metrics) return;
+  if (!mrow.p) mrow.alloc((size_t)max_batch * FT_METRIC_W, s);
+  if (hmetric.size() < (size_t)FT_METRIC_W * slots) {
+    metric.alloc((size_t)FT_METRIC_W * slots, s);
+    hmetric.assign((size_t)FT_METRIC_W * slots, 0.0f);
+  }
+}
+
+/* the call's metrics from its nb batches' sums, which losses() fetched: the batches added in float64 */
+void FtLoss::metrics_of(int nb, int32_t nr) {
+  double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int b = 0; b < nb; ++b)
+    for (int k = 0; k < 6; ++k) sum[k] += (double)hmetric[(size_t)FT_METRIC_W * b + k];
+  const double ws = sum[5];
+  auto mean = [&](int k) { return ws > 0.0 ? sum[k] / ws : 0.0; };
+  lastm = ca_fit_metrics{sizeof(ca_fit_metrics), top_k, nr, ws, mean(0), mean(1), mean(2), mean(3), mean(4)};
+}
+
+void FtLoss::losses(rt_stream_t s, const FtBatches &bs, double *out, float *per, FtReg reg, FtOpt &opt) {
+  const int nb = bs.nb;
+  const int32_t nr = bs.n_rows;
+  const bool with_r = reg != FtReg::none, each = reg == FtReg::per_batch;
+  rt_d2h(hloss.data(), loss.p, (size_t)2 * nb * sizeof(float), s);
+  if (with_r) opt.fetch(each ? nb : 1, s);
+  if (bs.metrics) rt_d2h(hmetric.data(), metric.p, (size_t)FT_METRIC_W * nb * sizeof(float), s);
+  rt_sync(s);
+  if (bs.metrics) metrics_of(nb, nr);
+  const float vw = args.value_weight, pw = args.policy_weight; /* 1.0f * lv has the bits of lv */
+  double sv = 0.0, sp = 0.0, sr = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    const int rb = bs.size(b);
+    const float lv = hloss[2 * b] / (float)rb, lp = hloss[2 * b + 1] / (float)rb;
+    if (per) {
+      per[3 * b] = with_r ? vw * lv + pw * lp + (float)opt.R(each ? b : 0) : vw * lv + pw * lp;
+      per[3 * b + 1] = lv;
+      per[3 * b + 2] = lp;
+    }
+    sv += (double)lv * rb;
+    sp += (double)lp * rb;
+    if (with_r) sr += opt.R(each ? b : 0) * rb;
+  }
+  if (out) {
+    out[1] = nr ? sv / nr : 0.0;
+    out[2] = nr ? sp / nr : 0.0;
+    out[0] = (double)vw * out[1] + (double)pw * out[2];
+    if (with_r) out[0] += nr ? sr / nr : 0.0;
+  }
 }

@@ -1,6 +1,11 @@
-// nn_train_opt.hip -- the training step with fit options: the L1L2 regulariser, decoupled weight decay and gradient
-// clipping (the definition: corintho_hip.h, "fit options"; DESIGN.md, "Network training", "Fit options").  A fitter
-// whose options are all 0 never comes here: it runs ft_k_update (nn_train.hip) as before.
+// nn_train_opt.hip -- the end of a training step (FtStepEnd, nn_train.h): the update kernels, Adam's arguments with the
+// third slot and the averaged weights (ft_k_average_swap, ft_k_average_apply), and the fit options (FtOpt): the L1L2
+// regulariser, decoupled weight decay and gradient clipping (the definitions: corintho_hip.h, "Adam's arguments" and
+// "fit options"; DESIGN.md, "Network training").  FtStepEnd::step is the one function that chooses among the four
+// update kernels: ft_k_update at every default (one launch sums the split partials in a fixed order, applies Adam as TF
+// ResourceApplyAdam does and moves the moving statistics), ft_k_update_adam with Adam's arguments off theirs, and with
+// fit options on ft_k_opt_update or ft_k_opt_update_adam behind the options' two reducing launches.  A fitter whose
+// options are all 0 never touches FtOpt.
 //
 // The weight vector is cut into pieces of at most FT_PIECE floats that lie within one tensor; workgroup p owns piece p
 // in the two kernels that walk the weights.  Every sum is float64 and has a fixed shape: 256 values of a piece by a
@@ -171,6 +176,71 @@ __global__ __launch_bounds__(FT_PIECE) void ft_k_opt_update_adam(const int4 *__r
   ft_opt_update_piece<true>(pieces, w, m, v, gsum, sidx, stat, scale, clipvalue, decay, lr_t, A);
 }
 
+/* The end of a step, one thread per weight of the nw: its gradient is the sum of its partials in order.  sidx[i] < 0:
+ * a trainable weight with ns0 (FT_SPLIT0), ns1 (FT_SPLIT1) or one (FT_WHOLE) partial, Adam (TF ResourceApplyAdam,
+ * epsilon outside the root; ft_adam, nn_train.h); sidx[i] >= 0: a moving statistic, moved toward the batch statistic
+ * stat[sidx[i]] with momentum 0.99.  apply = 0: write the summed gradient to gout only.  PARAM: with Adam's arguments A,
+ * and a moving statistic's new value goes to the average as well. */
+template <bool PARAM>
+__device__ __forceinline__ void ft_update_weight(float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
+                                                 const float *__restrict__ g, int nw, int ns0, int ns1,
+                                                 const int32_t *__restrict__ sidx, const float *__restrict__ stat,
+                                                 float lr_t, int apply, float *__restrict__ gout, const FtAdamArgs &A) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nw) return;
+  const int si = sidx[i];
+  const int nsplit = si == FT_SPLIT0 ? ns0 : si == FT_SPLIT1 ? ns1 : 1;
+  if (!apply) {
+    float s = 0.0f;
+    if (si < 0)
+      for (int k = 0; k < nsplit; ++k) s += g[(long)k * nw + i];
+    gout[i] = s;
+    return;
+  }
+  if (si >= 0) {
+    const float mv = w[i];
+    const float nv = mv - (mv - stat[si]) * 0.01f;
+    w[i] = nv;
+    if (PARAM && A.a) A.a[i] = nv;
+    return;
+  }
+  float s = 0.0f;
+  for (int k = 0; k < nsplit; ++k) s += g[(long)k * nw + i];
+  ft_adam<PARAM>(w, m, v, i, w[i], s, lr_t, A);
+}
+
+/* the Adam defaults: the kernel of a step before Adam had arguments, instruction for instruction */
+__global__ __launch_bounds__(256) void ft_k_update(float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
+                                                  const float *__restrict__ g, int nw, int ns0, int ns1,
+                                                  const int32_t *__restrict__ sidx, const float *__restrict__ stat,
+                                                  float lr_t, int apply, float *__restrict__ gout) {
+  ft_update_weight<false>(w, m, v, g, nw, ns0, ns1, sidx, stat, lr_t, apply, gout, FtAdamArgs{});
+}
+
+__global__ __launch_bounds__(256) void ft_k_update_adam(float *__restrict__ w, float *__restrict__ m, float *__restrict__ v,
+                                                       const float *__restrict__ g, int nw, int ns0, int ns1,
+                                                       const int32_t *__restrict__ sidx, const float *__restrict__ stat,
+                                                       float lr_t, FtAdamArgs A) {
+  ft_update_weight<true>(w, m, v, g, nw, ns0, ns1, sidx, stat, lr_t, 1, (float *)nullptr, A);
+}
+
+/* w <-> a, every entry of the weight vector (ca_fitter_swap_average) */
+__global__ __launch_bounds__(256) void ft_k_average_swap(float *__restrict__ w, float *__restrict__ a, int nw) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nw) return;
+  const float t = w[i];
+  w[i] = a[i];
+  a[i] = t;
+}
+
+/* w := a on the trainable weights (ca_fitter_apply_average) */
+__global__ __launch_bounds__(256) void ft_k_average_apply(float *__restrict__ w, const float *__restrict__ a,
+                                                         const int32_t *__restrict__ sidx, int nw) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nw) return;
+  if (sidx[i] < 0) w[i] = a[i];
+}
+
 /* ------------------------------------------------------------------ host */
 void FtOpt::plan(const std::vector<FtTensor> &tensors, int nw, rt_stream_t s) {
   if (pieces.p) return;
@@ -222,21 +292,146 @@ void FtOpt::regularization(rt_stream_t s, const float *w, int slot) {
             scale.p, out.p + 4 + slot, (FtOptStats *)nullptr);
 }
 
-void FtOpt::step(rt_stream_t s, float *w, float *m, float *v, float *gsum, const int32_t *sidx, const float *stat, float lr,
-                 float lr_t, int slot, const FtAdamArgs *adam) {
+void FtOpt::reduce(rt_stream_t s, const float *w, float *gsum, int slot) {
   const int mode = o.clipvalue > 0.0f ? FT_OPT_MODE_VALUE : o.clipnorm > 0.0f ? FT_OPT_MODE_NORM
                  : o.global_clipnorm > 0.0f ? FT_OPT_MODE_GLOBAL : FT_OPT_MODE_NONE;
   const float clip = mode == FT_OPT_MODE_VALUE ? o.clipvalue : mode == FT_OPT_MODE_NORM ? o.clipnorm : o.global_clipnorm;
-  RT_LAUNCH(ft_k_opt_partials, npieces, FT_PIECE, s, (const int4 *)pieces.p, (const float *)w, gsum, o.l1, o.l2,
-            2.0f * o.l2, ft_opt_reg_mask(o), o.clipvalue, 0, part.p);
+  RT_LAUNCH(ft_k_opt_partials, npieces, FT_PIECE, s, (const int4 *)pieces.p, w, gsum, o.l1, o.l2, 2.0f * o.l2,
+            ft_opt_reg_mask(o), o.clipvalue, 0, part.p);
   RT_LAUNCH(ft_k_opt_combine, 1, 1024, s, (const double *)part.p, (const int32_t *)tfirst.p, nt, mode, clip, scale.p,
             out.p + 4 + slot, (FtOptStats *)out.p);
-  if (adam)
-    RT_LAUNCH(ft_k_opt_update_adam, npieces, FT_PIECE, s, (const int4 *)pieces.p, w, m, v, (const float *)gsum, sidx, stat,
-              (const float *)scale.p, o.clipvalue, lr * o.weight_decay, lr_t, *adam);
-  else
-    RT_LAUNCH(ft_k_opt_update, npieces, FT_PIECE, s, (const int4 *)pieces.p, w, m, v, (const float *)gsum, sidx, stat,
-              (const float *)scale.p, o.clipvalue, lr * o.weight_decay, lr_t);
 }
 
 void FtOpt::fetch(int n, rt_stream_t s) { rt_d2h(hout.data(), out.p, (4 + (size_t)n) * sizeof(double), s); }
+
+/* ------------------------------------------------------------------ the end of a step */
+/* is every one of Adam's arguments at its default?  Then a step runs the kernels that know of none. */
+bool FtStepEnd::adam_default() const {
+  return adam.beta_1 == 0.9f && adam.beta_2 == 0.999f && adam.epsilon == 1e-7f && !adam.amsgrad && !(adam.ema_momentum > 0.0f);
+}
+
+/* Adam's arguments of the step that brings the step count to `step`.  The third slot and the average get their memory
+ * at their first use (zeroed, on the stream); an invalid average starts as the weights before the step. */
+FtAdamArgs FtStepEnd::adam_args(int64_t step) {
+  FtAdamArgs A = {adam.beta_1, adam.beta_2, adam.epsilon, adam.ema_momentum, nullptr, nullptr, 0};
+  if (adam.amsgrad) {
+    if (!vhat.p) vhat.alloc(W.nw, s);
+    A.h = vhat.p;
+  }
+  if (adam.ema_momentum > 0.0f) {
+    if (!avg.p) avg.alloc(W.nw, s);
+    if (!avg_valid) rt_d2d(avg.p, W.w, (size_t)W.nw * sizeof(float), s);
+    avg_valid = true;
+    A.a = avg.p;
+    A.overwrite = adam.ema_overwrite_frequency > 0 && step % adam.ema_overwrite_frequency == 0;
+  }
+  return A;
+}
+
+void FtStepEnd::sum_gradient(FtSplits ns) {
+  RT_LAUNCH(ft_k_update, (W.nw + 255) / 256, 256, s, W.w, W.m, W.v, (const float *)W.g, W.nw, ns.rows, ns.pixels, W.sidx,
+            W.stat, 0.0f, 0, W.gsum);
+}
+
+void FtStepEnd::step(FtSplits ns, float lr, int64_t step, int slot) {
+  /* Keras Adam: local_step = iterations + 1, lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), in float32 */
+  const float t = (float)step;
+  const float lr_t = lr * (sqrtf(1.0f - powf(adam.beta_2, t)) / (1.0f - powf(adam.beta_1, t)));
+  const bool adam_on = !adam_default();
+  const FtAdamArgs A = adam_on ? adam_args(step) : FtAdamArgs{};
+  if (!ft_options_on(opt.o)) { /* one launch: the partials summed, Adam, the moving statistics */
+    if (adam_on)
+      RT_LAUNCH(ft_k_update_adam, (W.nw + 255) / 256, 256, s, W.w, W.m, W.v, (const float *)W.g, W.nw, ns.rows, ns.pixels,
+                W.sidx, W.stat, lr_t, A);
+    else
+      RT_LAUNCH(ft_k_update, (W.nw + 255) / 256, 256, s, W.w, W.m, W.v, (const float *)W.g, W.nw, ns.rows, ns.pixels,
+                W.sidx, W.stat, lr_t, 1, W.gsum);
+    return;
+  }
+  /* with options: the summed gradient to gsum as ca_fitter_gradients has it, then steps 1 to 4 */
+  sum_gradient(ns);
+  opt.reduce(s, W.w, W.gsum, slot);
+  const float clipvalue = opt.o.clipvalue, decay = lr * opt.o.weight_decay;
+  if (adam_on)
+    RT_LAUNCH(ft_k_opt_update_adam, opt.npieces, FT_PIECE, s, (const int4 *)opt.pieces.p, W.w, W.m, W.v,
+              (const float *)W.gsum, W.sidx, W.stat, (const float *)opt.scale.p, clipvalue, decay, lr_t, A);
+  else
+    RT_LAUNCH(ft_k_opt_update, opt.npieces, FT_PIECE, s, (const int4 *)opt.pieces.p, W.w, W.m, W.v, (const float *)W.gsum,
+              W.sidx, W.stat, (const float *)opt.scale.p, clipvalue, decay, lr_t);
+}
+
+FtReg FtStepEnd::begin(int nb) {
+  last = ca_fit_stats{sizeof(ca_fit_stats), 0, 0, 0, 0.0, 0.0, 0.0};
+  if (!ft_options_on(opt.o)) return FtReg::none;
+  opt.begin(nb, s);
+  return FtReg::per_batch;
+}
+
+void FtStepEnd::finish(int nb) {
+  if (!ft_options_on(opt.o)) return;
+  const double *st = opt.hout.data(); /* the statistics came back with the losses */
+  last.steps = nb;
+  last.clipped_steps = (int64_t)st[3];
+  last.regularization = st[0] / nb;
+  last.grad_norm = st[1] / nb;
+  last.grad_norm_max = st[2];
+}
+
+FtReg FtStepEnd::begin_evaluate() {
+  if (!ft_regularized(opt.o)) return FtReg::none;
+  opt.begin(1, s);
+  opt.regularization(s, W.w, 0);
+  return FtReg::once;
+}
+
+/* Those kernels take a weight for a moving statistic by its tensor's class and ft_k_update by its code: the two tables
+ * must agree. */
+void FtStepEnd::plan_options(const FtNet &net) {
+  if (opt.pieces.p) return;
+  std::vector<FtTensor> tt;
+  std::vector<int32_t> si;
+  net.tensor_table(tt);
+  net.update_table(si);
+  for (const FtTensor &t : tt)
+    for (int32_t i = t.off; i < t.off + t.count && i >= 0 && i < W.nw; ++i)
+      if ((si[i] >= 0) != (t.cls == CA_TENSOR_MOVING))
+        throw CaError(CA_ERR_INTERNAL, "ca_fitter: tensor_table and update_table disagree about the moving statistics");
+  opt.plan(tt, W.nw, s);
+}
+
+void FtStepEnd::slots_replaced() {
+  if (vhat.p) rt_memset(vhat.p, 0, W.nw * sizeof(float), s);
+}
+
+void FtStepEnd::need_average(const char *who) const {
+  if (!avg_valid) throw CaError(CA_ERR_STATE, std::string(who) + ": the fitter has no average (no step with ema_momentum > 0, no ca_fitter_set_slot)");
+}
+
+void FtStepEnd::set_slot(int32_t which, const float *values) {
+  DevBuf<float> &b = which == CA_SLOT_VHAT ? vhat : avg;
+  if (!b.p) b.alloc(W.nw, s);
+  rt_h2d(b.p, values, W.nw * sizeof(float), s);
+  rt_sync(s);
+  if (which == CA_SLOT_AVERAGE) avg_valid = true;
+}
+
+void FtStepEnd::get_slot(int32_t which, float *values) {
+  if (which == CA_SLOT_AVERAGE) need_average("ca_fitter_get_slot");
+  const DevBuf<float> &b = which == CA_SLOT_VHAT ? vhat : avg;
+  if (!b.p) { /* a third slot that no step has used yet */
+    for (int i = 0; i < W.nw; ++i) values[i] = 0.0f;
+    return;
+  }
+  rt_d2h(values, b.p, W.nw * sizeof(float), s);
+  rt_sync(s);
+}
+
+void FtStepEnd::swap_average() {
+  need_average("ca_fitter_swap_average");
+  RT_LAUNCH(ft_k_average_swap, (W.nw + 255) / 256, 256, s, W.w, avg.p, W.nw);
+}
+
+void FtStepEnd::apply_average() {
+  need_average("ca_fitter_apply_average");
+  RT_LAUNCH(ft_k_average_apply, (W.nw + 255) / 256, 256, s, W.w, (const float *)avg.p, W.sidx, W.nw);
+}

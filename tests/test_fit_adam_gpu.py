@@ -1,4 +1,4 @@
-"""Adam's arguments on the MI355X (csrc/nn_train.hip ft_k_update_adam, csrc/nn_train_opt.hip ft_k_opt_update_adam, the
+"""Adam's arguments on the MI355X (csrc/nn_train_opt.hip ft_k_update_adam and ft_k_opt_update_adam, the
 swap and apply kernels; include/corintho_hip.h, "Adam's arguments").  With every argument at its default a step is what
 it was; off the defaults the slots are what the definition says, judged from the device's own gradients() and pre-step
 state pushed through tests/fit_ref_adam.py: m', v', h' and a' are sums, differences, products and a maximum only, so the

@@ -1,4 +1,4 @@
-"""The fitter's packed data set on the MI355X (csrc/nn_train.hip ft_k_assemble, corintho_ai_amd.fit): un-augmented
+"""The fitter's packed data set on the MI355X (csrc/nn_train_data.hip ft_k_assemble, corintho_ai_amd.fit): un-augmented
 samples on the device whose 8 n virtual rows -- row v is sample v // 8 under symmetry v % 8 -- must be, float for float,
 the rows of the host expansion (`expand_samples`, the host routine ca_expand_samples).  Everything downstream of the
 batch gather is the same code launched the same way, so every comparison between the two forms here is of bytes."""

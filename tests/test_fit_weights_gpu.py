@@ -1,5 +1,5 @@
-"""Per-sample weights in the fitter on the MI355X (csrc/nn_train.hip: ft_k_loss<true>, ft_k_assemble<true>; Keras's
-model.fit(sample_weight=...)), for both networks.  Weights of 1 and of 2 are compared by bytes (a multiply by 1 changes
+"""Per-sample weights in the fitter on the MI355X (csrc/nn_train_loss.hip ft_k_loss<true>,
+csrc/nn_train_data.hip ft_k_assemble<true>; Keras's model.fit(sample_weight=...)), for both networks.  Weights of 1 and of 2 are compared by bytes (a multiply by 1 changes
 no bit, a power of two scales exactly through the linear backward pass); general weights go against the float64
 restatement of tests/fit_ref_weighted.py by the rule of tests/test_fit_gpu.py::test_gradients_of_one_batch: the
 device's error is at most 4 x the float32 restatement's own error, plus 2e-5 of the tensor's largest entry."""
