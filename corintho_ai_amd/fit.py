@@ -41,21 +41,17 @@ is fitted by the kernels that know of none.
 Fit options (FitOptions; include/corintho_hip.h "fit options" is the definition): what the reference's model declares and
 leaves at zero -- kernel_regularizer=L1L2() on its hidden Dense layers -- and what its Adam's constructor takes:
     res = fit_resident(fitter, weights, options=FitOptions(l2=1e-4, weight_decay=1e-4, global_clipnorm=1.0))
-l1, l2: the regulariser, on the trunk kernels (regularize=0) or on all kernels (1); its R(w) is part of "loss" and
-"val_loss", as Keras adds layer losses.  weight_decay: decoupled, on the kernels, times the learning rate.  clipvalue,
-clipnorm (per tensor), global_clipnorm: at most one.  Everything runs in the device's step (csrc/nn_train_opt.hip); with
-every option 0 a step is what it is without them, kernel for kernel and bit for bit.  fit_resident puts the fitter into
-the state its call asks for: options=None switches a Fitter's options off.  With an option on, `history` gains
-"regularization_loss", "grad_norm" (both means over the epoch's steps) and "clipped_steps", one entry per epoch.
+The regulariser's R(w) is part of "loss" and "val_loss", as Keras adds layer losses; at most one clip mode may be set.
+With an option on, `history` gains "regularization_loss", "grad_norm" (both means over the epoch's steps) and
+"clipped_steps", one entry per epoch.
 
 Adam's arguments (AdamOptions; include/corintho_hip.h "Adam's arguments" is the definition): beta_1, beta_2, epsilon,
 amsgrad (a third slot, "vhat") and averaged weights (Keras's use_ema, ema_momentum, ema_overwrite_frequency):
     res = fit_resident(fitter, weights, adam=AdamOptions(beta_2=0.99, amsgrad=True, ema_momentum=0.99))
-adam=None means the defaults, and a fitter left with other values is set back.  With ema_momentum > 0 a fit is Keras 3's
-SwapEMAWeights(swap_on_epoch=True) plus the finalisation its fit() does: every epoch is judged by the averaged weights
-(swap, evaluate, swap back), so "val_loss", the best-epoch checkpoint and the plateau rule see those numbers and
-best_weights are the averaged weights of the best epoch; at the end the average is applied, so `weights` and the fitter
-hold it.  With every argument at its default a step is what it is without them, kernel for kernel and bit for bit.
+With ema_momentum > 0 a fit is Keras 3's SwapEMAWeights(swap_on_epoch=True) plus the finalisation its fit() does: every
+epoch is judged by the averaged weights (swap, evaluate, swap back), so "val_loss", the best-epoch checkpoint and the
+plateau rule see those numbers and best_weights are the averaged weights of the best epoch; at the end the average is
+applied, so `weights` and the fitter hold it.
 
 The loss and the metrics (LossOptions; include/corintho_hip.h "loss and metrics" is the definition): the other half of
 the reference's model.compile() -- loss_weights, CategoricalCrossentropy(label_smoothing=), Huber(delta) on the value head
@@ -63,17 +59,21 @@ and metrics=:
     res = fit_resident(fitter, weights, loss=LossOptions(value_weight=0.7, policy_weight=1.3, label_smoothing=0.1,
                                                          value_loss="huber", huber_delta=0.5), metrics={"top_k": 3})
 "loss" and "val_loss" are value_weight x value + policy_weight x policy (+ R), and the checkpoint and the plateau rule see
-them; "value_loss" and "policy_loss" stay the means of the two terms.  loss=None means the reference's loss, decided by
-the call.  With metrics the history gains METRIC_HISTORY_KEYS, one entry per epoch: how often the network's best move is
-the target's (and within its top k), the value head's mean absolute error, and the entropies of the policy and of its
-target -- during the epoch from each step's own forward, as Keras logs them, and "val_" + each from the validation pass
-(the averaged weights' with ema_momentum > 0).  They come from two launches on the head outputs a step already has;
-with metrics off nothing is launched, and on or off the losses and the weights of a fit are the same bytes.
-Fitter.predict(rows) reads the heads themselves.
+them; "value_loss" and "policy_loss" stay the means of the two terms.  With metrics the history gains
+METRIC_HISTORY_KEYS, one entry per epoch: how often the network's best move is the target's (and within its top k), the
+value head's mean absolute error, and the entropies of the policy and of its target -- during the epoch from each step's
+own forward, as Keras logs them, and "val_" + each from the validation pass (the averaged weights' with
+ema_momentum > 0).  On or off, the losses and the weights of a fit are the same bytes.  Fitter.predict(rows) reads the
+heads themselves.
+
+The three families work alike.  Each is a frozen dataclass whose fields are declared once (_opt); a call takes an
+instance, a dict of its fields or None, and the call decides: None means the family's defaults, and a fitter left with
+other values is set back.  With a family at its defaults a step is what it is without it, kernel for kernel and bit for
+bit.  A backend other than Fitter that lacks a family's setter serves the calls that ask for that family's defaults.
 """
 import ctypes as C
 import inspect
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields, replace
 
 import numpy as np
 
@@ -115,125 +115,179 @@ def _packed(state_policy, outcome, who):
     return sp, oc
 
 
-OPTION_NAMES = ("l1", "l2", "weight_decay", "clipvalue", "clipnorm", "global_clipnorm")
-OPTION_HISTORY_KEYS = ("regularization_loss", "grad_norm", "clipped_steps")
+# ---- the three option families: one description of a field, and everything else from it ----
+_NUMBER = (int, float, np.floating, np.integer)
+_BOOL = (bool, np.bool_)
+# the kinds of float: what the float32 value must satisfy, and how the error says it
+_FLOAT_KINDS = {"nonneg": (lambda x: np.isfinite(x) and x >= 0, "be finite and >= 0"),
+                "unit": (lambda x: 0 <= x < 1, "lie in [0, 1)"),
+                "positive": (lambda x: np.isfinite(x) and x > 0, "be finite and > 0")}
+
+
+def _opt(default, kind, arg=None):
+    """one field of a family: its default, its kind -- "nonneg", "unit" or "positive" (a float), "bool", "int" (arg: the
+    bounds, both included) or "enum" (arg: {name: the C value}) -- and, as the field's own name, the name of the field
+    of the C struct"""
+    return field(default=default, metadata={"kind": kind, "arg": arg})
+
+
+def _narrow(x):
+    with np.errstate(over="ignore", under="ignore"):
+        return np.float32(x)
+
+
+class _Family:
+    """What FitOptions, AdamOptions and LossOptions share.  A family names itself in errors (WHO), the keyword of fit()
+    that takes it (ARG; the backend's setter is "set_" + ARG) and its C struct (STRUCT), and declares each field once with
+    _opt(); a rule that spans fields is the family's own _rules()."""
+
+    @classmethod
+    def _table(cls):
+        return [(f.name, f.metadata["kind"], f.metadata["arg"], f.default) for f in fields(cls)]
+
+    def check(self):
+        """ValueError unless the values are ones the device takes (judged in float32, as it does); returns self"""
+        for name, kind, arg, _ in self._table():
+            x, bad = getattr(self, name), None
+            if kind in _FLOAT_KINDS:
+                ok, text = _FLOAT_KINDS[kind]
+                if isinstance(x, _BOOL) or not isinstance(x, _NUMBER) or not np.isfinite(x):
+                    bad = "must be a finite number"
+                elif not ok(_narrow(x)):
+                    bad = "must %s in float32" % text
+            elif kind == "bool":
+                if not isinstance(x, _BOOL) and x not in (0, 1):
+                    bad = "must be a bool"
+            elif kind == "int":
+                if isinstance(x, _BOOL) or not isinstance(x, (int, np.integer)) or not arg[0] <= x <= arg[1]:
+                    bad = "must be an integer in %d..%d" % arg
+            elif not isinstance(x, str) or x not in arg:
+                bad = "must be %s" % " or ".join('"%s"' % c for c in arg)
+            if bad:
+                raise ValueError("%s: %s %s, got %r" % (self.WHO, name, bad, x))
+        self._rules()
+        return self
+
+    def _rules(self):
+        pass
+
+    def _seen(self):
+        """the values as the device sees them"""
+        return tuple(_narrow(getattr(self, name)) if kind in _FLOAT_KINDS else getattr(self, name)
+                     for name, kind, _, _ in self._table())
+
+    def is_default(self):
+        """is every value at its default (in float32, as the device sees them)"""
+        return self._seen() == type(self)()._seen()
+
+    def as_dict(self):
+        as_type = {"bool": bool, "int": int, "enum": str}
+        return {name: as_type.get(kind, float)(getattr(self, name)) for name, kind, _, _ in self._table()}
+
+    @classmethod
+    def parse(cls, x):
+        """None or an instance (or a mapping of its fields), checked; None stays None"""
+        if x is None:
+            return None
+        if isinstance(x, dict):
+            unknown = sorted(set(x) - {f.name for f in fields(cls)})
+            if unknown:
+                raise ValueError("%s: unknown %s" % (cls.WHO, ", ".join(unknown)))
+            x = cls(**x)
+        if not isinstance(x, cls):
+            raise ValueError("fit: %s must be %s %s, a dict of its fields or None, got %r"
+                             % (cls.ARG, "an" if cls.__name__[0] in "AEIOU" else "a", cls.__name__, x))
+        return x.check()
+
+    def to_c(self):
+        """the family's C struct, the floats rounded to float32"""
+        as_c = {"bool": lambda x, _: int(bool(x)), "int": lambda x, _: int(x), "enum": lambda x, arg: arg[x]}
+        return self.STRUCT(struct_size=C.sizeof(self.STRUCT),
+                           **{name: as_c.get(kind, lambda x, _: float(_narrow(x)))(getattr(self, name), arg)
+                              for name, kind, arg, _ in self._table()})
+
+    @classmethod
+    def from_c(cls, c):
+        from_c = {"bool": lambda x, _: bool(x), "int": lambda x, _: int(x),
+                  "enum": lambda x, arg: {v: k for k, v in arg.items()}[int(x)]}
+        return cls(**{name: from_c.get(kind, lambda x, _: float(x))(getattr(c, name), arg)
+                      for name, kind, arg, _ in cls._table()})
 
 
 @dataclass(frozen=True)
-class FitOptions:
+class FitOptions(_Family):
     """ca_fit_options: every value 0 is off.  The device takes the values in float32."""
-    l1: float = 0.0
-    l2: float = 0.0
-    regularize: int = 0          # 0: l1 and l2 on the trunk kernels, 1: on all kernels
-    weight_decay: float = 0.0
-    clipvalue: float = 0.0
-    clipnorm: float = 0.0
-    global_clipnorm: float = 0.0
+    WHO, ARG, STRUCT = "fit options", "options", _lib.CaFitOptions
+    l1: float = _opt(0.0, "nonneg")
+    l2: float = _opt(0.0, "nonneg")
+    regularize: int = _opt(0, "int", (0, 1))  # 0: l1 and l2 on the trunk kernels, 1: on all kernels
+    weight_decay: float = _opt(0.0, "nonneg")
+    clipvalue: float = _opt(0.0, "nonneg")
+    clipnorm: float = _opt(0.0, "nonneg")
+    global_clipnorm: float = _opt(0.0, "nonneg")
 
-    def check(self):
-        """ValueError unless the options are ones the device takes; returns self"""
-        for k in OPTION_NAMES:
-            x = getattr(self, k)
-            if not isinstance(x, (int, float, np.floating, np.integer)) or not np.isfinite(x) or x < 0:
-                raise ValueError("fit options: %s must be finite and >= 0, got %r" % (k, x))
-            with np.errstate(over="ignore"):
-                narrow = np.float32(x)
-            if not np.isfinite(narrow):
-                raise ValueError("fit options: %s = %r is not finite in float32" % (k, x))
-        if self.regularize not in (0, 1):
-            raise ValueError("fit options: regularize must be 0 (trunk kernels) or 1 (all kernels), got %r" % (self.regularize,))
-        if sum(1 for k in ("clipvalue", "clipnorm", "global_clipnorm") if np.float32(getattr(self, k)) > 0) > 1:
+    def _rules(self):
+        if sum(1 for k in ("clipvalue", "clipnorm", "global_clipnorm") if _narrow(getattr(self, k)) > 0) > 1:
             raise ValueError("fit options: at most one of clipvalue, clipnorm and global_clipnorm may be set")
-        return self
 
     def any(self):
         """is any option on (in float32, as the device sees them)"""
-        return any(np.float32(getattr(self, k)) > 0 for k in OPTION_NAMES)
+        return any(_narrow(getattr(self, k)) > 0 for k in OPTION_NAMES)
 
-    def as_dict(self):
-        d = {k: float(getattr(self, k)) for k in OPTION_NAMES}
-        d["regularize"] = int(self.regularize)
-        return d
+    def is_default(self):
+        """is every option off (regularize is not read then)"""
+        return not self.any()
 
 
-ADAM_NAMES = ("beta_1", "beta_2", "epsilon", "amsgrad", "ema_momentum", "ema_overwrite_frequency")
+OPTION_NAMES = tuple(name for name, kind, _, _ in FitOptions._table() if kind == "nonneg")
+OPTION_HISTORY_KEYS = ("regularization_loss", "grad_norm", "clipped_steps")
 SLOTS = {"vhat": 0, "average": 1}  # CA_SLOT_VHAT, CA_SLOT_AVERAGE
 
 
 @dataclass(frozen=True)
-class AdamOptions:
+class AdamOptions(_Family):
     """ca_fit_adam: the defaults are Keras Adam's.  The device takes the floats in float32."""
-    beta_1: float = 0.9
-    beta_2: float = 0.999
-    epsilon: float = 1e-7
-    amsgrad: bool = False
-    ema_momentum: float = 0.0    # 0: no averaged weights
-    ema_overwrite_frequency: int = 0
+    WHO, ARG, STRUCT = "adam", "adam", _lib.CaFitAdam
+    beta_1: float = _opt(0.9, "unit")
+    beta_2: float = _opt(0.999, "unit")
+    epsilon: float = _opt(1e-7, "positive")
+    amsgrad: bool = _opt(False, "bool")
+    ema_momentum: float = _opt(0.0, "unit")  # 0: no averaged weights
+    ema_overwrite_frequency: int = _opt(0, "int", (0, 2 ** 31 - 1))
 
-    def check(self):
-        """ValueError unless the arguments are ones the device takes (judged in float32, as it does); returns self"""
-        for k in ("beta_1", "beta_2", "epsilon", "ema_momentum"):
-            x = getattr(self, k)
-            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.floating, np.integer)) or not np.isfinite(x):
-                raise ValueError("adam: %s must be a finite number, got %r" % (k, x))
-        with np.errstate(over="ignore", under="ignore"):
-            b1, b2, eps, mom = (np.float32(getattr(self, k)) for k in ("beta_1", "beta_2", "epsilon", "ema_momentum"))
-        for k, x in (("beta_1", b1), ("beta_2", b2), ("ema_momentum", mom)):
-            if not 0 <= x < 1:
-                raise ValueError("adam: %s must lie in [0, 1) in float32, got %r" % (k, getattr(self, k)))
-        if not (np.isfinite(eps) and eps > 0):
-            raise ValueError("adam: epsilon must be finite and > 0 in float32, got %r" % (self.epsilon,))
-        if not isinstance(self.amsgrad, (bool, np.bool_)) and self.amsgrad not in (0, 1):
-            raise ValueError("adam: amsgrad must be a bool, got %r" % (self.amsgrad,))
-        k = self.ema_overwrite_frequency
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 0 or k >= 2 ** 31:
-            raise ValueError("adam: ema_overwrite_frequency must be an integer >= 0, got %r" % (k,))
-        if k > 0 and not mom > 0:
+    def _rules(self):
+        if self.ema_overwrite_frequency > 0 and not self.averaged():
             raise ValueError("adam: ema_overwrite_frequency needs ema_momentum > 0")
-        return self
-
-    def is_default(self):
-        """is every argument at its default (in float32, as the device sees them)"""
-        d = AdamOptions()
-        return (all(np.float32(getattr(self, k)) == np.float32(getattr(d, k)) for k in ("beta_1", "beta_2", "epsilon"))
-                and not self.amsgrad and not self.averaged())
 
     def averaged(self):
-        return bool(np.float32(self.ema_momentum) > 0)
-
-    def as_dict(self):
-        return {"beta_1": float(self.beta_1), "beta_2": float(self.beta_2), "epsilon": float(self.epsilon),
-                "amsgrad": bool(self.amsgrad), "ema_momentum": float(self.ema_momentum),
-                "ema_overwrite_frequency": int(self.ema_overwrite_frequency)}
+        return bool(_narrow(self.ema_momentum) > 0)
 
 
-def _adam(adam):
-    """None or an AdamOptions (or a mapping of its fields), checked; None stays None"""
-    if adam is None:
-        return None
-    if isinstance(adam, dict):
-        unknown = sorted(set(adam) - set(ADAM_NAMES))
-        if unknown:
-            raise ValueError("adam: unknown %s" % ", ".join(unknown))
-        adam = AdamOptions(**adam)
-    if not isinstance(adam, AdamOptions):
-        raise ValueError("fit: adam must be an AdamOptions, a dict of its fields or None, got %r" % (adam,))
-    return adam.check()
-
-
-def _apply_adam(be, adam):
-    """as _apply_options: a backend that has set_adam gets the call's arguments (None: the defaults); one that has none
-    serves only a call that asks for the defaults.  Returns the AdamOptions if any is off its default, else None"""
-    on = adam is not None and not adam.is_default()
-    if inspect.getattr_static(be, "set_adam", None) is not None:
-        be.set_adam(adam if adam is not None else AdamOptions())
-    elif on:
-        raise ValueError("fit: the backend %s has no set_adam" % type(be).__name__)
-    return adam if on else None
-
-
-LOSS_NAMES = ("value_weight", "policy_weight", "label_smoothing", "value_loss", "huber_delta")
+ADAM_NAMES = tuple(f.name for f in fields(AdamOptions))
 VALUE_LOSSES = {"mse": 0, "huber": 1}  # CA_VALUE_LOSS_MSE, CA_VALUE_LOSS_HUBER
+
+
+@dataclass(frozen=True)
+class LossOptions(_Family):
+    """ca_fit_loss: the defaults are the reference's compile(): MSE + 0.25 x cross-entropy.  The device takes the floats
+    in float32."""
+    WHO, ARG, STRUCT = "loss", "loss", _lib.CaFitLoss
+    value_weight: float = _opt(1.0, "nonneg")
+    policy_weight: float = _opt(0.25, "nonneg")
+    label_smoothing: float = _opt(0.0, "unit")
+    value_loss: str = _opt("mse", "enum", VALUE_LOSSES)
+    huber_delta: float = _opt(1.0, "positive")  # read only with "huber"
+
+    def _rules(self):
+        if _narrow(self.value_weight) == 0 and _narrow(self.policy_weight) == 0:
+            raise ValueError("loss: value_weight and policy_weight may not both be 0 (in float32)")
+
+    def is_default(self):
+        """is the loss the reference's (in float32, as the device sees it; huber_delta is not read with "mse")"""
+        return _Family.is_default(replace(self, huber_delta=1.0) if self.value_loss == "mse" else self)
+
+
+LOSS_NAMES = tuple(f.name for f in fields(LossOptions))
 METRIC_NAMES = ("categorical_accuracy", "top_k_categorical_accuracy", "mean_absolute_error", "policy_entropy",
                 "target_entropy")  # ca_fit_metrics' fields, and the keys of Fitter.metrics()
 # what a fit's history calls them (Keras's names for a model whose outputs are "policy" and "value"), then their val_ forms
@@ -241,65 +295,6 @@ METRIC_KEYS = ("policy_categorical_accuracy", "policy_top_k_categorical_accuracy
                "policy_entropy", "target_entropy")
 METRIC_HISTORY_KEYS = METRIC_KEYS + tuple("val_" + k for k in METRIC_KEYS)
 DEFAULT_TOP_K = 5
-
-
-@dataclass(frozen=True)
-class LossOptions:
-    """ca_fit_loss: the defaults are the reference's compile(): MSE + 0.25 x cross-entropy.  The device takes the floats
-    in float32."""
-    value_weight: float = 1.0
-    policy_weight: float = 0.25
-    label_smoothing: float = 0.0
-    value_loss: str = "mse"      # or "huber"
-    huber_delta: float = 1.0     # read only with "huber"
-
-    def check(self):
-        """ValueError unless the values are ones the device takes (judged in float32, as it does); returns self"""
-        for k in ("value_weight", "policy_weight", "label_smoothing", "huber_delta"):
-            x = getattr(self, k)
-            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.floating, np.integer)) or not np.isfinite(x):
-                raise ValueError("loss: %s must be a finite number, got %r" % (k, x))
-        with np.errstate(over="ignore", under="ignore"):
-            vw, pw, ls, delta = (np.float32(getattr(self, k)) for k in ("value_weight", "policy_weight", "label_smoothing",
-                                                                        "huber_delta"))
-        for k, x in (("value_weight", vw), ("policy_weight", pw)):
-            if not (np.isfinite(x) and x >= 0):
-                raise ValueError("loss: %s must be finite and >= 0 in float32, got %r" % (k, getattr(self, k)))
-        if vw == 0 and pw == 0:
-            raise ValueError("loss: value_weight and policy_weight may not both be 0 (in float32)")
-        if not 0 <= ls < 1:
-            raise ValueError("loss: label_smoothing must lie in [0, 1) in float32, got %r" % (self.label_smoothing,))
-        if not isinstance(self.value_loss, str) or self.value_loss not in VALUE_LOSSES:
-            raise ValueError('loss: value_loss must be "mse" or "huber", got %r' % (self.value_loss,))
-        if not (np.isfinite(delta) and delta > 0):
-            raise ValueError("loss: huber_delta must be finite and > 0 in float32, got %r" % (self.huber_delta,))
-        return self
-
-    def is_default(self):
-        """is the loss the reference's (in float32, as the device sees it; huber_delta is not read with "mse")"""
-        d = LossOptions()
-        return (all(np.float32(getattr(self, k)) == np.float32(getattr(d, k)) for k in ("value_weight", "policy_weight",
-                                                                                       "label_smoothing"))
-                and self.value_loss == "mse")
-
-    def as_dict(self):
-        return {"value_weight": float(self.value_weight), "policy_weight": float(self.policy_weight),
-                "label_smoothing": float(self.label_smoothing), "value_loss": str(self.value_loss),
-                "huber_delta": float(self.huber_delta)}
-
-
-def _loss(loss):
-    """None or a LossOptions (or a mapping of its fields), checked; None stays None"""
-    if loss is None:
-        return None
-    if isinstance(loss, dict):
-        unknown = sorted(set(loss) - set(LOSS_NAMES))
-        if unknown:
-            raise ValueError("loss: unknown %s" % ", ".join(unknown))
-        loss = LossOptions(**loss)
-    if not isinstance(loss, LossOptions):
-        raise ValueError("fit: loss must be a LossOptions, a dict of its fields or None, got %r" % (loss,))
-    return loss.check()
 
 
 def _top_k(metrics):
@@ -313,54 +308,10 @@ def _top_k(metrics):
         if unknown:
             raise ValueError("metrics: unknown %s" % ", ".join(unknown))
         k = metrics.get("top_k", DEFAULT_TOP_K)
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= NUM_MOVES:
+        if isinstance(k, _BOOL) or not isinstance(k, (int, np.integer)) or not 1 <= k <= NUM_MOVES:
             raise ValueError("metrics: top_k must be an integer in 1..%d, got %r" % (NUM_MOVES, k))
         return int(k)
     raise ValueError('fit: metrics must be False, True or {"top_k": k}, got %r' % (metrics,))
-
-
-def _apply_loss(be, loss, top_k):
-    """as _apply_options: a backend that has set_loss / set_metrics gets what the call asks for (None: the default loss,
-    metrics off); one that has neither serves only a call that asks for the defaults.  Returns whether metrics are on"""
-    def has(name):
-        return inspect.getattr_static(be, name, None) is not None
-
-    if has("set_loss"):
-        be.set_loss(loss if loss is not None else LossOptions())
-    elif loss is not None and not loss.is_default():
-        raise ValueError("fit: the backend %s has no set_loss" % type(be).__name__)
-    if has("set_metrics"):
-        be.set_metrics(top_k is not None, top_k if top_k is not None else DEFAULT_TOP_K)
-    elif top_k is not None:
-        raise ValueError("fit: the backend %s has no set_metrics" % type(be).__name__)
-    return top_k is not None
-
-
-def _options(options):
-    """None or a FitOptions (or a mapping of its fields), checked; None stays None"""
-    if options is None:
-        return None
-    if isinstance(options, dict):
-        unknown = sorted(set(options) - set(OPTION_NAMES + ("regularize",)))
-        if unknown:
-            raise ValueError("fit options: unknown %s" % ", ".join(unknown))
-        options = FitOptions(**options)
-    if not isinstance(options, FitOptions):
-        raise ValueError("fit: options must be a FitOptions, a dict of its fields or None, got %r" % (options,))
-    return options.check()
-
-
-def _apply_options(be, opts):
-    """put the backend into the state the call asks for: a backend that has options gets them (None: all off); one that
-    has none serves only a call that asks for none"""
-    def has(name):  # (without asking a backend's __getattr__)
-        return inspect.getattr_static(be, name, None) is not None
-
-    if has("set_options"):
-        be.set_options(opts if opts is not None else FitOptions())
-    elif opts is not None and opts.any():
-        raise ValueError("fit: the backend %s has no set_options" % type(be).__name__)
-    return opts is not None and opts.any() and has("train_stats")
 
 
 class Fitter:
@@ -395,6 +346,15 @@ class Fitter:
 
     def _check(self, rc):
         _lib.check(self._L, rc)
+
+    def _set(self, family, value, setter):
+        """hand the device a family's struct: value is an instance, a dict of its fields, or None for the defaults"""
+        self._check(setter(self._h, C.byref((family.parse(value) or family()).to_c())))
+
+    def _get(self, struct, getter):
+        c = struct(struct_size=C.sizeof(struct))
+        self._check(getter(self._h, C.byref(c)))
+        return c
 
     def set_weights(self, weights):
         w = _f32(weights).ravel()
@@ -507,22 +467,16 @@ class Fitter:
     def set_options(self, options=None):
         """the regulariser, weight decay and clipping of every later step (FitOptions, or a dict of its fields); None:
         all off.  They stay until set again."""
-        o = _options(options) or FitOptions()
-        c = _lib.CaFitOptions(struct_size=C.sizeof(_lib.CaFitOptions), regularize=int(o.regularize),
-                              **{k: float(np.float32(getattr(o, k))) for k in OPTION_NAMES})
-        self._check(self._L.ca_fitter_set_options(self._h, C.byref(c)))
+        self._set(FitOptions, options, self._L.ca_fitter_set_options)
 
     def get_options(self):
-        c = _lib.CaFitOptions(struct_size=C.sizeof(_lib.CaFitOptions))
-        self._check(self._L.ca_fitter_get_options(self._h, C.byref(c)))
-        return FitOptions(regularize=int(c.regularize), **{k: float(getattr(c, k)) for k in OPTION_NAMES})
+        return FitOptions.from_c(self._get(_lib.CaFitOptions, self._L.ca_fitter_get_options))
 
     def train_stats(self):
         """of the last train(): {"steps", "clipped_steps", "regularization_loss", "grad_norm", "grad_norm_max"} -- the
         means over the steps of R(w) and of the norm of the regularised gradient before clipping, and that norm's
         maximum; zeros when no option is set"""
-        c = _lib.CaFitStats(struct_size=C.sizeof(_lib.CaFitStats))
-        self._check(self._L.ca_fitter_train_stats(self._h, C.byref(c)))
+        c = self._get(_lib.CaFitStats, self._L.ca_fitter_train_stats)
         return {"steps": int(c.steps), "clipped_steps": int(c.clipped_steps), "regularization_loss": float(c.regularization),
                 "grad_norm": float(c.grad_norm), "grad_norm_max": float(c.grad_norm_max)}
 
@@ -530,18 +484,10 @@ class Fitter:
     def set_adam(self, adam=None):
         """Adam's arguments of every later step (AdamOptions, or a dict of its fields); None: the defaults.  They stay
         until set again."""
-        a = _adam(adam) or AdamOptions()
-        c = _lib.CaFitAdam(struct_size=C.sizeof(_lib.CaFitAdam), beta_1=float(np.float32(a.beta_1)),
-                           beta_2=float(np.float32(a.beta_2)), epsilon=float(np.float32(a.epsilon)),
-                           amsgrad=int(bool(a.amsgrad)), ema_momentum=float(np.float32(a.ema_momentum)),
-                           ema_overwrite_frequency=int(a.ema_overwrite_frequency))
-        self._check(self._L.ca_fitter_set_adam(self._h, C.byref(c)))
+        self._set(AdamOptions, adam, self._L.ca_fitter_set_adam)
 
     def get_adam(self):
-        c = _lib.CaFitAdam(struct_size=C.sizeof(_lib.CaFitAdam))
-        self._check(self._L.ca_fitter_get_adam(self._h, C.byref(c)))
-        return AdamOptions(beta_1=float(c.beta_1), beta_2=float(c.beta_2), epsilon=float(c.epsilon), amsgrad=bool(c.amsgrad),
-                           ema_momentum=float(c.ema_momentum), ema_overwrite_frequency=int(c.ema_overwrite_frequency))
+        return AdamOptions.from_c(self._get(_lib.CaFitAdam, self._L.ca_fitter_get_adam))
 
     @staticmethod
     def _slot(which):
@@ -572,19 +518,10 @@ class Fitter:
     def set_loss(self, loss=None):
         """the loss of every later step, evaluation and gradients() (LossOptions, or a dict of its fields); None: the
         reference's value MSE + 0.25 policy cross-entropy.  It stays until set again."""
-        o = _loss(loss) or LossOptions()
-        c = _lib.CaFitLoss(struct_size=C.sizeof(_lib.CaFitLoss), value_weight=float(np.float32(o.value_weight)),
-                           policy_weight=float(np.float32(o.policy_weight)),
-                           label_smoothing=float(np.float32(o.label_smoothing)), value_loss=VALUE_LOSSES[o.value_loss],
-                           huber_delta=float(np.float32(o.huber_delta)))
-        self._check(self._L.ca_fitter_set_loss(self._h, C.byref(c)))
+        self._set(LossOptions, loss, self._L.ca_fitter_set_loss)
 
     def get_loss(self):
-        c = _lib.CaFitLoss(struct_size=C.sizeof(_lib.CaFitLoss))
-        self._check(self._L.ca_fitter_get_loss(self._h, C.byref(c)))
-        name = {v: k for k, v in VALUE_LOSSES.items()}[int(c.value_loss)]
-        return LossOptions(value_weight=float(c.value_weight), policy_weight=float(c.policy_weight),
-                           label_smoothing=float(c.label_smoothing), value_loss=name, huber_delta=float(c.huber_delta))
+        return LossOptions.from_c(self._get(_lib.CaFitLoss, self._L.ca_fitter_get_loss))
 
     def set_metrics(self, on=True, top_k=DEFAULT_TOP_K):
         """switch the metrics of train() and evaluate() on or off; top_k in 1..96"""
@@ -593,8 +530,7 @@ class Fitter:
     def metrics(self):
         """of the last train() or evaluate(): METRIC_NAMES' means weighted by the sample weights, and "rows",
         "weight_sum" and "top_k"; an EngineError (CA_ERR_STATE) while metrics are off"""
-        c = _lib.CaFitMetrics(struct_size=C.sizeof(_lib.CaFitMetrics))
-        self._check(self._L.ca_fitter_metrics(self._h, C.byref(c)))
+        c = self._get(_lib.CaFitMetrics, self._L.ca_fitter_metrics)
         out = {k: float(getattr(c, k)) for k in METRIC_NAMES}
         out.update(rows=int(c.rows), weight_sum=float(c.weight_sum), top_k=int(c.top_k))
         return out
@@ -671,10 +607,9 @@ def epoch_order(rng, n_train, shuffle):
     return rng.permutation(n_train).astype(np.int32) if shuffle else np.arange(n_train, dtype=np.int32)
 
 
-def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed, stats=False,
-            adam=None, metrics=False):
+def _epochs(be, n, split_at, call, stats=False, adam=None, metrics=False):
     """the epochs of model.fit on the n rows the backend holds, rows [0, split_at) training; the callbacks' logic.
-    stats: an option is on, the backend's train_stats() of every epoch go to the history.
+    call: the _Call.  stats: an option is on, the backend's train_stats() of every epoch go to the history.
     adam: the call's AdamOptions if any is off its default.  With ema_momentum > 0 this is Keras 3's
     SwapEMAWeights(swap_on_epoch=True) plus the finalisation fit() does: an epoch is judged by the averaged weights (swap,
     evaluate, swap back), the checkpoint holds them, and at the end the average is applied to the weights.
@@ -685,12 +620,13 @@ def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_
     def slots():
         return {k: be.get_slot(k) for k in names} if names else None
 
-    rng = np.random.default_rng(seed)
-    lr = np.float32(learning_rate)
+    batch_size, shuffle, anneal_factor, patience = call.batch_size, call.shuffle, call.anneal_factor, call.patience
+    rng = np.random.default_rng(call.seed)
+    lr = np.float32(call.learning_rate)
     history = {k: [] for k in HISTORY_KEYS + (OPTION_HISTORY_KEYS if stats else ()) + (METRIC_HISTORY_KEYS if metrics else ())}
     ckpt_best, plateau_best, wait = np.inf, np.inf, 0
     best = None
-    for epoch in range(epochs):
+    for epoch in range(call.epochs):
         order = epoch_order(rng, split_at, shuffle)
         loss = be.train(order, batch_size, lr)
         if metrics:
@@ -733,7 +669,30 @@ def _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_
                      slots=slots())
 
 
-def _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_factor, patience):
+@dataclass(frozen=True)
+class _Call:
+    """what one call of fit() or of a relative asks for, checked: made by _call() before any fitter is"""
+    learning_rate: float
+    batch_size: int
+    epochs: int
+    validation_split: float
+    shuffle: bool
+    anneal_factor: float
+    patience: int
+    seed: object
+    optimizer_state: tuple  # (m, v, iterations), or None: Adam starts from zeros
+    slots: dict             # {"vhat": ..., "average": ...} to resume from, or None
+    options: FitOptions     # the three families, parsed; None: the defaults
+    adam: AdamOptions
+    loss: LossOptions
+    top_k: int              # None: metrics off
+
+
+def _call(*, learning_rate=0.001, batch_size=2048, epochs=1, validation_split=0.3, shuffle=True, anneal_factor=0.5,
+          patience=3, seed=0, optimizer_state=None, options=None, adam=None, slots=None, loss=None, metrics=False):
+    """the keywords fit() and its relatives share, with their defaults, as a _Call; ValueError on a bad one"""
+    options, adam, loss = FitOptions.parse(options), AdamOptions.parse(adam), LossOptions.parse(loss)
+    top_k = _top_k(metrics)
     if int(batch_size) != batch_size or batch_size < 1:
         raise ValueError("fit: batch_size must be a positive integer")
     if int(epochs) != epochs or epochs < 1:
@@ -742,6 +701,76 @@ def _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_
         raise ValueError("fit: validation_split must lie in (0, 1)")
     if not learning_rate > 0.0 or not 0.0 < anneal_factor < 1.0 or int(patience) != patience or patience < 0:
         raise ValueError("fit: learning_rate > 0, anneal_factor in (0, 1) and patience >= 0 are required")
+    return _Call(learning_rate, int(batch_size), int(epochs), validation_split, shuffle, anneal_factor, patience, seed,
+                 optimizer_state, slots, options, adam, loss, top_k)
+
+
+def _weights(weights, net, who):
+    """the flat float32 weights of a network of kind `net`, checked"""
+    name, num_weights = net_info(net)
+    w = _f32(weights).ravel()
+    if w.size != num_weights:
+        raise ValueError("%s: %s weights have %d floats, got %d" % (who, name, num_weights, w.size))
+    return w
+
+
+def _sample_weight(sample_weight, n, who):
+    """the weights of n rows or samples, checked; None stays None"""
+    if sample_weight is None:
+        return None
+    sw = np.ascontiguousarray(sample_weight, dtype=np.float32).ravel()
+    if sw.size != n:
+        raise ValueError("%s: sample_weight must be [n] for n = %d, got %d" % (who, n, sw.size))
+    if not np.all(np.isfinite(sw)) or np.any(sw < 0):
+        raise ValueError("%s: every sample weight must be finite and >= 0" % who)
+    return sw
+
+
+def _apply(be, call):
+    """put the backend into the state the call asks for: a backend that has a family's setter gets the call's values
+    (None: the defaults); one that has none serves only a call that asks for that family's defaults.  The same for the
+    metrics.  Returns what _epochs takes: (do train_stats go to the history, the AdamOptions if any is off its default,
+    are metrics on)"""
+    def has(name):  # (without asking a backend's __getattr__)
+        return inspect.getattr_static(be, name, None) is not None
+
+    on = {}
+    for family, asked in ((FitOptions, call.options), (AdamOptions, call.adam), (LossOptions, call.loss)):
+        on[family] = asked is not None and not asked.is_default()
+        if has("set_" + family.ARG):
+            getattr(be, "set_" + family.ARG)(asked if asked is not None else family())
+        elif on[family]:
+            raise ValueError("fit: the backend %s has no set_%s" % (type(be).__name__, family.ARG))
+    if has("set_metrics"):
+        be.set_metrics(call.top_k is not None, call.top_k if call.top_k is not None else DEFAULT_TOP_K)
+    elif call.top_k is not None:
+        raise ValueError("fit: the backend %s has no set_metrics" % type(be).__name__)
+    return on[FitOptions] and has("train_stats"), call.adam if on[AdamOptions] else None, call.top_k is not None
+
+
+def _run(be, n, w, call, who):
+    """the fit a call asks for, on a backend that holds its n rows: the split, the starting point, the families, the epochs"""
+    split_at = split_index(n, call.validation_split)
+    if split_at < 1 or split_at >= n:
+        raise ValueError("%s: %d rows leave no training or no validation rows at validation_split=%g"
+                         % (who, n, call.validation_split))
+    be.set_weights(w)
+    m, v, it = call.optimizer_state if call.optimizer_state is not None else (np.zeros_like(w), np.zeros_like(w), 0)
+    be.set_optimizer(m, v, it)
+    for k in sorted(call.slots or {}):
+        be.set_slot(k, call.slots[k])
+    return _epochs(be, n, split_at, call, *_apply(be, call))
+
+
+def _run_filled(fill, w, call, device, net, backend, who):
+    """_run on a fitter of its own (unless a backend is given) that fill(fitter) gives its data; fill returns the rows"""
+    own = backend is None
+    be = Fitter(max_batch=call.batch_size, device=device, net=net) if own else backend
+    try:
+        return _run(be, fill(be), w, call, who)
+    finally:
+        if own:
+            be.close()
 
 
 def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epochs=1, validation_split=0.3, shuffle=True,
@@ -757,31 +786,17 @@ def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epoch
     optimizer state; None starts vhat from zeros and the average from `weights`.  loss: a LossOptions; None: the
     reference's loss.  metrics: True or {"top_k": k}: the history gains METRIC_HISTORY_KEYS; False: off.  Both are decided
     by the call in the same way."""
-    opts, adam, loss, top_k = _options(options), _adam(adam), _loss(loss), _top_k(metrics)
+    call = _call(learning_rate=learning_rate, batch_size=batch_size, epochs=epochs, validation_split=validation_split,
+                 shuffle=shuffle, anneal_factor=anneal_factor, patience=patience, seed=seed,
+                 optimizer_state=optimizer_state, options=options, adam=adam, slots=slots, loss=loss, metrics=metrics)
     w = _f32(weights).ravel()
     num_weights = getattr(fitter, "num_weights", w.size)
     if w.size != num_weights:
         raise ValueError("fit_resident: the fitter's network has %d floats, got %d" % (num_weights, w.size))
-    _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_factor, patience)
-    n = int(fitter.data_info()[0])
-    split_at = split_index(n, validation_split)
-    if split_at < 1 or split_at >= n:
-        raise ValueError("fit_resident: %d rows leave no training or no validation rows at validation_split=%g"
-                         % (n, validation_split))
-    fitter.set_weights(w)
-    if optimizer_state is None:
-        fitter.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
-    else:
-        m, v, it = optimizer_state
-        fitter.set_optimizer(m, v, it)
-    for k in sorted(slots or {}):
-        fitter.set_slot(k, slots[k])
-    stats = _apply_options(fitter, opts)
-    return _epochs(fitter, n, split_at, learning_rate, int(batch_size), int(epochs), shuffle, anneal_factor, patience,
-                   seed, stats, _apply_adam(fitter, adam), _apply_loss(fitter, loss, top_k))
+    return _run(fitter, int(fitter.data_info()[0]), w, call, "fit_resident")
 
 
-def fit_samples(weights, state_policy, outcome, *, batch_size=2048, device=0, net=NET_MLP12X100, sample_weight=None,
+def fit_samples(weights, state_policy, outcome, *, device=0, net=NET_MLP12X100, sample_weight=None,
                 merge_duplicates=False, _backend=None, **kw):
     """fit() from un-augmented samples (Trainer.export_samples, dist.SampleGather.rows): a packed data set, 668 bytes
     a sample on the device instead of 5 344.  fit_samples(w, sp, oc, seed=s) equals fit(w, *expand_samples(sp, oc),
@@ -789,73 +804,40 @@ def fit_samples(weights, state_policy, outcome, *, batch_size=2048, device=0, ne
     epoch's permutation are the same.  sample_weight: one weight per sample (Keras's sample_weight; the sample's 8
     virtual rows share it).  merge_duplicates: Fitter.merge_duplicates(normalize=True) on the set, weights and all,
     before the fit -- the same as fitting samples_io.merge_duplicates_host's three arrays.  Keywords as fit_resident's."""
-    name, num_weights = net_info(net)
-    if _f32(weights).size != num_weights:
-        raise ValueError("fit_samples: %s weights have %d floats, got %d" % (name, num_weights, _f32(weights).size))
+    call = _call(**kw)
+    w = _weights(weights, net, "fit_samples")
     sp, oc = _packed(state_policy, outcome, "fit_samples")
     sw = _sample_weight(sample_weight, sp.shape[0], "fit_samples")
 
-    def add(be):
+    def fill(be):
+        be.clear_data()
         be.add_samples(sp, oc)
         if sw is not None:
             be.set_sample_weights(sw)
         if merge_duplicates:
             be.merge_duplicates(normalize=True)
+        return int(be.data_info()[0])
 
-    return _fit_added(add, weights, batch_size, device, net, _backend, kw)
-
-
-def _sample_weight(sample_weight, n, who):
-    """the weights of n rows or samples, checked; None stays None"""
-    if sample_weight is None:
-        return None
-    sw = np.ascontiguousarray(sample_weight, dtype=np.float32).ravel()
-    if sw.size != n:
-        raise ValueError("%s: sample_weight must be [n] for n = %d, got %d" % (who, n, sw.size))
-    if not np.all(np.isfinite(sw)) or np.any(sw < 0):
-        raise ValueError("%s: every sample weight must be finite and >= 0" % who)
-    return sw
+    return _run_filled(fill, w, call, device, net, _backend, "fit_resident")
 
 
-def fit_trainer(weights, trainers, *, batch_size=2048, device=0, net=NET_MLP12X100, _backend=None, **kw):
+def fit_trainer(weights, trainers, *, device=0, net=NET_MLP12X100, _backend=None, **kw):
     """fit() from the samples of one finished Trainer, or of a sequence of them added in that order, taken device to
     device (Fitter.add_trainer_samples).  fit_trainer(w, t, seed=s) equals fit(w, *samples_io.get_samples(t), seed=s) to
     the bit.  Keywords as fit_resident's; the trainers must be on `device`."""
+    call = _call(**kw)
     ts = [trainers] if isinstance(trainers, Trainer) else list(trainers)
     if not ts:
         raise ValueError("fit_trainer: no trainer given")
-    name, num_weights = net_info(net)
-    if _f32(weights).size != num_weights:
-        raise ValueError("fit_trainer: %s weights have %d floats, got %d" % (name, num_weights, _f32(weights).size))
+    w = _weights(weights, net, "fit_trainer")
 
-    def add(be):
+    def fill(be):
+        be.clear_data()
         for t in ts:
             be.add_trainer_samples(t)
+        return int(be.data_info()[0])
 
-    return _fit_added(add, weights, batch_size, device, net, _backend, kw)
-
-
-def _fit_added(add, weights, batch_size, device, net, backend, kw):
-    """a fitter of its own (unless a backend is given), emptied, filled by add(fitter), and fit_resident on it"""
-    # the arguments are checked before a fitter is made, with the defaults of fit_resident's own signature
-    args = inspect.signature(fit_resident).bind(None, weights, batch_size=batch_size, **kw)
-    args.apply_defaults()
-    a = args.arguments
-    _check_fit_args(a["learning_rate"], a["batch_size"], a["epochs"], a["validation_split"], a["anneal_factor"],
-                    a["patience"])
-    _options(a["options"])
-    _adam(a["adam"])
-    _loss(a["loss"])
-    _top_k(a["metrics"])
-    own = backend is None
-    be = Fitter(max_batch=int(batch_size), device=device, net=net) if own else backend
-    try:
-        be.clear_data()
-        add(be)
-        return fit_resident(be, weights, batch_size=batch_size, **kw)
-    finally:
-        if own:
-            be.close()
+    return _run_filled(fill, w, call, device, net, _backend, "fit_resident")
 
 
 def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, batch_size=2048, epochs=1,
@@ -869,11 +851,10 @@ def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, 
     options: a FitOptions (the module docstring); None: none.
     adam: an AdamOptions (the module docstring); None: Adam's defaults.
     loss: a LossOptions (the module docstring); None: the reference's loss.  metrics: True or {"top_k": k}; False: off."""
-    opts, adam, loss, top_k = _options(options), _adam(adam), _loss(loss), _top_k(metrics)
-    name, num_weights = net_info(net)
-    w = _f32(weights).ravel()
-    if w.size != num_weights:
-        raise ValueError("fit: %s weights have %d floats, got %d" % (name, num_weights, w.size))
+    call = _call(learning_rate=learning_rate, batch_size=batch_size, epochs=epochs, validation_split=validation_split,
+                 shuffle=shuffle, anneal_factor=anneal_factor, patience=patience, seed=seed,
+                 optimizer_state=optimizer_state, options=options, adam=adam, loss=loss, metrics=metrics)
+    w = _weights(weights, net, "fit")
     states = _f32(game_states)
     n = states.shape[0] if states.ndim == 2 else -1
     if states.ndim != 2 or states.shape[1] != GAME_STATE_SIZE:
@@ -882,29 +863,12 @@ def fit(weights, game_states, eval_labels, prob_labels, *, learning_rate=0.001, 
     probs = _f32(prob_labels)
     if evals.size != n or probs.shape != (n, NUM_MOVES):
         raise ValueError("fit: eval_labels must be [n] and prob_labels [n, %d] for n = %d" % (NUM_MOVES, n))
-    _check_fit_args(learning_rate, batch_size, epochs, validation_split, anneal_factor, patience)
-    split_at = split_index(n, validation_split)
-    if split_at < 1 or split_at >= n:
-        raise ValueError("fit: %d rows leave no training or no validation rows at validation_split=%g"
-                         % (n, validation_split))
-    batch_size, epochs = int(batch_size), int(epochs)
     sw = _sample_weight(sample_weight, n, "fit")
 
-    own = _backend is None
-    be = Fitter(max_batch=batch_size, device=device, net=net) if own else _backend
-    try:
-        be.set_weights(w)
-        if optimizer_state is None:
-            be.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
-        else:
-            m, v, it = optimizer_state
-            be.set_optimizer(m, v, it)
+    def fill(be):
         be.set_data(states, evals, probs)
         if sw is not None:
             be.set_sample_weights(sw)
-        stats = _apply_options(be, opts)
-        return _epochs(be, n, split_at, learning_rate, batch_size, epochs, shuffle, anneal_factor, patience, seed, stats,
-                       _apply_adam(be, adam), _apply_loss(be, loss, top_k))
-    finally:
-        if own:
-            be.close()
+        return n
+
+    return _run_filled(fill, w, call, device, net, _backend, "fit")

@@ -60,6 +60,8 @@ PLAY_KINDS = {
     ("rescnn4", "x6"): _trainer.NET_RESCNN4_X6, ("rescnn4", "h3"): _trainer.NET_RESCNN4_H3,
 }
 VALIDATION_SPLIT = 0.3  # main.pyx:255
+# a field of an option family that RunParams holds under another name: `epsilon` is the search's noise weight
+FAMILY_FIELDS = {(AdamOptions, "epsilon"): "adam_epsilon"}
 # train_loss.csv: Keras's CSVLogger writes "epoch" and then the sorted log keys, which puts val_loss last
 # (main.pyx:244, read back by write_loss at main.pyx:65-66); the names here sort differently, so the order is spelled out
 LOSS_COLUMNS = ("loss", "lr", "policy_loss", "value_loss", "val_policy_loss", "val_value_loss", "val_loss")
@@ -160,21 +162,22 @@ class RunParams:
         if not 1 <= self.top_k <= nets.NUM_MOVES:
             raise ValueError("top_k must be in 1..%d, not %r" % (nets.NUM_MOVES, self.top_k))
 
+    def _family(self, family):
+        """one of fit's option families from the fields of the same names (FAMILY_FIELDS has the exceptions), checked"""
+        return family(**{f.name: getattr(self, FAMILY_FIELDS.get((family, f.name), f.name))
+                         for f in dataclasses.fields(family)}).check()
+
     def fit_options(self):
         """the fit options of the run as a fit.FitOptions, checked"""
-        return FitOptions(l1=self.l1, l2=self.l2, regularize=self.regularize, weight_decay=self.weight_decay,
-                          clipvalue=self.clipvalue, clipnorm=self.clipnorm, global_clipnorm=self.global_clipnorm).check()
+        return self._family(FitOptions)
 
     def adam_options(self):
         """Adam's arguments of the run as a fit.AdamOptions, checked"""
-        return AdamOptions(beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.adam_epsilon, amsgrad=self.amsgrad,
-                           ema_momentum=self.ema_momentum, ema_overwrite_frequency=self.ema_overwrite_frequency).check()
+        return self._family(AdamOptions)
 
     def loss_options(self):
         """the loss of the run as a fit.LossOptions, checked"""
-        return LossOptions(value_weight=self.value_weight, policy_weight=self.policy_weight,
-                           label_smoothing=self.label_smoothing, value_loss=self.value_loss,
-                           huber_delta=self.huber_delta).check()
+        return self._family(LossOptions)
 
     def as_dict(self):
         d = {f.name: getattr(self, f.name) for f in dataclasses.fields(self)}

@@ -1,19 +1,15 @@
 """TEST INFRASTRUCTURE: the fit options (include/corintho_hip.h, "fit options": the L1L2 regulariser, decoupled weight
-decay, gradient clipping) restated in numpy, in float64 (the yardstick) or float32, around the restatements of the plain
-step (tests/fit_ref.py, tests/fit_ref_rescnn4.py), which are imported unchanged.  Steps 1 to 3 and 5 of the definition
-are here; step 4 is the base module's adam_step on what they leave.
+decay, gradient clipping) restated in numpy, in float64 (the yardstick) or float32, as functions of the flat weights
+and gradient.  Steps 1 to 3 and 5 of the definition are here; step 4 is Adam's update on what they leave, and
+tests/fit_ref_step.py puts them around it.
 
     r, R = reg_grad(net, w, o), reg_loss(net, w, o)        step 1, step 5
     g2, info = clip(net, add_reg(net, g, w, o), o)         step 2 on g' = g + r
-    w1 = decay(net, w, lr, o)                              step 3
-RefBackend(net, dtype) is the base module's RefBackend with set_options / train_stats, for fit.fit(..., options=...)."""
+    w1 = decay(net, w, lr, o)                              step 3"""
 import numpy as np
 
 from corintho_ai_amd import nets
-from corintho_ai_amd.fit import FitOptions
-from tests import fit_ref, fit_ref_rescnn4
 
-BASE = {"mlp12x100": fit_ref, "rescnn4": fit_ref_rescnn4}
 KERNELS = ("trunk_kernel", "head_kernel")
 
 
@@ -94,62 +90,3 @@ def decay(net, w, lr, o, f=np.float64):
     if np.float32(o.weight_decay) > 0:
         w[k] = w[k] - (f(np.float32(lr)) * f(np.float32(o.weight_decay))) * w[k]
     return w
-
-
-def RefBackend(net, dtype=None):
-    """the options-aware backend of `net` for fit.fit / fit_resident: the base module's RefBackend, its train() and
-    evaluate() restated with steps 1 to 3 and 5 around the base's loss_and_grad and adam_step"""
-    base = BASE[net]
-    dtype = dtype or base.torch.float64
-
-    class Backend(base.RefBackend):
-        def __init__(self):
-            super().__init__(dtype)
-            self.options = FitOptions()
-            self.stats = dict(steps=0, clipped_steps=0, regularization_loss=0.0, grad_norm=0.0, grad_norm_max=0.0)
-            self.set_options_calls = []
-            self.step_norms = []  # the norm of g' of every step trained with an option on
-
-        def set_options(self, options=None):
-            self.options = options or FitOptions()
-            self.set_options_calls.append(self.options)
-
-        def get_options(self):
-            return self.options
-
-        def train_stats(self):
-            return dict(self.stats)
-
-        def train(self, rows, batch_size, lr, batch_losses=False):
-            o, f = self.options, self.np_dtype
-            if not o.any():
-                self.stats = dict(steps=0, clipped_steps=0, regularization_loss=0.0, grad_norm=0.0, grad_norm_max=0.0)
-                return super().train(rows, batch_size, lr, batch_losses)
-            rows = np.asarray(rows)
-            self.trained_rows.append(rows.copy())
-            s, e, p = self.data
-            tot, per, regs, norms, clipped = np.zeros(3), [], [], [], 0
-            for b0 in range(0, rows.size, batch_size):
-                r = rows[b0:b0 + batch_size]
-                g, ls, st = base.loss_and_grad(self.w, s[r], e[r], p[r], self.dtype)
-                R = reg_loss(net, self.w, o)
-                g2, info = clip(net, add_reg(net, g, self.w, o, f), o, f)
-                self.w[:] = decay(net, self.w, lr, o, f)
-                self.it = base.adam_step(self.w, self.m, self.v, g2, self.it, lr, st, f)
-                ls = (ls[0] + R, ls[1], ls[2])
-                per.append(ls)
-                tot += np.asarray(ls) * r.size
-                regs.append(R)
-                norms.append(info["norm"])
-                self.step_norms.append(info["norm"])
-                clipped += bool(info["clipped"])
-            self.stats = dict(steps=len(per), clipped_steps=clipped, regularization_loss=float(np.mean(regs)),
-                              grad_norm=float(np.mean(norms)), grad_norm_max=float(np.max(norms)))
-            out = tuple(tot / rows.size)
-            return (out, np.asarray(per)) if batch_losses else out
-
-        def evaluate(self, row0, n_rows, batch_size):
-            tot, lv, lp = super().evaluate(row0, n_rows, batch_size)
-            return tot + (reg_loss(net, self.w, self.options) if self.options.any() else 0.0), lv, lp
-
-    return Backend()

@@ -1,22 +1,21 @@
-"""TEST INFRASTRUCTURE: the training step of rescnn4 restated in torch on the CPU, in float64 (the yardstick) or float32
-(its own error is the scale the device is judged by).  The reference has no CNN, so this file is the definition: the
-recipe of tests/fit_ref.py (the Keras step of the MLP) applied to the network of corintho_ai_amd/nets.py:
+"""TEST INFRASTRUCTURE: what is particular to rescnn4 in the restatement of the training step (tests/fit_ref_step.py has
+the step, for this network and for tests/fit_ref.py's): the forward in torch on the CPU, in any dtype, and where the
+layout keeps what.  The reference has no CNN, so this file is the definition: the recipe of the Keras step of the MLP
+applied to the network of corintho_ai_amd/nets.py:
 
   * every conv + bias -> BatchNorm -> ReLU (the stem, both convolutions of the four blocks, the two 1x1 head
     convolutions) normalises, in training mode, with the batch mean and the BIASED batch variance per channel over all
     B x 16 (row, pixel) pairs, epsilon 1e-3; a block adds its input to the second BatchNorm's output before the ReLU;
     the dense layers have no BatchNorm.  Inference mode uses the moving statistics (tests/ref_nets.rescnn4_forward_f64);
-  * the 11 BatchNorms' moving statistics move by moving -= (moving - batch_stat) * 0.01;
-  * loss = mean (tanh v - z)^2 + 0.25 * mean(-sum t log_softmax(logits)), and Adam = TF ResourceApplyAdam, as fit_ref.
-Weights, gradients and Adam's slots use the flat layout of nets._rescnn4_shapes().  RefBackend drives
-corintho_ai_amd.fit.fit(..., net=NET_RESCNN4) with it."""
+Weights, gradients and Adam's slots use the flat layout of nets._rescnn4_shapes()."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from corintho_ai_amd import nets
-from tests.fit_ref import ADAM_EPS, B1, B2, MOMENTUM, losses, synthetic_samples  # noqa: F401
+from tests.fit_ref import synthetic_samples  # noqa: F401
 
+NET = "rescnn4"
 # the BatchNorms in the order of the layout (and of the batch statistics forward() returns)
 BN_PREFIXES = ["stem"] + ["b%d_c%d" % (b, c) for b in range(nets.RES_BLOCKS) for c in (1, 2)] + ["p", "v"]
 
@@ -44,6 +43,12 @@ def stat_mask():
         m[_slice(off, pre + "_bn2")] = True
         m[_slice(off, pre + "_bn3")] = True
     return m
+
+
+def bn_slices():
+    """[(moving mean, moving variance)] as slices, in the order of the batch statistics forward() returns"""
+    off = offsets()
+    return [(_slice(off, pre + "_bn2"), _slice(off, pre + "_bn3")) for pre in BN_PREFIXES]
 
 
 def tensors():
@@ -111,109 +116,3 @@ def forward(wt, x, train=True):
     v = relu(v @ W["v_d1k"] + W["v_d1b"])
     v = (v @ W["v_d2k"]).view(-1) + W["v_d2b"]
     return logits, v, {"stats": stats if train else None, "relu_inputs": pre_relu}
-
-
-def _t(a, dtype):
-    return torch.as_tensor(np.asarray(a), dtype=dtype)
-
-
-def loss_and_grad(w, states, evals, probs, dtype=torch.float64):
-    """(flat gradient of value + 0.25 policy, (total, value, policy), batch statistics) for one batch, train mode"""
-    wt = _t(w, dtype).clone().requires_grad_(True)
-    logits, v, aux = forward(wt, _t(states, dtype), True)
-    lv, lp = losses(logits, v, _t(evals, dtype), _t(probs, dtype))
-    loss = lv + 0.25 * lp
-    loss.backward()
-    g = wt.grad.detach().numpy().copy()
-    g[stat_mask()] = 0.0
-    st = [(m.detach().numpy(), s.detach().numpy()) for m, s in aux["stats"]]
-    return g, (float(loss.detach()), float(lv.detach()), float(lp.detach())), st
-
-
-def kink_margin(w, states):
-    """smallest |ReLU input| / its tensor's largest, over the batch in float64 (training mode): where it is tiny a ReLU
-    sits at its kink, the gradient is not defined there, and float32 rounding picks either side"""
-    with torch.no_grad():
-        _, _, aux = forward(_t(w, torch.float64), _t(states, torch.float64), True)
-    return min(float(t.abs().min() / t.abs().max()) for t in aux["relu_inputs"])
-
-
-def evaluate(w, states, evals, probs, dtype=torch.float64):
-    """inference mode (moving statistics): (total, value, policy) means and the outputs (tanh v, softmax)"""
-    with torch.no_grad():
-        logits, v, _ = forward(_t(w, dtype), _t(states, dtype), False)
-        lv, lp = losses(logits, v, _t(evals, dtype), _t(probs, dtype))
-        return (float(lv + 0.25 * lp), float(lv), float(lp)), (torch.tanh(v).numpy(), torch.softmax(logits, 1).numpy())
-
-
-def adam_step(w, m, v, g, iterations, lr, stats, np_dtype=np.float64):
-    """one step in place of (w, m, v): Adam on the trainable weights, the moving statistics toward `stats`"""
-    t = iterations + 1
-    f = np_dtype
-    lr_t = f(lr) * np.sqrt(f(1) - f(B2) ** f(t)) / (f(1) - f(B1) ** f(t))
-    mask = ~stat_mask()
-    gg = g.astype(f)
-    m[mask] = m[mask] + (gg[mask] - m[mask]) * (f(1) - f(B1))
-    v[mask] = v[mask] + (gg[mask] * gg[mask] - v[mask]) * (f(1) - f(B2))
-    w[mask] = w[mask] - lr_t * m[mask] / (np.sqrt(v[mask]) + f(ADAM_EPS))
-    off = offsets()
-    for pre, (bm, bv) in zip(BN_PREFIXES, stats):
-        for name, bs in ((pre + "_bn2", bm), (pre + "_bn3", bv)):
-            sl = _slice(off, name)
-            w[sl] = w[sl] - (w[sl] - bs.astype(f)) * f(1 - MOMENTUM)
-    return t
-
-
-class RefBackend:
-    """the Fitter interface of corintho_ai_amd.fit for rescnn4, computed by this restatement (float64 by default)"""
-
-    def __init__(self, dtype=torch.float64):
-        self.dtype = dtype
-        self.np_dtype = np.float64 if dtype == torch.float64 else np.float32
-        self.trained_rows = []  # the row order of every train() call
-        self.lrs = []
-
-    def set_weights(self, w):
-        self.w = np.asarray(w, self.np_dtype).copy()
-
-    def get_weights(self):
-        return self.w.astype(np.float32)
-
-    def set_optimizer(self, m, v, iterations):
-        self.m = np.asarray(m, self.np_dtype).copy()
-        self.v = np.asarray(v, self.np_dtype).copy()
-        self.it = int(iterations)
-
-    def get_optimizer(self):
-        return self.m.astype(np.float32), self.v.astype(np.float32), self.it
-
-    def set_data(self, s, e, p):
-        self.data = (np.asarray(s), np.asarray(e), np.asarray(p))
-
-    def train(self, rows, batch_size, lr, batch_losses=False):
-        rows = np.asarray(rows)
-        self.trained_rows.append(rows.copy())
-        self.lrs.append(float(lr))
-        s, e, p = self.data
-        tot = np.zeros(3)
-        per = []
-        for b0 in range(0, rows.size, batch_size):
-            r = rows[b0:b0 + batch_size]
-            g, ls, st = loss_and_grad(self.w, s[r], e[r], p[r], self.dtype)
-            self.it = adam_step(self.w, self.m, self.v, g, self.it, lr, st, self.np_dtype)
-            per.append(ls)
-            tot += np.asarray(ls) * r.size
-        out = tuple(tot / rows.size)
-        return (out, np.asarray(per)) if batch_losses else out
-
-    def evaluate(self, row0, n_rows, batch_size):
-        s, e, p = self.data
-        tot = np.zeros(3)
-        for b0 in range(row0, row0 + n_rows, batch_size):
-            b1 = min(b0 + batch_size, row0 + n_rows)
-            ls, _ = evaluate(self.w, s[b0:b1], e[b0:b1], p[b0:b1], self.dtype)
-            tot += np.asarray(ls) * (b1 - b0)
-        return tuple(tot / n_rows)
-
-    def close(self):
-        pass

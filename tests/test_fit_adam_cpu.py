@@ -15,6 +15,7 @@ from corintho_ai_amd.fit import HISTORY_KEYS, FitResult
 from tests import fit_ref
 from tests import fit_ref_adam as A
 from tests import fit_ref_options as O
+from tests import fit_ref_step as S
 from tests.test_run_cpu import StubFitter, open_run, small
 
 
@@ -91,12 +92,12 @@ def test_restatement_by_hand():
     mask = np.array([True, False])
     u = A.adam_update(w[mask], m[mask], v[mask], None, None, g[mask], 4, 1e-3, AdamOptions(), np.float64)
     f = np.float64
-    lt = f(1e-3) * np.sqrt(f(1) - f(fit_ref.B2) ** f(5)) / (f(1) - f(fit_ref.B1) ** f(5))
-    m1 = 0.01 + (0.5 - 0.01) * (1 - fit_ref.B1)
-    v1 = 0.002 + (0.25 - 0.002) * (1 - fit_ref.B2)
+    lt = f(1e-3) * np.sqrt(f(1) - f(S.B2) ** f(5)) / (f(1) - f(S.B1) ** f(5))
+    m1 = 0.01 + (0.5 - 0.01) * (1 - S.B1)
+    v1 = 0.002 + (0.25 - 0.002) * (1 - S.B2)
     # the restatement holds the constants as the device does, in float32: 1 - float32(0.999) is off by 2^-25 / 0.001 =
     # 3e-5 of itself, which is the largest of the differences; 1e-4 of the step covers them
-    step = lt * m1 / (np.sqrt(v1) + fit_ref.ADAM_EPS)
+    step = lt * m1 / (np.sqrt(v1) + S.ADAM_EPS)
     assert abs(u["w3"][0] - (0.3 - step)) < 1e-4 * step
 
 
@@ -104,8 +105,8 @@ def test_restatement_by_hand():
 def test_defaults_give_todays_result():
     s, z, p = _tiny()
     w = nets.init_mlp12x100(1, bn_noise=True)
-    plain = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, _backend=fit_ref.RefBackend())
-    be = A.RefBackend("mlp12x100")
+    plain = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, _backend=S.RefBackend("mlp12x100"))
+    be = S.RefBackend("mlp12x100")
     for adam in (None, AdamOptions(), AdamOptions().as_dict()):
         res = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, adam=adam, _backend=be)
         assert tuple(res.history) == HISTORY_KEYS and res.history == plain.history
@@ -124,7 +125,8 @@ def test_defaults_give_todays_result():
 def test_backend_without_adam():
     s, z, p = _tiny()
     w = nets.init_mlp12x100(1)
-    for be in (fit_ref.RefBackend(), O.RefBackend("mlp12x100")):
+    for be in (S.BaseOnly(S.RefBackend("mlp12x100")),
+               S.BaseOnly(S.RefBackend("mlp12x100"), "set_options", "get_options", "train_stats")):
         assert not hasattr(be, "set_adam")
         fit(w, s, z, p, batch_size=32, epochs=1, _backend=be)
         fit(w, s, z, p, batch_size=32, epochs=1, adam=AdamOptions(), _backend=be)
@@ -136,7 +138,7 @@ def test_fit_judges_epochs_by_the_averaged_weights():
     s, z, p = _tiny()
     w = nets.init_mlp12x100(1, bn_noise=True)
     ad = AdamOptions(beta_2=0.99, amsgrad=True, ema_momentum=0.9)
-    be = A.RefBackend("mlp12x100")
+    be = S.RefBackend("mlp12x100")
     seen = []  # (val_loss, evaluated weights, averaged weights, raw weights) of every evaluate
     evaluate = be.evaluate
 
@@ -151,7 +153,7 @@ def test_fit_judges_epochs_by_the_averaged_weights():
     assert be.set_adam_calls == [ad] and be.swaps == 6 and be.applied == 1
     assert tuple(res.history) == HISTORY_KEYS and len(seen) == 3
     # every epoch's val_loss is that of the averaged weights: the same epochs by hand, swapping ourselves
-    hand = A.RefBackend("mlp12x100")
+    hand = S.RefBackend("mlp12x100")
     hand.set_weights(w)
     hand.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
     hand.set_data(s, z, p)
@@ -182,7 +184,7 @@ def test_fit_judges_epochs_by_the_averaged_weights():
     assert raw.optimizer[0].tobytes() == res.optimizer[0].tobytes()  # without overwrite the iterates are the same
     # and the next call with the defaults sets the backend back
     off = fit(w, s, z, p, batch_size=16, epochs=3, seed=1, _backend=be)
-    plain = fit(w, s, z, p, batch_size=16, epochs=3, seed=1, _backend=fit_ref.RefBackend())
+    plain = fit(w, s, z, p, batch_size=16, epochs=3, seed=1, _backend=S.RefBackend("mlp12x100"))
     assert be.set_adam_calls[-1] == AdamOptions() and off.weights.tobytes() == plain.weights.tobytes()
     assert off.slots is None
 
@@ -191,7 +193,7 @@ def test_fit_resident_resumes_from_slots():
     s, z, p = _tiny()
     w = nets.init_mlp12x100(1, bn_noise=True)
     ad = AdamOptions(amsgrad=True, ema_momentum=0.5)
-    be = A.RefBackend("mlp12x100")
+    be = S.RefBackend("mlp12x100")
     be.data_info = lambda: (64, 0)
     be.set_data(s, z, p)
     planted = {"vhat": np.full(w.size, 1e6, np.float32), "average": np.zeros(w.size, np.float32)}

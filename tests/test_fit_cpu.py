@@ -6,8 +6,11 @@ import pytest
 import torch
 
 from corintho_ai_amd import nets
-from corintho_ai_amd.fit import HISTORY_KEYS, MIN_DELTA, fit, split_index
+from corintho_ai_amd.fit import (HISTORY_KEYS, METRIC_HISTORY_KEYS, MIN_DELTA, OPTION_HISTORY_KEYS, AdamOptions, FitOptions,
+                                 LossOptions, fit, split_index)
 from tests import fit_ref as R
+from tests import fit_ref_loss as L
+from tests import fit_ref_step as S
 
 
 def _data(n, seed=0):
@@ -19,7 +22,7 @@ def test_gradients_match_central_differences():
     tensor, 12-layer net, batch 8"""
     w = nets.init_mlp12x100(3, bn_noise=True).astype(np.float64)
     s, z, p = _data(8, 1)
-    g, _, _ = R.loss_and_grad(w, s, z, p)
+    g, _, _ = S.loss_and_grad(R, w, s, z, p)
     lay, (kv, bv, kp, bp) = R.layer_offsets()
     rng = np.random.default_rng(2)
     coords = []
@@ -32,7 +35,7 @@ def test_gradients_match_central_differences():
     def loss(wv):
         with torch.no_grad():
             logits, v, _ = R.forward(torch.as_tensor(wv), torch.as_tensor(s, dtype=torch.float64), True)
-            lv, lp = R.losses(logits, v, torch.as_tensor(z, dtype=torch.float64), torch.as_tensor(p, dtype=torch.float64))
+            _, lv, lp = L.batch_losses(logits, v, torch.as_tensor(z, dtype=torch.float64), torch.as_tensor(p, dtype=torch.float64), LossOptions())
             return float(lv + 0.25 * lp)
 
     h = 1e-6
@@ -47,14 +50,14 @@ def test_gradients_match_central_differences():
 def test_moving_variance_is_the_biased_batch_variance():
     w = nets.init_mlp12x100(4, bn_noise=True).astype(np.float64)
     s, z, p = _data(16, 2)
-    g, _, st = R.loss_and_grad(w, s, z, p)
+    g, _, st = S.loss_and_grad(R, w, s, z, p)
     lay, _ = R.layer_offsets()
     k, b, _, _, mu, va, fi = lay[0]
     a = np.maximum(s.astype(np.float64) @ w[k:k + fi * 100].reshape(fi, 100) + w[b:b + 100], 0.0)
     assert np.allclose(st[0][1], a.var(0, ddof=0)) and not np.allclose(st[0][1], a.var(0, ddof=1))
     m, v = np.zeros_like(w), np.zeros_like(w)
     w2 = w.copy()
-    R.adam_step(w2, m, v, g, 0, 1e-3, st)
+    S.adam_step(R, w2, m, v, g, 0, 1e-3, st)
     assert np.allclose(w2[va:va + 100], w[va:va + 100] - (w[va:va + 100] - a.var(0, ddof=0)) * 0.01)
     assert np.allclose(w2[mu:mu + 100], 0.99 * w[mu:mu + 100] + 0.01 * a.mean(0))
     assert not m[R.stat_mask()].any() and not v[R.stat_mask()].any()
@@ -64,17 +67,17 @@ def test_one_adam_update_by_hand():
     """TF ResourceApplyAdam with epsilon outside the root, at step 1 and step 3"""
     w = nets.init_mlp12x100(5).astype(np.float64)
     s, z, p = _data(8, 3)
-    g, _, st = R.loss_and_grad(w, s, z, p)
+    g, _, st = S.loss_and_grad(R, w, s, z, p)
     i = int(np.argmax(np.abs(g[:7000])))  # a layer-0 kernel entry with a gradient
     assert g[i] != 0.0
     m, v, w2 = np.zeros_like(w), np.zeros_like(w), w.copy()
-    assert R.adam_step(w2, m, v, g, 0, 0.001, st) == 1
+    assert S.adam_step(R, w2, m, v, g, 0, 0.001, st) == 1
     lr_t = 0.001 * np.sqrt(1 - 0.999) / (1 - 0.9)
     mm, vv = 0.1 * g[i], 0.001 * g[i] ** 2
     assert np.isclose(m[i], mm) and np.isclose(v[i], vv)
     assert np.isclose(w2[i], w[i] - lr_t * mm / (np.sqrt(vv) + 1e-7))
     m[i], v[i], w3 = 0.5, 0.25, w2.copy()
-    R.adam_step(w3, m, v, g, 2, 0.001, st)
+    S.adam_step(R, w3, m, v, g, 2, 0.001, st)
     lr_t = 0.001 * np.sqrt(1 - 0.999 ** 3) / (1 - 0.9 ** 3)
     mm, vv = 0.5 + (g[i] - 0.5) * 0.1, 0.25 + (g[i] ** 2 - 0.25) * 0.001
     assert np.isclose(w3[i], w2[i] - lr_t * mm / (np.sqrt(vv) + 1e-7))
@@ -85,7 +88,7 @@ def test_cross_entropy_from_logits():
     logits = torch.tensor(rng.normal(0, 3, (5, 96)), requires_grad=True)
     t = torch.tensor(rng.dirichlet(np.ones(96), 5))
     v = torch.zeros(5, dtype=torch.float64)
-    _, lp = R.losses(logits, v, torch.zeros(5, dtype=torch.float64), t)
+    _, _, lp = L.batch_losses(logits, v, torch.zeros(5, dtype=torch.float64), t, LossOptions())
     sm = np.exp(logits.detach().numpy())
     sm /= sm.sum(1, keepdims=True)
     assert np.isclose(float(lp), np.mean(-(t.numpy() * np.log(sm)).sum(1)))
@@ -152,7 +155,7 @@ def test_split_before_shuffling_and_every_training_row_once():
 def test_partial_last_batch_with_the_restatement():
     """n_train % batch != 0: the restatement's steps cover every training row once, the last batch partial"""
     s, z, p = _data(30, 4)
-    be = R.RefBackend()
+    be = S.RefBackend("mlp12x100")
     res = fit(nets.init_mlp12x100(1), s, z, p, batch_size=8, epochs=2, _backend=be)
     assert split_index(30, 0.3) == 21
     for r in be.trained_rows:
@@ -203,9 +206,9 @@ def test_fit_with_the_restatement_keeps_the_best_epoch():
     """the checkpoint's weights give the history's smallest val_loss, computed on the validation rows alone"""
     s, z, p = _data(200, 5)
     w = nets.init_mlp12x100(2)
-    be = R.RefBackend()
+    be = S.RefBackend("mlp12x100")
     res = fit(w, s, z, p, batch_size=32, epochs=3, learning_rate=0.003, _backend=be)
-    best = R.evaluate(res.best_weights.astype(np.float64), s[140:], z[140:], p[140:])[0][0]
+    best = S.evaluate(R, res.best_weights.astype(np.float64), s[140:], z[140:], p[140:])[0][0]
     assert np.isclose(min(res.history["val_loss"]), best, rtol=1e-5)
     assert res.best_epoch == int(np.argmin(res.history["val_loss"]))
 
@@ -226,3 +229,39 @@ def test_argument_validation():
             fit(args["weights"], args["game_states"], args["eval_labels"], args["prob_labels"], _backend=be, **kw)
     with pytest.raises(ValueError):  # one row leaves no training rows
         fit(w, s[:1], z[:1], p[:1], _backend=be)
+
+
+def test_every_family_at_once_and_each_switched_off_again():
+    """a Huber loss with smoothing, the regulariser with a clip, AMSGrad with averaged weights, sample weights and
+    metrics in one fit: the history has every family's keys, and the same fit without one family, on the backend that
+    just had it, is to the byte the fit of a backend that was never given that family"""
+    s, z, p = _data(64, 5)
+    w = nets.init_mlp12x100(1, bn_noise=True)
+    sw = np.where(np.arange(64) % 3 == 0, 0.0, 1.5).astype(np.float32)
+    calls = {"loss": (LossOptions(value_loss="huber", huber_delta=0.5, label_smoothing=0.1), ("set_loss", "get_loss")),
+             "options": (FitOptions(l2=1e-3, global_clipnorm=0.05), ("set_options", "get_options", "train_stats")),
+             "adam": (AdamOptions(amsgrad=True, ema_momentum=0.9),
+                      ("set_adam", "get_adam", "set_slot", "get_slot", "swap_average", "apply_average"))}
+    others = ("set_sample_weights", "set_metrics", "metrics")
+    kw = dict(batch_size=16, epochs=2, seed=1, sample_weight=sw, metrics=True)
+    be = S.RefBackend("mlp12x100")
+    full = fit(w, s, z, p, _backend=be, **kw, **{k: v[0] for k, v in calls.items()})
+    assert tuple(full.history) == HISTORY_KEYS + OPTION_HISTORY_KEYS + METRIC_HISTORY_KEYS
+    assert all(len(x) == 2 for x in full.history.values()) and set(full.slots) == {"vhat", "average"}
+    plain = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, _backend=S.RefBackend("mlp12x100"))
+    assert full.weights.tobytes() != plain.weights.tobytes()
+    assert [full.history[k] for k in HISTORY_KEYS[:-1]] != [plain.history[k] for k in HISTORY_KEYS[:-1]]
+
+    def arrays(res):
+        out = [res.weights, res.best_weights, *res.optimizer[:2], *res.best_optimizer[:2]]
+        return [a.tobytes() for a in out + [d[k] for d in (res.slots, res.best_slots) for k in sorted(d or {})]]
+
+    for off in calls:
+        rest = {k: v[0] for k, v in calls.items() if k != off}
+        again = fit(w, s, z, p, _backend=be, **kw, **rest)
+        never = S.BaseOnly(S.RefBackend("mlp12x100"), *others, *(n for k, v in calls.items() if k != off for n in v[1]))
+        assert not any(hasattr(never, n) for n in calls[off][1])
+        want = fit(w, s, z, p, _backend=never, **kw, **rest)
+        assert again.history == want.history and again.best_epoch == want.best_epoch, off
+        assert arrays(again) == arrays(want) and again.optimizer[2] == want.optimizer[2] == 6, off
+        assert again.weights.tobytes() != full.weights.tobytes(), off

@@ -9,6 +9,8 @@ from corintho_ai_amd import NET_MLP12X100, NET_RESCNN4, Trainer, nets, samples_i
 from corintho_ai_amd.fit import Fitter, fit, net_info, split_index
 from tests import fit_ref as R
 from tests import fit_ref_rescnn4
+from tests import fit_ref_step as S
+from tests.fit_ref_step import within as _within
 
 pytestmark = pytest.mark.gpu
 
@@ -30,12 +32,6 @@ def _tensors():
                   ("bp", slice(bp, bp + 96))]
 
 
-def _within(dev, f32, f64, floor):
-    e_dev = float(np.max(np.abs(np.asarray(dev, np.float64) - f64)))
-    e_32 = float(np.max(np.abs(np.asarray(f32, np.float64) - f64)))
-    return e_dev <= 4.0 * e_32 + floor, e_dev, e_32
-
-
 @pytest.fixture(scope="module")
 def selfplay():
     t = Trainer(64, "", 21, 50, 16, 1.0, 0.25, 0, 1, False, stagger=False)
@@ -44,22 +40,6 @@ def selfplay():
     s, z, p = samples_io.get_samples(t)
     assert s.shape[0] >= 2048
     return s, z, p
-
-
-def _kink_margin(w, states):
-    """smallest |pre-activation| / its layer's largest, over the batch in float64 (training mode): where it is tiny a
-    ReLU sits at its kink, the gradient is not defined there, and float32 rounding picks either side"""
-    lay, _ = R.layer_offsets()
-    wt = R.torch.as_tensor(w, dtype=R.torch.float64)
-    h = R.torch.as_tensor(states, dtype=R.torch.float64)
-    m = np.inf
-    for (k, b, ga, be, _, _, fi) in lay:
-        z = h @ wt[k:k + fi * 100].view(fi, 100) + wt[b:b + 100]
-        m = min(m, float(z.abs().min() / z.abs().max()))
-        a = R.torch.relu(z)
-        mu = a.mean(0)
-        h = wt[ga:ga + 100] * ((a - mu) * R.torch.rsqrt(((a - mu) ** 2).mean(0) + nets.BN_EPS)) + wt[be:be + 100]
-    return m
 
 
 def test_gradients_of_one_batch(selfplay):
@@ -78,10 +58,10 @@ def test_gradients_of_one_batch(selfplay):
                     rows = rng.choice(data[0].shape[0], B, replace=False).astype(np.int32)
                     g, losses = f.gradients(rows)
                     s, z, p = (a[rows] for a in data)
-                    g64, l64, _ = R.loss_and_grad(w, s, z, p)
-                    g32, l32, _ = R.loss_and_grad(w, s, z, p, dtype=R.torch.float32)
+                    g64, l64, _ = S.loss_and_grad(R, w, s, z, p)
+                    g32, l32, _ = S.loss_and_grad(R, w, s, z, p, dtype=R.torch.float32)
                     assert not g[R.stat_mask()].any(), "gradient at a moving statistic"
-                    kink = _kink_margin(w, s) < 2e-7
+                    kink = S.kink_margin(R, w, s) < 2e-7
                     cases += 1
                     kinked += kink
                     for name, sl in _tensors():
@@ -116,7 +96,7 @@ def test_twenty_adam_steps(kind, init, ref):
     assert it == 20
     refs = {}
     for dt in (ref.torch.float64, ref.torch.float32):
-        be = ref.RefBackend(dt)
+        be = S.RefBackend(ref.NET, dt)
         be.set_weights(w)
         be.set_optimizer(zeros, zeros, 0)
         be.set_data(s, z, p)
@@ -131,9 +111,9 @@ def test_twenty_adam_steps(kind, init, ref):
     print("moving statistics dev %.3e f32 %.3e" % (ed, e3))
     assert ok, ("moving statistics", ed, e3)
     held = slice(5120, 5632)
-    out64 = ref.evaluate(w64, s[held], z[held], p[held])[1]
-    out32 = ref.evaluate(w32, s[held], z[held], p[held])[1]
-    outd = ref.evaluate(wd.astype(np.float64), s[held], z[held], p[held])[1]
+    out64 = S.evaluate(ref, w64, s[held], z[held], p[held])[1]
+    out32 = S.evaluate(ref, w32, s[held], z[held], p[held])[1]
+    outd = S.evaluate(ref, wd.astype(np.float64), s[held], z[held], p[held])[1]
     for k, name in enumerate(("value", "policy")):
         ok, ed, e3 = _within(outd[k], out32[k], out64[k], 1e-6)
         print("%s dev %.3e f32 %.3e" % (name, ed, e3))

@@ -15,6 +15,7 @@ from corintho_ai_amd import run as R
 from corintho_ai_amd.fit import HISTORY_KEYS, METRIC_HISTORY_KEYS, METRIC_KEYS, METRIC_NAMES, MIN_DELTA
 from tests import fit_ref
 from tests import fit_ref_loss as L
+from tests import fit_ref_step as S
 from tests.emu import emulib
 from tests.test_run_cpu import StubFitter, comparable, open_run, small
 
@@ -176,8 +177,8 @@ def _plateau(vals, lr, anneal, patience):
 def test_defaults_give_todays_history():
     s, z, p = _tiny()
     w = nets.init_mlp12x100(1, bn_noise=True)
-    plain = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, _backend=fit_ref.RefBackend())
-    be = L.RefBackend("mlp12x100")
+    plain = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, _backend=S.RefBackend("mlp12x100"))
+    be = S.RefBackend("mlp12x100")
     for loss in (None, LossOptions(), LossOptions().as_dict()):
         res = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, loss=loss, metrics=False, _backend=be)
         assert tuple(res.history) == HISTORY_KEYS and res.history == plain.history
@@ -193,7 +194,7 @@ def test_fit_with_loss_and_metrics():
     s, z, p = _tiny()
     w = nets.init_mlp12x100(1, bn_noise=True)
     loss = LossOptions(value_weight=2.0, policy_weight=0.5, label_smoothing=0.1, value_loss="huber", huber_delta=0.5)
-    be = L.RefBackend("mlp12x100")
+    be = S.RefBackend("mlp12x100")
     res = fit(w, s, z, p, batch_size=16, epochs=5, seed=1, patience=1, anneal_factor=0.5, loss=loss, metrics={"top_k": 3},
               _backend=be)
     h = res.history
@@ -209,7 +210,7 @@ def test_fit_with_loss_and_metrics():
     assert all(0.0 <= x <= 1.0 for k in METRIC_HISTORY_KEYS if "accuracy" in k for x in h[k])
     assert all(a <= b for a, b in zip(h["val_policy_categorical_accuracy"], h["val_policy_top_k_categorical_accuracy"]))
     assert len(set(h["val_target_entropy"])) == 1 and h["val_target_entropy"][0] > 0  # the targets do not move
-    lo, v = L.predict(fit_ref, be.w, s[44:], False)
+    lo, v = S.predict(fit_ref, be.w, s[44:], False)
     want = L.metrics(lo, v, z[44:], p[44:], 3)
     for k, name in zip(METRIC_KEYS, METRIC_NAMES):
         assert abs(h["val_" + k][-1] - want[name]) < 1e-12, k
@@ -228,7 +229,7 @@ def test_fit_with_loss_and_metrics():
 def test_backend_without_loss_or_metrics():
     s, z, p = _tiny()
     w = nets.init_mlp12x100(1)
-    be = fit_ref.RefBackend()
+    be = S.BaseOnly(S.RefBackend("mlp12x100"))
     fit(w, s, z, p, batch_size=32, epochs=1, loss=LossOptions(), metrics=False, _backend=be)
     with pytest.raises(ValueError, match="set_loss"):
         fit(w, s, z, p, batch_size=32, epochs=1, loss=LossOptions(value_weight=2.0), _backend=be)
@@ -240,9 +241,9 @@ def test_sample_weights_enter_the_metrics():
     s, z, p = _tiny()
     w = nets.init_mlp12x100(1, bn_noise=True)
     sw = np.where(np.arange(64) % 3 == 0, 0.0, 1.5).astype(np.float32)
-    be = L.RefBackend("mlp12x100")
+    be = S.RefBackend("mlp12x100")
     res = fit(w, s, z, p, batch_size=16, epochs=1, seed=1, sample_weight=sw, metrics=True, _backend=be)
-    lo, v = L.predict(fit_ref, be.w, s[44:], False)
+    lo, v = S.predict(fit_ref, be.w, s[44:], False)
     want = L.metrics(lo, v, z[44:], p[44:], 5, w=sw[44:])
     assert be.metrics()["weight_sum"] == float(sw[44:].sum()) == want["weight_sum"]
     assert abs(res.history["val_value_mean_absolute_error"][0] - want["mean_absolute_error"]) < 1e-12
@@ -255,14 +256,14 @@ def test_the_synthetic_set_yields_batches_off_hubers_kink(net):
     found off Huber's kink within the three redraws (the ReLU kink has its exception there)"""
     from tests import test_fit_loss_gpu as G
 
-    ref = L.BASE[net]
+    ref = S.BASE[net]
     data = G.expanded(_cdll=emulib.load())
     w = G.KINDS[net][1](5, bn_noise=True)
     relu = []
     for name, loss, weighted in G.GENERAL:
         rng = G.general_rng(name)
         for B in G.BATCHES:
-            rows, relu_ok, huber_ok = L.draw_batch(ref, w, data[0], data[1], rng, B, loss, G.general_candidates(weighted, B))
+            rows, relu_ok, huber_ok = S.draw_batch(ref, w, data[0], data[1], rng, B, loss, G.general_candidates(weighted, B))
             assert huber_ok, (name, B)
             assert not weighted or (G.sample_weights()[rows // 8] == 0).any() == (B > 1)
             assert rows.size == B and len(set(rows.tolist())) == B
@@ -301,7 +302,7 @@ class LossFitter(StubFitter):
 
     def __init__(self):
         super().__init__()
-        self.inner = L.RefBackend("mlp12x100", torch.float32)
+        self.inner = S.RefBackend("mlp12x100", torch.float32)
         self.inner.data = None
 
     def set_loss(self, loss=None):

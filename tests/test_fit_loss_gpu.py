@@ -17,7 +17,8 @@ from corintho_ai_amd.fit import HISTORY_KEYS, METRIC_HISTORY_KEYS, METRIC_NAMES,
 from tests import fit_ref, fit_ref_rescnn4
 from tests import fit_ref_loss as L
 from tests import fit_ref_weighted as RW
-from tests.test_fit_gpu import _within
+from tests import fit_ref_step as S
+from tests.fit_ref_step import within as _within
 
 pytestmark = pytest.mark.gpu
 
@@ -76,7 +77,7 @@ class Ctx:
     def __init__(self, net):
         self.net = net
         self.kind, init = KINDS[net]
-        self.ref = L.BASE[net]
+        self.ref = S.BASE[net]
         self.w = init(5, bn_noise=True)
         self.zeros = np.zeros_like(self.w)
         self.data = expanded()
@@ -186,14 +187,14 @@ def test_general_values_against_float64(ctx):
         rng = general_rng(name)
         f = ctx.start(loss, weights=sw if weighted else None)
         for B in BATCHES:
-            r, relu_ok, huber_ok = L.draw_batch(ref, w, data[0], data[1], rng, B, loss, general_candidates(weighted, B))
+            r, relu_ok, huber_ok = S.draw_batch(ref, w, data[0], data[1], rng, B, loss, general_candidates(weighted, B))
             assert huber_ok, (name, B)
             assert not weighted or B == 1 or (sw[r // 8] == 0).any()  # a row of weight 0 is in the larger batches
             g, losses = f.gradients(r)
             s, z, p = (a[r] for a in data)
             swr = sw[r // 8] if weighted else None
-            g64, l64, _ = L.loss_and_grad(ref, w, s, z, p, loss, swr)
-            g32, l32, _ = L.loss_and_grad(ref, w, s, z, p, loss, swr, dtype=ref.torch.float32)
+            g64, l64, _ = S.loss_and_grad(ref, w, s, z, p, loss, swr)
+            g32, l32, _ = S.loss_and_grad(ref, w, s, z, p, loss, swr, dtype=ref.torch.float32)
             assert not g[ref.stat_mask()].any(), "gradient at a moving statistic"
             kink = not relu_ok
             cases += 1
@@ -219,8 +220,8 @@ def test_general_values_against_float64(ctx):
 # ---------------------------------------------------------------------------------------------------- 4. predict
 def outputs_within(got, ref, w, states, train, what):
     """the heads of predict against the float64 forward by the _within rule, floor 1e-6 of the output's scale"""
-    o64 = L.predict(ref, w, states, train)
-    o32 = L.predict(ref, w, states, train, ref.torch.float32)
+    o64 = S.predict(ref, w, states, train)
+    o32 = S.predict(ref, w, states, train, ref.torch.float32)
     for name, d, a32, a64 in zip(("logits", "values"), got, o32, o64):
         ok, ed, e3 = _within(d, a32, a64, 1e-6 * max(1.0, float(np.max(np.abs(a64)))))
         print("%s %s dev %.3e f32 %.3e" % (what, name, ed, e3))
@@ -374,8 +375,8 @@ def test_fit_end_to_end(net):
     assert a.best_epoch == b.best_epoch and same(a.optimizer[0], b.optimizer[0]) and same(a.optimizer[1], b.optimizer[1])
     assert tuple(a.history) == HISTORY_KEYS + METRIC_HISTORY_KEYS and all(len(x) == 3 for x in a.history.values())
     data = expanded()
-    ref = L.BASE[net]
-    h64, h32 = (fit(w, *data, net=kind, _backend=L.RefBackend(net, dt), **kw) for dt in (ref.torch.float64, ref.torch.float32))
+    ref = S.BASE[net]
+    h64, h32 = (fit(w, *data, net=kind, _backend=S.RefBackend(net, dt), **kw) for dt in (ref.torch.float64, ref.torch.float32))
     assert a.best_epoch == h64.best_epoch and a.history["lr"] == h64.history["lr"]
     split_at = split_index(384, 0.3)
     for k in HISTORY_KEYS[:-1] + METRIC_HISTORY_KEYS:

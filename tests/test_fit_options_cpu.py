@@ -14,6 +14,7 @@ from corintho_ai_amd import run as R
 from corintho_ai_amd.fit import HISTORY_KEYS, OPTION_HISTORY_KEYS
 from tests import fit_ref, fit_ref_options as O
 from tests import fit_ref_rescnn4
+from tests import fit_ref_step as S
 from tests.test_run_cpu import StubFitter, open_run, small
 
 NETS = pytest.mark.parametrize("net", ["mlp12x100", "rescnn4"])
@@ -134,7 +135,7 @@ def _tiny():
 def test_fit_history_and_reset():
     s, z, p = _tiny()
     w = nets.init_mlp12x100(1, bn_noise=True)
-    be = O.RefBackend("mlp12x100")
+    be = S.RefBackend("mlp12x100")
     o = FitOptions(l2=1e-3, weight_decay=1e-2, global_clipnorm=0.05)
     on = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, options=o, _backend=be)
     assert be.set_options_calls == [o]
@@ -149,7 +150,7 @@ def test_fit_history_and_reset():
     # the next call asks for none: the backend is reset, the keys are the old ones, the result that of a plain backend
     off = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, _backend=be)
     assert be.set_options_calls == [o, FitOptions()] and tuple(off.history) == HISTORY_KEYS
-    plain = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, _backend=fit_ref.RefBackend())
+    plain = fit(w, s, z, p, batch_size=16, epochs=2, seed=1, _backend=S.RefBackend("mlp12x100"))
     assert off.weights.tobytes() == plain.weights.tobytes() and off.history == plain.history
     assert on.weights.tobytes() != plain.weights.tobytes()
     # all-zero options are no options
@@ -163,7 +164,7 @@ def test_fit_history_and_reset():
 def test_backend_without_options():
     s, z, p = _tiny()
     w = nets.init_mlp12x100(1)
-    be = fit_ref.RefBackend()
+    be = S.BaseOnly(S.RefBackend("mlp12x100"))
     assert not hasattr(be, "set_options")
     fit(w, s, z, p, batch_size=32, epochs=1, _backend=be)
     fit(w, s, z, p, batch_size=32, epochs=1, options=FitOptions(), _backend=be)

@@ -19,6 +19,7 @@ from corintho_ai_amd import run as R
 from corintho_ai_amd.fit import Fitter, fit_resident, fit_samples
 from tests import fit_ref
 from tests import fit_ref_options as O
+from tests import fit_ref_step as S
 
 pytestmark = pytest.mark.gpu
 
@@ -371,7 +372,7 @@ def test_twenty_steps_with_options(net):
     """l2, weight_decay and global_clipnorm together, 20 steps of 256 rows, by the rule and floors of
     test_fit_gpu.test_twenty_adam_steps: the device's error against float64 at most 4 x the float32 restatement's + 1e-6"""
     kind, init = KINDS[net]
-    ref = O.BASE[net]
+    ref = S.BASE[net]
     o = FitOptions(l2=1e-3, weight_decay=1e-2, global_clipnorm=0.5)
     s, z, p = ref.synthetic_samples(5120 + 512, 12)
     w = init(5, bn_noise=True)
@@ -388,7 +389,7 @@ def test_twenty_steps_with_options(net):
         assert f.get_optimizer()[2] == 20 and st["steps"] == 20
     refs = {}
     for dt in (ref.torch.float64, ref.torch.float32):
-        be = O.RefBackend(net, dt)
+        be = S.RefBackend(net, dt)
         be.set_weights(w)
         be.set_optimizer(zeros, zeros, 0)
         be.set_data(s, z, p)
@@ -408,9 +409,9 @@ def test_twenty_steps_with_options(net):
     print("moving statistics dev %.3e f32 %.3e" % (ed, e3))
     assert ok, ("moving statistics", ed, e3)
     held = slice(5120, 5632)
-    out64 = ref.evaluate(w64, s[held], z[held], p[held])[1]
-    out32 = ref.evaluate(w32, s[held], z[held], p[held])[1]
-    outd = ref.evaluate(wd.astype(np.float64), s[held], z[held], p[held])[1]
+    out64 = S.evaluate(ref, w64, s[held], z[held], p[held])[1]
+    out32 = S.evaluate(ref, w32, s[held], z[held], p[held])[1]
+    outd = S.evaluate(ref, wd.astype(np.float64), s[held], z[held], p[held])[1]
     for k, name in enumerate(("value", "policy")):
         ok, ed, e3 = _within(outd[k], out32[k], out64[k], 1e-6)
         print("%s dev %.3e f32 %.3e" % (name, ed, e3))

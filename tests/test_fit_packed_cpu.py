@@ -7,14 +7,15 @@ import pytest
 from corintho_ai_amd import expand_samples, nets
 from corintho_ai_amd.fit import fit, fit_resident, fit_samples, fit_trainer
 from tests import fit_ref as R
+from tests import fit_ref_step as S
 from tests.emu import emulib
 
 
-class PackedRefBackend(R.RefBackend):
+class PackedRefBackend(S.RefBackend):
     """RefBackend with the packed protocol: the samples are kept un-augmented and expanded by ca_expand_samples"""
 
     def __init__(self):
-        super().__init__()
+        super().__init__("mlp12x100")
         self.calls = []
         self.clear_data()
 
@@ -32,7 +33,7 @@ class PackedRefBackend(R.RefBackend):
         return 8 * self.sp.shape[0], self.sp.shape[0]
 
 
-class PlainBackend(R.RefBackend):
+class PlainBackend(S.RefBackend):
     """what tests/test_fit_cpu.py drives fit() with; any other method fit() reached for would be missing"""
 
     def __getattr__(self, name):
@@ -59,7 +60,7 @@ def _same_fit(a, b):
 @pytest.fixture(scope="module")
 def expanded_fit(samples):
     sp, oc = samples
-    be = PlainBackend()
+    be = PlainBackend("mlp12x100")
     res = fit(nets.init_mlp12x100(1), *expand_samples(sp, oc, _cdll=emulib.load()), _backend=be, **KW)
     return res, be
 

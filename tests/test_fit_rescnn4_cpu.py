@@ -7,7 +7,10 @@ import torch
 
 from corintho_ai_amd import NET_RESCNN4, nets
 from corintho_ai_amd.fit import HISTORY_KEYS, MIN_DELTA, fit, split_index
+from corintho_ai_amd.fit import LossOptions
+from tests import fit_ref_loss as L
 from tests import fit_ref_rescnn4 as R
+from tests import fit_ref_step as S
 from tests import ref_nets
 
 WEIGHTS = [("init", lambda: nets.init_rescnn4(0)), ("bn-noise", lambda: nets.init_rescnn4(7, bn_noise=True)),
@@ -19,7 +22,7 @@ def test_inference_mode_is_the_projects_forward(name, make):
     w = make()
     s, z, p = R.synthetic_samples(48, 2)
     ev64, pr64 = ref_nets.rescnn4_forward_f64(w, s)
-    _, (ev, pr) = R.evaluate(w, s, z, p)
+    _, (ev, pr) = S.evaluate(R, w, s, z, p)
     assert np.max(np.abs(ev - ev64)) <= 1e-6 and np.max(np.abs(pr - pr64)) <= 1e-6  # the oracle returns float32
 
 
@@ -43,14 +46,14 @@ def test_gradients_match_central_differences():
     batch 6, weights with every BatchNorm term perturbed"""
     w = nets.init_rescnn4(3, bn_noise=True).astype(np.float64)
     s, z, p = R.synthetic_samples(6, 1)
-    g, _, _ = R.loss_and_grad(w, s, z, p)
+    g, _, _ = S.loss_and_grad(R, w, s, z, p)
     rng = np.random.default_rng(2)
     st, zt, pt = (torch.as_tensor(a, dtype=torch.float64) for a in (s, z, p))
 
     def loss(wv):
         with torch.no_grad():
             logits, v, _ = R.forward(torch.as_tensor(wv), st, True)
-            lv, lp = R.losses(logits, v, zt, pt)
+            _, lv, lp = L.batch_losses(logits, v, zt, pt, LossOptions())
             return float(lv + 0.25 * lp)
 
     h = 1e-6
@@ -75,7 +78,7 @@ def test_moving_statistics_by_hand():
     every moving statistic moves 1 % of the way toward its batch statistic"""
     w = nets.init_rescnn4(4, bn_noise=True).astype(np.float64)
     s, z, p = R.synthetic_samples(5, 2)
-    g, _, st = R.loss_and_grad(w, s, z, p)
+    g, _, st = S.loss_and_grad(R, w, s, z, p)
     assert len(st) == len(R.BN_PREFIXES) == 11
     W = nets.rescnn4_unpack(w.astype(np.float32))
     x = np.pad(nets.rescnn4_input_planes(s).astype(np.float64), ((0, 0), (1, 1), (1, 1), (0, 0)))
@@ -88,7 +91,7 @@ def test_moving_statistics_by_hand():
     assert np.allclose(st[0][0], zc.mean(0)) and np.allclose(st[0][1], zc.var(0, ddof=0))
     assert not np.allclose(st[0][1], zc.var(0, ddof=1))
     m, v, w2 = np.zeros_like(w), np.zeros_like(w), w.copy()
-    R.adam_step(w2, m, v, g, 0, 1e-3, st)
+    S.adam_step(R, w2, m, v, g, 0, 1e-3, st)
     off = R.offsets()
     for pre, (bm, bv) in zip(R.BN_PREFIXES, st):
         mu, va = R._slice(off, pre + "_bn2"), R._slice(off, pre + "_bn3")
@@ -101,18 +104,18 @@ def test_one_adam_update_by_hand():
     """TF ResourceApplyAdam with epsilon outside the root, at step 1 and step 3, on a block kernel entry"""
     w = nets.init_rescnn4(5).astype(np.float64)
     s, z, p = R.synthetic_samples(8, 3)
-    g, _, st = R.loss_and_grad(w, s, z, p)
+    g, _, st = S.loss_and_grad(R, w, s, z, p)
     sl = R._slice(R.offsets(), "b1_c2_k")
     i = sl.start + int(np.argmax(np.abs(g[sl])))
     assert g[i] != 0.0
     m, v, w2 = np.zeros_like(w), np.zeros_like(w), w.copy()
-    assert R.adam_step(w2, m, v, g, 0, 0.001, st) == 1
+    assert S.adam_step(R, w2, m, v, g, 0, 0.001, st) == 1
     lr_t = 0.001 * np.sqrt(1 - 0.999) / (1 - 0.9)
     mm, vv = 0.1 * g[i], 0.001 * g[i] ** 2
     assert np.isclose(m[i], mm) and np.isclose(v[i], vv)
     assert np.isclose(w2[i], w[i] - lr_t * mm / (np.sqrt(vv) + 1e-7))
     m[i], v[i], w3 = 0.5, 0.25, w2.copy()
-    R.adam_step(w3, m, v, g, 2, 0.001, st)
+    S.adam_step(R, w3, m, v, g, 2, 0.001, st)
     lr_t = 0.001 * np.sqrt(1 - 0.999 ** 3) / (1 - 0.9 ** 3)
     mm, vv = 0.5 + (g[i] - 0.5) * 0.1, 0.25 + (g[i] ** 2 - 0.25) * 0.001
     assert np.isclose(w3[i], w2[i] - lr_t * mm / (np.sqrt(vv) + 1e-7))
@@ -122,7 +125,7 @@ def test_fit_rescnn4_with_the_restatement():
     """fit(..., net=NET_RESCNN4) on rescnn4 weights: history, the checkpoint, ReduceLROnPlateau, the size check"""
     s, z, p = R.synthetic_samples(60, 5)
     w = nets.init_rescnn4(2)
-    be = R.RefBackend(torch.float64)
+    be = S.RefBackend("rescnn4", torch.float64)
     # a learning rate too large for 60 rows: the validation loss rises after the first epoch, so ReduceLROnPlateau acts
     res = fit(w, s, z, p, batch_size=16, epochs=6, learning_rate=0.01, patience=2, anneal_factor=0.5, net=NET_RESCNN4,
               _backend=be)
@@ -151,15 +154,15 @@ def test_fit_rescnn4_with_the_restatement():
         assert sorted(r.tolist()) == list(range(split))
     assert res.optimizer[2] == 6 * -(-split // 16)
     assert res.best_weights.size == nets.RESCNN4_NUM_WEIGHTS
-    best = R.evaluate(res.best_weights.astype(np.float64), s[split:], z[split:], p[split:])[0][0]
+    best = S.evaluate(R, res.best_weights.astype(np.float64), s[split:], z[split:], p[split:])[0][0]
     assert np.isclose(min(vals), best, rtol=1e-5)
     # a real learning rate moves the weights and the moving statistics
-    res2 = fit(w, s, z, p, batch_size=16, epochs=1, learning_rate=1e-3, net=NET_RESCNN4, _backend=R.RefBackend())
+    res2 = fit(w, s, z, p, batch_size=16, epochs=1, learning_rate=1e-3, net=NET_RESCNN4, _backend=S.RefBackend("rescnn4"))
     mask = R.stat_mask()
     assert np.any(res2.weights[mask] != w[mask]) and np.any(res2.weights[~mask] != w[~mask])
     with pytest.raises(ValueError, match="rescnn4"):
-        fit(nets.init_mlp12x100(0), s, z, p, net=NET_RESCNN4, _backend=R.RefBackend())
+        fit(nets.init_mlp12x100(0), s, z, p, net=NET_RESCNN4, _backend=S.RefBackend("rescnn4"))
     with pytest.raises(ValueError, match="mlp12x100"):
-        fit(w, s, z, p, _backend=R.RefBackend())
+        fit(w, s, z, p, _backend=S.RefBackend("rescnn4"))
     with pytest.raises(ValueError):
-        fit(w, s, z, p, net=7, _backend=R.RefBackend())
+        fit(w, s, z, p, net=7, _backend=S.RefBackend("rescnn4"))

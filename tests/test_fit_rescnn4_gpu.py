@@ -12,7 +12,8 @@ from corintho_ai_amd.fit import Fitter, fit, split_index
 from tests import fit_ref
 from tests import fit_ref_rescnn4 as R
 from tests import ref_nets
-from tests.test_fit_gpu import _within
+from tests import fit_ref_step as S
+from tests.fit_ref_step import within as _within
 
 pytestmark = pytest.mark.gpu
 
@@ -25,8 +26,8 @@ def _check_gradient(f, w, data, rows, tag, kink, bad):
     """one batch's device gradient and losses against the two restatements; failures are appended to bad"""
     g, losses = f.gradients(rows)
     s, z, p = (a[rows] for a in data)
-    g64, l64, _ = R.loss_and_grad(w, s, z, p)
-    g32, l32, _ = R.loss_and_grad(w, s, z, p, dtype=R.torch.float32)
+    g64, l64, _ = S.loss_and_grad(R, w, s, z, p)
+    g32, l32, _ = S.loss_and_grad(R, w, s, z, p, dtype=R.torch.float32)
     assert not g[R.stat_mask()].any(), "gradient at a moving statistic"
     for name, sl, scale in R.tensors():
         top = float(np.max(np.abs(g64[scale])))
@@ -56,7 +57,7 @@ def test_gradients_of_small_batches():
             f.set_weights(w)
             for B in (1, 2, 5, 16, 17, 24):
                 rows = rng.choice(4096, B, replace=False).astype(np.int32)
-                margin = R.kink_margin(w, data[0][rows])
+                margin = S.kink_margin(R, w, data[0][rows])
                 kink = margin < KINK
                 print("%s B=%d margin %.3e" % (wname, B, margin))
                 cases += 1
@@ -82,7 +83,7 @@ def test_gradients_at_scale_without_a_kink():
             f.set_weights(w)
             for B in (256, 2047, 2048):
                 rows = rng.choice(4096, B, replace=False).astype(np.int32)
-                margin = R.kink_margin(w, data[0][rows])
+                margin = S.kink_margin(R, w, data[0][rows])
                 print("seed %d B=%d margin %.3e" % (seed, B, margin))
                 assert margin >= KINK, (seed, B, margin)
                 _check_gradient(f, w, data, rows, "seed %d B=%d" % (seed, B), False, bad)
@@ -109,8 +110,8 @@ def test_whole_loop_small(tmp_path):
     assert min(vals) < start, (vals, start)
     assert res.best_epoch == int(np.argmin(vals))
     # the best epoch's val_loss is the restatement's on the checkpoint
-    l64 = R.evaluate(res.best_weights, s[split:], z[split:], p[split:])[0]
-    l32 = R.evaluate(res.best_weights, s[split:], z[split:], p[split:], dtype=R.torch.float32)[0]
+    l64 = S.evaluate(R, res.best_weights, s[split:], z[split:], p[split:])[0]
+    l32 = S.evaluate(R, res.best_weights, s[split:], z[split:], p[split:], dtype=R.torch.float32)[0]
     ok, ed, e3 = _within(vals[res.best_epoch], l32[0], l64[0], 1e-6 * abs(l64[0]))
     print("val_loss dev %.3e f32 %.3e" % (ed, e3))
     assert ok, ("val_loss of the best epoch", ed, e3)

@@ -24,7 +24,9 @@ import pytest
 from corintho_ai_amd import NET_RESCNN4, nets
 from corintho_ai_amd.fit import Fitter
 from tests import fit_ref
-from tests.test_fit_gpu import _kink_margin, _tensors, _within
+from tests import fit_ref_step as S
+from tests.fit_ref_step import within as _within
+from tests.test_fit_gpu import _tensors
 from tests.test_fit_rescnn4_gpu import KINK, R, _check_gradient
 
 pytestmark = pytest.mark.gpu
@@ -75,7 +77,7 @@ def test_gradients_above_2048_rows_without_a_kink(large, B):
     """strictly, as test_gradients_at_scale_without_a_kink: with 12 added to every beta each BatchNorm-fed ReLU is
     active, and no ReLU input of these batches lies within 2e-7 of its kink"""
     f, w, data, rows = large
-    margin = R.kink_margin(w, data[0][rows[B]])
+    margin = S.kink_margin(R, w, data[0][rows[B]])
     print("seed %d B=%d margin %.3e plan %s" % (SEED, B, margin, _plan(B)))
     assert margin >= KINK, (SEED, B, margin)
     bad = []
@@ -104,10 +106,10 @@ def test_mlp_gradients_of_4097_rows():
         f.set_weights(w)
         g, losses = f.gradients(rows)
     s, z, p = (a[rows] for a in data)
-    g64, l64, _ = fit_ref.loss_and_grad(w, s, z, p)
-    g32, l32, _ = fit_ref.loss_and_grad(w, s, z, p, dtype=fit_ref.torch.float32)
+    g64, l64, _ = S.loss_and_grad(fit_ref, w, s, z, p)
+    g32, l32, _ = S.loss_and_grad(fit_ref, w, s, z, p, dtype=fit_ref.torch.float32)
     assert not g[fit_ref.stat_mask()].any(), "gradient at a moving statistic"
-    kink = _kink_margin(w, s) < 2e-7
+    kink = S.kink_margin(fit_ref, w, s) < 2e-7
     bad = []
     for name, sl in _tensors():
         top = float(np.max(np.abs(g64[sl])))

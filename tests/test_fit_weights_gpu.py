@@ -10,7 +10,7 @@ from corintho_ai_amd import NET_MLP12X100, NET_RESCNN4, expand_samples, nets
 from corintho_ai_amd.fit import Fitter, fit, fit_samples, net_info
 from tests import fit_ref, fit_ref_rescnn4
 from tests import fit_ref_weighted as RW
-from tests.test_fit_gpu import _within
+from tests.fit_ref_step import within as _within
 
 pytestmark = pytest.mark.gpu
 

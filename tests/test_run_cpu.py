@@ -15,17 +15,18 @@ import torch
 from corintho_ai_amd import Run, RunParams, expand_samples, samples_io, train_generation
 from corintho_ai_amd import run as R
 from tests import fit_ref
+from tests import fit_ref_step as S
 from tests.conftest import REFERENCE, ROOT
 from tests.emu import emulib
 
 TOML = os.path.join(REFERENCE, "toml")
 
 
-class StubFitter(fit_ref.RefBackend):
+class StubFitter(S.RefBackend):
     """fit_ref's restatement in float32 behind the packed protocol of fit.Fitter; it records what the driver gives it"""
 
     def __init__(self):
-        super().__init__(torch.float32)
+        super().__init__("mlp12x100", torch.float32)
         self.num_weights = R.nets.MLP_NUM_WEIGHTS
         self.started_from = []   # (weights, m, v, iterations) of every fit
         self.datasets = []       # (state_policy, outcome) every fit ran on
