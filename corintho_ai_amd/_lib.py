@@ -169,6 +169,7 @@ EXPORTS = [
     "ca_fitter_set_adam", "ca_fitter_get_adam", "ca_fitter_set_slot", "ca_fitter_get_slot", "ca_fitter_swap_average",
     "ca_fitter_apply_average",
     "ca_fitter_set_loss", "ca_fitter_get_loss", "ca_fitter_set_metrics", "ca_fitter_metrics", "ca_fitter_predict",
+    "ca_fitter_set_augmentation", "ca_fitter_get_augmentation", "ca_fitter_canonicalize",
 ]
 # the caller-supplied network: an earlier build of the library has none of these
 NET_FN_EXPORTS = ["ca_trainer_request_rows", "ca_trainer_set_net_fn", "ca_tourney_set_net_fn", "ca_net_create", "ca_net_forward_device",
@@ -187,8 +188,10 @@ ADAM_EXPORTS = ["ca_fitter_set_adam", "ca_fitter_get_adam", "ca_fitter_set_slot"
                 "ca_fitter_apply_average"]
 # the loss options, the metrics and predict: likewise
 LOSS_EXPORTS = ["ca_fitter_set_loss", "ca_fitter_get_loss", "ca_fitter_set_metrics", "ca_fitter_metrics", "ca_fitter_predict"]
+# the augmentation choice of a packed set and the canonical orientation: likewise
+AUG_EXPORTS = ["ca_fitter_set_augmentation", "ca_fitter_get_augmentation", "ca_fitter_canonicalize"]
 assert set(NET_FN_EXPORTS + GROUP_EXPORTS + WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS + ADAM_EXPORTS
-           + LOSS_EXPORTS) <= set(EXPORTS)
+           + LOSS_EXPORTS + AUG_EXPORTS) <= set(EXPORTS)
 
 
 def declare(L):
@@ -283,7 +286,8 @@ def declare(L):
             continue
         if name in GROUP_EXPORTS and not group:
             continue
-        if name in WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS + ADAM_EXPORTS + LOSS_EXPORTS and not hasattr(L, name):
+        if (name in WEIGHT_EXPORTS + NET_IO_EXPORTS + OPTION_EXPORTS + ADAM_EXPORTS + LOSS_EXPORTS + AUG_EXPORTS
+                and not hasattr(L, name)):
             continue
         fn = getattr(L, name)
         if name not in ("ca_last_error", "ca_trainer_destroy", "ca_tourney_destroy", "ca_fitter_destroy", "ca_net_destroy",
@@ -334,6 +338,10 @@ def _declare_fitter(L, vp, f64p):
         L.ca_fitter_set_metrics.argtypes = [vp, C.c_int32, C.c_int32]
         L.ca_fitter_metrics.argtypes = [vp, C.POINTER(CaFitMetrics)]
         L.ca_fitter_predict.argtypes = [vp, i32p, C.c_int32, C.c_int32, f32p, f32p]
+    if hasattr(L, "ca_fitter_canonicalize"):  # (likewise)
+        L.ca_fitter_set_augmentation.argtypes = [vp, C.c_int32]
+        L.ca_fitter_get_augmentation.argtypes = [vp, i32p]
+        L.ca_fitter_canonicalize.argtypes = [vp, i32p]
 
 
 _lib = None

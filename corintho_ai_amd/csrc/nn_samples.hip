@@ -21,7 +21,15 @@
 // probe loop is bounded by the table's size and raises a flag (CA_ERR_INTERNAL) when it runs out; so does a sort
 // position or a member index outside [0, n).  The products w * p of two float32 are exact in float64; the division and
 // the conversions are IEEE (the build has no fast-math: build.py).
+//
+// Also here: the canonical orientation of a packed set's samples (ca_fitter_canonicalize; DESIGN.md, "Canonical
+// orientation"), sm_k_canonicalize, after which the merge above is a merge up to the eight symmetries.
 #include "nn_train.h"
+#include "tables.inc"
+
+/* the engine's symmetry tables (kernels.h CO_SPACE_SYM, CO_MOVE_SYM), from the same initialisers of tables.inc */
+__constant__ int32_t SM_SPACE_SYM[CA_NUM_SYMMETRIES][16] = CO_SPACE_SYM_INIT;
+__constant__ int32_t SM_MOVE_SYM[CA_NUM_SYMMETRIES][CA_NUM_MOVES] = CO_MOVE_SYM_INIT;
 
 #define SM_STATE CA_GAME_STATE_SIZE
 #define SM_ROW (CA_GAME_STATE_SIZE + CA_NUM_MOVES)
@@ -282,7 +290,61 @@ __global__ __launch_bounds__(256) void sm_k_compact(const float *__restrict__ ts
   }
 }
 
+/* The canonical orientation of a sample (ca_fitter_canonicalize, corintho_hip.h; DESIGN.md, "Canonical orientation"),
+ * in place.  One wavefront per sample, four per workgroup as sm_k_segment.  Lane l holds board word l as its bit
+ * pattern; candidate k is one cross-lane gather of it, the source lane SS[k][l / 4] * 4 + l % 4 from the table.  A
+ * candidate is compared with the best so far by the ballot of the lanes where they differ: the first such lane holds
+ * the most significant difference, and the two words there decide, as unsigned integers.  Everything the decision
+ * reads is the same in all lanes, so it is wave-uniform and the kernel has no LDS and no barrier.  On a tie the earlier
+ * k stays.  The policy moves through MC[k*] (MS with rows 2 and 6 exchanged, from the one table) in the same way: two
+ * registers hold its 96 entries.  The row's floats are all in registers before any is stored, and a sample with
+ * k* == 0 stores nothing; cells 64..69 never move.  moved: the count of samples with k* != 0, an integer atomic. */
+__global__ __launch_bounds__(256) void sm_k_canonicalize(float *__restrict__ sp, int n, int32_t *__restrict__ moved) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return; /* whole waves leave; the kernel has no barrier */
+  uint32_t *row = (uint32_t *)sp + (long)i * SM_ROW;
+  const uint32_t w = row[lane];
+  const uint32_t p0 = row[SM_STATE + lane];
+  const uint32_t p1 = lane < CA_NUM_MOVES - 64 ? row[SM_STATE + 64 + lane] : 0u;
+  uint32_t best = w;
+  int kb = 0;
+  for (int k = 1; k < CA_NUM_SYMMETRIES; ++k) {
+    const uint32_t cand = (uint32_t)__shfl((int)w, SM_SPACE_SYM[k][lane >> 2] * 4 + (lane & 3));
+    const unsigned long long diff = __ballot(cand != best);
+    if (diff == 0ull) continue; /* (wave-uniform) a tie: the lower k stays */
+    const int at = __ffsll(diff) - 1;
+    const uint32_t a = (uint32_t)__shfl((int)cand, at), b = (uint32_t)__shfl((int)best, at);
+    if (a < b) {
+      best = cand;
+      kb = k;
+    }
+  }
+  if (kb == 0) return; /* (wave-uniform) */
+  const int km = (kb & 3) == 2 ? kb ^ 4 : kb; /* MC's row kb */
+  const int m0 = SM_MOVE_SYM[km][lane], m1 = lane < CA_NUM_MOVES - 64 ? SM_MOVE_SYM[km][64 + lane] : 0;
+  /* entry m comes from lane m % 64 of the register that holds it; every lane takes part in every gather */
+  const uint32_t q0a = (uint32_t)__shfl((int)p0, m0 & 63), q0b = (uint32_t)__shfl((int)p1, m0 & 63);
+  const uint32_t q1a = (uint32_t)__shfl((int)p0, m1 & 63), q1b = (uint32_t)__shfl((int)p1, m1 & 63);
+  row[lane] = best;
+  row[SM_STATE + lane] = m0 < 64 ? q0a : q0b;
+  if (lane < CA_NUM_MOVES - 64) row[SM_STATE + 64 + lane] = m1 < 64 ? q1a : q1b;
+  if (lane == 0) atomicAdd(moved, 1);
+}
+
 /* ------------------------------------------------------------------ host */
+int32_t ft_canonicalize(rt_stream_t s, float *sp, int32_t n) {
+  if (n <= 0) return 0;
+  DevBuf<int32_t> moved;
+  moved.alloc(1, s); /* zeroed */
+  RT_LAUNCH(sm_k_canonicalize, (n + 3) / 4, 256, s, sp, n, moved.p);
+  int32_t m = 0;
+  rt_d2h(&m, moved.p, sizeof(m), s);
+  rt_sync(s);
+  if (m < 0 || m > n) throw CaError(CA_ERR_INTERNAL, "ca_fitter_canonicalize: moved count out of range");
+  return m;
+}
+
 /* exclusive scan of a[0..m) in place; sums: room for ceil(m / 1024) values */
 static void sm_scan(rt_stream_t s, int32_t *a, long m, int32_t *sums) {
   const int nb = (int)((m + SM_SCAN - 1) / SM_SCAN);

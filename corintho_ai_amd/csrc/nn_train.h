@@ -160,6 +160,9 @@ struct FtMerged {
   int32_t count = 0, cap = 0;
 };
 FtMerged ft_merge_duplicates(rt_stream_t s, const float *sp, const float *oc, const float *wt, int32_t n, bool normalize);
+/* The n samples of sp[n][166] brought into their canonical orientation in place (nn_samples.hip; the definition:
+ * ca_fitter_canonicalize in corintho_hip.h).  Returns how many changed their orientation; s is synchronised on return. */
+int32_t ft_canonicalize(rt_stream_t s, float *sp, int32_t n);
 
 #define FT_SAMPLE_FLOATS (CA_GAME_STATE_SIZE + CA_NUM_MOVES) /* a packed row: state[70], policy[96] */
 typedef void (*FtCopy)(void *, const void *, size_t, rt_stream_t); /* rt_h2d or rt_d2d */
@@ -189,6 +192,9 @@ struct FtData {
   void add(const float *state_policy, const float *outcome, int32_t count, FtCopy copy); /* all four, and the copy */
   void drop(int32_t n_oldest);                                  /* ca_fitter_drop_samples */
   void merge(bool normalize, int32_t *before, int32_t *after);  /* ca_fitter_merge_duplicates */
+  void canonicalize(int32_t *moved);                            /* ca_fitter_canonicalize */
+  void set_augmentation(int32_t a);                             /* ca_fitter_set_augmentation: CA_AUG_* */
+  int32_t augmentation() const { return aug; }
   void set_weights(const float *weights, int32_t count);        /* ca_fitter_set_sample_weights */
   void get_weights(float *out, int32_t count);
   void fetch_rows(const int32_t *rows, int32_t n_rows, float *st, float *ev, float *pr);
@@ -200,6 +206,7 @@ struct FtData {
   bool expanded = false;      /* the form: set by set_expanded, until clear */
   int32_t ns = 0, cap = 0;    /* packed samples, and how many sp and oc have room for */
   bool weighted = false;      /* set_weights, merge; until clear */
+  int32_t aug = CA_AUG_REFERENCE; /* which move table a packed set's virtual rows go through; the fitter's, not the set's */
   DevBuf<float> states, evals, probs;          /* the expanded set */
   DevBuf<float> sp, oc;                        /* the packed set: state_policy[cap][166], outcome[cap] */
   DevBuf<float> wt;                            /* when `weighted`: [n] of an expanded set, [cap] beside sp and oc */

@@ -395,6 +395,25 @@ extern "C" int ca_fitter_merge_duplicates(ca_fitter *f, int normalize, int32_t *
   });
 }
 
+/* ------------------------------------------------------------------ augmentation choice, canonical orientation */
+extern "C" int ca_fitter_set_augmentation(ca_fitter *f, int32_t augmentation) {
+  return co_guard(f, [&] { f->data.set_augmentation(augmentation); });
+}
+
+extern "C" int ca_fitter_get_augmentation(ca_fitter *f, int32_t *augmentation) {
+  return co_guard(f, [&] {
+    if (!augmentation) throw CaError(CA_ERR_ARG, "ca_fitter_get_augmentation: null output");
+    *augmentation = f->data.augmentation();
+  });
+}
+
+extern "C" int ca_fitter_canonicalize(ca_fitter *f, int32_t *moved) {
+  return co_guard(f, [&] {
+    if (!moved) throw CaError(CA_ERR_ARG, "ca_fitter_canonicalize: null output");
+    f->data.canonicalize(moved);
+  });
+}
+
 /* ------------------------------------------------------------------ fit options */
 extern "C" int ca_fitter_set_options(ca_fitter *f, const ca_fit_options *options) {
   return co_guard(f, [&] {

@@ -4,8 +4,9 @@
 // un-augmented rows of co_k_pack_samples, whose 8n virtual rows (row v = sample v / 8 under symmetry v % 8) exist only
 // batch by batch: one launch (ft_k_assemble) writes the batch's rows as the expanded arrays would hold them and the
 // same kernels, launched the same way, read that batch through an identity index -- so a step is the same to the bit in
-// either form.  Here: ft_k_assemble and the symmetry tables it gathers through; the set's buffers, counts and sample
-// weights; the row checks and the rows of a call; growing, sliding, dropping and merging of a packed set; fetch_rows.
+// either form.  Here: ft_k_assemble and the symmetry tables it gathers through (and ft_k_assemble_consistent, the packed
+// rows through the consistent move table: CA_AUG_CONSISTENT); the set's buffers, counts and sample weights; the row
+// checks and the rows of a call; growing, sliding, dropping, merging and canonicalizing of a packed set; fetch_rows.
 #include "nn_train.h"
 #include "tables.inc"
 
@@ -58,11 +59,43 @@ __global__ __launch_bounds__(256) void ft_k_assemble(FtSource d, const int32_t *
   }
 }
 
+/* The packed half of ft_k_assemble under CA_AUG_CONSISTENT: the policy goes through MC[k], which is MS with rows 2 and
+ * 6 exchanged -- row k ^ 4 of the one table where (k & 3) == 2.  A kernel of its own, for a packed set only (d.sp is
+ * never null here): sharing a body with ft_k_assemble changed that kernel's weighted instantiation, and the kernels of
+ * the reference's pairing stay instruction for instruction what they were before there was a choice. */
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void ft_k_assemble_consistent(FtSource d, const int32_t *__restrict__ rows, int B,
+                                                               float *__restrict__ bs, float *__restrict__ be,
+                                                               float *__restrict__ bp, const float *__restrict__ wt,
+                                                               float *__restrict__ bw) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * FT_SAMPLE_FLOATS) return;
+  const int r = e / FT_SAMPLE_FLOATS, c = e % FT_SAMPLE_FLOATS;
+  const int v = rows[r];
+  const int i = v >> 3, k = v & 7;
+  const float *src = d.sp + (long)i * FT_SAMPLE_FLOATS;
+  if (c < CA_GAME_STATE_SIZE) {
+    bs[(long)r * CA_GAME_STATE_SIZE + c] = src[c < 64 ? FT_SPACE_SYM[k][c >> 2] * 4 + (c & 3) : c];
+  } else {
+    const int m = c - CA_GAME_STATE_SIZE;
+    bp[(long)r * CA_NUM_MOVES + m] = src[CA_GAME_STATE_SIZE + FT_MOVE_SYM[(k & 3) == 2 ? k ^ 4 : k][m]];
+  }
+  if (c == 0) be[r] = d.oc[i];
+  if (WEIGHTED && c == 0) bw[r] = wt[i];
+}
+
 /* ------------------------------------------------------------------ host */
 void FtData::assemble(const int32_t *rows, int B) {
   const FtSource src = {expanded ? nullptr : sp.p, oc.p, states.p, evals.p, probs.p};
   const int grid = (B * FT_SAMPLE_FLOATS + 255) / 256;
-  if (weighted)
+  const bool consistent = !expanded && aug == CA_AUG_CONSISTENT; /* an expanded set's rows are the caller's */
+  if (consistent && weighted)
+    RT_LAUNCH(ft_k_assemble_consistent<true>, grid, 256, s, src, rows, B, bstates.p, bevals.p, bprobs.p, (const float *)wt.p,
+              bwts.p);
+  else if (consistent)
+    RT_LAUNCH(ft_k_assemble_consistent<false>, grid, 256, s, src, rows, B, bstates.p, bevals.p, bprobs.p,
+              (const float *)nullptr, (float *)nullptr);
+  else if (weighted)
     RT_LAUNCH(ft_k_assemble<true>, grid, 256, s, src, rows, B, bstates.p, bevals.p, bprobs.p, (const float *)wt.p, bwts.p);
   else
     RT_LAUNCH(ft_k_assemble<false>, grid, 256, s, src, rows, B, bstates.p, bevals.p, bprobs.p, (const float *)nullptr,
@@ -217,6 +250,20 @@ void FtData::merge(bool normalize, int32_t *before, int32_t *after) {
   weighted = true;
   cap = m.cap;
   added(m.count - ns);
+}
+
+void FtData::set_augmentation(int32_t a) {
+  if (a != CA_AUG_REFERENCE && a != CA_AUG_CONSISTENT)
+    throw CaError(CA_ERR_ARG, "ca_fitter_set_augmentation: the augmentation must be CA_AUG_REFERENCE or CA_AUG_CONSISTENT");
+  rt_sync(s);
+  aug = a;
+}
+
+void FtData::canonicalize(int32_t *moved) {
+  if (expanded) throw CaError(CA_ERR_STATE, "ca_fitter_canonicalize: the data set is expanded");
+  if (ns <= 0) throw CaError(CA_ERR_STATE, "ca_fitter_canonicalize: no samples (ca_fitter_add_samples)");
+  rt_sync(s);
+  *moved = ft_canonicalize(s, sp.p, ns);
 }
 
 void FtData::set_weights(const float *weights, int32_t count) {

@@ -38,6 +38,14 @@ Fitter.merge_duplicates merges the duplicate positions of a packed set on the de
 (DESIGN.md "Merging duplicate positions"; samples_io.merge_duplicates_host is its definition).  A set without weights
 is fitted by the kernels that know of none.
 
+The reference's move table does not belong to its space table for the two quarter-turns (DESIGN.md, quirk list): the
+policies of virtual rows 8 i + 2 and 8 i + 6 are each other's.  Fitter.set_augmentation("consistent"), or
+fit_samples(..., augmentation="consistent"), expands a packed set through the move table with those two rows exchanged;
+the default stays the reference's, bit for bit.  Fitter.canonicalize() turns every sample of a packed set into the
+smallest of its eight images (samples_io.canonicalize_host is its definition), and merge_duplicates(symmetries=True)
+merges up to symmetry that way (DESIGN.md "Canonical orientation").  fit_resident leaves the fitter's augmentation alone,
+as it leaves the data alone.
+
 Fit options (FitOptions; include/corintho_hip.h "fit options" is the definition): what the reference's model declares and
 leaves at zero -- kernel_regularizer=L1L2() on its hidden Dense layers -- and what its Adam's constructor takes:
     res = fit_resident(fitter, weights, options=FitOptions(l2=1e-4, weight_decay=1e-4, global_clipnorm=1.0))
@@ -79,6 +87,7 @@ import numpy as np
 
 from . import _lib
 from .nets import GAME_STATE_SIZE, MLP_NUM_WEIGHTS, NUM_MOVES, RESCNN4_NUM_WEIGHTS
+from .samples_io import AUGMENTATIONS
 from .trainer import NET_MLP12X100, NET_RESCNN4, Trainer
 
 SAMPLE_FLOATS = GAME_STATE_SIZE + NUM_MOVES  # a packed row: state[70], policy[96]
@@ -451,14 +460,44 @@ class Fitter:
         self._check(self._L.ca_fitter_get_sample_weights(self._h, _ptr(w), w.size))
         return w
 
-    def merge_duplicates(self, normalize=True):
+    # ---- the augmentation of a packed set and its canonical orientation (include/corintho_hip.h) ----
+    def set_augmentation(self, augmentation="reference"):
+        """how virtual row 8 i + k of a packed set is expanded: "reference" -- the policy through the reference's move
+        table, whose rows 2 and 6 belong to each other's rotation -- or "consistent" -- through the move table with those
+        two rows exchanged (samples_io.symmetry_tables, samples_io.expand_host).  It belongs to the fitter and stays
+        until set again; an expanded set (set_data) is never touched."""
+        if augmentation not in AUGMENTATIONS:
+            raise ValueError('the augmentation must be "reference" or "consistent", got %r' % (augmentation,))
+        self._check(self._L.ca_fitter_set_augmentation(self._h, AUGMENTATIONS[augmentation]))
+
+    def get_augmentation(self):
+        a = C.c_int32()
+        self._check(self._L.ca_fitter_get_augmentation(self._h, C.byref(a)))
+        return {v: k for k, v in AUGMENTATIONS.items()}[a.value]
+
+    def canonicalize(self):
+        """Bring every sample of a packed set into its canonical orientation on the device: of the eight symmetric images
+        of its board the one whose 64 words are smallest as unsigned patterns, the policy moved along through the
+        consistent move table (samples_io.canonicalize_host is the definition, and equals this bit for bit).  Outcomes
+        and weights stay, and the set takes more samples afterwards.  Returns how many samples changed."""
+        moved = C.c_int32()
+        self._check(self._L.ca_fitter_canonicalize(self._h, C.byref(moved)))
+        return moved.value
+
+    def merge_duplicates(self, normalize=True, symmetries=False):
         """Merge the duplicate positions of a packed set on the device: samples whose 70 state floats have the same
         bits become one sample at the rank of the first of them, with the weighted mean of their policies and outcomes
         (float64 sums over the members in ascending index, rounded once) and the sum W of their weights as its weight
         (samples_io.merge_duplicates_host is the definition, and equals this bit for bit).  normalize: the weights are
         scaled to mean one.  A group whose weights are all 0 has W = 0 and no mean: it is dropped, members and all.
         The set carries weights afterwards, so add_* is refused until clear_data: merge once, after the last add.
-        Returns (samples before, samples after)."""
+        Returns (samples before, samples after).
+        symmetries: canonicalize() first, so that positions which are images of one another merge as well; the merge
+        itself is the same.  Under set_augmentation("consistent") the merged set expands to the rows the unmerged one
+        expands to, with mean targets; under "reference" the rows 2 and 6 of an image are other (wrong) rows than those
+        of the sample, and the merge is not that equivalence ("Canonical orientation")."""
+        if symmetries:
+            self.canonicalize()
         before, after = C.c_int32(), C.c_int32()
         self._check(self._L.ca_fitter_merge_duplicates(self._h, 1 if normalize else 0, C.byref(before), C.byref(after)))
         return before.value, after.value
@@ -796,36 +835,59 @@ def fit_resident(fitter, weights, *, learning_rate=0.001, batch_size=2048, epoch
     return _run(fitter, int(fitter.data_info()[0]), w, call, "fit_resident")
 
 
+def _set_augmentation(be, augmentation):
+    """a call's augmentation on the backend that is being filled: the call decides.  A backend without the setter
+    serves the calls that ask for the reference's."""
+    if inspect.getattr_static(be, "set_augmentation", None) is not None:
+        be.set_augmentation(augmentation)
+    elif augmentation != "reference":
+        raise ValueError("fit: the backend %s has no set_augmentation" % type(be).__name__)
+
+
+def _check_augmentation(augmentation, who):
+    if augmentation not in AUGMENTATIONS:
+        raise ValueError('%s: augmentation must be "reference" or "consistent", got %r' % (who, augmentation))
+
+
 def fit_samples(weights, state_policy, outcome, *, device=0, net=NET_MLP12X100, sample_weight=None,
-                merge_duplicates=False, _backend=None, **kw):
+                merge_duplicates=False, merge_symmetries=False, augmentation="reference", _backend=None, **kw):
     """fit() from un-augmented samples (Trainer.export_samples, dist.SampleGather.rows): a packed data set, 668 bytes
     a sample on the device instead of 5 344.  fit_samples(w, sp, oc, seed=s) equals fit(w, *expand_samples(sp, oc),
     seed=s) to the bit: the 8 n virtual rows are in expand_samples' row order, so the validation split and every
     epoch's permutation are the same.  sample_weight: one weight per sample (Keras's sample_weight; the sample's 8
     virtual rows share it).  merge_duplicates: Fitter.merge_duplicates(normalize=True) on the set, weights and all,
-    before the fit -- the same as fitting samples_io.merge_duplicates_host's three arrays.  Keywords as fit_resident's."""
+    before the fit -- the same as fitting samples_io.merge_duplicates_host's three arrays; with merge_symmetries the
+    merge is up to the eight symmetries (merge_duplicates(symmetries=True); it implies the merge).  augmentation: "reference" or "consistent",
+    how the 8 n virtual rows are expanded (Fitter.set_augmentation): with "consistent" the fit equals fit(w,
+    *samples_io.expand_host(sp, oc, "consistent"), seed=s) to the bit.  The call decides: a fitter left with another
+    augmentation is set to this one.  Keywords as fit_resident's."""
     call = _call(**kw)
+    _check_augmentation(augmentation, "fit_samples")
     w = _weights(weights, net, "fit_samples")
     sp, oc = _packed(state_policy, outcome, "fit_samples")
     sw = _sample_weight(sample_weight, sp.shape[0], "fit_samples")
 
     def fill(be):
         be.clear_data()
+        _set_augmentation(be, augmentation)
         be.add_samples(sp, oc)
         if sw is not None:
             be.set_sample_weights(sw)
-        if merge_duplicates:
+        if merge_symmetries:
+            be.merge_duplicates(normalize=True, symmetries=True)
+        elif merge_duplicates:
             be.merge_duplicates(normalize=True)
         return int(be.data_info()[0])
 
     return _run_filled(fill, w, call, device, net, _backend, "fit_resident")
 
 
-def fit_trainer(weights, trainers, *, device=0, net=NET_MLP12X100, _backend=None, **kw):
+def fit_trainer(weights, trainers, *, device=0, net=NET_MLP12X100, augmentation="reference", _backend=None, **kw):
     """fit() from the samples of one finished Trainer, or of a sequence of them added in that order, taken device to
     device (Fitter.add_trainer_samples).  fit_trainer(w, t, seed=s) equals fit(w, *samples_io.get_samples(t), seed=s) to
-    the bit.  Keywords as fit_resident's; the trainers must be on `device`."""
+    the bit.  augmentation: as fit_samples'.  Keywords as fit_resident's; the trainers must be on `device`."""
     call = _call(**kw)
+    _check_augmentation(augmentation, "fit_trainer")
     ts = [trainers] if isinstance(trainers, Trainer) else list(trainers)
     if not ts:
         raise ValueError("fit_trainer: no trainer given")
@@ -833,6 +895,7 @@ def fit_trainer(weights, trainers, *, device=0, net=NET_MLP12X100, _backend=None
 
     def fill(be):
         be.clear_data()
+        _set_augmentation(be, augmentation)
         for t in ts:
             be.add_trainer_samples(t)
         return int(be.data_info()[0])

@@ -24,6 +24,12 @@ What is deliberately not the reference's:
     than once become one sample each, with the mean of their targets and a weight equal to their share
     (Fitter.merge_duplicates, normalised to mean one, so that a batch weighs what an unweighted one does; val_loss
     is lower all the same, because the merged targets are means: profiles/sample_merge.md).  samples.npz stays the un-merged export and fit_time.txt counts the generation's samples, as the reference does.
+  * merge_symmetries (off by default; implies merge_duplicates): the merge is up to the eight symmetries -- every sample
+    is first turned into the smallest of its eight images (Fitter.canonicalize; DESIGN.md "Canonical orientation").
+  * augmentation ("reference" by default): "consistent" expands the fit's samples through the move table that belongs
+    to the space table (the reference's rows 2 and 6 are each other's: DESIGN.md, quirk list).  It is written with the
+    other settings into every generation's metadata.txt; generation_settings() reads one back, and a run directory
+    from before the setting existed reads as "reference".
   * l1, l2, regularize, weight_decay, clipvalue, clipnorm, global_clipnorm (all off by default): the fit options of
     fit.FitOptions -- the regulariser the reference declares on its hidden layers and leaves at zero, and the arguments
     its Adam's constructor takes.  A generation that fits with any of them writes training_logs/fit_options.json: the
@@ -36,6 +42,7 @@ What is deliberately not the reference's:
 """
 import argparse
 import dataclasses
+import inspect
 import json
 import os
 import shutil
@@ -98,6 +105,8 @@ class RunParams:
     init_weights: object = None  # flat array or .npz for generation 0
     zip_logs: bool = False
     merge_duplicates: bool = False  # True: duplicate positions of the fit's window become one weighted sample each
+    merge_symmetries: bool = False  # True: the same up to the eight symmetries (implies merge_duplicates)
+    augmentation: str = "reference"  # or "consistent": the move table that belongs to the space table (fit.Fitter.set_augmentation)
     # the fit options (fit.FitOptions; include/corintho_hip.h "fit options"): 0 is off
     l1: float = 0.0
     l2: float = 0.0
@@ -153,7 +162,10 @@ class RunParams:
         if self.seed < 0:
             raise ValueError("seed must not be negative")
         self.mix_old, self.zip_logs = bool(self.mix_old), bool(self.zip_logs)
-        self.merge_duplicates = bool(self.merge_duplicates)
+        self.merge_symmetries = bool(self.merge_symmetries)
+        self.merge_duplicates = bool(self.merge_duplicates) or self.merge_symmetries
+        if self.augmentation not in samples_io.AUGMENTATIONS:
+            raise ValueError('augmentation must be "reference" or "consistent", not %r' % (self.augmentation,))
         self.amsgrad = bool(self.amsgrad)
         self.fit_options()  # ValueError: a negative value, two clip modes
         self.adam_options()  # ValueError: a beta outside [0, 1), ...
@@ -204,6 +216,17 @@ class GenerationResult:
 
 
 # ---------------------------------------------------------------------------------------------------- files
+def generation_settings(metadata_file):
+    """the settings a generation was trained with, from its metadata.txt; a setting that did not exist when the file was
+    written has its default (augmentation: "reference")"""
+    with open(metadata_file, encoding="utf-8") as f:
+        d = json.load(f)
+    for f in dataclasses.fields(RunParams):
+        if f.name not in d and f.default is not dataclasses.MISSING:
+            d[f.name] = f.default
+    return d
+
+
 def _write_text(path, text):
     """a metadata file, whole or not at all"""
     tmp = path + ".tmp"
@@ -389,6 +412,10 @@ def train_generation(params, state, *, _cdll=None, _fitter=None, _hook=None):
                                     *_trainer.expand_samples(state_policy, outcome, device=p.device, _cdll=_cdll))
         del state_policy, outcome
         _fitter.clear_data()
+        if inspect.getattr_static(_fitter, "set_augmentation", None) is not None:  # the run decides, not what the fitter was left with
+            _fitter.set_augmentation(p.augmentation)
+        elif p.augmentation != "reference":
+            raise ValueError("the fitter %s has no set_augmentation" % type(_fitter).__name__)
         if _fitter.add_trainer_samples(trainer) != num_samples:
             raise RuntimeError("generation %d: the fitter took another number of samples than the file" % generation)
     finally:
@@ -399,7 +426,8 @@ def train_generation(params, state, *, _cdll=None, _fitter=None, _hook=None):
             _fitter.add_samples(old_sp, old_oc)
     merged = None
     if p.merge_duplicates:  # after the last add: a set that carries weights takes no more samples
-        merged = tuple(int(x) for x in _fitter.merge_duplicates(normalize=True))
+        more = {"symmetries": True} if p.merge_symmetries else {}  # (a fitter from before the keyword serves the plain merge)
+        merged = tuple(int(x) for x in _fitter.merge_duplicates(normalize=True, **more))
         print("generation %d: merged %d samples into %d distinct positions" % (generation, merged[0], merged[1]), flush=True)
     times["samples"] = time.perf_counter() - t0
 
@@ -701,6 +729,14 @@ def _parser():
         elif f.name == "merge_duplicates":
             ap.add_argument("--merge-duplicates", "--merge_duplicates", dest="merge_duplicates", action="store_true",
                             default=False, help="Merge duplicate positions of the fit's samples into weighted ones")
+        elif f.name == "merge_symmetries":
+            ap.add_argument("--merge-symmetries", "--merge_symmetries", dest="merge_symmetries", action="store_true",
+                            default=False, help="Merge positions that are images of one another under the eight "
+                            "symmetries as well (implies --merge-duplicates)")
+        elif f.name == "augmentation":
+            ap.add_argument("--augmentation", choices=sorted(samples_io.AUGMENTATIONS), default="reference",
+                            help="Move table of the fit's symmetry expansion: reference (the reference's pairing) or "
+                            "consistent (rows 2 and 6 exchanged, so that policy and state turn alike). Default reference.")
         elif f.name == "amsgrad":
             ap.add_argument("--amsgrad", action="store_true", default=False, help="AMSGrad variant of the fit's Adam")
         elif f.name == "metrics":

@@ -92,9 +92,101 @@ def load_packed(sample_folder):
                          sample_folder)
 
 
-def merge_duplicates_host(state_policy, outcome, weights=None, normalize=True):
+AUGMENTATIONS = {"reference": 0, "consistent": 1}  # CA_AUG_* of include/corintho_hip.h
+_TABLES = None
+
+
+def symmetry_tables():
+    """(space [8, 16], move [8, 96], move_consistent [8, 96]) int32: the symmetry tables the kernels gather through,
+    read from the initialisers of csrc/tables.inc that they are compiled from.  space and move are the reference's
+    space_symmetries and move_symmetries.  move_consistent is move with rows 2 and 6 exchanged (row k ^ 4 where
+    (k & 3) == 2): the move table that belongs to space, row for row ("Canonical orientation")."""
+    global _TABLES
+    if _TABLES is None:
+        import re
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "tables.inc"), encoding="utf-8") as f:
+            text = f.read()
+        out = []
+        for name, width in (("CO_SPACE_SYM_INIT", 16), ("CO_MOVE_SYM_INIT", NUM_MOVES)):
+            m = re.search(r"#define %s \{(.*?)\n\}" % name, text, re.S)
+            if not m:
+                raise ValueError("csrc/tables.inc: no %s" % name)
+            t = np.array([int(x) for x in re.findall(r"\d+", m.group(1))], np.int32)
+            if t.size != NUM_SYMMETRIES * width:
+                raise ValueError("csrc/tables.inc: %s has %d entries" % (name, t.size))
+            out.append(t.reshape(NUM_SYMMETRIES, width))
+        space, move = out
+        consistent = move[[k ^ 4 if (k & 3) == 2 else k for k in range(NUM_SYMMETRIES)]]
+        for t in (space, move, consistent):
+            t.setflags(write=False)
+        _TABLES = (space, move, consistent)
+    return _TABLES
+
+
+def _state_gather(space):
+    """[8, 70]: where the cells of a state under symmetry k come from (cells 64..69 do not move)"""
+    c = np.arange(GAME_STATE_SIZE)
+    board = space[:, np.minimum(c, 63) >> 2] * 4 + (c & 3)
+    return np.where(c < 64, board, c)
+
+
+def _augmentation(augmentation, who):
+    if augmentation not in AUGMENTATIONS:
+        raise ValueError('%s: augmentation must be "reference" or "consistent", not %r' % (who, augmentation))
+    return augmentation
+
+
+def expand_host(state_policy, outcome, augmentation="reference"):
+    """The eight symmetry copies of un-augmented samples in plain numpy: -> (game_states [8 n, 70], eval_labels [8 n],
+    prob_labels [8 n, 96]) in Trainer.writeSamples' row order, sample i under symmetry k at row 8 i + k.  The state goes
+    through space[k]; the policy through move[k] ("reference": what the reference, writeSamples and expand_samples do)
+    or through move_consistent[k] ("consistent": rows 8 i + 2 and 8 i + 6 then carry each other's policy)."""
+    sp, oc = _check_packed(state_policy, outcome, "expand_host")
+    space, move, consistent = symmetry_tables()
+    table = consistent if _augmentation(augmentation, "expand_host") == "consistent" else move
+    n = sp.shape[0]
+    states = sp[:, :GAME_STATE_SIZE][:, _state_gather(space)]  # [n, 8, 70]
+    probs = sp[:, GAME_STATE_SIZE:][:, table]                  # [n, 8, 96]
+    return (np.ascontiguousarray(states.reshape(n * NUM_SYMMETRIES, GAME_STATE_SIZE)), np.repeat(oc, NUM_SYMMETRIES),
+            np.ascontiguousarray(probs.reshape(n * NUM_SYMMETRIES, NUM_MOVES)))
+
+
+def canonicalize_host(state_policy):
+    """The canonical orientation of un-augmented samples: -> (state_policy [n, 166] float32, k_star [n] int32).  This
+    is the definition that Fitter.canonicalize computes on the device, bit for bit.
+
+    Of a sample (s, p) the eight candidates are s_k[c] = s[space[k][c >> 2] * 4 + (c & 3)] for c < 64; cells 64..69 do
+    not move.  k* is the k whose candidate is smallest when words 0..63 are compared in ascending order as unsigned
+    32-bit patterns (so -0.0 sorts after 0.0), the lowest k on a tie.  The canonical sample is
+    (s_k*, p[move_consistent[k*]]): the policy always moves through the consistent table, the only pairing with the
+    space table that is a group action.  Samples that are images of one another get the same state."""
+    sp = np.ascontiguousarray(state_policy, dtype=np.float32)
+    if sp.ndim != 2 or sp.shape[1] != SAMPLE_FLOATS:
+        raise ValueError("canonicalize_host: state_policy must be [n, %d], got %s" % (SAMPLE_FLOATS, sp.shape))
+    space, _, consistent = symmetry_tables()
+    n = sp.shape[0]
+    if n == 0:
+        return sp.copy(), np.zeros(0, np.int32)
+    cand = sp[:, :GAME_STATE_SIZE][:, _state_gather(space)]  # [n, 8, 70]
+    words = np.ascontiguousarray(cand[:, :, :64]).view(np.uint32)
+    rows = np.arange(n)
+    k_star = np.zeros(n, np.int32)
+    best = words[:, 0]
+    for k in range(1, NUM_SYMMETRIES):  # candidate k against the best so far: the first word that differs decides
+        differs = words[:, k] != best
+        at = np.argmax(differs, axis=1)
+        better = differs.any(axis=1) & (words[rows, k, at] < best[rows, at])
+        best = np.where(better[:, None], words[:, k], best)
+        k_star[better] = k
+    policy = sp[:, GAME_STATE_SIZE:][rows[:, None], consistent[k_star]]
+    return np.ascontiguousarray(np.concatenate([cand[rows, k_star], policy], axis=1)), k_star
+
+
+def merge_duplicates_host(state_policy, outcome, weights=None, normalize=True, symmetries=False):
     """Merge the duplicate positions of un-augmented samples: -> (state_policy, outcome, weights) float32.  This is the
-    definition that Fitter.merge_duplicates computes on the device, bit for bit.
+    definition that Fitter.merge_duplicates computes on the device, bit for bit.  symmetries: the samples are brought
+    into their canonical orientation first (canonicalize_host), so that positions which are images of one another
+    under the eight symmetries merge as well; everything below then holds of the canonical samples.
 
     Two samples are equal when their 70 state floats have the same bit patterns.  A group of equal samples becomes one
     sample at the rank of its first member (groups keep the order of their first members).  With w_i the members'
@@ -104,6 +196,8 @@ def merge_duplicates_host(state_policy, outcome, weights=None, normalize=True):
     weight-0 members with it.  normalize: every weight is then W * (after / sum W), in float64 with the groups' W summed
     in order, rounded once, so that the weights have mean one and a weighted fit keeps an unweighted one's loss scale."""
     sp, oc = _check_packed(state_policy, outcome, "merge_duplicates_host")
+    if symmetries:
+        sp = canonicalize_host(sp)[0]
     n = sp.shape[0]
     if weights is None:
         w = np.ones(n, np.float64)

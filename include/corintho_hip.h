@@ -527,6 +527,29 @@ int ca_fitter_get_sample_weights(ca_fitter *f, float *out, int32_t n);
  * pass reported an impossible state (its probe loops are bounded); the set is unchanged. */
 int ca_fitter_merge_duplicates(ca_fitter *f, int normalize, int32_t *before, int32_t *after);
 
+/* ---- the augmentation of a packed set, and its canonical orientation ("Canonical orientation") ----
+ * SS = the space table and MS = the move table of the reference (space_symmetries, move_symmetries).  The reference
+ * pairs SS[k] with MS[k] (selfplayer.cpp:95-108), but MS[2] is the move permutation of the quarter-turn SS[6] performs
+ * and MS[6] that of SS[2]: the two tables do not belong together for k = 2 and 6.  MC is MS with rows 2 and 6 exchanged,
+ * MC[k] = MS[(k & 3) == 2 ? k ^ 4 : k]; with it (state through SS[k], policy through MC[k]) is one action of the eight
+ * symmetries on a sample.
+ *   CA_AUG_REFERENCE   virtual row 8 i + k of a packed set: policy through MS[k], as the reference expands (the default)
+ *   CA_AUG_CONSISTENT  the policy through MC[k]; state and outcome as before
+ * A property of the fitter, not of the set: it stays until set again, through ca_fitter_clear_data too, and never touches
+ * an expanded set (ca_fitter_set_data), whose rows are the caller's.  Any other value: CA_ERR_ARG, nothing changes. */
+#define CA_AUG_REFERENCE 0
+#define CA_AUG_CONSISTENT 1
+int ca_fitter_set_augmentation(ca_fitter *f, int32_t augmentation);
+int ca_fitter_get_augmentation(ca_fitter *f, int32_t *augmentation);
+/* Brings every sample of a packed set into its canonical orientation, in place on the device.  Of a sample (s, p) the
+ * eight candidates are s_k[c] = s[SS[k][c >> 2] * 4 + (c & 3)] for c < 64 (cells 64..69 do not move); k* is the k whose
+ * candidate is smallest when words 0..63 are compared in ascending order as unsigned 32-bit patterns, the lowest k on a
+ * tie; the sample becomes (s_k*, p[MC[k*]]).  The policy moves through MC whatever the augmentation is: MC is the only
+ * pairing that is a group action.  Outcomes and weights are untouched, and the set does not become a weighted one.
+ * *moved: how many samples had k* != 0.  Samples that are images of one another have equal states afterwards, so
+ * ca_fitter_merge_duplicates then merges up to symmetry.  An expanded or an empty set: CA_ERR_STATE. */
+int ca_fitter_canonicalize(ca_fitter *f, int32_t *moved);
+
 /* ---- fit options: the L1L2 regulariser, decoupled weight decay and gradient clipping, on the device ----
  * What the reference's model declares and leaves at zero (kernel_regularizer=regularizers.L1L2() on its twelve hidden
  * Dense layers, wrapper.py:263) and what its optimizer's constructor takes (Adam(weight_decay=, clipnorm=,

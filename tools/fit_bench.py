@@ -34,6 +34,14 @@ through set_loss, which must cost nothing; `on` is loss weights (0.7, 1.3), labe
 parametrised loss kernel in ft_k_loss's place.  --metrics switches the metrics on (top 5): two launches more per step.
 --lib FILE times another build of the library (the parent commit's, built with `python -m corintho_ai_amd.build --out`).
 
+--augmentation-ab PARENT.so measures something else again: the step on a packed set of rows / 8 samples three ways in
+one process, in turn, --reps times -- this library with augmentation "reference", this library with "consistent"
+(ft_k_assemble_consistent in ft_k_assemble's place), and the parent commit's library -- and reports each way's ms per
+step, the spread (max - min) of the parent's own repetitions, and the consistent step's best minus the parent's best.
+The two ways of this library are one fitter whose augmentation is set before every call, so their difference is the
+kernel's; the parent's is a fitter of its own (other buffers), and "reference" against it shows what that alone makes.
+--ab-two-fitters gives each way of this library a fitter of its own instead.
+
     python tools/fit_bench.py --torch [--net rescnn4] [--rows 1000000 --batch 2048 --steps 200 --reps 3] [--out file.json]
     python tools/fit_bench.py --packed [--net rescnn4]
     python tools/fit_bench.py --handoff [--games 4096 --sims 400]
@@ -237,6 +245,52 @@ def handoff(a):
                         "speedup": min(old) / min(new)}}
 
 
+def augmentation_ab(a):
+    """the packed step by this library under both augmentations and by the parent's library, alternating"""
+    import ctypes as C
+
+    from corintho_ai_amd.fit import net_info
+
+    net = NET_RESCNN4 if a.net == "rescnn4" else NET_MLP12X100
+    w = nets.init_rescnn4(0, bn_noise=True) if a.net == "rescnn4" else nets.init_mlp12x100(0, bn_noise=True)
+    k = a.rows // 8
+    s, z, p = samples(k)
+    sp = np.concatenate([s, p], axis=1)
+    parent = Fitter.__new__(Fitter)  # a Fitter served by the other build, which lacks the newer entry points
+    parent.net, parent.num_weights, parent._L, parent._h, parent.max_batch, parent._data = (
+        net, net_info(net)[1], _lib.declare(C.CDLL(os.path.abspath(a.augmentation_ab))), C.c_void_p(), a.batch, None)
+    _lib.check(parent._L, parent._L.ca_fitter_create_net(a.device, int(net), a.batch, C.byref(parent._h)))
+    mine = Fitter(max_batch=a.batch, device=a.device, net=net)
+    other = Fitter(max_batch=a.batch, device=a.device, net=net) if a.ab_two_fitters else mine
+    ways = [("reference", mine), ("consistent", other), ("parent library", parent)]
+    fitters = [mine, parent] + ([other] if other is not mine else [])
+    rng = np.random.default_rng(1)
+    need = (a.steps + a.warmup) * a.batch
+    order = np.concatenate([rng.permutation(8 * k) for _ in range(-(-need // (8 * k)))])[:need].astype(np.int32)
+    for f in fitters:
+        f.add_samples(sp, z)
+        f.set_weights(w)
+        f.set_optimizer(np.zeros_like(w), np.zeros_like(w), 0)
+    for name, f in ways:
+        if f is not parent:
+            f.set_augmentation(name)
+        f.train(order[:a.warmup * a.batch], a.batch, 1e-3)
+    ms = {name: [] for name, _ in ways}
+    for _ in range(a.reps):
+        for name, f in ways:
+            if f is not parent:
+                f.set_augmentation(name)
+            t0 = time.perf_counter()
+            f.train(order[a.warmup * a.batch:], a.batch, 1e-3)
+            ms[name].append((time.perf_counter() - t0) * 1e3 / a.steps)
+    for f in fitters:
+        f.close()
+    return {"two_fitters": bool(a.ab_two_fitters), "net": a.net, "batch": a.batch, "samples": k, "steps": a.steps, "reps": a.reps, "ms_per_step": ms,
+            "best": {n: min(v) for n, v in ms.items()}, "median": {n: float(np.median(v)) for n, v in ms.items()},
+            "parent_spread_ms": max(ms["parent library"]) - min(ms["parent library"]),
+            "consistent_minus_parent_ms": min(ms["consistent"]) - min(ms["parent library"])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--net", choices=("mlp12x100", "rescnn4"), default="mlp12x100")
@@ -261,7 +315,13 @@ def main():
                     help="set the loss: the reference's, or loss weights, label smoothing and Huber on")
     ap.add_argument("--metrics", action="store_true", help="switch the metrics on")
     ap.add_argument("--lib", default="", help="another build of libcorintho_hip.so to time")
+    ap.add_argument("--augmentation-ab", default="", metavar="PARENT.so",
+                    help="time the packed step under both augmentations and by this build of the parent commit instead")
+    ap.add_argument("--ab-two-fitters", action="store_true", help="--augmentation-ab: a fitter of its own for each way")
     a = ap.parse_args()
+    if a.augmentation_ab:
+        emit(augmentation_ab(a), a.out)
+        return
     if a.lib:
         _lib.LIB_PATH = os.path.abspath(a.lib)
     loss = {None: None, "default": LossOptions(),

@@ -12,6 +12,11 @@ with those weights, and reports
     library (the parent commit's, built with `python -m corintho_ai_amd.build --out LIB.so CSRC_DIR`);
   * best val_loss both ways, and the arena score (--arena games) of each fit's best weights against the initial ones.
 
+With --symmetries every set is also canonicalized and merged up to the eight symmetries (Fitter.canonicalize,
+merge_duplicates(symmetries=True)): the samples left, the milliseconds of canonicalize alone (the set added anew before
+every repetition) and of the whole merge, and a third way of the fit, "merged up to symmetry".  --augmentation sets how
+this library's fitter expands the packed rows in every fit (the parent's library knows only the reference's).
+
 With --merge-only it stops after the merges of the first generation: the process to put under
 `rocprofv3 --kernel-trace --stats` for the kernels' shares (tools/rocpd_summary.py reads the result).
 
@@ -55,15 +60,26 @@ def play(a, kind, weights, seed):
     return sp, oc, time.perf_counter() - t0
 
 
-def time_merge(f, sp, oc, reps):
+def time_merge(f, sp, oc, reps, **kw):
     ms, counts = [], None
     for _ in range(reps):
         f.clear_data()
         f.add_samples(sp, oc)
         t0 = time.perf_counter()
-        counts = f.merge_duplicates(normalize=True)
+        counts = f.merge_duplicates(normalize=True, **kw)
         ms.append((time.perf_counter() - t0) * 1e3)
     return counts, ms
+
+
+def time_canonicalize(f, sp, oc, reps):
+    ms, moved = [], None
+    for _ in range(reps):
+        f.clear_data()
+        f.add_samples(sp, oc)
+        t0 = time.perf_counter()
+        moved = f.canonicalize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return moved, ms
 
 
 def largest_group(sp):
@@ -87,6 +103,9 @@ def main():
     ap.add_argument("--fit-reps", type=int, default=2)
     ap.add_argument("--arena", type=int, default=1600)
     ap.add_argument("--parent-lib")
+    ap.add_argument("--symmetries", action="store_true", help="also canonicalize and merge up to the eight symmetries")
+    ap.add_argument("--augmentation", default="reference", choices=("reference", "consistent"),
+                    help="how this library's fitter expands the packed rows in the fits")
     ap.add_argument("--merge-only", action="store_true")
     ap.add_argument("--check-host", action="store_true", help="compare the first generation's merge with the host's, by bytes")
     ap.add_argument("--out")
@@ -113,6 +132,10 @@ def main():
 
     with Fitter(max_batch=a.batch, net=net) as f:
         time_merge(f, sets[0][1][:4096], sets[0][2][:4096], 1)  # the kernels' code objects
+        if a.symmetries:
+            time_canonicalize(f, sets[0][1][:4096], sets[0][2][:4096], 1)
+        if a.augmentation != "reference":
+            f.set_augmentation(a.augmentation)
         for name, sp, oc in sets:
             counts, ms = time_merge(f, sp, oc, a.reps)
             row = {"set": name, "before": counts[0], "after": counts[1], "largest_group": largest_group(sp),
@@ -121,6 +144,16 @@ def main():
             print("%-42s before %8d after %8d (%.1f %% duplicates), largest group %6d, merge %.2f ms best, %.2f median"
                   % (name, counts[0], counts[1], 100.0 * (1 - counts[1] / counts[0]), row["largest_group"], min(ms),
                      float(np.median(ms))), flush=True)
+            if a.symmetries:
+                moved, cms = time_canonicalize(f, sp, oc, a.reps)
+                scounts, sms = time_merge(f, sp, oc, a.reps, symmetries=True)
+                row.update(after_symmetries=scounts[1], moved=moved, canonicalize_ms_best=min(cms),
+                           canonicalize_ms_median=float(np.median(cms)), merge_symmetries_ms_best=min(sms),
+                           merge_symmetries_ms_median=float(np.median(sms)))
+                print("%-42s up to symmetry: after %8d (%.1f %% duplicates), %d samples turned; canonicalize %.2f ms best, "
+                      "%.2f median; canonicalize + merge %.2f ms best, %.2f median"
+                      % ("", scounts[1], 100.0 * (1 - scounts[1] / scounts[0]), moved, min(cms), float(np.median(cms)), min(sms),
+                         float(np.median(sms))), flush=True)
         if a.check_host:
             _, sp, oc = sets[0]
             f.clear_data()
@@ -133,12 +166,25 @@ def main():
             out["equals_host"] = bool(same)
             print("the device's merge of generation 1 equals the host's by bytes: %s" % same, flush=True)
             assert same
+            if a.symmetries:
+                f.clear_data()
+                f.add_samples(sp, oc)
+                n = f.merge_duplicates(symmetries=True)[1]
+                s, e, p = f.fetch_rows(8 * np.arange(n, dtype=np.int32))  # (row 8 i: symmetry 0, whatever the augmentation)
+                want = merge_duplicates_host(sp, oc, symmetries=True)
+                same = (np.concatenate([s, p], 1).tobytes() == want[0].tobytes() and e.tobytes() == want[1].tobytes()
+                        and f.get_sample_weights().tobytes() == want[2].tobytes())
+                out["equals_host_symmetries"] = bool(same)
+                print("the device's merge up to symmetry of generation 1 equals the host's by bytes: %s" % same, flush=True)
+                assert same
         if a.merge_only:
             return
 
         # the fit of the first generation, without and with the merge (and by the parent's library), alternating
         _, sp, oc = sets[0]
         ways = [("unmerged", f, False), ("merged", f, True)]
+        if a.symmetries:
+            ways.append(("merged up to symmetry", f, "symmetries"))
         if a.parent_lib:
             ways.append(("unmerged, parent library", fitter_on(_lib.declare(C.CDLL(os.path.abspath(a.parent_lib))), a.batch, net),
                          False))
@@ -148,7 +194,10 @@ def main():
                 be.clear_data()
                 be.add_samples(sp, oc)
                 t0 = time.perf_counter()
-                counts = be.merge_duplicates(normalize=True) if merge else None
+                if merge == "symmetries":
+                    be.merge_duplicates(normalize=True, symmetries=True)
+                elif merge:
+                    be.merge_duplicates(normalize=True)
                 t1 = time.perf_counter()
                 res = fit_resident(be, w0, learning_rate=a.learning_rate, batch_size=a.batch, epochs=a.epochs,
                                    anneal_factor=0.5, patience=2, seed=7)
@@ -159,7 +208,9 @@ def main():
                 best.setdefault(name, res.best_weights)
                 print("fit %-26s rep %d: %9d rows, merge %.3f s, fit %.2f s, best val_loss %.4f (epoch %d)"
                       % (name, rep, row["rows"], row["merge_s"], row["fit_s"], row["best_val_loss"], res.best_epoch), flush=True)
-        for name, _, _ in ways[:2]:
+        for name, be, _ in ways:
+            if be is not f:
+                continue
             t = Trainer(a.arena, "", 301, a.searches, a.spe, 3.0, 0.25, 0, 1, True)
             try:
                 t.set_net(kind, w0, slot=0)
@@ -169,8 +220,9 @@ def main():
             finally:
                 t.close()
             print("arena of the %s fit's best weights against the initial ones: %.4f" % (name, out["arena_" + name]), flush=True)
-        for _, be, _ in ways[2:]:
-            be.close()
+        for _, be, _ in ways:
+            if be is not f:
+                be.close()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w", encoding="utf-8") as fh:
